@@ -12,11 +12,13 @@ All of it goes through the product's plugin surface (retake.visual_compression /
 retake.longvideo_cache), i.e. the C ABI of libretake_hip.so.  N > 1: one process per GPU over RCCL,
 the video's frame chunks are sharded across ranks (strong scaling), see retake/sharded.py.
 
-Prints ONE short JSON line (rank 0, stdout, < 4 KB: the contract keys + one number per extra measurement); the full
-report (per-kernel tables, companions, memory split) goes to bench_report.json and stderr (`contract_line` / `emit`).
-`roofline` is for the dominant kernel, measured with HIP events on the launch stream inside the timed region
-(rtk_profile_*); `cpu_baseline` times the CPU oracle (oracle/, test infrastructure) on a bounded sample of the same
-workload on this host's cores.
+A plain run (N = 1) sets up, warms up, times the steps and prints ONE short JSON line (stdout, the headline keys:
+`value` frames/s, `ms_per_step`, ...) - nothing else.  `--full` adds everything else this file measures or checks: the
+line then carries one number per extra measurement (< 4 KB) and the full report (per-kernel tables, companions, memory
+split) goes to bench_report.json and stderr (`contract_line` / `emit`).  `roofline` is for the dominant kernel, measured
+with HIP events on the launch stream inside the timed region (rtk_profile_*); `cpu_baseline` times the CPU oracle
+(oracle/, test infrastructure) on a bounded sample of the same workload on this host's cores.
+`--dump-outputs DIR` writes what the last timed step computed (`dump_outputs`) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -105,7 +107,15 @@ def parse():
     ap.add_argument("--no-self-check", action="store_true")
     ap.add_argument("--cpu-sample-updates", type=int, default=10,
                     help="timed repetitions of the CPU PivotKV update (~0.7-1 s each on the GPU box's host: ~10 s of CPU work)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: HIP events on the score passes, per-kernel tables and rooflines, "
+                         "memory block, self-check, cache checksum, companions, CPU baseline, the report file (N = 1)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class Rotary:
@@ -206,11 +216,47 @@ def cache_checksum(keys, values, pos):
             "k_abs_sum": kabs}
 
 
+DUMP_MIB = {"dpselect_frames": 4, "keypatch_mask": 8, "key_cache": 16, "value_cache": 16, "position_ids": 16}   # 60 MiB in all
+
+
+def _sample(t, n, seed):
+    """t as a flat float32 array (float64 for integer tensors): every element when t has at most n, else n elements at
+    seeded positions (sorted flat indices drawn with replacement) - a function of (t.shape, n, seed) alone, so two runs
+    with the same arguments read the same elements."""
+    wide = not (t.is_floating_point() or t.dtype == torch.bool)
+    if t.numel() > n:
+        flat = np.sort(np.random.default_rng(seed).integers(0, t.numel(), n))
+        t = t[tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(flat, tuple(t.shape)))]
+    return t.reshape(-1).to(torch.float64 if wide else torch.float32).cpu().numpy()
+
+
+def dump_outputs(path, cache, mask, dpselect_frames):
+    """What a caller of the timed path receives from its last step, as <path>/<name>.npy: DPSelect's compressed frame bank
+    and key-patch mask, and per layer the compressed cache's K / V rows and the position ids of the cached tokens
+    ([layers, n] each).  Arrays beyond their DUMP_MIB share are replaced by a fixed, seeded sample of their elements."""
+    os.makedirs(path, exist_ok=True)
+    layers = len(cache.key_cache)
+    per_layer = [(cache.key_cache[l], cache.value_cache[l], cache.position_cache[l]) for l in range(layers)]
+
+    def cap(name, itemsize, parts=1):
+        return DUMP_MIB[name] * 2 ** 20 // (itemsize * parts)
+
+    arrays = {"dpselect_frames": _sample(dpselect_frames, cap("dpselect_frames", 4), 1),
+              "keypatch_mask": _sample(mask, cap("keypatch_mask", 4), 2)}
+    for j, name in enumerate(("key_cache", "value_cache", "position_ids")):
+        size = 8 if name == "position_ids" else 4
+        arrays[name] = np.stack([_sample(p[j], cap(name, size, layers), (3 + j, l)) for l, p in enumerate(per_layer)])
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 NO_VISUAL_COMPRESSION = False   # companion `no_keypatch_mask`: the reference's videomme config (visual_compression: False)
 
 
-def run_video(frames, pool, masks, pos_base, rotary, layers, tdtype, pre_rope=False):
+def run_video(frames, pool, masks, pos_base, rotary, layers, tdtype, pre_rope=False, outputs=None):
     """One step on one GPU: DPSelect + all (chunk, layer) PivotKV updates.  Returns retained tokens.
+    outputs: a dict that receives DPSelect's compressed frame bank (`dpselect_frames`; the cache and the mask are returned).
     pre_rope: the pool holds PRE-RoPE projections and every update is the attention patch's fused prologue
     (PivotKVCache.update_pre_rope: continuity shift + RoPE of q / k + append + scoring operands in one kernel).  In the
     model the rotated queries overwrite q_proj's fresh output; the pool's tensors are reused, so here they go to a
@@ -223,6 +269,8 @@ def run_video(frames, pool, masks, pos_base, rotary, layers, tdtype, pre_rope=Fa
         out, mask = frames, None
     else:
         out, mask = vc.memory_bank_compress_keyframe(frames, T, 3, sync=False)
+    if outputs is not None:
+        outputs["dpselect_frames"] = out
     n_chunks = T // FRAMES_PER_CHUNK
     L = FRAMES_PER_CHUNK * N_PATCH
     # capacity hint, as the patched model forward gives it (_prefill.expected_cache_tokens): compressed video + one chunk
@@ -811,12 +859,14 @@ def contract_line(report: dict, report_path=None) -> dict:
     return line
 
 
-def emit(report: dict, path=None):
-    """Report -> `path` (default: bench_report.json at the repo root + in gpurun_out/) and stderr; the short contract line
-    -> stdout, LAST."""
+def emit(report: dict, path=None, full=True):
+    """Report -> `path` (default: bench_report.json at the repo root + in the run's output directory) and stderr; the short
+    contract line -> stdout, LAST.  full=False (a plain run): the line alone, the report only to an explicit `path`."""
     text = json.dumps(report)
     where = None
     targets = [path] if path else [os.path.join(d, REPORT_NAME) for d in (ROOT, os.path.join(ROOT, "gpurun_out")) if os.path.isdir(d)]
+    if not full:
+        targets = [path] if path else []
     for t in targets:
         try:
             with open(t, "w") as f:
@@ -825,8 +875,9 @@ def emit(report: dict, path=None):
         except OSError:
             pass
     line = contract_line(report, where)
-    sys.stderr.write(text + "\n")
-    sys.stderr.flush()
+    if full:
+        sys.stderr.write(text + "\n")
+        sys.stderr.flush()
     try:   # anything a C library left in stdio's buffer (RCCL's banner) goes out BEFORE the line, not at exit after it
         import ctypes
 
@@ -922,36 +973,43 @@ def main():
     torch.cuda.synchronize()
     # HIP events bracket the dominant kernels (the two score passes) on their launch streams INSIDE the timed
     # region; timing every small kernel as well costs ~9 % of wall time, so the full per-kernel table comes
-    # from a short extra segment after the timed region.
-    use_events = not args.no_kernel_events
+    # from a short extra segment after the timed region.  (--full only: a plain run times the bare steps.)
+    use_events = args.full and not args.no_kernel_events
     if use_events:
         ids = nv.profile_kernel_ids()
         nv.check(nv.lib.rtk_profile_reset(), "profile_reset")
         nv.check(nv.lib.rtk_profile_enable_mask((1 << ids["score_pass1"]) | (1 << ids["score_pass2"])), "profile_enable")
     gc.collect()
     torch.cuda.synchronize()
-    resident_inputs = torch.cuda.memory_allocated()     # frame bank + (q, k, v) pool + ids: the bench's own tensors
-    torch.cuda.reset_peak_memory_stats()
+    if args.full:
+        resident_inputs = torch.cuda.memory_allocated()     # frame bank + (q, k, v) pool + ids: the bench's own tensors
+        torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
     retained = 0
     cache = None
     for _ in range(args.steps):
         cache = None     # the previous video's cache is released first, as after a finished `generate`
-        r, cache, kp_mask = run_video(frames, pool, masks, pos_base, rotary, args.layers, tdtype, args.pre_rope)
+        step_out = {} if args.dump_outputs else None
+        r, cache, kp_mask = run_video(frames, pool, masks, pos_base, rotary, args.layers, tdtype, args.pre_rope, step_out)
         retained += r
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     cache.check()   # a bounded device-side wait that ran out (the in-launch id shift) raises: no number for a wrong path
-    peak_alloc, peak_reserved = torch.cuda.max_memory_allocated(), torch.cuda.max_memory_reserved()
-    mem = memory_block(cache, peak_alloc, peak_reserved, resident_inputs,
-                       frames.numel() * frames.element_size() + 5 * T * N_PATCH, args.layers, L, n_chunks, es)
+    mem = check = checksum = None
     prof, prof_all = {}, {}
-    if use_events:
-        nv.check(nv.lib.rtk_profile_enable(0), "profile_enable")
-        prof = nv.profile_read()
-    check = self_check(cache, pool, kp_mask, n_chunks, args.layers, rotary) if not args.no_self_check else None
-    checksum = cache_checksum([cache.key_cache[l] for l in range(args.layers)],
-                              [cache.value_cache[l] for l in range(args.layers)], cache.position_cache)
+    if args.full:
+        peak_alloc, peak_reserved = torch.cuda.max_memory_allocated(), torch.cuda.max_memory_reserved()
+        mem = memory_block(cache, peak_alloc, peak_reserved, resident_inputs,
+                           frames.numel() * frames.element_size() + 5 * T * N_PATCH, args.layers, L, n_chunks, es)
+        if use_events:
+            nv.check(nv.lib.rtk_profile_enable(0), "profile_enable")
+            prof = nv.profile_read()
+        check = self_check(cache, pool, kp_mask, n_chunks, args.layers, rotary) if not args.no_self_check else None
+        checksum = cache_checksum([cache.key_cache[l] for l in range(args.layers)],
+                                  [cache.value_cache[l] for l in range(args.layers)], cache.position_cache)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, cache, kp_mask, step_out["dpselect_frames"])
+        step_out = None
     del cache
     if use_events:
         # untimed: every kernel, up to 64 chunks' worth of frames / updates on one stream (>= 64 launches of the per-chunk
@@ -1001,8 +1059,9 @@ def main():
     out["config"]["pass2_live_key_fraction"] = 1.0 - out["config"]["key_patch_mask_rate"]
     if check is not None:
         out["self_check"] = check
-    out["cache_checksum"] = checksum   # the sharded runs (--gpus N) print the same fingerprint of the assembled cache
-    out["memory"] = mem
+    if args.full:
+        out["cache_checksum"] = checksum   # the sharded runs (--gpus N) print the same fingerprint of the assembled cache
+        out["memory"] = mem
     if prof:
         kern = {k: {"launches": n, "avg_us": ms / n * 1e3, "total_ms": ms} for k, (n, ms) in prof_all.items()}
         out["kernels_untimed_single_stream"] = dict(kern)
@@ -1112,7 +1171,7 @@ def main():
                                             "over_peak": ev_bytes / t_unit / 1e9 / HBM_PEAK_GBS}}
         out["roofline_hbm_kernels"] = extra
         out["hbm_achievable"] = achievable
-    if args.also_streams > 0 and args.streams == 0:
+    if args.full and args.also_streams > 0 and args.streams == 0:
         # same workload with scoring / selection / eviction on worker HIP streams (PivotKVCache
         # overlap_streams): kernels of independent updates overlap, so per-kernel event durations no longer
         # measure a kernel that owns the chip; the sustained MFMA rate is total score flops / wall time
@@ -1129,7 +1188,7 @@ def main():
         out["overlap"] = {"worker_streams": args.also_streams, "value": args.frames * args.steps / dt2, "unit": "frames/s",
                           "ms_per_step": dt2 / args.steps * 1e3,
                           "sustained_score_tflops": flops_step * args.steps / dt2 / 1e12}
-    if not args.no_extras and args.geometry == "baseline" and args.dtype == "bf16" and args.score_rounding == "fp32":
+    if args.full and not args.no_extras and args.geometry == "baseline" and args.dtype == "bf16" and args.score_rounding == "fp32":
         # Companions of the headline, each measured the same way in small AFTER the timed region above (none of them
         # enters `value`): (1) the real Qwen2-VL geometry SURVEY 8(d) names beside the synthetic one; (2) the price
         # of reproducing the reference's own bf16 roundings bit for bit; (3) the parity dtype.
@@ -1183,11 +1242,11 @@ def main():
         # the base of the scaling curve: the SHARDED path (`bench.py --gpus N`'s host code and kernels) at world size 1
         out["n1_same_arithmetic"] = n1_same_arithmetic(args)
         frames = torch.cat([chunk_frames(c, dev, tdtype) for c in range(min(n_chunks, 4))])[None]
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         sample_T = 128
         out["cpu_baseline"] = cpu_baseline(args, frames[:, :sample_T].float().cpu().numpy(), args.cpu_sample_updates)
         out["speedup_vs_cpu_baseline"] = fps / out["cpu_baseline"]["value"]
-    emit(out, args.report)
+    emit(out, args.report, args.full)
 
 
 if __name__ == "__main__":

@@ -108,3 +108,69 @@ def test_a_failed_world1_companion_is_reported_in_the_line_not_raised():
     assert isinstance(line["n1_same_arithmetic"], str) and len(line["n1_same_arithmetic"]) <= 80
     assert line["n1_same_arithmetic"].startswith("the world-size-1 sharded run did not finish")
     assert len(json.dumps(line)) < bench.LINE_LIMIT and line["value"] == pytest.approx(rep["value"], rel=1e-6)
+
+
+def test_plain_emit_prints_only_the_line(tmp_path, capsys):
+    """A plain run (no --full): the line on stdout and nothing on stderr; no report file unless a path is given."""
+    rep = {k: v for k, v in _canned().items() if k in CONTRACT[:-2]}
+    line = bench.emit(rep, None, full=False)
+    out, err = capsys.readouterr()
+    assert json.loads(out.strip()) == line and err == "" and "report" not in line
+    assert line["value"] == pytest.approx(rep["value"], rel=1e-6) and line["cpu_baseline"] is None
+    path = os.path.join(str(tmp_path), "plain.json")
+    line = bench.emit(rep, path, full=False)
+    out, err = capsys.readouterr()
+    assert json.load(open(path)) == rep and err == "" and line["report"].endswith("plain.json")
+
+
+def _fake_cache(torch, layers, tokens):
+    g = torch.Generator().manual_seed(7)
+    k = [torch.randn((1, 4, tokens, 128), generator=g).bfloat16() for _ in range(layers)]
+    v = [torch.randn((1, 4, tokens, 128), generator=g).bfloat16() for _ in range(layers)]
+    pos = [torch.randint(0, 1 << 20, (3, 1, tokens), generator=g) for _ in range(layers)]
+    import types
+
+    return types.SimpleNamespace(key_cache=k, value_cache=v, position_cache=pos), g
+
+
+def test_dump_outputs_is_float_bounded_and_a_fixed_sample(tmp_path):
+    """`bench.py --dump-outputs`: float32 / float64 arrays, 64 MB at most in all, every element of an array that fits its
+    share, a sample at fixed positions of one that does not - the same positions in two runs with the same shapes."""
+    import numpy as np
+    import torch
+
+    layers, tokens = 2, 5000          # 2.56 M K elements per layer: beyond a layer's share of 16 MiB
+    cache, g = _fake_cache(torch, layers, tokens)
+    frames = torch.randn((1, 64, 196, 128), generator=g).bfloat16()      # 1.6 M elements: beyond 4 MiB of float32
+    mask = torch.rand((64 * 196,), generator=g) < 0.3
+    d1, d2 = os.path.join(str(tmp_path), "a"), os.path.join(str(tmp_path), "b")
+    shapes = bench.dump_outputs(d1, cache, mask, frames)
+    bench.dump_outputs(d2, cache, mask, frames)
+    names = {"dpselect_frames", "keypatch_mask", "key_cache", "value_cache", "position_ids"}
+    assert set(shapes) == names and sorted(os.listdir(d1)) == sorted(n + ".npy" for n in names)
+    total = 0
+    for n in names:
+        a, b = np.load(os.path.join(d1, n + ".npy")), np.load(os.path.join(d2, n + ".npy"))
+        assert a.dtype == (np.float64 if n == "position_ids" else np.float32), (n, a.dtype)
+        assert np.array_equal(a, b), n
+        total += os.path.getsize(os.path.join(d1, n + ".npy"))
+    assert total <= 64 * 2 ** 20
+    ld = lambda n: np.load(os.path.join(d1, n + ".npy"))  # noqa: E731
+    # small arrays whole and exact
+    assert np.array_equal(ld("keypatch_mask"), mask.numpy().astype(np.float32))
+    assert np.array_equal(ld("position_ids"), np.stack([p.reshape(-1).double().numpy() for p in cache.position_cache]))
+    # large arrays: a share-sized sample of the exact values (bf16 -> float32 is exact)
+    fr = ld("dpselect_frames")
+    assert fr.shape == (2 ** 20,) and np.isin(fr, frames.float().numpy()).all()
+    kc = ld("key_cache")
+    assert kc.shape == (layers, 16 * 2 ** 20 // (4 * layers))
+    for l in range(layers):
+        assert np.isin(kc[l], cache.key_cache[l].float().numpy()).all()
+    assert not np.array_equal(kc[0], kc[1])
+    # the positions depend on the shapes alone: other values at the same shapes are read at the same places
+    cache2, _ = _fake_cache(torch, layers, tokens)
+    cache2.key_cache = [torch.arange(t.numel(), dtype=torch.float32).view(t.shape) for t in cache.key_cache]
+    bench.dump_outputs(d2, cache2, mask, frames)
+    idx = np.load(os.path.join(d2, "key_cache.npy")).astype(np.int64)
+    assert (np.diff(idx, axis=1) >= 0).all() and np.array_equal(
+        cache.key_cache[0].float().numpy().reshape(-1)[idx[0]], kc[0])

@@ -2328,14 +2328,14 @@ def test_p2p_across_gpus():
 
 
 def _bench(args, tmp_path, name, env=None):
-    """Run bench.py in a child process -> (the short contract line of its stdout, the full report it wrote)."""
+    """Run `bench.py --full` in a child process -> (the short contract line of its stdout, the full report it wrote)."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     rep = os.path.join(str(tmp_path), name + ".json")
-    r = _run_job([sys.executable, os.path.join(root, "bench.py")] + args + ["--report", rep], env, 600, root)
+    r = _run_job([sys.executable, os.path.join(root, "bench.py"), "--full"] + args + ["--report", rep], env, 600, root)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     last = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]
     assert len(last) < 4096, len(last)            # the contract: a line the driver's 8 KB stdout tail always holds whole
@@ -2428,6 +2428,37 @@ def test_bench_default_line_is_short_and_names_every_companion(tmp_path):
     assert set(a["memory"]) == {"product_peak_bytes", "peak_allocated_bytes", "product_peak_over_reference_formula"}
     assert all(isinstance(v, float) for v in a["roofline_hbm_kernels"].values())
     assert "kernels_timed_region" in rep and "split_bytes" in rep["memory"] and "step_ms" in rep["real_geometry"]
+
+
+def test_bench_plain_run_is_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full), twice with the same arguments: the line holds the headline keys and none of --full's
+    measurements, `--steps` is the number of timed steps, and `--dump-outputs` writes the same arrays both times."""
+    import json
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for name in ("a", "b"):
+        d = os.path.join(str(tmp_path), name)
+        r = _run_job([sys.executable, os.path.join(root, "bench.py"), "--frames", "256", "--layers", "2", "--steps", "3",
+                      "--warmup", "1", "--dump-outputs", d], None, 300, root)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    a = lines[0]
+    assert a["steps"] == 3 and a["warmup"] == 1 and a["value"] > 0 and a["ms_per_step"] > 0 and a["higher_is_better"] is True
+    assert a["metric"].startswith("frames/sec") and a["unit"] == "frames/s" and a["dtype"] == "bf16"
+    assert a["value"] == pytest.approx(256 * 1e3 / a["ms_per_step"], rel=1e-4)
+    for key in ("roofline", "self_check", "memory", "companions_frames_per_s", "n1_same_arithmetic", "report"):
+        assert key not in a, key
+    assert a["cpu_baseline"] is None
+    assert set(dumps[0]) == {"dpselect_frames", "keypatch_mask", "key_cache", "value_cache", "position_ids"}
+    assert sum(x.nbytes for x in dumps[0].values()) <= 64 * 2 ** 20
+    assert dumps[0]["keypatch_mask"].shape == (256 * 196,) and dumps[0]["key_cache"].shape[0] == 2
+    assert dumps[0]["position_ids"].shape == (2, 3 * 8 * 1568)          # 8 chunks x keep 1568, three M-RoPE rows
+    for k, x in dumps[0].items():
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), k
+        assert np.array_equal(x, dumps[1][k]), k
 
 
 @pytest.mark.parametrize("L,Hq,Hkv", [(1, 28, 4), (31, 28, 4), (130, 28, 4), (257, 28, 4), (515, 28, 4), (1000, 28, 4),

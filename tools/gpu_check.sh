@@ -12,7 +12,7 @@ else
   timeout 900 python -m pytest tests -m gpu -x -q > $out/pytest.log 2>&1 < /dev/null
 fi
 tail -4 $out/pytest.log
-timeout 300 rocprofv3 --kernel-trace -d $out/kt -o kt --output-format csv -- python3 bench.py --frames $frames --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-events --also-streams 0 > $out/kt.log 2>&1 < /dev/null
+timeout 300 rocprofv3 --kernel-trace -d $out/kt -o kt --output-format csv -- python3 bench.py --full --frames $frames --steps 1 --warmup 1 --no-cpu-baseline --no-kernel-events --also-streams 0 > $out/kt.log 2>&1 < /dev/null
 f=$(find $out/kt -name "*kernel_trace.csv" | head -1)
 python tools/trace_gaps.py $f > $out/trace_summary.txt 2>&1 < /dev/null
 head -30 $out/trace_summary.txt

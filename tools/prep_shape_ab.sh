@@ -17,7 +17,7 @@ for rep in 1 2; do
       extra=$([ $mode = prerope ] && echo --pre-rope)
       for geo in qwen448 baseline; do
         [ $geo = baseline ] && [ $rep != 1 ] && continue
-        RETAKE_HIP_LIB=$lib timeout 300 python bench.py --geometry $geo --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-self-check $extra \
+        RETAKE_HIP_LIB=$lib timeout 300 python bench.py --full --geometry $geo --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-self-check $extra \
             --report $out/$tag.$mode.$geo.$rep.json > /dev/null 2> $out/$tag.$mode.$geo.$rep.err < /dev/null
         summ $out/$tag.$mode.$geo.$rep.json "$tag $mode $geo rep$rep" | tee -a $out/summary.txt
       done

@@ -1,5 +1,7 @@
 #!/bin/bash
-# Build A/B variants of libretake_hip.so:  tools/variants.sh name "extra hipcc flags" [name2 "flags2" ...]
+# Build A/B variants of libretake_hip.so:  [RTK_SRC=dir] tools/variants.sh name "extra hipcc flags" [name2 "flags2" ...]
+# A variant is a modified copy of csrc/ (RTK_SRC, default: the in-tree sources) and/or extra compiler flags; the sources
+# themselves hold no build-time knobs.
 # Output: video-retake_amd/retake/_lib/variants/libretake_hip_<name>.so   (select with RETAKE_HIP_LIB=...)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

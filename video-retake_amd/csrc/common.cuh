@@ -228,12 +228,20 @@ __device__ __forceinline__ void rotate_chunk_pair(const u32x4& lo, const u32x4& 
     }
 }
 
+// Shape of the per-update kernels (fused prepare, attention prologue) - A/B: profiles/r12_ab_prologue_shape.txt
+constexpr int PREP_BLOCK = 64;    // threads per workgroup
+constexpr int PREP_NW = 1;        // 16-bit dtypes: 32-bit words per thread and row half (fp32: 4)
+constexpr int PREP_HU = 7;        // query heads whose rows are requested together (register batch)
+constexpr int PREP_YSPLIT = 2;    // the query heads are split over this many workgroups per token range (k and v go to the
+                                  // first and the last)
+
 // NW 32-bit words of a row as one aligned load / store (the narrow-chunk forms of the per-update kernels)
 template <int NW> struct alignas(4 * NW) WV { uint32_t w[NW]; };
 
 // NW-dword accesses through a buffer descriptor: address = descriptor base + soff (SGPR: the head's offset) + voff (VGPR: the
 // thread's offset inside a head, computed once) + a compile-time immediate - no vector ALU work per access (the per-update
-// kernels touch 2 x 18 rows per thread and were spending a third of their vector instructions on 64-bit row addresses).
+// kernels touch 2 x 18 rows per thread and were spending a third of their vector instructions on 64-bit row addresses;
+// A/B: profiles/r15_ab_prepare_addressing.txt).
 // Offsets are 32-bit: the launchers check that a tensor's extent fits (RTK_EUNSUPPORTED otherwise).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p) {   // p must be wave-uniform (readfirstlane says so)
     const unsigned long long a = (unsigned long long)p;

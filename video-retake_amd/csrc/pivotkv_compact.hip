@@ -21,7 +21,6 @@
 // heads of the block) while the row loads are in flight; the rotation rounds through v_cvt_pk_bf16_f32 - one
 // instruction per pair instead of the integer sequence of rtk_pivotkv_evict_batched_rope, which was VALU-bound.
 #include "common.cuh"
-#include "variants.h"
 
 namespace rtk {
 
@@ -30,11 +29,12 @@ struct CompactUnits {
 };
 
 constexpr int CMP_BLOCK = 256;
-constexpr int CMP_HU = RTK_CMP_HU;            // KV heads per workgroup
+constexpr int CMP_HU = 4;            // KV heads per workgroup (A/B: profiles/r13_ab_compact.txt)
+constexpr int CMP_WAVES = 4;         // waves per SIMD the register allocation is bounded for (same record)
 constexpr int CMP_HDR = 32;          // ints before the flags of a (unit, head group): [0] ticket, [1] finished blocks
 
 template <int DT, int KMODE>
-__global__ __launch_bounds__(CMP_BLOCK, RTK_CMP_WAVES) void compact_units_kernel(CompactUnits units, int Hkv, int HG, int D, int keep,
+__global__ __launch_bounds__(CMP_BLOCK, CMP_WAVES) void compact_units_kernel(CompactUnits units, int Hkv, int HG, int D, int keep,
                                                                   int P, const float* __restrict__ inv_freq,
                                                                   float scaling, RowSel rs, int round_mode,
                                                                   int32_t* __restrict__ sync,

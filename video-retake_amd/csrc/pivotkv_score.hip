@@ -25,7 +25,6 @@
 #include <type_traits>
 
 #include "common.cuh"
-#include "variants.h"   // A/B knobs (production builds define none of them)
 
 // LLVM sched_group_barrier masks
 #define SGB_VALU 0x2
@@ -211,23 +210,23 @@ __global__ __launch_bounds__(256) void unrotate_pack_vec_kernel(const char* __re
 //   three launches become one.  One thread = one token x one 16-byte chunk pair; blockIdx.y splits the heads
 //   in two: y = 0 the first half of the q heads + k (k~ and the k tail), y = 1 the second half + the v tail.
 // ------------------------------------------------------------------------------------------------
-// NW = 32-bit words per thread and row half: 4 (16-byte accesses; fp32) or, for the 16-bit dtypes, 1 (2: A/B builds).  A
+// NW = 32-bit words per thread and row half: 4 (16-byte accesses; fp32) or, for the 16-bit dtypes, PREP_NW = 1.  A
 // wave of the 16-byte form issues ~3500 VALU instructions (the per-op rounding chains of 18 heads plus 8 correctly
 // rounded sin / cos pairs) and a chunk of 2304 tokens gives barely half the chip's SIMDs one such wave: that form is bound
 // by the serial instruction stream of its waves.  Narrow chunks split the same work over 4x the waves; what remains is the
 // read + write traffic (45 MB per call at L = 2304) at ~3 TB/s plus the launch ramp.
 
-constexpr int RTK_SHIFT_COUNTERS = 64;   // arrival counters of RTK_UPDATE_SHIFT_NEXT (<= RTK_PREP_BLOCK: one per watching thread)
+constexpr int RTK_SHIFT_COUNTERS = 64;   // arrival counters of RTK_UPDATE_SHIFT_NEXT (<= PREP_BLOCK: one per watching thread)
 constexpr int RTK_SHIFT_STRIDE = 32;     // ... 128 bytes apart
 constexpr int RTK_SHIFT_STATUS = RTK_SHIFT_STRIDE - 1;     // word of the first line that latches a wait that ran out
 // polls of the watching workgroup before it gives up (an agent-scope load, a barrier and s_sleep 4 per poll: ~2-3 s; the
 // workers need microseconds).  Same policy as compact_units_kernel's bounded wait, but latched instead of trapped: the
 // host can raise, reset and carry on, and the test suite can force it.
 constexpr unsigned RTK_SHIFT_MAX_POLLS = 1u << 21;
-static_assert(RTK_SHIFT_COUNTERS <= RTK_PREP_BLOCK, "one watching thread per counter");
+static_assert(RTK_SHIFT_COUNTERS <= PREP_BLOCK, "one watching thread per counter");
 
 template <int DT, int DIV, bool FAST = false, int NW = 4>
-__global__ __launch_bounds__(RTK_PREP_BLOCK) void prepare_native_kernel(const char* __restrict__ q, int64_t q_sh, int64_t q_sl,
+__global__ __launch_bounds__(PREP_BLOCK) void prepare_native_kernel(const char* __restrict__ q, int64_t q_sh, int64_t q_sl,
                                                             const char* __restrict__ k, int64_t k_sh, int64_t k_sl,
                                                             const char* __restrict__ v, int64_t v_sh, int64_t v_sl,
                                                             int Hq, int Hkv, int L, int D,
@@ -318,13 +317,9 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prepare_native_kernel(const ch
     const int l = id / lpr, d = (id - l * lpr) * VE;
     if (pos_copy && blockIdx.y == 0 && d == 0)   // the ids the caller may shift in place before the deferred selection runs
         for (int p = 0; p < P; ++p) pos_copy[(size_t)p * L + l] = pos[(size_t)p * pos_ld + l];
-    constexpr int HU = RTK_PREP_HU;   // heads per batch: all loads of a batch are issued before its arithmetic and stores
+    constexpr int HU = PREP_HU;   // heads per batch: all loads of a batch are issued before its arithmetic and stores
     const int ny = gridDim.y, qper = (Hq + ny - 1) / ny;
-#if RTK_PREP_UBASE
     const int qb = uniform_int(min((int)blockIdx.y * qper, Hq)), qe = uniform_int(min(qb + qper, Hq));   // (head loops in SGPRs)
-#else
-    const int qb = min((int)blockIdx.y * qper, Hq), qe = min(qb + qper, Hq);
-#endif
     // the KV heads: y = 0 takes k (k~ for the scoring / eviction + the rotated rows for the tail), the last y takes v
     const bool has_kv = blockIdx.y == 0 || (int)blockIdx.y == ny - 1;
     const char* src = blockIdx.y == 0 ? k : v;
@@ -335,7 +330,6 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prepare_native_kernel(const ch
     // are requested before batch b is un-rotated and stored, and the first batch before the table arithmetic
     // (sin / cos are ~25 fp64 operations per value) - with ~1.5 waves per SIMD nothing else hides a round trip.
     W lo[HU], hi[HU], lon[HU], hin[HU];
-#if RTK_PREP_UBASE
     // a row's address = descriptor (tensor base) + soffset (the head: wave-uniform, a scalar multiply) + voffset (this
     // thread's byte offset inside a head, computed once); the launcher has checked that every extent fits 31 bits
     const uint32_t off_q = (uint32_t)(((int64_t)l * q_sl + d) * ES), off_kv = (uint32_t)(((int64_t)l * sl + d) * ES);
@@ -345,35 +339,22 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prepare_native_kernel(const ch
                                  r_tail = buf_rsrc(tail), r_kf = buf_rsrc(k_fast);
     const uint32_t hs_q = (uint32_t)(q_sh * ES), hs_kv = (uint32_t)(sh * ES), hs_o = (uint32_t)((int64_t)L * D * ES),
                    hs_t = (uint32_t)(tail_sh * ES);
-#endif
     auto load_q = [&](W* a, W* b, int hb) {
 #pragma unroll
         for (int u = 0; u < HU; ++u) {
             const int h = min(hb + u, qe - 1);
-#if RTK_PREP_UBASE
             const uint32_t so = (uint32_t)uniform_int((int)((uint32_t)h * hs_q));
             a[u] = buf_load<NW>(r_q, off_q, so);
             b[u] = buf_load<NW>(r_q, off_q2, so);
-#else
-            const char* row = q + ((size_t)h * q_sh + (size_t)l * q_sl) * ES;
-            a[u] = *(const W*)(row + (size_t)d * ES);
-            b[u] = *(const W*)(row + (size_t)(d + h2) * ES);
-#endif
         }
     };
     auto load_kv = [&](W* a, W* b, int hb) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int h = min(hb + u, Hkv - 1);
-#if RTK_PREP_UBASE
             const uint32_t so = (uint32_t)uniform_int((int)((uint32_t)h * hs_kv));
             a[u] = buf_load<NW>(r_src, off_kv, so);
             b[u] = buf_load<NW>(r_src, off_kv2, so);
-#else
-            const char* row = src + ((size_t)h * sh + (size_t)l * sl) * ES;
-            a[u] = *(const W*)(row + (size_t)d * ES);
-            b[u] = *(const W*)(row + (size_t)(d + h2) * ES);
-#endif
         }
     };
     float pid[3];   // the token's ids (t / h / w rows; a 1-D id fills all three)
@@ -448,15 +429,9 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prepare_native_kernel(const ch
                 olo = to_f16(olo, qscale);
                 ohi = to_f16(ohi, qscale);
             }
-#if RTK_PREP_UBASE
             const uint32_t so = (uint32_t)uniform_int((int)((uint32_t)h * hs_o));
             buf_store<NW>(olo, r_qo, off_o, so);
             buf_store<NW>(ohi, r_qo, off_o2, so);
-#else
-            char* orow = q_out + ((size_t)h * L + l) * D * ES;
-            *(W*)(orow + (size_t)d * ES) = olo;
-            *(W*)(orow + (size_t)(d + h2) * ES) = ohi;
-#endif
         }
 #pragma unroll
         for (int u = 0; u < HU; ++u) {
@@ -470,19 +445,12 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prepare_native_kernel(const ch
         for (int u = 0; u < 4; ++u) {
             const int h = hb + u;
             if (h >= nkv) break;
-#if RTK_PREP_UBASE
             const uint32_t sot = (uint32_t)uniform_int((int)((uint32_t)h * hs_t));
             buf_store<NW>(lo[u], r_tail, off_o, sot);
             buf_store<NW>(hi[u], r_tail, off_o2, sot);
-#else
-            char* trow = tail + ((size_t)h * tail_sh + (size_t)l * D) * ES;
-            *(W*)(trow + (size_t)d * ES) = lo[u];
-            *(W*)(trow + (size_t)(d + h2) * ES) = hi[u];
-#endif
             if (blockIdx.y == 0) {
                 W olo, ohi;
                 unrot(lo[u], hi[u], olo, ohi);
-#if RTK_PREP_UBASE
                 const uint32_t so = (uint32_t)uniform_int((int)((uint32_t)h * hs_o));
                 buf_store<NW>(olo, r_ko, off_o, so);
                 buf_store<NW>(ohi, r_ko, off_o2, so);
@@ -490,16 +458,6 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prepare_native_kernel(const ch
                     buf_store<NW>(to_f16(olo, 1.f), r_kf, off_o, so);
                     buf_store<NW>(to_f16(ohi, 1.f), r_kf, off_o2, so);
                 }
-#else
-                char* orow = k_out + ((size_t)h * L + l) * D * ES;
-                *(W*)(orow + (size_t)d * ES) = olo;
-                *(W*)(orow + (size_t)(d + h2) * ES) = ohi;
-                if constexpr (FAST) {   // the same k~ as fp16 for the score passes (exact re-encoding)
-                    char* frow = k_fast + ((size_t)h * L + l) * D * ES;
-                    *(W*)(frow + (size_t)d * ES) = to_f16(olo, 1.f);
-                    *(W*)(frow + (size_t)(d + h2) * ES) = to_f16(ohi, 1.f);
-                }
-#endif
             }
         }
 #pragma unroll
@@ -744,7 +702,8 @@ struct RowStat {  // online max / sum of one query row, over the keys this lane 
 //       per SIMD), lazy max in pass 1, the next tile's DMA pieces issued inside block 0's softmax, all fragment reads of
 //       a block ahead of its MFMAs which alternate strictly between the two accumulators, a last tile that is at most
 //       half full on the one-block body, pass 2's normalisers by LDS-DMA from wave 0.
-// The only compile-time knobs left are the ones variants.h lists (A/B builds; production never defines them).
+constexpr int P1_NB = 2;   // bf16 LDS-DMA kernels: 32-row register blocks per wave, pass 1
+constexpr int P2_NB = 2;   // bf16 LDS-DMA kernels: 32-key register blocks per wave, pass 2
 template <int DT> struct RegBlocks {
     static constexpr int NB = 1;
     static constexpr int PF = 1;
@@ -1822,7 +1781,6 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void score_pass1_fixup_kernel(   // (2
     const char* __restrict__ q, const char* __restrict__ k, int Hq, int Hkv, int L, int keys_per_split, int row_tiles,
     int n_tiles, float* __restrict__ lse_part, size_t q_unit_bytes, size_t k_unit_bytes, size_t lse_unit_floats,
     int neg_out, QView qv) {
-    if (RTK_FIXUP_PROBE == 1) return;
     const int q_hs = qv.row_pitch ? qv.head_stride : L * HD * 2, q_pitch = qv.row_pitch ? qv.row_pitch : HD * 2;
     q = qv.row_pitch ? qv.unit[blockIdx.y] : q + blockIdx.y * q_unit_bytes;
     k += blockIdx.y * k_unit_bytes;
@@ -1834,7 +1792,7 @@ __global__ __launch_bounds__(SC_BLOCK, 2) void score_pass1_fixup_kernel(   // (2
     __syncthreads();
     if (mine) atomicOr(&nan_tiles, mine);
     __syncthreads();
-    unsigned todo = RTK_FIXUP_PROBE >= 2 ? 0u : nan_tiles;           // uniform: the whole workgroup takes the same path
+    unsigned todo = nan_tiles;   // uniform: the whole workgroup takes the same path
     while (todo) {
         const int u = __builtin_ctz(todo);
         todo &= todo - 1;
@@ -2021,7 +1979,7 @@ struct ScoreWs {
     bool h16;   // RTK_F16 / RTK_F16_REFROUND: fp16 payloads (un-rotation rounds to fp16, the passes use the fp16 matrix instruction)
 };
 static ScoreWs score_ws(int Hq, int Hkv, int L, int D, int dtype) {
-    const bool many = !RTK_IGNORE_MANY_UNITS && (dtype & RTK_SCORE_MANY_UNITS) != 0;   // the caller batches many units per launch
+    const bool many = (dtype & RTK_SCORE_MANY_UNITS) != 0;   // the caller batches many units per launch
     dtype &= ~RTK_SCORE_MANY_UNITS;
     const size_t es = dtype == RTK_F32 ? 4 : 2;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -2049,8 +2007,6 @@ static ScoreWs score_ws(int Hq, int Hkv, int L, int D, int dtype) {
             if ((Hkv * eff) % NXCD == 0) { w.RS = t; break; }
         }
     }
-    if (RTK_FORCE_KS > 0 && D == HD && dtype != RTK_F32) w.KS = RTK_FORCE_KS;   // A/B builds only (variants.h)
-    if (RTK_FORCE_RS > 0 && D == HD && dtype != RTK_F32) w.RS = RTK_FORCE_RS;
     w.q_off = 0;
     w.k_off = al((size_t)Hq * L * D * es);
     w.lse_off = w.k_off + al((size_t)Hkv * L * D * es);
@@ -2216,8 +2172,8 @@ static int score_impl(const void* q, int64_t qsh, int64_t qsl, const void* k, in
         const uint64_t dev_bit = 1ull << (dev_id & 63);
         if (!(opted[DT == RTK_BF16].load(std::memory_order_relaxed) & dev_bit)) {
             if constexpr (DT == RTK_BF16) {
-                (void)hipFuncSetAttribute((const void*)score_pass1_dma_kernel<RTK_P1_NB, RTK_P1_LAZY>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
-                (void)hipFuncSetAttribute((const void*)score_pass2_dma_kernel<RTK_P2_NB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
+                (void)hipFuncSetAttribute((const void*)score_pass1_dma_kernel<P1_NB, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
+                (void)hipFuncSetAttribute((const void*)score_pass2_dma_kernel<P2_NB>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
             } else {
                 (void)hipFuncSetAttribute((const void*)score_pass1_kernel<DT, NBR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS1);
                 (void)hipFuncSetAttribute((const void*)score_pass2_kernel<DT, NBR>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS2);
@@ -2234,24 +2190,23 @@ static int score_impl(const void* q, int64_t qsh, int64_t qsl, const void* k, in
         constexpr bool dma = (DT == RTK_BF16);
         if (stages & RTK_SCORE_PASSES) {
             if constexpr (dma) {
-                const int jt1 = (L + REG_ROWS * RTK_P1_NB - 1) / (REG_ROWS * RTK_P1_NB);
+                const int jt1 = (L + REG_ROWS * P1_NB - 1) / (REG_ROWS * P1_NB);
                 // raw row sums + a fix-up launch (1/16 of the grid) for the rows whose sum left fp32's range; the
                 // fast mode's pass 2 starts its accumulators from -lse, so whoever writes the final lse negates it
                 const int n_tiles = Hkv * ks_n * jt1 * G;
                 const dim3 g1(n_tiles, n_units), gf((n_tiles + FIX_TILES - 1) / FIX_TILES, n_units);
                 const int x1 = (int)((Hkv * ks_n) % NXCD == 0), neg = (int)(w.fast && ks_n == 1);
 #define RTK_P1(MODEV)                                                                                                  \
-    RTK_LAUNCH(KID_PASS1, (score_pass1_dma_kernel<RTK_P1_NB, RTK_P1_LAZY, MODEV>), g1, dim3(SC_BLOCK), LDS1, st,           \
+    RTK_LAUNCH(KID_PASS1, (score_pass1_dma_kernel<P1_NB, true, MODEV>), g1, dim3(SC_BLOCK), LDS1, st,                   \
                (const char*)qt, (const char*)kt, Hq, Hkv, L, kps, jt1, x1, lse, ws_stride, k_stride,                     \
                ws_stride / sizeof(float), neg, qv);                                                                     \
     if ((MODEV) & P1_RAW)                                                                                               \
-        RTK_LAUNCH(KID_FINALIZE, (score_pass1_fixup_kernel<RTK_P1_NB, (MODEV) & ~P1_RAW>), gf, dim3(SC_BLOCK), (RTK_FIXUP_PROBE == 3 ? 0 : LDS1), st,   \
+        RTK_LAUNCH(KID_FINALIZE, (score_pass1_fixup_kernel<P1_NB, (MODEV) & ~P1_RAW>), gf, dim3(SC_BLOCK), LDS1, st,    \
                    (const char*)qt, (const char*)kt, Hq, Hkv, L, kps, jt1, n_tiles, lse, ws_stride, k_stride,            \
                    ws_stride / sizeof(float), neg, qv)
-                constexpr int RAWF = RTK_P1_RAW ? P1_RAW : 0;
                 if (w.fast) { RTK_P1(P1_F16 | P1_SCALED | P1_RAW); }
-                else if (w.h16) { RTK_P1(P1_F16 | RAWF); }
-                else { RTK_P1(RAWF); }
+                else if (w.h16) { RTK_P1(P1_F16 | P1_RAW); }
+                else { RTK_P1(P1_RAW); }
 #undef RTK_P1
             }
             else
@@ -2264,19 +2219,19 @@ static int score_impl(const void* q, int64_t qsh, int64_t qsl, const void* k, in
                            ks_n, ws_stride / sizeof(float), (int)w.fast);
             }
             if constexpr (dma) {
-                const int jt2 = (L + REG_ROWS * RTK_P2_NB - 1) / (REG_ROWS * RTK_P2_NB);
+                const int jt2 = (L + REG_ROWS * P2_NB - 1) / (REG_ROWS * P2_NB);
                 if (w.fast)
-                    RTK_LAUNCH(KID_PASS2, (score_pass2_dma_kernel<RTK_P2_NB, true>), dim3(Hkv * rs_n * jt2, n_units), dim3(SC_BLOCK), LDS2, st,
+                    RTK_LAUNCH(KID_PASS2, (score_pass2_dma_kernel<P2_NB, true>), dim3(Hkv * rs_n * jt2, n_units), dim3(SC_BLOCK), LDS2, st,
                                (const char*)qt, (const char*)kt, (const float*)lse, Hq, Hkv, L, rps, jt2, rs_n,
                                (int)((Hkv * rs_n) % NXCD == 0), part, ws_stride, k_stride, ws_stride / sizeof(float),
                                part_stride, key_index, qv);
                 else if (w.h16)
-                    RTK_LAUNCH(KID_PASS2, (score_pass2_dma_kernel<RTK_P2_NB, false, true>), dim3(Hkv * rs_n * jt2, n_units), dim3(SC_BLOCK), LDS2, st,
+                    RTK_LAUNCH(KID_PASS2, (score_pass2_dma_kernel<P2_NB, false, true>), dim3(Hkv * rs_n * jt2, n_units), dim3(SC_BLOCK), LDS2, st,
                                (const char*)qt, (const char*)kt, (const float*)lse, Hq, Hkv, L, rps, jt2, rs_n,
                                (int)((Hkv * rs_n) % NXCD == 0), part, ws_stride, k_stride, ws_stride / sizeof(float),
                                part_stride, key_index, qv);
                 else
-                RTK_LAUNCH(KID_PASS2, (score_pass2_dma_kernel<RTK_P2_NB>), dim3(Hkv * rs_n * jt2, n_units), dim3(SC_BLOCK), LDS2, st,
+                RTK_LAUNCH(KID_PASS2, (score_pass2_dma_kernel<P2_NB>), dim3(Hkv * rs_n * jt2, n_units), dim3(SC_BLOCK), LDS2, st,
                            (const char*)qt, (const char*)kt, (const float*)lse, Hq, Hkv, L, rps, jt2, rs_n,
                            (int)((Hkv * rs_n) % NXCD == 0), part, ws_stride, k_stride, ws_stride / sizeof(float),
                            part_stride, key_index, qv);
@@ -2512,16 +2467,16 @@ static int prepare_impl(const void* q, int64_t qsh, int64_t qsl, const void* k, 
     // 16-bit dtypes: 4-byte chunks per thread - four times the waves of the 16-byte form, a quarter of the instruction
     // stream each (same-box A/B, profiles/r11_ab_prepare_chunk_width.txt: 20.0 -> 16.1 us at L = 2304, 29.6 -> 28.4 at 6272)
     int nw = 4;
-    if constexpr (DT != RTK_F32) nw = RTK_PREP_NW;
+    if constexpr (DT != RTK_F32) nw = PREP_NW;
     const int VE = nw * 4 / (DT == RTK_F32 ? 4 : 2);
     const int threads = L * (D / 2 / VE);
-    static_assert(RTK_PREP_YSPLIT >= 2, "the first y-slice takes k and the LAST one v: one slice would never append v");
+    static_assert(PREP_YSPLIT >= 2, "the first y-slice takes k and the LAST one v: one slice would never append v");
     // (+ one column of workgroups when the next layer's id shift rides along: its last one does the shift)
-    const dim3 grid((threads + RTK_PREP_BLOCK - 1) / RTK_PREP_BLOCK + (shift_row ? 1 : 0), RTK_PREP_YSPLIT);
+    const dim3 grid((threads + PREP_BLOCK - 1) / PREP_BLOCK + (shift_row ? 1 : 0), PREP_YSPLIT);
     char* kf = nullptr;
     float qscale = 1.f;
     auto launch = [&](auto kern) {
-        RTK_LAUNCH(KID_UNROT, kern, grid, dim3(RTK_PREP_BLOCK), 0, st, (const char*)q, qsh, qsl, (const char*)k, ksh, ksl, (const char*)v,
+        RTK_LAUNCH(KID_UNROT, kern, grid, dim3(PREP_BLOCK), 0, st, (const char*)q, qsh, qsl, (const char*)k, ksh, ksl, (const char*)v,
                    vsh, vsl, Hq, Hkv, L, D, pos, pos_stride, inv_freq, a, rs, round_bf16, a2, rcp, qt, kt, (char*)k_tail,
                    (char*)v_tail, tail_sh, P, pos_copy, kf, qscale, shift_row, next_prev, ticket, status);
     };

@@ -11,7 +11,6 @@
 #include <vector>
 
 #include "common.cuh"
-#include "variants.h"
 
 namespace rtk {
 
@@ -42,7 +41,7 @@ __device__ __forceinline__ uint32_t upd_pack2_f16(float lo, float hi) {   // sat
 // before batch b is rotated and stored, and the first batch before the table arithmetic.
 // ------------------------------------------------------------------------------------------------
 template <int DT, bool FAST, int NW, bool RT = false>
-__global__ __launch_bounds__(RTK_PREP_BLOCK) void prologue_kernel(const char* q, int64_t q_sh, int64_t q_sl,
+__global__ __launch_bounds__(PREP_BLOCK) void prologue_kernel(const char* q, int64_t q_sh, int64_t q_sl,
                                                       const char* __restrict__ k, int64_t k_sh, int64_t k_sl,
                                                       const char* __restrict__ v, int64_t v_sh, int64_t v_sl,
                                                       int Hq, int Hkv, int L, int D,
@@ -89,13 +88,9 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prologue_kernel(const char* q,
     // same id) and a single aligned 8-byte atomic store cannot be seen torn, so no workgroup order is needed
     if (shift_back && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
         __hip_atomic_store(shift_back, (int64_t)ids[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    constexpr int HU = RTK_PREP_HU;
+    constexpr int HU = PREP_HU;
     const int ny = gridDim.y, qper = (Hq + ny - 1) / ny;
-#if RTK_PREP_UBASE
     const int qb = uniform_int(min((int)blockIdx.y * qper, Hq)), qe = uniform_int(min(qb + qper, Hq));   // (head loops in SGPRs)
-#else
-    const int qb = min((int)blockIdx.y * qper, Hq), qe = min(qb + qper, Hq);
-#endif
     const bool is_k = blockIdx.y == 0;
     const bool has_kv = is_k || (int)blockIdx.y == ny - 1;
     const char* src = is_k ? k : v;
@@ -103,7 +98,6 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prologue_kernel(const char* q,
     char* tail = is_k ? k_tail : v_tail;
     const int nkv = has_kv ? Hkv : 0;
     W lo[HU], hi[HU], lon[HU], hin[HU];
-#if RTK_PREP_UBASE
     // a row's address = descriptor (tensor base) + soffset (the head: wave-uniform, a scalar multiply) + voffset (this
     // thread's byte offset inside a head, computed once); the launcher has checked that every extent fits 31 bits
     const uint32_t off_q = (uint32_t)(((int64_t)l * q_sl + d) * ES), off_kv = (uint32_t)(((int64_t)l * sl + d) * ES);
@@ -115,33 +109,20 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prologue_kernel(const char* q,
     const uint32_t hs_q = (uint32_t)(q_sh * ES), hs_kv = (uint32_t)(sh * ES), hs_o = (uint32_t)((int64_t)L * D * ES),
                    hs_t = (uint32_t)(tail_sh * ES), hs_qr = (uint32_t)(qr_sh * ES);
     auto soff = [](int h, uint32_t hs) { return (uint32_t)uniform_int((int)((uint32_t)h * hs)); };
-#endif
     auto load_q = [&](W* a, W* b, int hb) {
 #pragma unroll
         for (int u = 0; u < HU; ++u) {
             const int h = min(hb + u, qe - 1);
-#if RTK_PREP_UBASE
             a[u] = buf_load<NW>(r_q, off_q, soff(h, hs_q));
             b[u] = buf_load<NW>(r_q, off_q2, soff(h, hs_q));
-#else
-            const char* row = q + ((size_t)h * q_sh + (size_t)l * q_sl) * ES;
-            a[u] = *(const W*)(row + (size_t)d * ES);
-            b[u] = *(const W*)(row + (size_t)(d + h2) * ES);
-#endif
         }
     };
     auto load_kv = [&](W* a, W* b, int hb) {
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const int h = min(hb + u, Hkv - 1);
-#if RTK_PREP_UBASE
             a[u] = buf_load<NW>(r_src, off_kv, soff(h, hs_kv));
             b[u] = buf_load<NW>(r_src, off_kv2, soff(h, hs_kv));
-#else
-            const char* row = src + ((size_t)h * sh + (size_t)l * sl) * ES;
-            a[u] = *(const W*)(row + (size_t)d * ES);
-            b[u] = *(const W*)(row + (size_t)(d + h2) * ES);
-#endif
         }
     };
     float pid[3];
@@ -241,23 +222,11 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prologue_kernel(const char* q,
                     ql = to_f16(ql, qscale);
                     qh = to_f16(qh, qscale);
                 }
-#if RTK_PREP_UBASE
                 buf_store<NW>(ql, r_qo, off_o, soff(h, hs_o));
                 buf_store<NW>(qh, r_qo, off_o2, soff(h, hs_o));
-#else
-                char* orow = q_out + ((size_t)h * L + l) * D * ES;
-                *(W*)(orow + (size_t)d * ES) = ql;
-                *(W*)(orow + (size_t)(d + h2) * ES) = qh;
-#endif
             }
-#if RTK_PREP_UBASE
             buf_store<NW>(olo, r_qr, off_qr, soff(h, hs_qr));
             buf_store<NW>(ohi, r_qr, off_qr2, soff(h, hs_qr));
-#else
-            char* rrow = q_rot + ((size_t)h * qr_sh + (size_t)l * qr_sl) * ES;
-            *(W*)(rrow + (size_t)d * ES) = olo;
-            *(W*)(rrow + (size_t)(d + h2) * ES) = ohi;
-#endif
         }
 #pragma unroll
         for (int u = 0; u < HU; ++u) {
@@ -271,7 +240,6 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prologue_kernel(const char* q,
         for (int u = 0; u < 4; ++u) {
             const int h = hb + u;
             if (h >= nkv) break;
-#if RTK_PREP_UBASE
             const uint32_t so_t = soff(h, hs_t), so_o = soff(h, hs_o);
             if (is_k) {
                 W olo, ohi;
@@ -292,30 +260,6 @@ __global__ __launch_bounds__(RTK_PREP_BLOCK) void prologue_kernel(const char* q,
                 buf_store<NW>(lo[u], r_tail, off_o, so_t);
                 buf_store<NW>(hi[u], r_tail, off_o2, so_t);
             }
-#else
-            char* trow = tail + ((size_t)h * tail_sh + (size_t)l * D) * ES;
-            if (is_k) {
-                W olo, ohi;
-                rot(lo[u], hi[u], olo, ohi);
-                W kl = lo[u], kh = hi[u];
-                if constexpr (RT) unrot(olo, ohi, kl, kh);
-                if (k_out) {   // k~ := k0 / (RT) un-rotated tail row (a plain append - text segments, decode - scores nothing: no k~)
-                    char* orow = k_out + ((size_t)h * L + l) * D * ES;
-                    *(W*)(orow + (size_t)d * ES) = kl;
-                    *(W*)(orow + (size_t)(d + h2) * ES) = kh;
-                }
-                if constexpr (FAST) {
-                    char* frow = k_fast + ((size_t)h * L + l) * D * ES;
-                    *(W*)(frow + (size_t)d * ES) = to_f16(kl, 1.f);
-                    *(W*)(frow + (size_t)(d + h2) * ES) = to_f16(kh, 1.f);
-                }
-                *(W*)(trow + (size_t)d * ES) = olo;
-                *(W*)(trow + (size_t)(d + h2) * ES) = ohi;
-            } else {
-                *(W*)(trow + (size_t)d * ES) = lo[u];
-                *(W*)(trow + (size_t)(d + h2) * ES) = hi[u];
-            }
-#endif
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -342,13 +286,13 @@ static int prologue_launch(const PrologueGeom& g, const rtk_update_io* io, const
     const int div = !roundtrip || a2 == 1.0f ? 0 : ((DT == RTK_BF16 && bf16_rcp_is_exact(a2)) ? 1 : 2);
     const float rcp_a2 = 1.0f / a2;
     int nw = 4;
-    if constexpr (DT != RTK_F32) nw = RTK_PREP_NW;
+    if constexpr (DT != RTK_F32) nw = PREP_NW;
     const int VE = nw * 4 / (DT == RTK_F32 ? 4 : 2);
     const int threads = g.L * (g.D / 2 / VE);
-    const dim3 grid((threads + RTK_PREP_BLOCK - 1) / RTK_PREP_BLOCK, RTK_PREP_YSPLIT);
+    const dim3 grid((threads + PREP_BLOCK - 1) / PREP_BLOCK, PREP_YSPLIT);
     const float qscale = k_fast ? 1.4426950408889634f / sqrtf((float)g.D) : 1.f;
     auto launch = [&](auto kern) {
-        RTK_LAUNCH(KID_PROLOGUE, kern, grid, dim3(RTK_PREP_BLOCK), 0, st, (const char*)io->q, io->q_stride_h, io->q_stride_l,
+        RTK_LAUNCH(KID_PROLOGUE, kern, grid, dim3(PREP_BLOCK), 0, st, (const char*)io->q, io->q_stride_h, io->q_stride_l,
                    (const char*)io->k, io->k_stride_h, io->k_stride_l, (const char*)io->v, io->v_stride_h, io->v_stride_l,
                    g.Hq, g.Hkv, g.L, g.D, io->pos, io->pos_stride, prev, g.inv_freq, g.scaling, rs, g.round_mode,
                    (char*)io->q_rot, io->qr_stride_h, io->qr_stride_l, q_out, k_out, k_tail, v_tail, tail_sh, g.P, pos_copy,

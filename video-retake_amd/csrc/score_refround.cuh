@@ -182,8 +182,8 @@ __device__ __forceinline__ void score_pass1_ref_body(const char* __restrict__ q,
     }
 }
 
-constexpr int REF_NB = RTK_REF_P1_NB;    // 32-row register blocks per wave, pass 1 of the reference-rounding kernels
-constexpr int REF_NB2 = RTK_REF_P2_NB;   // 32-key register blocks per wave, pass 2
+constexpr int REF_NB = 2;    // 32-row register blocks per wave, pass 1 of the reference-rounding kernels (2: 3 waves per SIMD)
+constexpr int REF_NB2 = 1;   // 32-key register blocks per wave, pass 2
 
 // blockIdx.x -> (row tile bx, head h, key split ks), blockIdx.y = unit of a batched launch
 template <int DIV, bool F16>

@@ -32,8 +32,6 @@ every rank's assembled cache, so `finalize` has nothing left to copy.
 from __future__ import annotations
 
 import ctypes as C
-import json
-import math
 import os
 import sys
 import time
@@ -726,7 +724,6 @@ def sharded_video_step(frames, has_halo: bool, T: int, c0: int, c1: int, layers:
 
     L = B.FRAMES_PER_CHUNK * B.N_PATCH
     phases = (state or {}).get("phases")     # a PhaseTimer the caller wants filled (bench.py --gpus N)
-    watch = (state or {}).get("watch")       # debugging aid: called with a label after every chunk / the assembly
     if phases is not None:
         phases.begin()
     out, mask, idx, dis = dpselect_sharded(frames, has_halo, T, 3, sync=False, group=group)
@@ -755,12 +752,8 @@ def sharded_video_step(frames, has_halo: bool, T: int, c0: int, c1: int, layers:
         cache.after_forward()
         if overlap:
             sh.gather_chunk()   # this chunk's kept rows leave now, beside the next chunk's scoring
-        if watch is not None:
-            watch(f"after chunk {c} of the block (its push started: {overlap})")
     _mark(phases, "blocks")
     keys, values, pos = sh.finalize(rotary.inv_freq, B.MROPE, assemble=True, phases=phases)
-    if watch is not None:
-        watch("after finalize")
     if state is not None:
         state["chunk_gather"] = sh.chunk_gather
     return (c1 - c0) * layers * keep, (keys, values, pos)
@@ -778,83 +771,6 @@ def _rotate_at(x0: torch.Tensor, pos: torch.Tensor, rotary, mrope_section):
         cos, sin = cos.unsqueeze(1), sin.unsqueeze(1)
     D = x0.shape[-1]
     return x0 * cos + torch.cat((-x0[..., D // 2:], x0[..., : D // 2]), dim=-1) * sin
-
-
-class _PoolWatch:
-    """RETAKE_VERIFY_POOL_WATCH=1 (debugging aid of the multi-rank check): did a LIVE input tensor of this process change,
-    when, where and into what?  One int64 fingerprint (sum of the bit patterns) per resident tensor at construction;
-    every call recomputes them and, on the first difference, regenerates that tensor from its seed, reports the damaged
-    256-byte rows (count, runs, first values), the tensor's address beside the ranges this process has MAPPED from its
-    peers, whether the guard regions of its own landing buffers are intact (RETAKE_P2P_GUARD=1) - and raises."""
-
-    def __init__(self, rank, world, pool, frames_all, mask, layers, n_chunks, dname, dev, td, group):
-        self.rank, self.world, self.pool, self.layers, self.dname, self.dev, self.td, self.group = rank, world, pool, layers, dname, dev, td, group
-        self.n_chunks = n_chunks
-        self.extra = [("frames", frames_all), ("mask", mask.view(torch.uint8))]
-        self.calls = 0
-        self.ref = self._sums()
-
-    @staticmethod
-    def _bits(t):
-        t = t.contiguous() if t.is_contiguous() else t.transpose(1, 2).contiguous()
-        v = t.view(torch.int16) if t.element_size() == 2 else (t.view(torch.int32) if t.element_size() == 4 else t.view(torch.uint8))
-        return v.sum(dtype=torch.int64)
-
-    def _sums(self):
-        s = [self._bits(t) for trip in self.pool for t in trip] + [self._bits(t) for _, t in self.extra]
-        return torch.stack(s).cpu()
-
-    def __call__(self, label):
-        self.calls += 1
-        now = self._sums()
-        bad = (now != self.ref).nonzero().flatten().tolist()
-        p2p = _P2P.get(self.group)
-        guards = p2p.guards_intact() if p2p is not None else None
-        if not bad and guards in (None, True):
-            return
-        import bench as B
-
-        torch.cuda.synchronize(self.dev)
-        again = self._sums()                 # the same fingerprints, computed once more
-        still = (again != self.ref).nonzero().flatten().tolist()
-        lines = [f"POOLWATCH rank {self.rank} ({self.dname}, {self.n_chunks} chunks): fingerprints of {len(bad)} resident tensor(s) "
-                 f"differ, first seen {label} (look {self.calls}); recomputed at once: {len(still)} differ; guard regions intact: {guards}"]
-        persistent = False
-        for i in bad[:3]:
-            if i >= 3 * len(self.pool):
-                lines.append(f"  {self.extra[i - 3 * len(self.pool)][0]}: fingerprint differed")
-                continue
-            si, j = divmod(i, 3)
-            t = self.pool[si][j]
-            fresh = B.pool_set(si, self.dev, self.td, projection_layout=True)[j]
-            mem = t.transpose(1, 2).contiguous().view(-1)         # the projection layout's memory order [L, H, D]
-            ref = fresh.transpose(1, 2).contiguous().view(-1)
-            D = t.shape[-1]
-            rows = (mem.view(-1, D) != ref.view(-1, D)).any(dim=1).nonzero().flatten()
-            if rows.numel() == 0:
-                # the tensor IS what its seed says: it was the READ that went wrong (the reduction that fingerprinted it saw
-                # other bytes, or lost its scratch), not the tensor
-                lines.append(f"  pool set {si} (chunk {si // self.layers}, layer {si % self.layers}) {'qkv'[j]}: fingerprint was "
-                             f"{int(now[i])}, is {int(again[i])} on recomputation, reference {int(self.ref[i])}; the tensor EQUALS its "
-                             f"regeneration element by element -> a transient wrong READ, nothing was written")
-                continue
-            persistent = True
-            r0, r1, n = int(rows[0]), int(rows[-1]), int(rows.numel())
-            runs = int((rows[1:] - rows[:-1] != 1).sum().item()) + 1
-            row_b = D * t.element_size()
-            lines.append(f"  pool set {si} (chunk {si // self.layers}, layer {si % self.layers}) {'qkv'[j]}: {n} of {mem.numel() // D} rows of "
-                         f"{row_b} B differ, rows {r0}..{r1} in {runs} run(s); tensor at {t.data_ptr():#x} (+{r0 * row_b:#x}), "
-                         f"{t.numel() * t.element_size()} B; first damaged row now {mem.view(-1, D)[r0, :6].float().tolist()} "
-                         f"was {ref.view(-1, D)[r0, :6].float().tolist()}; all-zero damaged rows "
-                         f"{int((mem.view(-1, D)[rows] == 0).all(dim=1).sum())}")
-        if p2p is not None:
-            rng = p2p.mapped_ranges()
-            lines.append("  ranges mapped from peers (buffer, peer, address, bytes): "
-                         + ", ".join(f"({b},{r},{a:#x},{nb})" for b, r, a, nb, _ in rng if r != self.rank)[:1500])
-        print("\n".join(lines), flush=True)
-        if persistent or still or guards is False:
-            raise AssertionError(lines[0])
-        self.transients = getattr(self, "transients", 0) + 1
 
 
 def verify_sharded_equals_sequential(rank: int, world: int, dev, rotary, layers: int = 2, chunk_counts=None,
@@ -893,39 +809,18 @@ def verify_sharded_equals_sequential(rank: int, world: int, dev, rotary, layers:
 
         frames_all = torch.cat([B.chunk_frames(c, dev, td) for c in range(n_chunks)])[None]
         _, mask = vc.memory_bank_compress_keyframe(frames_all, T, 3, sync=False)
-        def sequential():
-            q_rot = torch.empty_like(pool[0][0])   # where the rotated queries go (one scratch per build)
-            seq = lc.build_kvcache(B.make_cache_config(layers))
-            seq.prologue_operands = "pre_rope"    # what the blocks score (ShardedPivotKV): operands that never see an id
-            for c in range(n_chunks):
-                seq.keypatches_mask_chunk = mask[c * L:(c + 1) * L]
-                seq.kvcache_compression = True
-                pos = B.chunk_position_ids(c, dev)
-                for l in range(layers):
-                    q0, k0, v = inputs(c, l, pos)
-                    if seq.update_pre_rope(q0, k0, v, l, pos, rotary, B.MROPE, query_out=q_rot) is None:
-                        raise AssertionError("update_pre_rope declined a chunk of the sequential reference run")
-                seq.after_forward()
-            return seq
-
-        if os.environ.get("RETAKE_VERIFY_POOL_WATCH") == "1":
-            # debugging aid (profiles/r15_p2p_hunt.log): fingerprints of every resident input tensor of this rank, taken now
-            # and looked at again after every push epoch - the first label at which one differs, which tensor, where in it
-            # and what was written there
-            state["watch"] = _PoolWatch(rank, world, pool, frames_all, mask, layers, n_chunks, dname, dev, td, group)
-        seq = sequential()
-        if state.get("watch") is not None:
-            state["watch"]("after the sequential build")
-        if os.environ.get("RETAKE_VERIFY_SEQ_TWICE") == "1":   # debugging aid: is the single-GPU build itself reproducible here?
-            again = sequential()
+        q_rot = torch.empty_like(pool[0][0])   # where the rotated queries go (one scratch per build)
+        seq = lc.build_kvcache(B.make_cache_config(layers))
+        seq.prologue_operands = "pre_rope"    # what the blocks score (ShardedPivotKV): operands that never see an id
+        for c in range(n_chunks):
+            seq.keypatches_mask_chunk = mask[c * L:(c + 1) * L]
+            seq.kvcache_compression = True
+            pos = B.chunk_position_ids(c, dev)
             for l in range(layers):
-                for what, a, b in (("ids", seq.position_cache[l], again.position_cache[l]),
-                                   ("V", seq.value_cache[l], again.value_cache[l]), ("K", seq.key_cache[l], again.key_cache[l])):
-                    if not torch.equal(a, b):
-                        d = (a != b).reshape(-1, a.shape[-1]) if what == "ids" else (a != b).any(dim=3).any(dim=1)
-                        raise AssertionError(f"rank {rank} layer {l} {dname}: two SEQUENTIAL builds of the same video differ in {what}; "
-                                             f"differing entries per kept chunk {d.any(0).reshape(-1, keep).sum(1).tolist()}")
-            del again
+                q0, k0, v = inputs(c, l, pos)
+                if seq.update_pre_rope(q0, k0, v, l, pos, rotary, B.MROPE, query_out=q_rot) is None:
+                    raise AssertionError("update_pre_rope declined a chunk of the sequential reference run")
+            seq.after_forward()
         blocks = shard_chunks(n_chunks, world)
         c0, c1 = blocks[rank]
         even = len({b - a for a, b in blocks}) == 1
@@ -935,52 +830,17 @@ def verify_sharded_equals_sequential(rank: int, world: int, dev, rotary, layers:
         pos_base = [B.chunk_position_ids(c, dev) for c in range(c0, c1)]
         _, (keys, values, pos) = sharded_video_step(fr, halo, T, c0, c1, layers, pool, pos_base, rotary, even, group=group,
                                                     state=state, inputs=inputs, pre_rope=True)
-        state.pop("watch", None)
         if _P2P.get(group) is not None:
             _P2P.get(group).check()   # a bounded wait that ran out is reported as that, not as the mismatch it leaves behind
         for l in range(layers):
             assert keys[l].shape[2] == n_chunks * keep, (keys[l].shape, n_chunks * keep)
             if not torch.equal(pos[l], seq.position_cache[l]):
                 bad = (pos[l] != seq.position_cache[l]).reshape(-1, pos[l].shape[-1]).any(0).reshape(-1, keep).sum(1)
-                if os.environ.get("RETAKE_VERIFY_LOOK_AGAIN") == "1":   # debugging aid: late, or never?  ids only, or the rows too?
-                    torch.cuda.synchronize(dev)
-                    time.sleep(2.0)
-                    torch.cuda.synchronize(dev)
-                    again = (pos[l] != seq.position_cache[l]).reshape(-1, pos[l].shape[-1]).any(0).reshape(-1, keep).sum(1)
-                    vrows = (values[l] != seq.value_cache[l]).any(dim=3).any(dim=1)[0].reshape(-1, keep).sum(1)
-                    c = int(bad.nonzero()[0])
-
-                    def bits(t):
-                        return int(t.contiguous().view(torch.int16 if t.element_size() == 2 else torch.int32).to(torch.int64).sum())
-
-                    fresh = B.pool_set((c * layers + l) % len(pool), dev, td, projection_layout=True)
-                    sums = {"q k v as used": [bits(t) for t in inputs(c, l, None)], "q k v regenerated": [bits(t) for t in fresh],
-                            "frames as used": bits(frames_all[0, c * B.FRAMES_PER_CHUNK:(c + 1) * B.FRAMES_PER_CHUNK]),
-                            "frames regenerated": bits(B.chunk_frames(c, dev, td)), "mask": int(mask[c * L:(c + 1) * L].sum())}
-                    print(f"LOOK rank {rank} chunk {c} layer {l}: {sums}", flush=True)
-                    got = pos[l].reshape(-1, pos[l].shape[-1])[:, c * keep:(c + 1) * keep]
-                    want = seq.position_cache[l].reshape(-1, pos[l].shape[-1])[:, c * keep:(c + 1) * keep]
-                    raise AssertionError(f"rank {rank} layer {l} {dname}: ids differ; wrong ids per kept chunk "
-                                         f"{[(i, int(x)) for i, x in enumerate(bad.tolist()) if x]}; two seconds later "
-                                         f"{[(i, int(x)) for i, x in enumerate(again.tolist()) if x]}; V rows wrong "
-                                         f"{[(i, int(x)) for i, x in enumerate(vrows.tolist()) if x]}; chunk {c}: got "
-                                         f"{got[:, :6].tolist()} .. {got[:, -3:].tolist()} want {want[:, :6].tolist()} .. {want[:, -3:].tolist()}")
                 raise AssertionError(f"rank {rank} layer {l} {dname}: ids differ; wrong ids per kept chunk {bad.tolist()}; first "
                                      f"rows {pos[l].reshape(-1, pos[l].shape[-1])[0, ::keep].tolist()} vs "
                                      f"{seq.position_cache[l].reshape(-1, pos[l].shape[-1])[0, ::keep].tolist()}")
             if not torch.equal(values[l], seq.value_cache[l]):   # say where: differing rows per kept chunk of the assembled rows
                 rows = (values[l] != seq.value_cache[l]).any(dim=3).any(dim=1)[0].reshape(-1, keep).sum(1)
-                if os.environ.get("RETAKE_VERIFY_LOOK_AGAIN") == "1":   # debugging aid: late, or never?
-                    bad = (values[l] != seq.value_cache[l]).any(dim=3).any(dim=1)[0].nonzero().flatten()
-                    torch.cuda.synchronize(dev)
-                    time.sleep(2.0)
-                    torch.cuda.synchronize(dev)
-                    again = (values[l] != seq.value_cache[l]).any(dim=3).any(dim=1)[0].reshape(-1, keep).sum(1)
-                    elems = (values[l] != seq.value_cache[l])[0, :, bad[0]].sum(-1).tolist()
-                    raise AssertionError(f"rank {rank} layer {l} {dname}: V differs; wrong rows per kept chunk "
-                                         f"{[(i, int(x)) for i, x in enumerate(rows.tolist()) if x]}; two seconds later "
-                                         f"{[(i, int(x)) for i, x in enumerate(again.tolist()) if x]}; first wrong rows "
-                                         f"{bad[:12].tolist()} (+{int(bad.numel())}), wrong elements per head in the first {elems}")
                 raise AssertionError(f"rank {rank} layer {l} {dname}: V differs; wrong rows per kept chunk {rows.tolist()}; "
                                      f"NaN entries {int(torch.isnan(values[l].float()).sum())}, all-zero rows "
                                      f"{int((values[l] == 0).all(dim=3).all(dim=1).sum())}")

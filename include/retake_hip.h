@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (56 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (58 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -39,7 +39,9 @@
  *                                       rtk_position_shift (+ rtk_pivotkv_shift_ticket_ints): what the shipped
  *                                       package calls per update / per chunk / per decode step
  *   §H  "Direct peer-to-peer all-gather over xGMI"  rtk_p2p_alloc / _free / _export / _open / _close / _push / _wait
- *   §I  "Measurement support"           rtk_profile_* (off by default)
+ *   §I  "Chunk attention"               rtk_attention_forward (+ rtk_attention_workspace_bytes): the chunk's queries over
+ *                                       [compressed prefix | current chunk], opt-in (attention_kernel="hip")
+ *   §J  "Measurement support"           rtk_profile_* (off by default)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -707,6 +709,42 @@ int rtk_p2p_push(const void* src, size_t seg_bytes, int nseg, size_t src_stride_
                  rtk_stream_t stream);
 int rtk_p2p_wait(const uint32_t* own_flags, int world, uint32_t epoch, int timeout_ms, uint32_t* status,
                  rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Chunk attention: the attention of a chunk's queries over [compressed prefix | current chunk], which the reference's
+ * attention patches hand to torch / flash_attn after the cache update (qwen2_vl.py:88-117 eager: repeat_kv, matmul, mask
+ * add, fp32 softmax, matmul, transpose + contiguous; :188-219 SDPA: repeat_kv, contiguous, scaled_dot_product_attention
+ * with the 4-D mask; :303-358 FlashAttention-2: _flash_attention_forward; llava_onevision.py:118-139).
+ *
+ *   out[i, h, :] = softmax_j( q[h, i, :] . k[h / (Hq/Hkv), j, :] * scale ) . v[h / (Hq/Hkv), j, :]   over j <= q_offset + i, j < Lk
+ *
+ * Batch 1, forward only, causal by index, no mask operand, no dropout, no sliding window, no returned weights.
+ * q_offset = Lk - Lq is bottom-right causal: the queries are the LAST Lq rows of the Lk keys (what flash-attn computes for
+ * an unpadded sequence).  A larger q_offset restates the reference's 4-D additive mask, which HF builds over the
+ * UNCOMPRESSED positions [1, 1, Lq, T] and the patches slice to the Lk <= T keys the compressed cache holds
+ * (qwen2_vl.py:96-97, :196-198): row i then sees j <= (T - Lq) + i, i.e. q_offset = T - Lq.  Only the mask's width enters.
+ * Softmax statistics and accumulation are fp32; out has the tensor dtype.
+ *   q    [Hq, Lq, D] by pointer + element strides (q_stride_h, q_stride_l), D contiguous - a transposed view of the
+ *        projection's [1, Lq, Hq*D] output or the prologue's packed buffer, read where it is;
+ *   k, v [Hkv, Lk, D] with common strides (kv_stride_h, kv_stride_l) - the [:Lk] view of a layer's cache buffer as
+ *        PivotKVCache.update returns it (head stride = capacity * D).  Query head h reads kv head h / (Hq/Hkv): no
+ *        repeat_kv copy is made or expected;
+ *   out  [Lq, Hq, D] contiguous - what o_proj consumes after a reshape.
+ * dtype RTK_BF16 / RTK_F16 with D == 128: the flash-style MFMA kernel.  RTK_F32, or any D that is a multiple of 8 up to
+ * 256: the general kernel (fp32 FMA; no performance claim).  When there are too few query rows to fill the chip the keys
+ * are split over workgroups and the partial (max, sum, acc) triples are folded in split order by a second launch - no
+ * atomics; the split is a function of (Hq, Lq, Lk, D, dtype) alone, so results are bit-reproducible.  The partials
+ * live in `workspace`: rtk_attention_workspace_bytes() bytes (0 when the shape is not split; 0 as well, with the message
+ * set, for arguments rtk_attention_forward would reject), 16-byte aligned.
+ * Errors, all before any launch: RTK_EINVAL for NULL pointers, Hq % Hkv != 0, Lk < Lq, q_offset < Lk - Lq, non-positive sizes
+ * or scale;
+ * RTK_EUNSUPPORTED for another dtype code, a D that is not a multiple of 8 in [8, 256], pointers or strides that are not
+ * multiples of 16 bytes, or one head of q / k / v spanning 2 GiB or more; RTK_EWORKSPACE for a short workspace.
+ * ------------------------------------------------------------------------------------------- */
+size_t rtk_attention_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int D, int dtype);
+int rtk_attention_forward(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                          int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                          int D, int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Measurement support (bench.py).  When enabled, every kernel launch of this library is bracketed

@@ -1,0 +1,161 @@
+#!/usr/bin/env python
+"""Chunk attention: the native HIP call against the SDPA route of the attention patches, same tensors, same process.
+
+    python tools/bench_attention.py [--out profiles/attention_bench.json] [--reps 20] [--warmup 3] [--shapes chunk|all]
+                                    [--routes native,sdpa,fa2]      (--routes native: the run to put under rocprofv3)
+
+Per shape (Hq 28 / Hkv 4 / D 128; bf16, and fp16 once), inputs resident on the device (gaussian, tests/synth.py scale):
+  native   PivotKVCache.attention's call (retake.longvideo_cache.chunk_attention) on the patches' own tensors: q the
+           transposed view of [1, Lq, Hq*D], k / v the [:P0 + Lq] view of a [1, Hkv, capacity, D] cache buffer;
+  sdpa     what retake_Qwen2VLSdpaAttention_forward does with the same tensors when the switch is off: repeat_kv,
+           .contiguous(), scaled_dot_product_attention with the [1, 1, Lq, Lk] additive mask, transpose + contiguous;
+  fa2      transformers' _flash_attention_forward when the flash_attn package is importable (else recorded as absent).
+HIP events around each launch sequence, warm-up, then the median of `reps` launches.  A route that cannot run a shape (out
+of memory) is recorded with its error, not skipped.  Reported: microseconds, 4 Hq Lq (P0 + (Lq + 1) / 2) D flop over time
+as a fraction of 2.5 PFLOP/s (the dense bf16 MFMA peak), the allocator peak of each route above the resident inputs, and
+the ratio sdpa / native.  One JSON document; a markdown table on stdout.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "video-retake_amd"), os.path.join(ROOT, "tests")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import torch  # noqa: E402
+
+PEAK_FLOPS = 2.5e15
+HQ, HKV, D = 28, 4, 128
+CHUNK_SHAPES = [(2304, 0), (2304, 3456), (2304, 7488), (6272, 0), (6272, 50176), (6272, 98784)]
+FEW_ROW_SHAPES = [(5, 100352 - 5), (1, 100352 - 1)]   # text segment / decode step over Lk 100 352
+
+
+def flop(Lq, P0):
+    return 4.0 * HQ * Lq * (P0 + (Lq + 1) / 2.0) * D
+
+
+def make(Lq, P0, dtype, dev, seed=0):
+    g = torch.Generator(device=dev).manual_seed(seed)
+    Lk = P0 + Lq
+    cap = Lk + 256
+    q = (1.7 * torch.randn((1, Lq, HQ * D), generator=g, device=dev)).to(dtype).view(1, Lq, HQ, D).transpose(1, 2)
+    kb = (1.7 * torch.randn((1, HKV, cap, D), generator=g, device=dev)).to(dtype)
+    vb = (1.7 * torch.randn((1, HKV, cap, D), generator=g, device=dev)).to(dtype)
+    mask = torch.zeros((1, 1, Lq, Lk), dtype=dtype, device=dev)
+    rows = torch.arange(Lq, device=dev)[:, None]
+    mask[0, 0].masked_fill_(torch.arange(Lk, device=dev)[None, :] > P0 + rows, torch.finfo(dtype).min)
+    return q, kb[:, :, :Lk], vb[:, :, :Lk], mask
+
+
+def timed(fn, reps, warmup):
+    """(median us, allocator peak in bytes above what was held before, last result)."""
+    out = None
+    for _ in range(warmup):
+        out = fn()
+    torch.cuda.synchronize()
+    del out
+    held = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        out = fn()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e3)
+    return statistics.median(times), torch.cuda.max_memory_allocated() - held, out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attention_bench.json"))
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--shapes", choices=("chunk", "all"), default="all")
+    ap.add_argument("--routes", default="native,sdpa,fa2")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_attention.py needs the GPU: a CPU run measures nothing")
+    import retake.longvideo_cache as lc
+
+    try:
+        import flash_attn  # noqa: F401
+        from transformers.modeling_flash_attention_utils import _flash_attention_forward
+    except Exception:  # noqa: BLE001
+        _flash_attention_forward = None
+
+    dev = torch.device("cuda:0")
+    G = HQ // HKV
+    cases = [(s, torch.bfloat16, "chunk") for s in CHUNK_SHAPES] + [(CHUNK_SHAPES[1], torch.float16, "chunk")]
+    if args.shapes == "all":
+        cases += [(s, torch.bfloat16, "few rows") for s in FEW_ROW_SHAPES]
+    rows = []
+    for (Lq, P0), dtype, kind in cases:
+        q, k, v, mask = make(Lq, P0, dtype, dev)
+        ws = {}
+
+        def native():
+            return lc.chunk_attention(q, k, v, workspace=ws)
+
+        def sdpa():
+            kk, vv = lc.repeat_kv(k, G), lc.repeat_kv(v, G)
+            qc, kc, vc = (t.contiguous() for t in (q, kk, vv))
+            o = torch.nn.functional.scaled_dot_product_attention(qc, kc, vc, attn_mask=mask, dropout_p=0.0, is_causal=False)
+            return o.transpose(1, 2).contiguous()
+
+        def fa2():
+            kk, vv = lc.repeat_kv(k, G), lc.repeat_kv(v, G)
+            return _flash_attention_forward(q.transpose(1, 2), kk.transpose(1, 2), vv.transpose(1, 2), None, Lq, is_causal=True)
+
+        row = {"Lq": Lq, "P0": P0, "Lk": P0 + Lq, "Hq": HQ, "Hkv": HKV, "D": D, "dtype": str(dtype)[6:], "kind": kind,
+               "flop": flop(Lq, P0), "reps": args.reps}
+        outs = {}
+        for name, fn in (("native", native), ("sdpa", sdpa), ("fa2", fa2)):
+            if name not in args.routes.split(","):
+                row[name] = {"status": "not requested"}
+                continue
+            if name == "fa2" and _flash_attention_forward is None:
+                row["fa2"] = {"status": "flash_attn package not installed"}
+                continue
+            try:
+                us, peak, out = timed(fn, args.reps, args.warmup)
+                row[name] = {"status": "ok", "us": us, "fraction_of_2.5_PFLOPs": row["flop"] / (us * 1e-6) / PEAK_FLOPS,
+                             "tflops": row["flop"] / (us * 1e-6) / 1e12, "allocator_peak_bytes": int(peak)}
+                outs[name] = out
+            except torch.cuda.OutOfMemoryError as e:   # recorded, not skipped
+                row[name] = {"status": "out of memory", "error": str(e).split("\n")[0][:200]}
+            torch.cuda.empty_cache()
+        if "native" in outs and "sdpa" in outs:
+            row["max_abs_diff_native_vs_sdpa"] = (outs["native"].float() - outs["sdpa"].float()).abs().max().item()
+        if row["native"]["status"] == "ok" and row["sdpa"]["status"] == "ok":
+            row["ratio_sdpa_over_native"] = row["sdpa"]["us"] / row["native"]["us"]
+        rows.append(row)
+        del q, k, v, mask, outs, ws
+        torch.cuda.empty_cache()
+        print(json.dumps(row), flush=True)
+    doc = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "peak_flops": PEAK_FLOPS, "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("\n| dtype | Lq | P0 | native us | of 2.5 PF/s | native peak MiB | SDPA route us | SDPA peak MiB | SDPA / native |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        n, s = r["native"], r["sdpa"]
+        if n["status"] != "ok":
+            continue
+        s_us = f"{s['us']:.0f}" if s["status"] == "ok" else s["status"]
+        s_pk = f"{s['allocator_peak_bytes'] / 2**20:.0f}" if s["status"] == "ok" else "-"
+        ratio = f"{r['ratio_sdpa_over_native']:.2f}" if "ratio_sdpa_over_native" in r else "-"
+        print(f"| {r['dtype']} | {r['Lq']} | {r['P0']} | {n['us']:.0f} | {n['fraction_of_2.5_PFLOPs']:.3f} | "
+              f"{n['allocator_peak_bytes'] / 2**20:.0f} | {s_us} | {s_pk} | {ratio} |")
+
+
+if __name__ == "__main__":
+    main()

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _prefill
-from .longvideo_cache import apply_rotary_pos_emb, build_kvcache
+from .longvideo_cache import apply_rotary_pos_emb, build_kvcache, native_attention
 from .qwen2_vl import _compress_memory_bank, _visual_compression_settings
 
 DEBUG_MODE = False
@@ -99,6 +99,13 @@ def retake_Qwen2Attention_forward(self, hidden_states, position_embeddings, atte
         cache_kwargs = {"sin": sin, "cos": cos, "cache_position": cache_position,
                         "query_states": query_states, "position_ids": position_ids, "rotary_emb": self.rotary_emb}
         key_states, value_states = past_key_value.update(key_states, value_states, self.layer_idx, cache_kwargs)
+
+    # (build) attention_kernel="hip": the chunk's attention in one HIP launch on the views as they are; None = not asked
+    # for, or declined - the reference's dispatch below
+    native = native_attention(self, past_key_value, query_states, key_states, value_states, attention_mask,
+                              output_attentions=kwargs.get("output_attentions", False), scaling=self.scaling)
+    if native is not None:
+        return self.o_proj(native.reshape(*input_shape, -1)), None
 
     sliding_window = None
     if (self.config.use_sliding_window and getattr(self.config, "sliding_window", None) is not None

@@ -466,6 +466,105 @@ class _CacheView:
             self._o._adopt(len(self._o._layers) - 1, self._w, value)
 
 
+def chunk_attention(query_states, key_states, value_states, scaling=None, workspace=None, query_offset=None):
+    """Attention of a chunk's queries over [compressed prefix | current chunk] in one HIP launch (rtk_attention_forward):
+    what the reference's attention patches hand to torch / flash_attn after the cache update (qwen2_vl.py:88-117,
+    :188-219, :303-358; llava_onevision.py:118-139).
+
+    query_states [1, Hq, Lq, D], key_states / value_states [1, Hkv, Lk, D] with a contiguous head_dim and any head / row
+    strides - they are read where they are (the transposed projection output, the `[:P0 + L]` view of the cache buffer):
+    no repeat_kv, no .contiguous(), no mask.  One unpadded sequence; query row i sees keys j <= query_offset + i.  The
+    default, Lk - Lq, is bottom-right causal: the queries are the last Lq of the Lk positions (what flash-attn computes).  A
+    larger offset restates the 4-D additive mask HF builds over the UNCOMPRESSED positions, which the patches slice to the
+    keys the compressed cache holds: its width T gives query_offset = T - Lq (see native_attention).  Returns [1, Lq, Hq, D] (contiguous: `reshape(1, Lq, -1)` feeds o_proj), or None - nothing was
+    touched, take the existing route - when the library declines the shape (RTK_EUNSUPPORTED).
+
+    workspace: optional dict the key-split scratch is kept in between calls (PivotKVCache.attention passes its own)."""
+    nv.require_device(query_states, key_states, value_states)
+    if query_states.dim() != 4 or key_states.dim() != 4 or value_states.dim() != 4 or query_states.shape[0] != 1:
+        raise ValueError("chunk_attention takes [1, H, L, D] tensors (one unpadded sequence)")
+    if key_states.shape != value_states.shape or key_states.stride() != value_states.stride():
+        raise ValueError("key_states and value_states must share shape and strides")
+    if not (query_states.dtype == key_states.dtype == value_states.dtype):
+        raise ValueError("query, key and value states must share a dtype")
+    _, Hq, Lq, D = query_states.shape
+    _, Hkv, Lk, Dk = key_states.shape
+    if Dk != D:
+        raise ValueError("query and key head_dim differ")
+    if query_states.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return None
+    if query_states.stride(3) != 1 or key_states.stride(3) != 1:
+        return None
+    code = nv.dtype_code(query_states)
+    scale = float(D) ** -0.5 if scaling is None else float(scaling)
+    q_off = Lk - Lq if query_offset is None else int(query_offset)
+    need = nv.lib.rtk_attention_workspace_bytes(Hq, Hkv, Lq, Lk, D, code)
+    stream = nv.raw_stream(query_states.device.index)
+    ws = None
+    if need:
+        key = ("attention_ws", query_states.device.index, stream)   # per stream: calls on two streams may overlap
+        ws = None if workspace is None else workspace.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=query_states.device)
+            if workspace is not None:
+                workspace[key] = ws
+    out = torch.empty((1, Lq, Hq, D), dtype=query_states.dtype, device=query_states.device)
+    rc = nv.lib.rtk_attention_forward(nv.ptr(query_states), query_states.stride(1), query_states.stride(2),
+                                      nv.ptr(key_states), nv.ptr(value_states), key_states.stride(1), key_states.stride(2),
+                                      nv.ptr(out), Hq, Hkv, Lq, Lk, q_off, D, code, scale, nv.ptr(ws), need, stream)
+    if rc == nv.RTK_EUNSUPPORTED:
+        return None
+    nv.check(rc, "rtk_attention_forward")
+    return out
+
+
+def native_attention(module, cache, query_states, key_states, value_states, attention_mask, *, output_attentions=False,
+                     scaling=None):
+    """What the attention patches call after the prologue / cache update: the chunk's attention through `cache.attention`
+    iff the cache was built with attention_kernel="hip", the batch is one sequence on the GPU, no dropout is active, no
+    attention weights are wanted and the layer has no active sliding window.  [1, Lq, Hq, D], or None = take the patch's
+    existing route (nothing was touched).
+
+    attention_mask: the patch's additive mask [1, 1, Lq, T >= Lk], or "causal" for the flash-attn patch (no mask operand,
+    bottom-right causal).  The mask's VALUES are not read: the switch asserts one unpadded sequence - the only case the
+    reference supports (`assert bsz == 1`, longvideo_cache.py:246) - whose HF mask is 0 where j <= (T - Lq) + i and -inf
+    elsewhere (every recorded mask is: tests/test_attention_cpu.py).  Its WIDTH is: HF builds it over the uncompressed
+    positions and the patches slice it to the keys of the compressed cache, so row i sees keys j <= (T - Lq) + i, which for
+    T > Lk is more than bottom-right causal over the Lk keys - the native route returns what the patch's own route would.
+    A missing or differently shaped mask means something else on each patch's route: that call is declined."""
+    if getattr(cache, "attention_kernel", None) != "hip" or output_attentions:
+        return None
+    if query_states.shape[0] != 1 or not query_states.is_cuda:
+        return None
+    if module.training and getattr(module, "attention_dropout", 0.0):
+        return None
+    cfg = getattr(module, "config", None)
+    if (getattr(cfg, "use_sliding_window", False) and getattr(cfg, "sliding_window", None) is not None
+            and module.layer_idx >= getattr(cfg, "max_window_layers", 0)):
+        return None
+    Lq, Lk = query_states.shape[2], key_states.shape[2]
+    if isinstance(attention_mask, str):
+        if attention_mask != "causal":
+            return None
+        offset = Lk - Lq
+    else:
+        if attention_mask is None or attention_mask.dim() != 4 or tuple(attention_mask.shape[:3]) != (1, 1, Lq) \
+                or attention_mask.shape[3] < Lk:
+            return None
+        offset = attention_mask.shape[3] - Lq
+    return cache.attention(query_states, key_states, value_states, scaling=scaling, query_offset=offset)
+
+
+ATTENTION_KERNELS = (None, "hip")
+
+
+def _attention_kernel_of(config):
+    kind = config.longvideo_kwargs.get("attention_kernel", None)
+    if kind not in ATTENTION_KERNELS:
+        raise ValueError(f"attention_kernel must be None or 'hip', got {kind!r}")
+    return kind
+
+
 class PivotKVCache(DynamicCache):
     """Drop-in for the reference's PivotKVCache (longvideo_cache.py:119-323)."""
 
@@ -574,6 +673,20 @@ class PivotKVCache(DynamicCache):
         self._ws: Dict[str, torch.Tensor] = {}
         self._batch: Optional[_Batch] = None
         self._warned = False
+        # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it): "hip" makes the attention
+        # patches call `attention` below instead of torch / flash_attn; None (default) leaves them exactly as they are
+        self.attention_kernel = None
+        self.attention_calls = 0      # native attention launches so far (tests count them)
+        self._attn_ws: Dict[Any, torch.Tensor] = {}
+
+    def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None):
+        """The chunk's attention over the views `update` / `update_pre_rope` / `append_pre_rope` returned, in one HIP
+        launch (see chunk_attention).  [1, Lq, Hq, D], or None when the library declines the shape."""
+        out = chunk_attention(query_states, key_states, value_states, scaling=scaling, workspace=self._attn_ws,
+                              query_offset=query_offset)
+        if out is not None:
+            self.attention_calls += 1
+        return out
 
     # ---- diagnostics of the most recent compressed update (the selection may still be deferred: flush first) ----
     @property
@@ -603,12 +716,13 @@ class PivotKVCache(DynamicCache):
           selection         kept indices, ids of the pending chunk (old / new), selection scratch, compaction tickets
           staging           kept-row staging of the two-launch eviction (in_place_compaction=False / no reforge)
           deferred_queries  pre-RoPE queries kept alive for a flush that scores them where they lie (prologue_operands="pre_rope")
-          worker_scratch    per-update scratch of the stage-by-stage route / worker streams."""
+          worker_scratch    per-update scratch of the stage-by-stage route / worker streams
+          attention_workspace  key-split partials of the native chunk attention (attention_kernel="hip"; few-row shapes only)."""
         def nbytes(t):
             return 0 if t is None else t.numel() * t.element_size()
 
         out = dict.fromkeys(("cache_rows", "cache_headroom", "k_unrotated", "score_operands", "score_partials", "selection",
-                             "staging", "deferred_queries", "worker_scratch"), 0)
+                             "staging", "deferred_queries", "worker_scratch", "attention_workspace"), 0)
         for st in self._layers:
             if st.k is not None:
                 row = 2 * st.k.shape[1] * st.k.shape[3] * st.k.element_size()
@@ -631,6 +745,7 @@ class PivotKVCache(DynamicCache):
                     seen.add(t.data_ptr())
                     out["deferred_queries"] += nbytes(t)
         out["worker_scratch"] = sum(nbytes(t) for t in self._ws.values()) + sum(nbytes(t) for sd in self._sides for t in sd.ws.values())
+        out["attention_workspace"] = sum(nbytes(t) for t in self._attn_ws.values())
         out["total"] = sum(out.values())
         return out
 
@@ -1828,5 +1943,7 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None):
         return DynamicCache()
     compression_method = config.longvideo_kwargs["kvcache_compression_kwargs"]["compression_method"]
     if compression_method.lower() == "pivotkv":
-        return PivotKVCache(config, reserve_tokens=reserve_tokens)
+        cache = PivotKVCache(config, reserve_tokens=reserve_tokens)
+        cache.attention_kernel = _attention_kernel_of(config)
+        return cache
     raise NotImplementedError

@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _prefill
-from .longvideo_cache import apply_multimodal_rotary_pos_emb, build_kvcache, repeat_kv
+from .longvideo_cache import apply_multimodal_rotary_pos_emb, build_kvcache, native_attention, repeat_kv
 from .visual_compression import (memory_bank_compress_keyframe, memory_bank_compress_MALLM,
                                  memory_bank_compress_MALLM_hard, memory_bank_compress_MALLM_hard_to)
 
@@ -91,6 +91,12 @@ def retake_Qwen2VLAttention_forward(self, hidden_states, attention_mask=None, po
     bsz, q_len, _ = hidden_states.size()
     query_states, key_states, value_states = _qkv_and_cache_update(self, hidden_states, position_ids, past_key_value,
                                                                    cache_position)
+    # (build) attention_kernel="hip": the chunk's attention in one HIP launch on the views as they are; None = not asked
+    # for, or declined - the reference's op chain below
+    native = native_attention(self, past_key_value, query_states, key_states, value_states, attention_mask,
+                              output_attentions=output_attentions)
+    if native is not None:
+        return self.o_proj(native.reshape(bsz, q_len, -1)), None, past_key_value
     key_states = repeat_kv(key_states, self.num_key_value_groups)
     value_states = repeat_kv(value_states, self.num_key_value_groups)
     attn_weights = torch.matmul(query_states, key_states.transpose(2, 3)) / math.sqrt(self.head_dim)
@@ -118,6 +124,9 @@ def retake_Qwen2VLSdpaAttention_forward(self, hidden_states, attention_mask=None
     bsz, q_len, _ = hidden_states.size()
     query_states, key_states, value_states = _qkv_and_cache_update(self, hidden_states, position_ids, past_key_value,
                                                                    cache_position)
+    native = native_attention(self, past_key_value, query_states, key_states, value_states, attention_mask)   # (build) see the eager patch
+    if native is not None:
+        return self.o_proj(native.reshape(bsz, q_len, self.hidden_size)), None, past_key_value
     key_states = repeat_kv(key_states, self.num_key_value_groups)
     value_states = repeat_kv(value_states, self.num_key_value_groups)
     causal_mask = attention_mask
@@ -157,6 +166,22 @@ def retake_Qwen2VLFlashAttention2_forward(self, hidden_states, attention_mask=No
                 attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, -1:])], dim=-1)
     query_states, key_states, value_states = _qkv_and_cache_update(self, hidden_states, position_ids, past_key_value,
                                                                    cache_position)
+    if getattr(past_key_value, "attention_kernel", None) == "hip" and attention_mask is None and self.is_causal \
+            and not getattr(self, "_flash_attn_uses_top_left_mask", False):
+        # (build) the native route, before repeat_kv, with this patch's own fp32 -> weight-dtype cast (reference :318-333)
+        # so that it returns what the flash-attn route would; None = declined, the route below
+        native_qkv = (query_states, key_states, value_states)
+        if query_states.dtype == torch.float32:
+            if torch.is_autocast_enabled():
+                native_dtype = torch.get_autocast_gpu_dtype()
+            elif hasattr(self.config, "_pre_quantization_dtype"):
+                native_dtype = self.config._pre_quantization_dtype
+            else:
+                native_dtype = self.q_proj.weight.dtype
+            native_qkv = tuple(t.to(native_dtype) for t in native_qkv)
+        native = native_attention(self, past_key_value, *native_qkv, "causal")
+        if native is not None:
+            return self.o_proj(native.reshape(bsz, q_len, self.hidden_size)), None, past_key_value
     key_states = repeat_kv(key_states, self.num_key_value_groups)
     value_states = repeat_kv(value_states, self.num_key_value_groups)
     dropout_rate = 0.0 if not self.training else self.attention_dropout

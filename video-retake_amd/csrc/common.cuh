@@ -350,9 +350,15 @@ __device__ __forceinline__ void rope_chunk(const float* __restrict__ inv_freq, c
     for (int e = 0; e < VE; ++e) rope_elem(f[e], ra[e], rb[e], pid, scaling, round_bf16, c1[e], s1[e], c2[e], s2[e]);
 }
 
-// bf16(x * (1/a2)) == bf16(x / a2) for every finite bf16 x?  (pivotkv_score.hip; exhaustive, cached per a2)
+// bf16(x * (1/a2)) == bf16(x / a2) for every finite bf16 x?  (pivotkv_prepare.hip; exhaustive, cached per a2)
 bool bf16_rcp_is_exact(float a2);
-// rtk_pivotkv_prepare with the next layer's id shift in the launch (pivotkv_score.hip; used by rtk_pivotkv_update)
+// The RTK_SCORE_PREPARE stage of rtk_pivotkv_score (pivotkv_prepare.hip): un-rotate (cosv == NULL: copy) and pack q, k
+// into contiguous [H, L, D] copies.  payload: RTK_F32, RTK_BF16 or RTK_F16.  k_f16 != NULL (RTK_BF16_FAST): q~ is stored
+// as fp16 pre-scaled by log2(e)/sqrt(D), k~ as fp16 at k_f16 and, if k_out != NULL, as bf16 at k_out.
+int score_unrotate(int payload, const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, int64_t k_stride_h,
+                   int64_t k_stride_l, int Hq, int Hkv, int L, int D, const float* cosv, const float* sinv,
+                   float attention_scaling, char* q_out, char* k_out, char* k_f16, hipStream_t st);
+// rtk_pivotkv_prepare with the next layer's id shift in the launch (pivotkv_prepare.hip; used by rtk_pivotkv_update)
 int pivotkv_prepare_shift(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, int64_t k_stride_h,
                           int64_t k_stride_l, const void* v, int64_t v_stride_h, int64_t v_stride_l, int Hq, int Hkv, int L,
                           int D, int dtype, const int64_t* pos, int64_t pos_stride, int P, const float* inv_freq,

@@ -16,7 +16,7 @@ namespace rtk {
 
 using f32x2_t = __attribute__((ext_vector_type(2))) float;
 using f16x2_t = __attribute__((ext_vector_type(2))) _Float16;
-__device__ __forceinline__ uint32_t upd_pack2_f16(float lo, float hi) {   // saturating, like pivotkv_score.hip's pack2_f16
+__device__ __forceinline__ uint32_t upd_pack2_f16(float lo, float hi) {   // saturating, like score_mfma.cuh's pack2_f16
     const f32x2_t v = {__builtin_fminf(__builtin_fmaxf(lo, -65504.f), 65504.f),
                        __builtin_fminf(__builtin_fmaxf(hi, -65504.f), 65504.f)};
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));
@@ -285,9 +285,8 @@ static int prologue_launch(const PrologueGeom& g, const rtk_update_io* io, const
     const float a2 = (float)((double)g.scaling * (double)g.scaling);
     const int div = !roundtrip || a2 == 1.0f ? 0 : ((DT == RTK_BF16 && bf16_rcp_is_exact(a2)) ? 1 : 2);
     const float rcp_a2 = 1.0f / a2;
-    int nw = 4;
-    if constexpr (DT != RTK_F32) nw = PREP_NW;
-    const int VE = nw * 4 / (DT == RTK_F32 ? 4 : 2);
+    constexpr int NW = DT != RTK_F32 ? PREP_NW : 4;   // 32-bit words per thread and row half
+    constexpr int VE = NW * 4 / (DT == RTK_F32 ? 4 : 2);
     const int threads = g.L * (g.D / 2 / VE);
     const dim3 grid((threads + PREP_BLOCK - 1) / PREP_BLOCK, PREP_YSPLIT);
     const float qscale = k_fast ? 1.4426950408889634f / sqrtf((float)g.D) : 1.f;
@@ -298,27 +297,17 @@ static int prologue_launch(const PrologueGeom& g, const rtk_update_io* io, const
                    (char*)io->q_rot, io->qr_stride_h, io->qr_stride_l, q_out, k_out, k_tail, v_tail, tail_sh, g.P, pos_copy,
                    pos_copy_ld, k_fast, qscale, shift_back, a2, rcp_a2, div);
     };
-#define RTK_PRO_NWSEL(FASTV, RTV)                                                         \
-    do {                                                                                  \
-        if constexpr (DT != RTK_F32) {                                                    \
-            if (nw == 2) { launch(prologue_kernel<DT, FASTV, 2, RTV>); break; }           \
-            if (nw == 1) { launch(prologue_kernel<DT, FASTV, 1, RTV>); break; }           \
-        }                                                                                 \
-        launch(prologue_kernel<DT, FASTV, 4, RTV>);                                       \
-    } while (0)
-    bool done = false;
+    const bool fast = DT == RTK_BF16 && k_fast;
     if constexpr (DT == RTK_BF16) {
-        if (k_fast) {
-            if (roundtrip) RTK_PRO_NWSEL(true, true);
-            else RTK_PRO_NWSEL(true, false);
-            done = true;
+        if (fast) {
+            if (roundtrip) launch(prologue_kernel<DT, true, NW, true>);
+            else launch(prologue_kernel<DT, true, NW, false>);
         }
     }
-    if (!done) {
-        if (roundtrip) RTK_PRO_NWSEL(false, true);
-        else RTK_PRO_NWSEL(false, false);
+    if (!fast) {
+        if (roundtrip) launch(prologue_kernel<DT, false, NW, true>);
+        else launch(prologue_kernel<DT, false, NW, false>);
     }
-#undef RTK_PRO_NWSEL
     RTK_LAUNCH_CHECK("prologue_kernel");
     return RTK_OK;
 }

@@ -1,6 +1,6 @@
 // score_refround.cuh — PivotKV scoring in the REFERENCE's 16-bit semantics (dtype codes RTK_BF16_REFROUND and, template
-// flag F16, RTK_F16_REFROUND: the same chain with every "-> bf16" below read as "-> fp16"), included by
-// pivotkv_score.hip.  longvideo_cache.py:264-270 run on a bf16 model rounds
+// flag F16, RTK_F16_REFROUND: the same chain with every "-> bf16" below read as "-> fp16").
+// longvideo_cache.py:264-270 run on a bf16 model rounds
 //     matmul(q, k^T)                 -> bf16      (fp32 accumulation, one rounding)
 //     / math.sqrt(D)                 -> bf16
 //     softmax(dim=-1, dtype=float32) -> fp32 softmax of those bf16 logits
@@ -18,6 +18,7 @@
 // of their contract): measured against the reference on CPU, <= 1-2 scores per 6272 differ, by one bf16 ulp
 // (tests/test_hip_parity.py::test_pivotkv_reference_rounding_matches_reference_bf16).
 #pragma once
+#include "score_dma.cuh"
 
 namespace rtk {
 

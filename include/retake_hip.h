@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (58 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (62 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -42,6 +42,8 @@
  *   §I  "Chunk attention"               rtk_attention_forward (+ rtk_attention_workspace_bytes): the chunk's queries over
  *                                       [compressed prefix | current chunk], opt-in (attention_kernel="hip")
  *   §J  "Measurement support"           rtk_profile_* (off by default)
+ *   §K  "FP8 rows of the compressed cache"  rtk_pivotkv_archive_batched, rtk_attention_forward_fp8kv (+ _workspace_bytes_fp8kv),
+ *                                       rtk_fp8kv_dequant: opt-in (kv_cache_dtype="fp8_e4m3" with attention_kernel="hip")
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -761,6 +763,79 @@ int rtk_profile_read(int kernel_id, long long* launches, double* total_ms);
 /* Calibration for the HBM rooflines: dst = src over 16-byte vectors with non-temporal loads and stores - the device
  * copy the "achievable" bandwidth beside the nominal 8 TB/s is measured with (bench.py: hbm_achievable). */
 int rtk_profile_copy(void* dst, const void* src, size_t bytes, rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * FP8 rows of the compressed cache (opt-in: kv_cache_dtype="fp8_e4m3").  The kept K / V rows of compressed video chunks
+ * are stored as D one-byte OCP e4m3fn codes plus ONE power-of-two fp32 scale per (kv head, row): (D + 4) bytes instead of
+ * 2 D.  Lossy - the reference has no such option.  RTK_BF16 / RTK_F16 with head_dim 128 only.
+ *
+ * The rule, for one row of one kv head (D values of the model dtype, taken to fp32).  Supported inputs: finite, and a
+ * row's amax either 0 or >= 2^-117, so that its scale is a NORMAL fp32 number (>= 2^-126); below that - bf16 rows of
+ * magnitudes no K / V row has - the scale is subnormal, the scaled hardware convert of the dequantisation is not
+ * specified to honour it, and rule 5's exactness does not hold; such rows are not tested:
+ *   1. amax = max |x_d|;
+ *   2. amax == 0: scale = 1;
+ *   3. otherwise amax = m 2^E with m in [0.5, 1) (frexp); e = E - 9 if m <= 0.875, else E - 8; scale = 2^e, so that
+ *      amax / scale lies in (224, 448];
+ *   4. code_d = x_d 2^-e (exact) rounded to nearest even to e4m3fn - nothing saturates;
+ *   5. dequantised value = dtype(float(code_d) * scale): exactly representable in bf16 (3 mantissa bits against 7); in
+ *      fp16 as well, except that a row with |x| >= 65280 may round up to 65536 = inf.
+ * Layout: codes of row (h, r) at h*stride_h + r*D BYTES, scale at h*scale_stride_h + r floats.
+ *
+ * rtk_pivotkv_archive_batched: the eviction (longvideo_cache.py:278-288, :297-310) of n_units (layer, chunk) units that
+ * share Hkv, D, keep, P and dtype into such archives, in one launch per RTK_ARCHIVE_MAX_UNITS units.  Kept row r comes
+ * from chunk row keep_idx[r] (keep_idx NULL: row r, a chunk that keeps every token).  k_mode RTK_COMPACT_K_ROTATE: kept
+ * K = the k_src row (the un-rotated k~) rotated at its new ids pos_src and rounded to the model dtype - the bits
+ * rtk_pivotkv_compact_batched writes - then quantised; RTK_COMPACT_K_COPY: the k_src row verbatim (no reforge: pass the
+ * cache tail).  Kept V = the v_src row.  Sources and destinations must not alias; nothing else is synchronised.
+ * inv_freq / attention_scaling / sections / round_mode as rtk_pivotkv_compact_batched.
+ * Errors, all before any launch: RTK_EINVAL for NULL pointers, bad sizes or modes; RTK_EUNSUPPORTED for another dtype or
+ * head_dim and for pointers / strides that are not 16-byte aligned. */
+typedef struct rtk_archive_unit {
+    const void* k_src;        /* K rows of the chunk, element (h,l,d) at h*k_src_stride_h + l*D + d */
+    int64_t k_src_stride_h;
+    const void* v_src;        /* V rows of the chunk, same layout */
+    int64_t v_src_stride_h;
+    const int64_t* keep_idx;  /* [keep] from rtk_pivotkv_select[_batched], or NULL = identity */
+    const int64_t* pos_src;   /* ids of the kept rows [P, keep] (row stride pos_src_stride): the NEW ids the rotation uses ... */
+    int64_t pos_src_stride;
+    int64_t* pos_dst;         /* ... copied to the layer's position cache tail (row stride pos_dst_stride), or NULL */
+    int64_t pos_dst_stride;
+    void* k8;                 /* codes of kept row r of head h at h*dst_stride_h + r*D bytes: already offset to the first free row */
+    void* v8;
+    int64_t dst_stride_h;     /* bytes */
+    float* k_scale;           /* scale of kept row r of head h at h*scale_stride_h + r */
+    float* v_scale;
+    int64_t scale_stride_h;   /* floats */
+} rtk_archive_unit;
+#define RTK_ARCHIVE_MAX_UNITS 28   /* units per launch (the array travels as a kernel argument) */
+int rtk_pivotkv_archive_batched(const rtk_archive_unit* units, int n_units, int Hkv, int D, int keep, int P, int dtype,
+                                int k_mode, const float* inv_freq, float attention_scaling, const int* sections_host,
+                                int nsec, int round_mode, rtk_stream_t stream);
+
+/* Codes + scales -> dense rows of the model dtype (rule 5): out element (h,l,d) at h*out_stride_h + l*D + d (elements).
+ * The diagnostic dense view of PivotKVCache and the tests use it; nothing on the hot path does. */
+int rtk_fp8kv_dequant(const void* codes, int64_t codes_stride_h, const float* scales, int64_t scale_stride_h, void* out,
+                      int64_t out_stride_h, int H, int L, int D, int dtype, rtk_stream_t stream);
+
+/* rtk_attention_forward over keys in two segments: L8 archive rows (k8 / v8 / k_scale / v_scale, head strides
+ * stride8_h bytes and scale_stride_h floats) that precede, in sequence order, the Lk rows of the 16-bit segment k / v.
+ * Every archive row is visible to every query row; 16-bit row r is visible to query row i iff r <= q_offset + i, so Lk,
+ * q_offset (>= Lk - Lq) and Lk >= Lq describe the 16-bit segment alone (the caller passes the offset of the whole
+ * sequence minus L8).  The archive tiles are converted to the model dtype on their way into LDS and take the same MFMA /
+ * softmax body; archive tiles come first.  The result equals, bit for bit, rtk_attention_forward over
+ * [dequantised archive | 16-bit rows] with q_offset + L8 when L8 % 64 == 0 (otherwise the 16-bit rows start a new key
+ * tile, i.e. the fp32 sums are grouped differently); L8 == 0 IS rtk_attention_forward (k8 .. v_scale are not read).
+ * The key split of few-row shapes covers the concatenation: the workspace is rtk_attention_workspace_bytes_fp8kv().
+ * RTK_BF16 / RTK_F16 with D == 128 only (RTK_EUNSUPPORTED otherwise); the other errors as rtk_attention_forward, plus
+ * RTK_EINVAL for L8 < 0 or NULL archive pointers with L8 > 0, RTK_EUNSUPPORTED for archive pointers / stride8_h that are
+ * not multiples of 16 bytes or an archive head of 2 GiB or more. */
+size_t rtk_attention_workspace_bytes_fp8kv(int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype);
+int rtk_attention_forward_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                                const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
+                                int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,12 @@ HIP events around each launch sequence, warm-up, then the median of `reps` launc
 of memory) is recorded with its error, not skipped.  Reported: microseconds, 4 Hq Lq (P0 + (Lq + 1) / 2) D flop over time
 as a fraction of 2.5 PFLOP/s (the dense bf16 MFMA peak), the allocator peak of each route above the resident inputs, and
 the ratio sdpa / native.  One JSON document; a markdown table on stdout.
+
+    python tools/bench_attention.py --fp8kv [--out profiles/fp8kv_attention_bench.json]
+
+The same shapes with the first P0 keys as fp8 rows (kv_cache_dtype="fp8_e4m3"): the two-segment call
+(rtk_attention_forward_fp8kv: e4m3 archive + 16-bit tail) against the 16-bit kernel on [dequantised archive | tail], same
+process, same timing; whether the two outputs are bit-equal (they must be when P0 % 64 == 0) is recorded per shape.
 """
 from __future__ import annotations
 
@@ -73,9 +79,57 @@ def timed(fn, reps, warmup):
     return statistics.median(times), torch.cuda.max_memory_allocated() - held, out
 
 
+def main_fp8kv(args):
+    import retake.longvideo_cache as lc
+
+    dev = torch.device("cuda:0")
+    cases = [(s, torch.bfloat16, "chunk") for s in CHUNK_SHAPES] + [(CHUNK_SHAPES[1], torch.float16, "chunk")]
+    if args.shapes == "all":
+        cases += [(s, torch.bfloat16, "few rows") for s in FEW_ROW_SHAPES]
+    rows = []
+    for (Lq, P0), dtype, kind in cases:
+        q, k, v, _ = make(Lq, P0, dtype, dev)
+        del _
+        ak, sk = lc.fp8_quantize_rows(k[:, :, :P0].contiguous())
+        av, sv = lc.fp8_quantize_rows(v[:, :, :P0].contiguous())
+        kd, vd = k.clone(), v.clone()                   # [dequantised archive | tail]
+        lc.fp8_dequantize_rows(ak, sk, dtype, kd[:, :, :P0])
+        lc.fp8_dequantize_rows(av, sv, dtype, vd[:, :, :P0])
+        kt, vt = k[:, :, P0:], v[:, :, P0:]
+        archive = (ak, av, sk, sv)
+        ws = {}
+        row = {"Lq": Lq, "L8": P0, "Lk16": Lq, "Hq": HQ, "Hkv": HKV, "D": D, "dtype": str(dtype)[6:], "kind": kind,
+               "flop": flop(Lq, P0), "reps": args.reps, "kv_bytes_fp8kv": 2 * HKV * (P0 * (D + 4) + Lq * D * 2),
+               "kv_bytes_16bit": 2 * HKV * (P0 + Lq) * D * 2}
+        outs = {}
+        for name, fn in (("fp8kv", lambda: lc.chunk_attention(q, kt, vt, workspace=ws, archive=archive)),
+                         ("dense16", lambda: lc.chunk_attention(q, kd, vd, workspace=ws))):
+            us, peak, out = timed(fn, args.reps, args.warmup)
+            row[name] = {"status": "ok", "us": us, "fraction_of_2.5_PFLOPs": row["flop"] / (us * 1e-6) / PEAK_FLOPS,
+                         "allocator_peak_bytes": int(peak)}
+            outs[name] = out
+        row["ratio_fp8kv_over_dense16"] = row["fp8kv"]["us"] / row["dense16"]["us"]
+        row["bit_equal"] = bool(torch.equal(outs["fp8kv"], outs["dense16"]))
+        row["max_abs_diff"] = (outs["fp8kv"].float() - outs["dense16"].float()).abs().max().item()
+        rows.append(row)
+        del q, k, v, kd, vd, kt, vt, archive, ak, av, sk, sv, outs, ws
+        torch.cuda.empty_cache()
+        print(json.dumps(row), flush=True)
+    doc = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "peak_flops": PEAK_FLOPS, "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("\n| dtype | Lq | L8 | fp8kv us | 16-bit kernel on dequantised rows us | fp8kv / 16-bit | K/V bytes read fp8kv / 16-bit | bit-equal |")
+    print("|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['dtype']} | {r['Lq']} | {r['L8']} | {r['fp8kv']['us']:.0f} | {r['dense16']['us']:.0f} | "
+              f"{r['ratio_fp8kv_over_dense16']:.2f} | {r['kv_bytes_fp8kv'] / r['kv_bytes_16bit']:.2f} | {r['bit_equal']} |")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "attention_bench.json"))
+    ap.add_argument("--fp8kv", action="store_true", help="the two-segment fp8 call against the 16-bit kernel on dequantised rows")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--shapes", choices=("chunk", "all"), default="all")
@@ -83,6 +137,10 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_attention.py needs the GPU: a CPU run measures nothing")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "fp8kv_attention_bench.json" if args.fp8kv else "attention_bench.json")
+    if args.fp8kv:
+        return main_fp8kv(args)
     import retake.longvideo_cache as lc
 
     try:

@@ -27,7 +27,7 @@
 // number of splits is a function of the shape alone.
 #include <cmath>
 
-#include "common.cuh"
+#include "fp8kv.cuh"
 
 namespace rtk {
 namespace {
@@ -70,191 +70,40 @@ __device__ __forceinline__ int acc_row(int reg, int hf) { return (reg & 3) + 8 *
 __device__ __forceinline__ int swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
 __device__ __forceinline__ float safe_max(float m) { return m == -INFINITY ? 0.f : m; }
 
+// The e4m3 archive that precedes the 16-bit keys (retake_hip.h "FP8 rows of the compressed cache"): L8 rows per kv head.
+struct Archive8 {
+    const char *k8, *v8;        // codes, row (h, r) at h * sh8 + r * 128 bytes
+    const float *ks, *vs;       // scales, row (h, r) at h * shs + r
+    int64_t sh8, shs;
+    int L8;
+};
+
+// The body of both kernels is attention_d128_body.inc, included once each with FP8 false / true - a function the two
+// kernels share compiles the existing instantiations differently (tools/kernel_diff.py), the same text does not.
+// FP8: the keys are [archive | 16-bit rows].  Key tiles are counted in a padded index space - the archive takes
+// [0, L8p), L8p = L8 rounded up to a whole tile, the 16-bit row r sits at L8p + r - so a tile is of one kind, the split
+// plan and the diagonal arithmetic are those of a 16-bit call over L8p + Lk keys, and with L8 % 64 == 0 every fp32 sum
+// is grouped exactly as rtk_attention_forward groups it over the concatenation.
 template <int DT, bool SPLIT>
 __global__ __launch_bounds__(256, 2) void attn_fwd_d128_kernel(
     const char* __restrict__ q, int64_t q_sh, uint32_t q_row_bytes, uint32_t q_bytes, const char* __restrict__ k,
     const char* __restrict__ v, int64_t kv_sh, uint32_t kv_row_bytes, uint32_t kv_bytes, char* __restrict__ out,
     float* __restrict__ part_acc, float* __restrict__ part_ml, int Hq, int G, int Lq, int Lk, int off, float c2,
     int keys_per_split) {
-    using Hh = H16<DT>;
-    __shared__ __attribute__((aligned(16))) char lds[4 * AT_TILE];   // [buffer][K | V]
-    const int tid = threadIdx.x, lane = tid & 63, wave = uniform_int(tid >> 6);
-    const int r = lane & 31, hf = lane >> 5;
-    const int nqb = (Lq + AT_QB - 1) / AT_QB;
-    const int qb = nqb - 1 - (int)blockIdx.x / Hq;   // heaviest (last) query block first
-    const int hq = (int)blockIdx.x % Hq, hkv = hq / G;
-    const int row_base = qb * AT_QB, wrow0 = row_base + 32 * wave, qrow = wrow0 + r;
-    int k_lo = 0, k_hi = min(Lk, off + min(row_base + AT_QB, Lq));   // exclusive: first key no row of the block sees
-    if constexpr (SPLIT) {
-        k_lo = (int)blockIdx.y * keys_per_split;
-        k_hi = min(k_hi, k_lo + keys_per_split);
-    }
-    const int ntiles = k_hi > k_lo ? (k_hi - k_lo + AT_KT - 1) / AT_KT : 0;
-    const bool wave_rows = wrow0 < Lq;
-    const int wave_hi = min(Lk, off + min(wrow0 + 32, Lq));   // first key no row of this wave sees
+    constexpr bool FP8 = false;
+    const Archive8 a8{};
+#include "attention_d128_body.inc"
+}
 
-    const __amdgpu_buffer_rsrc_t rq = bounded_rsrc(q + (int64_t)hq * q_sh * 2, q_bytes);
-    const __amdgpu_buffer_rsrc_t rk = bounded_rsrc(k + (int64_t)hkv * kv_sh * 2, kv_bytes);
-    const __amdgpu_buffer_rsrc_t rv = bounded_rsrc(v + (int64_t)hkv * kv_sh * 2, kv_bytes);
-
-    // Q fragments: k-step s holds q[qrow][16 s + 8 hf .. + 8]
-    u32x4 qf[8];
-    {
-        const uint32_t qo = (uint32_t)qrow * q_row_bytes + 16u * hf;
-#pragma unroll
-        for (int s = 0; s < 8; ++s) qf[s] = load16(rq, qo + 32u * s);
-    }
-    // staging: thread -> rows (tid >> 4) + 16 u, chunk tid & 15
-    const int srow = tid >> 4, sch = tid & 15;
-    const uint32_t g_off = (uint32_t)srow * kv_row_bytes + 16u * sch;
-    const int l_off = 256 * srow + 16 * (sch ^ swz(srow));   // + 4096 u (rows 16 apart share the swizzle)
-    u32x4 kst[4], vst[4];
-    auto issue = [&](int kbase) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const uint32_t o = g_off + (uint32_t)(kbase + 16 * u) * kv_row_bytes;
-            kst[u] = load16(rk, o);
-            vst[u] = load16(rv, o);
-        }
-    };
-    auto commit = [&](int buf) {
-        char* t = lds + buf * 2 * AT_TILE + l_off;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            *(u32x4*)(t + 4096 * u) = kst[u];
-            *(u32x4*)(t + AT_TILE + 4096 * u) = vst[u];
-        }
-    };
-    // K row reads: key row r (+32), chunk 2 s + hf
-    const int k_rd = 256 * r, k_x = swz(r);
-    // V transposed reads: lane 4 q_ + p_ of a 16-lane group supplies row q_ of the 4-key block, columns 4 p_ .. 4 p_ + 3
-    const int g16 = lane >> 4, q_ = (lane & 15) >> 2, p_ = lane & 3;
-    const int v_rd = 256 * (4 * hf + q_) + 8 * (p_ & 1);
-    const int v_cl = 2 * (g16 & 1) + (p_ >> 1);   // low bits of the chunk: which 16 of a d-block's 32 columns, which half
-
-    f32x16 oacc[4];
-#pragma unroll
-    for (int db = 0; db < 4; ++db)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) oacc[db][e] = 0.f;
-    float m = -INFINITY, l = 0.f;
-
-    if (ntiles > 0) {
-        issue(k_lo);
-        commit(0);
-    }
-    __syncthreads();
-    for (int t = 0; t < ntiles; ++t) {
-        const int kbase = k_lo + t * AT_KT;
-        const bool more = t + 1 < ntiles;
-        if (more) issue(kbase + AT_KT);
-        if (wave_rows && kbase < wave_hi) {
-            const char* kt = lds + (t & 1) * 2 * AT_TILE;
-            const char* vt = kt + AT_TILE;
-            f32x16 s0, s1;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { s0[e] = 0.f; s1[e] = 0.f; }
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const int co = 16 * ((2 * s + hf) ^ k_x);
-                const u32x4 a0 = *(const u32x4*)(kt + k_rd + co);
-                const u32x4 a1 = *(const u32x4*)(kt + k_rd + 32 * 256 + co);
-                mma16<DT>(s0, a0, qf[s]);
-                mma16<DT>(s1, a1, qf[s]);
-            }
-            if (kbase + AT_KT - 1 > min(off + wrow0, Lk - 1)) {   // the tile straddles this wave's diagonal or the end of the keys
-                const int lim = min(off + qrow, Lk - 1) - kbase;
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int j = acc_row(e, hf);
-                    if (j > lim) s0[e] = -INFINITY;
-                    if (j + 32 > lim) s1[e] = -INFINITY;
-                }
-            }
-            float mx = fmaxf(s0[0], s1[0]);
-#pragma unroll
-            for (int e = 1; e < 16; ++e) mx = fmaxf(mx, fmaxf(s0[e], s1[e]));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
-            const float mnew = fmaxf(m, mx * c2);
-            if (!__all(mnew == m)) {   // some row's maximum grew: bring O and l to the new one (exact, no threshold)
-                const float alpha = __builtin_amdgcn_exp2f(m - safe_max(mnew));
-#pragma unroll
-                for (int db = 0; db < 4; ++db)
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) oacc[db][e] *= alpha;
-                l *= alpha;
-                m = mnew;
-            }
-            const float nm = -safe_max(m);
-            float ls = 0.f;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                s0[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[e], c2, nm));
-                s1[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[e], c2, nm));
-                ls += s0[e] + s1[e];
-            }
-            l += ls;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {   // k-step: keys 16 ks .. 16 ks + 15 of the tile
-                const f32x16& p = ks < 2 ? s0 : s1;
-                const int e0 = 8 * (ks & 1);
-                const u32x4 pf = {Hh::pack2(p[e0], p[e0 + 1]), Hh::pack2(p[e0 + 2], p[e0 + 3]),
-                                  Hh::pack2(p[e0 + 4], p[e0 + 5]), Hh::pack2(p[e0 + 6], p[e0 + 7])};
-#pragma unroll
-                for (int db = 0; db < 4; ++db) {
-                    u32x2 h2[2];
-#pragma unroll
-                    for (int jh = 0; jh < 2; ++jh) {
-                        // rows 16 ks + 8 jh + 4 hf + q_: (row & 3) = q_, ((row >> 2) & 3) = 2 jh + hf
-                        const int x = (q_ << 2) | (2 * jh + hf);
-                        const int a = v_rd + 256 * (16 * ks + 8 * jh) + 16 * ((4 * db + v_cl) ^ x);
-                        const i16x4 t4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                            (__attribute__((address_space(3))) i16x4*)(vt + a));
-                        h2[jh] = __builtin_bit_cast(u32x2, t4);
-                    }
-                    const u32x4 vf = {h2[0][0], h2[0][1], h2[1][0], h2[1][1]};
-                    mma16<DT>(oacc[db], vf, pf);
-                }
-            }
-        }
-        if (more) commit((t + 1) & 1);
-        __syncthreads();
-    }
-
-    const float l_tot = l + __shfl_xor(l, 32, WAVE);
-    if constexpr (SPLIT) {
-        if (qrow < Lq) {
-            const size_t row = ((size_t)blockIdx.y * Hq + hq) * Lq + qrow;
-            if (hf == 0) *(float2*)(part_ml + 2 * row) = make_float2(m, l_tot);
-            float* pa = part_acc + row * 128;
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int g4 = 0; g4 < 4; ++g4)
-                    *(f32x4*)(pa + 32 * db + 8 * g4 + 4 * hf) =
-                        f32x4{oacc[db][4 * g4], oacc[db][4 * g4 + 1], oacc[db][4 * g4 + 2], oacc[db][4 * g4 + 3]};
-        }
-    } else {
-        // every wave has left the tile loop (the barrier above): stage this wave's 32 rows, store them as whole rows
-        const float inv = 1.f / l_tot;
-        char* st = lds + wave * (32 * AT_OPITCH);
-#pragma unroll
-        for (int db = 0; db < 4; ++db)
-#pragma unroll
-            for (int g4 = 0; g4 < 4; ++g4)
-                *(u32x2*)(st + r * AT_OPITCH + 2 * (32 * db + 8 * g4 + 4 * hf)) =
-                    u32x2{Hh::pack2(oacc[db][4 * g4] * inv, oacc[db][4 * g4 + 1] * inv),
-                          Hh::pack2(oacc[db][4 * g4 + 2] * inv, oacc[db][4 * g4 + 3] * inv)};
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int rr = 4 * it + (lane >> 4), ch = lane & 15;
-            const u32x4 x = *(const u32x4*)(st + rr * AT_OPITCH + 16 * ch);
-            if (wrow0 + rr < Lq) *(u32x4*)(out + ((size_t)(wrow0 + rr) * Hq + hq) * 256 + 16 * ch) = x;
-        }
-    }
+// the same body over [e4m3 archive | 16-bit rows]: Lk and off describe the 16-bit segment
+template <int DT, bool SPLIT>
+__global__ __launch_bounds__(256, 2) void attn_fwd_d128_fp8kv_kernel(
+    const char* __restrict__ q, int64_t q_sh, uint32_t q_row_bytes, uint32_t q_bytes, const char* __restrict__ k,
+    const char* __restrict__ v, int64_t kv_sh, uint32_t kv_row_bytes, uint32_t kv_bytes, char* __restrict__ out,
+    float* __restrict__ part_acc, float* __restrict__ part_ml, int Hq, int G, int Lq, int Lk, int off, float c2,
+    int keys_per_split, Archive8 a8) {
+    constexpr bool FP8 = true;
+#include "attention_d128_body.inc"
 }
 
 template <int DT> __device__ __forceinline__ float ld_elem(const void* p, size_t i) {
@@ -458,6 +307,53 @@ int attn_launch(const AttnPlan& pl, const void* q, int64_t q_sh, int64_t q_sl, c
     return RTK_OK;
 }
 
+template <int DT>
+int attn_launch_fp8kv(const AttnPlan& pl, const void* q, int64_t q_sh, int64_t q_sl, const void* k, const void* v, int64_t kv_sh,
+                      int64_t kv_sl, const Archive8& a8, void* out, int Hq, int Hkv, int Lq, int Lk, int off, float c2, void* ws,
+                      hipStream_t st) {
+    constexpr int D = 128;
+    constexpr size_t es = 2;
+    float* part_acc = (float*)ws;
+    float* part_ml = part_acc ? part_acc + (size_t)pl.nsplit * Hq * Lq * D : nullptr;
+    const uint32_t q_bytes = (uint32_t)(((size_t)(Lq - 1) * q_sl + D) * es);
+    const uint32_t kv_bytes = (uint32_t)(((size_t)(Lk - 1) * kv_sl + D) * es);
+    const dim3 grid((unsigned)(Hq * ((Lq + AT_QB - 1) / AT_QB)), (unsigned)pl.nsplit);
+    if (pl.nsplit > 1)
+        hipLaunchKernelGGL((attn_fwd_d128_fp8kv_kernel<DT, true>), grid, dim3(256), 0, st, (const char*)q, q_sh,
+                           (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * es),
+                           kv_bytes, (char*)out, part_acc, part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8);
+    else
+        hipLaunchKernelGGL((attn_fwd_d128_fp8kv_kernel<DT, false>), grid, dim3(256), 0, st, (const char*)q, q_sh,
+                           (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * es),
+                           kv_bytes, (char*)out, part_acc, part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8);
+    RTK_LAUNCH_CHECK("attn_fwd_d128_fp8kv_kernel");
+    if (pl.nsplit > 1) {
+        const size_t total = (size_t)Lq * Hq * D;
+        hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc,
+                           part_ml, (char*)out, Hq, Lq, D, pl.nsplit);
+        RTK_LAUNCH_CHECK("attn_combine_kernel");
+    }
+    return RTK_OK;
+}
+
+// the archive padded to whole key tiles: the key count the split plan of an fp8kv call is made for
+inline long long fp8kv_keys(int Lk, int L8) { return (long long)Lk + ((long long)L8 + AT_KT - 1) / AT_KT * AT_KT; }
+
+int fp8kv_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype) {
+    const int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG(L8 >= 0, "%s: L8 %d is negative", who, L8);
+    if ((dtype != RTK_BF16 && dtype != RTK_F16) || D != 128) {
+        set_error("%s: unsupported dtype code %d / head_dim %d (RTK_BF16 or RTK_F16 with head_dim 128)", who, dtype, D);
+        return RTK_EUNSUPPORTED;
+    }
+    if (fp8kv_keys(Lk, L8) > 0x3fffffff || (long long)L8 * 128 >= (1ll << 31) - AT_KT * 128) {
+        set_error("%s: unsupported extent: %d archive rows + %d keys", who, L8, Lk);
+        return RTK_EUNSUPPORTED;
+    }
+    return RTK_OK;
+}
+
 }  // namespace
 }  // namespace rtk
 
@@ -511,4 +407,60 @@ extern "C" int rtk_attention_forward(const void* q, int64_t q_stride_h, int64_t 
         case RTK_BF16: return attn_launch<RTK_BF16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, c2, ws, st);
         default: return attn_launch<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, c2, ws, st);
     }
+}
+
+extern "C" size_t rtk_attention_workspace_bytes_fp8kv(int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype) {
+    if (fp8kv_check_shape("rtk_attention_workspace_bytes_fp8kv", Hq, Hkv, Lq, Lk, L8, D, dtype) != RTK_OK) return 0;
+    return attn_plan(Hq, Lq, (int)fp8kv_keys(Lk, L8), D, dtype).ws_bytes;
+}
+
+extern "C" int rtk_attention_forward_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                           int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                                           const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                           int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                                           int D, int dtype, float scale, void* workspace, size_t workspace_bytes,
+                                           rtk_stream_t stream) {
+    const char* who = "rtk_attention_forward_fp8kv";
+    RTK_CHECK_ARG(q && k && v && out, "%s: NULL q / k / v / out pointer", who);
+    const int rc = fp8kv_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype);
+    if (rc != RTK_OK) return rc;
+    if (L8 == 0)   // no archive yet: the 16-bit call itself
+        return rtk_attention_forward(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset,
+                                     D, dtype, scale, workspace, workspace_bytes, stream);
+    RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
+    RTK_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
+    RTK_CHECK_ARG(q_offset >= Lk - Lq && q_offset <= 0x3fffffff,
+                  "%s: q_offset %d < Lk - Lq = %d (the last keys would be visible to no row)", who, q_offset, Lk - Lq);
+    const size_t es = 2;
+    const bool aligned = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)k8 | (uintptr_t)v8) & 15) == 0 &&
+                         (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3) == 0 && stride8_h % 16 == 0 &&
+                         (q_stride_h * (int64_t)es) % 16 == 0 && (q_stride_l * (int64_t)es) % 16 == 0 &&
+                         (kv_stride_h * (int64_t)es) % 16 == 0 && (kv_stride_l * (int64_t)es) % 16 == 0;
+    if (!aligned || q_stride_l < D || kv_stride_l < D || q_stride_h < 0 || kv_stride_h < 0 || stride8_h < 0 || scale_stride_h < 0) {
+        set_error("%s: unsupported layout (16-byte aligned pointers and strides, row strides >= head_dim)", who);
+        return RTK_EUNSUPPORTED;
+    }
+    if (!fits_buffer_offsets(1, (int64_t)Lq + AT_QB, D, 0, q_stride_l, es) ||
+        !fits_buffer_offsets(1, (int64_t)Lk + AT_KT, D, 0, kv_stride_l, es)) {
+        set_error("%s: unsupported extent: one head of q or k / v spans 2 GiB or more", who);
+        return RTK_EUNSUPPORTED;
+    }
+    const AttnPlan pl = attn_plan(Hq, Lq, (int)fp8kv_keys(Lk, L8), D, dtype);
+    if (pl.ws_bytes) {
+        if (!workspace || workspace_bytes < pl.ws_bytes) {
+            set_error("%s: workspace too small (%zu < %zu bytes; query rtk_attention_workspace_bytes_fp8kv)", who,
+                      workspace ? workspace_bytes : (size_t)0, pl.ws_bytes);
+            return RTK_EWORKSPACE;
+        }
+        RTK_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    }
+    const float c2 = scale * 1.44269504088896340736f;
+    const Archive8 a8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
+    void* ws = pl.ws_bytes ? workspace : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RTK_BF16)
+        return attn_launch_fp8kv<RTK_BF16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, out, Hq, Hkv, Lq, Lk,
+                                           q_offset, c2, ws, st);
+    return attn_launch_fp8kv<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, out, Hq, Hkv, Lq, Lk,
+                                      q_offset, c2, ws, st);
 }

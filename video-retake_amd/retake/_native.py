@@ -55,7 +55,15 @@ class CompactUnit(C.Structure):
                 ("pos_dst_stride", _i64)]
 
 
+class ArchiveUnit(C.Structure):
+    """rtk_archive_unit (include/retake_hip.h)."""
+    _fields_ = [("k_src", _vp), ("k_src_stride_h", _i64), ("v_src", _vp), ("v_src_stride_h", _i64), ("keep_idx", _vp),
+                ("pos_src", _vp), ("pos_src_stride", _i64), ("pos_dst", _vp), ("pos_dst_stride", _i64), ("k8", _vp),
+                ("v8", _vp), ("dst_stride_h", _i64), ("k_scale", _vp), ("v_scale", _vp), ("scale_stride_h", _i64)]
+
+
 COMPACT_K_ROTATE, COMPACT_K_COPY, COMPACT_K_INPLACE = 0, 1, 2
+ARCHIVE_MAX_UNITS = 28
 P2P_MAX_RANKS, IPC_HANDLE_BYTES = 16, 64
 
 
@@ -151,6 +159,11 @@ _SIGNATURES = {
     "rtk_attention_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "rtk_attention_forward": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz,
                                     _vp]),
+    "rtk_pivotkv_archive_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
+    "rtk_fp8kv_dequant": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
+    "rtk_attention_workspace_bytes_fp8kv": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_forward_fp8kv": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp,
+                                          _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),
     "rtk_p2p_free": (C.c_int, [_vp]),
     "rtk_p2p_export": (C.c_int, [_vp, _vp, C.POINTER(_sz)]),

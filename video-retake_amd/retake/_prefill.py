@@ -48,6 +48,22 @@ def expected_cache_tokens(config, input_length: int, chunk_size: Optional[int]) 
     return int(math.ceil(min(1.0, ratio) * input_length)) + int(chunk_size) + 2048
 
 
+def cache_reserves(config, input_length: int, chunk_size: Optional[int], segments: Optional[List[Segment]] = None) -> dict:
+    """Keyword arguments for build_kvcache: `reserve_tokens` as expected_cache_tokens gives it - or, with
+    longvideo_kwargs["kv_cache_dtype"] = "fp8_e4m3", where the kept video rows live in the fp8 archive and the 16-bit
+    buffers hold only what is not one: reserve_archive_tokens = ceil(ratio x video tokens) and reserve_tokens = the
+    non-video prompt tokens + one chunk in flight + room for generation.  `segments`: segment_token_runs of the prompt."""
+    out = {"reserve_tokens": expected_cache_tokens(config, input_length, chunk_size)}
+    kwargs = getattr(config, "longvideo_kwargs", None)
+    if out["reserve_tokens"] is None or not kwargs.get("kv_cache_dtype") or segments is None:
+        return out
+    video = sum(e - s for s, e, kind in segments if kind == "video")
+    ratio = float(kwargs["kvcache_compression_kwargs"].get("compression_ratio", 1.0))
+    out["reserve_archive_tokens"] = int(math.ceil(min(1.0, ratio) * video))
+    out["reserve_tokens"] = (input_length - video) + int(chunk_size) + 2048
+    return out
+
+
 def prompt_guided(config) -> bool:
     kwargs = getattr(config, "longvideo_kwargs", None)
     if not kwargs or not kwargs.get("kvcache_compression", False):

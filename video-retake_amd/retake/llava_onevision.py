@@ -239,8 +239,8 @@ def retake_LlavaOnevisionForConditionalGeneration_forward(
         _prefill.apply_dynamic_compression_ratio(self.config, input_ids.shape[1])
         if chunk_size is not None:
             modality_segments = self.segment_input_ids(input_ids)
-            past_key_values = build_kvcache(self.config, reserve_tokens=_prefill.expected_cache_tokens(
-                self.config, input_ids.shape[1], chunk_size))
+            past_key_values = build_kvcache(self.config, **_prefill.cache_reserves(
+                self.config, input_ids.shape[1], chunk_size, modality_segments))
             use_cache = True
 
     cfg = self.config

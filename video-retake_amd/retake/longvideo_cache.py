@@ -163,7 +163,7 @@ class _LayerStore:
     """One layer's pre-allocated K/V buffers [1, Hkv, cap, D] and position ids [P, cap].  The numbers live in a
     rtk_layer_state block (`c`) the library reads and advances itself (rtk_pivotkv_update / rtk_pivotkv_flush)."""
 
-    __slots__ = ("c", "cref", "_k", "_v", "_pos", "pending_event", "pos_ndim")
+    __slots__ = ("c", "cref", "_k", "_v", "_pos", "pending_event", "pos_ndim", "k8", "v8", "ks8", "vs8", "len8", "archive_at")
 
     def __init__(self):
         self.c = nv.LayerState()
@@ -171,6 +171,11 @@ class _LayerStore:
         self._k = self._v = self._pos = None
         self.pending_event = None  # worker-stream completion of this layer's scoring (overlap_streams > 0)
         self.pos_ndim = 0          # 3: ids are [3, 1, n] (M-RoPE), 2: [1, n]
+        # kv_cache_dtype="fp8_e4m3": the archive of the kept video rows - e4m3 codes uint8 [1, Hkv, cap8, D], one fp32
+        # scale per (kv head, row) [1, Hkv, cap8], rows in use, and the 16-bit `length` at the first archive write
+        self.k8 = self.v8 = self.ks8 = self.vs8 = None
+        self.len8 = 0
+        self.archive_at = -1
 
     def _sync(self):
         k, v, c = self._k, self._v, self.c
@@ -449,6 +454,8 @@ class _CacheView:
             return []
         if st.pending:
             self._o._flush()
+        if st.len8:
+            return self._o._dense(st, self._w)
         buf = st.k if self._w == "k" else st.v
         return buf[:, :, :st.length]
 
@@ -466,7 +473,7 @@ class _CacheView:
             self._o._adopt(len(self._o._layers) - 1, self._w, value)
 
 
-def chunk_attention(query_states, key_states, value_states, scaling=None, workspace=None, query_offset=None):
+def chunk_attention(query_states, key_states, value_states, scaling=None, workspace=None, query_offset=None, archive=None):
     """Attention of a chunk's queries over [compressed prefix | current chunk] in one HIP launch (rtk_attention_forward):
     what the reference's attention patches hand to torch / flash_attn after the cache update (qwen2_vl.py:88-117,
     :188-219, :303-358; llava_onevision.py:118-139).
@@ -479,7 +486,12 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
     keys the compressed cache holds: its width T gives query_offset = T - Lq (see native_attention).  Returns [1, Lq, Hq, D] (contiguous: `reshape(1, Lq, -1)` feeds o_proj), or None - nothing was
     touched, take the existing route - when the library declines the shape (RTK_EUNSUPPORTED).
 
-    workspace: optional dict the key-split scratch is kept in between calls (PivotKVCache.attention passes its own)."""
+    workspace: optional dict the key-split scratch is kept in between calls (PivotKVCache.attention passes its own).
+
+    archive: optional (k8, v8, k_scale, v_scale) - e4m3 codes uint8 [1, Hkv, L8, D] and fp32 scales [1, Hkv, L8] of rows that
+    PRECEDE key_states / value_states in the sequence (kv_cache_dtype="fp8_e4m3"; rtk_attention_forward_fp8kv, bf16 / fp16
+    with head_dim 128 only).  Every query row sees all of them; query_offset then counts over the L8 + Lk keys (default
+    L8 + Lk - Lq)."""
     nv.require_device(query_states, key_states, value_states)
     if query_states.dim() != 4 or key_states.dim() != 4 or value_states.dim() != 4 or query_states.shape[0] != 1:
         raise ValueError("chunk_attention takes [1, H, L, D] tensors (one unpadded sequence)")
@@ -497,8 +509,23 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
         return None
     code = nv.dtype_code(query_states)
     scale = float(D) ** -0.5 if scaling is None else float(scaling)
-    q_off = Lk - Lq if query_offset is None else int(query_offset)
-    need = nv.lib.rtk_attention_workspace_bytes(Hq, Hkv, Lq, Lk, D, code)
+    L8 = 0
+    if archive is not None:
+        k8, v8, ks8, vs8 = archive
+        nv.require_device(k8, v8, ks8, vs8)
+        if k8.dtype != torch.uint8 or v8.dtype != torch.uint8 or ks8.dtype != torch.float32 or vs8.dtype != torch.float32:
+            raise ValueError("archive = (codes uint8, codes uint8, scales float32, scales float32)")
+        if k8.dim() != 4 or k8.shape[:2] != (1, Hkv) or k8.shape[3] != D or v8.shape != k8.shape or v8.stride() != k8.stride() \
+                or ks8.shape != k8.shape[:3] or vs8.shape != ks8.shape or vs8.stride() != ks8.stride():
+            raise ValueError("archive codes must be [1, Hkv, L8, D] and scales [1, Hkv, L8], K and V laid out alike")
+        if k8.stride(3) != 1 or k8.stride(2) != D or ks8.stride(2) != 1:
+            raise ValueError("archive rows must be dense (D codes per row, one scale per row)")
+        L8 = k8.shape[2]
+    q_off = L8 + Lk - Lq if query_offset is None else int(query_offset)
+    if archive is not None:
+        need = nv.lib.rtk_attention_workspace_bytes_fp8kv(Hq, Hkv, Lq, Lk, L8, D, code)
+    else:
+        need = nv.lib.rtk_attention_workspace_bytes(Hq, Hkv, Lq, Lk, D, code)
     stream = nv.raw_stream(query_states.device.index)
     ws = None
     if need:
@@ -509,12 +536,60 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
             if workspace is not None:
                 workspace[key] = ws
     out = torch.empty((1, Lq, Hq, D), dtype=query_states.dtype, device=query_states.device)
+    if archive is not None:   # (an empty archive included: the library then runs the 16-bit call itself)
+        rc = nv.lib.rtk_attention_forward_fp8kv(
+            nv.ptr(query_states), query_states.stride(1), query_states.stride(2), nv.ptr(key_states), nv.ptr(value_states),
+            key_states.stride(1), key_states.stride(2), nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), L8, k8.stride(1),
+            ks8.stride(1), nv.ptr(out), Hq, Hkv, Lq, Lk, q_off - L8, D, code, scale, nv.ptr(ws), need, stream)
+        if rc == nv.RTK_EUNSUPPORTED:
+            return None
+        nv.check(rc, "rtk_attention_forward_fp8kv")
+        return out
     rc = nv.lib.rtk_attention_forward(nv.ptr(query_states), query_states.stride(1), query_states.stride(2),
                                       nv.ptr(key_states), nv.ptr(value_states), key_states.stride(1), key_states.stride(2),
                                       nv.ptr(out), Hq, Hkv, Lq, Lk, q_off, D, code, scale, nv.ptr(ws), need, stream)
     if rc == nv.RTK_EUNSUPPORTED:
         return None
     nv.check(rc, "rtk_attention_forward")
+    return out
+
+
+def fp8_quantize_rows(x: torch.Tensor):
+    """x [1, Hkv, L, 128] (bf16 / fp16, dense rows, any head stride) -> (codes uint8 [1, Hkv, L, 128], scales fp32
+    [1, Hkv, L]) by the rule of include/retake_hip.h "FP8 rows of the compressed cache", on the device
+    (rtk_pivotkv_archive_batched in copy mode with the identity selection).  Tools and diagnostics; the cache's flush
+    fills its archive with the same kernel."""
+    nv.require_device(x)
+    if x.dim() != 4 or x.shape[0] != 1 or x.stride(3) != 1 or x.stride(2) != x.shape[3]:
+        raise ValueError("fp8_quantize_rows takes [1, Hkv, L, D] with dense rows")
+    _, H, L, D = x.shape
+    codes = torch.empty((1, H, L, D), dtype=torch.uint8, device=x.device)
+    scales = torch.empty((1, H, L), dtype=torch.float32, device=x.device)
+    if L == 0:
+        return codes, scales
+    dummy_c, dummy_s = torch.empty_like(codes), torch.empty_like(scales)   # (the kernel archives a K and a V per unit)
+    units = (nv.ArchiveUnit * 1)()
+    u = units[0]
+    u.k_src, u.k_src_stride_h, u.v_src, u.v_src_stride_h = x.data_ptr(), x.stride(1), x.data_ptr(), x.stride(1)
+    u.k8, u.v8, u.dst_stride_h = codes.data_ptr(), dummy_c.data_ptr(), L * D
+    u.k_scale, u.v_scale, u.scale_stride_h = scales.data_ptr(), dummy_s.data_ptr(), L
+    with torch.cuda.device(x.device):
+        nv.check(nv.lib.rtk_pivotkv_archive_batched(units, 1, H, D, L, 0, nv.dtype_code(x), nv.COMPACT_K_COPY, None, 1.0, None, 0,
+                                                    nv.round_mode(x.dtype), nv.stream()), "rtk_pivotkv_archive_batched")
+    return codes, scales
+
+
+def fp8_dequantize_rows(codes: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None):
+    """codes uint8 [1, Hkv, L, 128] + scales fp32 [1, Hkv, L] (dense rows, any head stride) -> [1, Hkv, L, 128] of `dtype`
+    (rtk_fp8kv_dequant), written into `out` (dense rows, any head stride) when given."""
+    nv.require_device(codes, scales)
+    _, H, L, D = codes.shape
+    if out is None:
+        out = torch.empty((1, H, L, D), dtype=dtype, device=codes.device)
+    if L:
+        with torch.cuda.device(codes.device):
+            nv.check(nv.lib.rtk_fp8kv_dequant(nv.ptr(codes), codes.stride(1), nv.ptr(scales), scales.stride(1), nv.ptr(out),
+                                              out.stride(1), H, L, D, nv.dtype_code(out), nv.stream()), "rtk_fp8kv_dequant")
     return out
 
 
@@ -532,30 +607,44 @@ def native_attention(module, cache, query_states, key_states, value_states, atte
     positions and the patches slice it to the keys of the compressed cache, so row i sees keys j <= (T - Lq) + i, which for
     T > Lk is more than bottom-right causal over the Lk keys - the native route returns what the patch's own route would.
     A missing or differently shaped mask means something else on each patch's route: that call is declined."""
-    if getattr(cache, "attention_kernel", None) != "hip" or output_attentions:
+    if getattr(cache, "attention_kernel", None) != "hip":
         return None
+    fp8 = getattr(cache, "kv_cache_dtype", None) is not None
+
+    def decline(why):
+        # with fp8 rows the patch's own route would read the 16-bit rows only and silently miss the archive
+        if fp8:
+            raise NotImplementedError(f"kv_cache_dtype={cache.kv_cache_dtype!r}: the native chunk attention is the only "
+                                      f"route that reads the fp8 rows, and it does not serve this call: {why}")
+        return None
+
+    if output_attentions:
+        return decline("attention weights are wanted (output_attentions)")
     if query_states.shape[0] != 1 or not query_states.is_cuda:
-        return None
+        return decline("a padded batch or CPU tensors (one unpadded sequence on the GPU only)")
     if module.training and getattr(module, "attention_dropout", 0.0):
-        return None
+        return decline("attention dropout is active")
     cfg = getattr(module, "config", None)
     if (getattr(cfg, "use_sliding_window", False) and getattr(cfg, "sliding_window", None) is not None
             and module.layer_idx >= getattr(cfg, "max_window_layers", 0)):
-        return None
-    Lq, Lk = query_states.shape[2], key_states.shape[2]
+        return decline("the layer has an active sliding window")
+    layer_idx = getattr(module, "layer_idx", None)
+    Lq = query_states.shape[2]
+    Lk = key_states.shape[2] + (cache.archive_len(layer_idx) if fp8 else 0)   # keys of the whole sequence
     if isinstance(attention_mask, str):
         if attention_mask != "causal":
-            return None
+            return decline(f"attention mask {attention_mask!r}")
         offset = Lk - Lq
     else:
         if attention_mask is None or attention_mask.dim() != 4 or tuple(attention_mask.shape[:3]) != (1, 1, Lq) \
                 or attention_mask.shape[3] < Lk:
-            return None
+            return decline("a missing attention mask, or one that is not [1, 1, Lq, T >= Lk] (a padded batch)")
         offset = attention_mask.shape[3] - Lq
-    return cache.attention(query_states, key_states, value_states, scaling=scaling, query_offset=offset)
+    return cache.attention(query_states, key_states, value_states, scaling=scaling, query_offset=offset, layer_idx=layer_idx)
 
 
 ATTENTION_KERNELS = (None, "hip")
+KV_CACHE_DTYPES = (None, "fp8_e4m3")
 
 
 def _attention_kernel_of(config):
@@ -568,11 +657,14 @@ def _attention_kernel_of(config):
 class PivotKVCache(DynamicCache):
     """Drop-in for the reference's PivotKVCache (longvideo_cache.py:119-323)."""
 
-    def __init__(self, config, reserve_tokens: Optional[int] = None) -> None:
+    def __init__(self, config, reserve_tokens: Optional[int] = None, reserve_archive_tokens: Optional[int] = None) -> None:
         """reserve_tokens (not in the reference): tokens per layer this cache is expected to hold at most - compressed
         prompt + one uncompressed chunk + generation.  The first allocation of a layer takes that size, which saves the
-        geometric regrowth copies (~0.4 % of a 2048-frame prefill) and half the memory; without it buffers double."""
+        geometric regrowth copies (~0.4 % of a 2048-frame prefill) and half the memory; without it buffers double.
+        reserve_archive_tokens: the same for the fp8 archive of the kept video rows (kv_cache_dtype="fp8_e4m3"), whose
+        rows then do not count towards reserve_tokens."""
         self.reserve_tokens = int(reserve_tokens) if reserve_tokens else 0
+        self.reserve_archive_tokens = int(reserve_archive_tokens) if reserve_archive_tokens else 0
         self._layers: List[_LayerStore] = []
         self._batch: Optional[_Batch] = None
         self._last_slot = None
@@ -676,17 +768,92 @@ class PivotKVCache(DynamicCache):
         # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it): "hip" makes the attention
         # patches call `attention` below instead of torch / flash_attn; None (default) leaves them exactly as they are
         self.attention_kernel = None
+        # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it): "fp8_e4m3" keeps the kept rows of
+        # compressed video chunks as e4m3 codes + one power-of-two scale per (kv head, row) in a per-layer ARCHIVE beside the
+        # 16-bit buffers (include/retake_hip.h "FP8 rows of the compressed cache").  The 16-bit buffers go on holding what is
+        # not a kept video row - text, the in-flight chunk, decode rows; a flush quantises the kept rows into the archive
+        # and leaves the 16-bit length where it was.  Lossy, not in the reference; needs attention_kernel="hip".
+        self.kv_cache_dtype = None
         self.attention_calls = 0      # native attention launches so far (tests count them)
         self._attn_ws: Dict[Any, torch.Tensor] = {}
 
-    def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None):
+    def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None, layer_idx=None):
         """The chunk's attention over the views `update` / `update_pre_rope` / `append_pre_rope` returned, in one HIP
-        launch (see chunk_attention).  [1, Lq, Hq, D], or None when the library declines the shape."""
+        launch (see chunk_attention).  [1, Lq, Hq, D], or None when the library declines the shape.
+        kv_cache_dtype="fp8_e4m3": `layer_idx` names the layer whose archive precedes those views; query_offset counts
+        over archive + views; a shape the library declines raises NotImplementedError (no other route reads the archive)."""
+        archive = None
+        if self.kv_cache_dtype is not None:
+            if layer_idx is None:
+                raise ValueError("PivotKVCache.attention needs layer_idx when kv_cache_dtype is set")
+            archive = self.archive(layer_idx)
         out = chunk_attention(query_states, key_states, value_states, scaling=scaling, workspace=self._attn_ws,
-                              query_offset=query_offset)
+                              query_offset=query_offset, archive=archive)
         if out is not None:
             self.attention_calls += 1
+        elif self.kv_cache_dtype is not None:
+            raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r}: the native chunk attention refuses this shape "
+                                      f"({nv.lib.rtk_last_error().decode(errors='replace')}) and no other route reads the fp8 rows")
         return out
+
+    # ---- the fp8 archive (kv_cache_dtype="fp8_e4m3") -----------------------------------------------
+    def archive_len(self, layer_idx) -> int:
+        """Archived (fp8) rows of the layer; a pending chunk's kept rows are not among them until its flush."""
+        if layer_idx is None or layer_idx >= len(self._layers):
+            return 0
+        return self._layers[layer_idx].len8
+
+    def archive(self, layer_idx):
+        """(k8, v8, k_scale, v_scale) views of the layer's archived rows - codes uint8 [1, Hkv, len8, D], scales fp32
+        [1, Hkv, len8] - or None while nothing is archived."""
+        n = self.archive_len(layer_idx)
+        if not n:
+            return None
+        st = self._layers[layer_idx]
+        return st.k8[:, :, :n], st.v8[:, :, :n], st.ks8[:, :, :n], st.vs8[:, :, :n]
+
+    def _archive_reserve(self, st: _LayerStore, more: int, Hkv: int, D: int, device):
+        need = st.len8 + more
+        if st.k8 is not None and st.k8.shape[2] >= need:
+            return
+        cap = max(need, 2 * (st.k8.shape[2] if st.k8 is not None else 0), self.reserve_archive_tokens or 1024)
+        new = [torch.empty((1, Hkv, cap, D), dtype=torch.uint8, device=device) for _ in range(2)] + \
+              [torch.empty((1, Hkv, cap), dtype=torch.float32, device=device) for _ in range(2)]
+        if st.len8:
+            for t, old in zip(new, (st.k8, st.v8, st.ks8, st.vs8)):
+                t[:, :, :st.len8].copy_(old[:, :, :st.len8])
+        st.k8, st.v8, st.ks8, st.vs8 = new
+
+    def _dense(self, st: _LayerStore, which: str):
+        """key_cache[l] / value_cache[l] with archived rows: a dense DEQUANTISED COPY (a diagnostic, not a view) in the order
+        [16-bit rows before the first archive write | archive | remaining 16-bit rows].  That is sequence order - row for
+        row the order of position_cache[l] - for a prompt with ONE run of video chunks.  With text between two videos the
+        second video's kept rows still join the archive, i.e. they come BEFORE the text rows that preceded them in the
+        sequence, while position_cache[l] stays in sequence order: the two then no longer line up row for row (attention
+        is unaffected: every archived row is visible to every later query)."""
+        buf, codes, scales = (st.k, st.k8, st.ks8) if which == "k" else (st.v, st.v8, st.vs8)
+        Hkv, D, n8, at = buf.shape[1], buf.shape[3], st.len8, st.archive_at
+        out = torch.empty((1, Hkv, st.length + n8, D), dtype=buf.dtype, device=buf.device)
+        out[:, :, :at].copy_(buf[:, :, :at])
+        out[:, :, at + n8:].copy_(buf[:, :, at:st.length])
+        fp8_dequantize_rows(codes[:, :, :n8], scales[:, :, :n8], buf.dtype, out[:, :, at:at + n8])
+        return out
+
+    def _fp8_refuse(self, dtype, D, reforge, rot, has_ids=True):
+        """What kv_cache_dtype="fp8_e4m3" does not serve, raised by the first compressed update before anything is launched."""
+        if self.kv_cache_dtype is None:
+            return
+        if reforge and not has_ids:
+            raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r} with pos_embed_reforge needs the chunk's "
+                                      "position ids: the archive kernel re-rotates the kept keys at their new ids")
+        if dtype not in (torch.bfloat16, torch.float16):
+            raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r} needs a bfloat16 or float16 model, got {dtype}")
+        if D != 128:
+            raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r} needs head_dim 128, got {D}")
+        if reforge and rot is None:
+            raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r} with pos_embed_reforge needs a rotary module of "
+                                      "the static inv_freq * position kind (native RoPE): the archive kernel re-rotates the "
+                                      "kept keys itself")
 
     # ---- diagnostics of the most recent compressed update (the selection may still be deferred: flush first) ----
     @property
@@ -728,6 +895,10 @@ class PivotKVCache(DynamicCache):
                 row = 2 * st.k.shape[1] * st.k.shape[3] * st.k.element_size()
                 out["cache_rows"] += row * st.length
                 out["cache_headroom"] += nbytes(st.k) + nbytes(st.v) - row * st.length
+            if st.k8 is not None:   # fp8 archive: D codes + one fp32 scale per (kv head, row), K and V
+                row8 = 2 * st.k8.shape[1] * (st.k8.shape[3] + 4)
+                out["cache_rows"] += row8 * st.len8
+                out["cache_headroom"] += nbytes(st.k8) + nbytes(st.v8) + nbytes(st.ks8) + nbytes(st.vs8) - row8 * st.len8
             if st.pos is not None:
                 out["cache_rows"] += 8 * st.pos.shape[0] * st.pos_len
                 out["cache_headroom"] += nbytes(st.pos) - 8 * st.pos.shape[0] * st.pos_len
@@ -774,6 +945,9 @@ class PivotKVCache(DynamicCache):
                 self._adopt(i, "v", v)
 
     def _adopt(self, i: int, which: str, value):
+        if getattr(self, "kv_cache_dtype", None) is not None:
+            raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r}: key_cache / value_cache are dequantised copies "
+                                      "of [16-bit rows | archive]; assigning through them is not supported")
         st = self._layers[i]
         if st.pending:
             self._flush()
@@ -791,7 +965,7 @@ class PivotKVCache(DynamicCache):
         if len(self._layers) <= layer_idx or self._layers[layer_idx].k is None:
             return 0
         st = self._layers[layer_idx]
-        return st.length + (st.pending_keep if st.pending else 0)
+        return st.length + st.len8 + (st.pending_keep if st.pending else 0)
 
     def __len__(self):
         return len(self._layers)
@@ -836,7 +1010,7 @@ class PivotKVCache(DynamicCache):
         need = st.pos_len + more
         if st.pos is not None and st.pos.shape[1] >= need:
             return
-        cap = max(need, 2 * (st.pos.shape[1] if st.pos is not None else 0), 4096, self.reserve_tokens)
+        cap = max(need, 2 * (st.pos.shape[1] if st.pos is not None else 0), 4096, self.reserve_tokens + self.reserve_archive_tokens)
         buf = torch.empty((P, cap), dtype=torch.int64, device=device)
         if st.pos is not None and st.pos_len:
             buf[:, :st.pos_len].copy_(st.pos[:, :st.pos_len])
@@ -1099,7 +1273,7 @@ class PivotKVCache(DynamicCache):
             self._shift_failed(b)
         if b is None or not b.pending:
             return
-        if b.c_pending == len(b.pending) and self._flush_c(b):
+        if self.kv_cache_dtype is None and b.c_pending == len(b.pending) and self._flush_c(b):
             return
         self._flush_general(b)
 
@@ -1230,13 +1404,17 @@ class PivotKVCache(DynamicCache):
             defer = bool(getattr(b, "defer", False))
             rot = self._rotary(b.rotary_emb_fn, b.device) if (b.reforge and P and not defer) else None
             rope_in_kernel = rot is not None
-            if b.reforge and not rope_in_kernel and not defer:
+            if b.reforge and not rope_in_kernel and not defer and self.kv_cache_dtype is None:
                 b.ensure_tables()
                 n = (hi - lo + 1) * keep
                 pos2d, ld = b.pos_new[:, lo:hi + 1].reshape(P, n), n  # a copy when the slot range is partial
                 self._rope_tables(b.cos_new[lo * keep:], b.sin_new[lo * keep:], b.rotary_emb_fn, b.x_like, pos2d, ld,
                                   3 if P == 3 else 2, b.mrope_section, n, D)
-            if b.compact_sync is not None and not b.keep_all and (rope_in_kernel or defer or not b.reforge):
+            fp8 = self.kv_cache_dtype is not None
+            if fp8:   # the kept rows go to the archive (keep-all chunks included), the 16-bit tail is left to the next chunk
+                self._archive(b, layers, rot, dt)
+                layers_done, layers = layers, []
+            elif b.compact_sync is not None and not b.keep_all and (rope_in_kernel or defer or not b.reforge):
                 self._compact(b, layers, rot, defer, dt, es)
                 layers_done, layers = layers, []
             else:
@@ -1309,7 +1487,10 @@ class PivotKVCache(DynamicCache):
             st = self._layers[l]
             b.q_keep[l + off] = None
             b.q_units[l + off] = None
-            st.length += keep
+            if self.kv_cache_dtype is not None:
+                st.len8 += keep
+            else:
+                st.length += keep
             st.pending = 0
             st.pending_keep = 0
             st.c.mask = None
@@ -1335,6 +1516,48 @@ class PivotKVCache(DynamicCache):
                 b.compact_sync.zero_()
             except Exception:  # noqa: BLE001  (a device-side abort leaves the context unusable; the first error is what is raised)
                 pass
+
+    def _archive(self, b: _Batch, layers, rot, dt):
+        """The eviction scan of the pending layers into their fp8 archives, one launch (rtk_pivotkv_archive_batched;
+        reference :278-310): kept K re-rotated at the new ids and rounded to the model dtype as the compaction does (taken
+        from the tail as it is without reforge), kept V from the tail, both quantised per (kv head, row) into rows
+        [len8, len8 + keep) of the archive; ids to the position cache.  The 16-bit length does not advance."""
+        keep, D, Hkv, P = b.keep, b.D, b.Hkv, b.P
+        if b.reforge and (rot is None or not P or getattr(b, "defer", False)):
+            raise NotImplementedError("kv_cache_dtype='fp8_e4m3' with pos_embed_reforge needs position ids and the native RoPE, "
+                                      "and no deferred re-rotation")
+        units = (nv.ArchiveUnit * len(layers))()
+        for i, l in enumerate(layers):
+            st = self._layers[l]
+            sl = b.slot(l)
+            cap = st.k.shape[2]
+            tail = st.length * D * 2
+            self._archive_reserve(st, keep, Hkv, D, b.device)
+            if st.archive_at < 0:
+                st.archive_at = st.length
+            u = units[i]
+            if b.reforge:
+                u.k_src, u.k_src_stride_h = b.k_unrot[sl].data_ptr(), b.L * D
+            else:
+                u.k_src, u.k_src_stride_h = st.k.data_ptr() + tail, cap * D
+            u.v_src, u.v_src_stride_h = st.v.data_ptr() + tail, cap * D
+            u.keep_idx = None if b.keep_all else b.keep_idx[sl].data_ptr()
+            if b.reforge and P:  # bookkeeping (reference :308-309)
+                self._pos_reserve(st, P, 3 if P == 3 else 2, keep, b.device)
+                u.pos_src, u.pos_src_stride = b.pos_new.data_ptr() + sl * keep * 8, b.slots * keep
+                u.pos_dst, u.pos_dst_stride = st.pos.data_ptr() + st.pos_len * 8, st.pos.shape[1]
+            else:
+                u.pos_src = u.pos_dst = None
+            cap8 = st.k8.shape[2]
+            u.k8, u.v8, u.dst_stride_h = st.k8.data_ptr() + st.len8 * D, st.v8.data_ptr() + st.len8 * D, cap8 * D
+            u.k_scale, u.v_scale, u.scale_stride_h = st.ks8.data_ptr() + st.len8 * 4, st.vs8.data_ptr() + st.len8 * 4, cap8
+        mode = nv.COMPACT_K_ROTATE if b.reforge else nv.COMPACT_K_COPY
+        sec = (C.c_int * len(b.mrope_section))(*b.mrope_section) if (b.mrope_section and b.reforge) else None
+        nv.check(nv.lib.rtk_pivotkv_archive_batched(
+            units, len(layers), Hkv, D, keep, P if b.reforge else 0, dt, mode, nv.ptr(rot.inv) if b.reforge else None,
+            rot.scaling if b.reforge else 1.0, sec, len(sec) if sec is not None else 0,
+            nv.round_mode(b.x_like.dtype) if b.x_like is not None else nv.round_mode(b.dtype), nv.stream()),
+            "rtk_pivotkv_archive_batched")
 
     def _compact(self, b: _Batch, layers, rot, defer, dt, es):
         """The eviction scan of the pending layers as one in-place launch (rtk_pivotkv_compact_batched; reference
@@ -1602,6 +1825,7 @@ class PivotKVCache(DynamicCache):
                                                          and key_states.dtype in (torch.bfloat16, torch.float16)):
                 return None   # (the reference's rounding chain scores the reference's operands)
             Hq, D = query_states.shape[1], query_states.shape[3]
+            self._fp8_refuse(key_states.dtype, D, True, rot)
             b = self._get_batch(layer_idx, Hq, key_states.shape[1], L, D, keep_len, 3 if position_ids.ndim == 3 else 1,
                                 key_states.dtype, dev)
             if not b.c_capable:
@@ -1666,7 +1890,7 @@ class PivotKVCache(DynamicCache):
             self._flush()
         st = self.reserve(layer_idx, n, k)
         self._pos_reserve(st, P, pos.ndim, n, dev)
-        if st.c.pos_len != st.c.length:   # a cache whose earlier rows carry no ids (filled without reforging): not ours
+        if st.c.pos_len != st.c.length + st.len8:   # a cache whose earlier rows carry no ids (filled without reforging): not ours
             return None
         io = self._aio
         io.q, io.q_stride_h, io.q_stride_l = q.data_ptr(), qs[1], qs[2]
@@ -1760,6 +1984,8 @@ class PivotKVCache(DynamicCache):
         if keep_len > q_len:   # compression_ratio > 1: the reference's topk refuses it (:276)
             raise RuntimeError(f"PivotKVCache.update: selected index k out of range (keep {keep_len} of {q_len} tokens)")
         reforge = bool(self.pos_embed_reforge)
+        self._fp8_refuse(key_states.dtype, D, reforge, self._rotary(rotary_emb_fn, dev) if reforge else None,
+                         position_ids is not None)
 
         mask = getattr(self, "keypatches_mask_chunk", None)
         if mask is not None:
@@ -1936,14 +2162,28 @@ class PivotKVCache(DynamicCache):
         return st.k[:, :, :P0 + n_new], st.v[:, :, :P0 + n_new]
 
 
-def build_kvcache(config, reserve_tokens: Optional[int] = None):
-    """DynamicCache unless longvideo_kwargs enables 'pivotkv' compression (reference :326-334).  reserve_tokens: optional
-    capacity hint for the pre-allocated PivotKV cache (see PivotKVCache.__init__)."""
+def _kv_cache_dtype_of(config):
+    kind = config.longvideo_kwargs.get("kv_cache_dtype", None)
+    if kind not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype must be None or 'fp8_e4m3', got {kind!r}")
+    return kind
+
+
+def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_tokens: Optional[int] = None):
+    """DynamicCache unless longvideo_kwargs enables 'pivotkv' compression (reference :326-334).  reserve_tokens /
+    reserve_archive_tokens: optional capacity hints for the pre-allocated PivotKV cache (see PivotKVCache.__init__)."""
     if getattr(config, "longvideo_kwargs", None) is None or not config.longvideo_kwargs.get("kvcache_compression", False):
         return DynamicCache()
     compression_method = config.longvideo_kwargs["kvcache_compression_kwargs"]["compression_method"]
     if compression_method.lower() == "pivotkv":
-        cache = PivotKVCache(config, reserve_tokens=reserve_tokens)
+        cache = PivotKVCache(config, reserve_tokens=reserve_tokens, reserve_archive_tokens=reserve_archive_tokens)
         cache.attention_kernel = _attention_kernel_of(config)
+        cache.kv_cache_dtype = _kv_cache_dtype_of(config)
+        if cache.kv_cache_dtype is not None:
+            if cache.attention_kernel != "hip":
+                raise ValueError("kv_cache_dtype='fp8_e4m3' needs attention_kernel='hip': the third-party attention routes "
+                                 "cannot read the fp8 rows")
+            if cache.defer_rerotation:
+                raise ValueError("kv_cache_dtype='fp8_e4m3' does not serve defer_rerotation (the sharded prefill)")
         return cache
     raise NotImplementedError

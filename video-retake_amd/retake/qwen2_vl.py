@@ -164,10 +164,19 @@ def retake_Qwen2VLFlashAttention2_forward(self, hidden_states, attention_mask=No
             if attention_mask is not None:
                 attention_mask = attention_mask[:, slicing_tokens:]
                 attention_mask = torch.cat([attention_mask, torch.ones_like(attention_mask[:, -1:])], dim=-1)
+    fp8_rows = getattr(past_key_value, "kv_cache_dtype", None) is not None
+    native_ok = attention_mask is None and self.is_causal and not getattr(self, "_flash_attn_uses_top_left_mask", False)
+    if fp8_rows and not native_ok:
+        # (before the cache is touched) the flash-attn route below would attend over the 16-bit rows `update` returns and
+        # silently miss the fp8 archive
+        raise NotImplementedError(
+            f"kv_cache_dtype={past_key_value.kv_cache_dtype!r}: the native chunk attention is the only route that reads the "
+            "fp8 rows, and it does not serve this call: "
+            + ("a 2-D padding mask (a padded batch)" if attention_mask is not None else
+               "a non-causal layer" if not self.is_causal else "a flash-attn build with top-left causal masks"))
     query_states, key_states, value_states = _qkv_and_cache_update(self, hidden_states, position_ids, past_key_value,
                                                                    cache_position)
-    if getattr(past_key_value, "attention_kernel", None) == "hip" and attention_mask is None and self.is_causal \
-            and not getattr(self, "_flash_attn_uses_top_left_mask", False):
+    if getattr(past_key_value, "attention_kernel", None) == "hip" and native_ok:
         # (build) the native route, before repeat_kv, with this patch's own fp32 -> weight-dtype cast (reference :318-333)
         # so that it returns what the flash-attn route would; None = declined, the route below
         native_qkv = (query_states, key_states, value_states)
@@ -364,8 +373,8 @@ def retake_Qwen2VLForConditionalGeneration_forward(
         _prefill.apply_dynamic_compression_ratio(self.config, input_ids.shape[1])
         if chunk_size is not None:
             modality_segments = self.segment_input_ids(input_ids)
-            past_key_values = build_kvcache(self.config, reserve_tokens=_prefill.expected_cache_tokens(
-                self.config, input_ids.shape[1], chunk_size))
+            past_key_values = build_kvcache(self.config, **_prefill.cache_reserves(
+                self.config, input_ids.shape[1], chunk_size, modality_segments))
             use_cache = True
 
     output_attentions = output_attentions if output_attentions is not None else self.config.output_attentions

@@ -255,6 +255,15 @@ class _Side:
         self.ws: Dict[str, torch.Tensor] = {}
 
 
+class _Update:
+    """One stage-by-stage update (PivotKVCache._update_general), handed from stage to stage: the batch, the layer with
+    its slot and store, the operands, the chunk's tail in the layer's buffers, and what the stages make."""
+
+    __slots__ = ("b", "layer", "slot", "st",
+                 "q", "k", "v", "ids", "mask", "a_scale", "k_tail", "v_tail",
+                 "pos_in", "cos", "sin")   # ids as [P, L]; cos / sin tables of the chunk's ids
+
+
 class _Rotary:
     """What the kernels need of an inv_freq * position rotary module (native RoPE): its inv_freq on the device and
     attention_scaling.  HF builds one rotary module per attention layer; modules with equal contents share an entry."""
@@ -269,6 +278,15 @@ def _version_of(t: torch.Tensor):
     """The tensor's version counter, None for tensors that do not keep one (created under torch.inference_mode()): for
     those a shift the previous layer's launch has already applied is simply applied again (it is idempotent)."""
     return None if t.is_inference() else t._version
+
+
+def _on_device(index: int, fn, *args):
+    """fn(*args) with device `index` current: entered through torch.cuda.device only when it is not already (the usual
+    case on the per-layer paths, where the context manager would cost more than the call)."""
+    if nv.current_device() == index:
+        return fn(*args)
+    with torch.cuda.device(index):
+        return fn(*args)
 
 
 def _inv_stamp(rotary_emb_fn):
@@ -300,6 +318,13 @@ class _Batch:
             | (self.score_dt & ~0xFF)
         self.Hkv, self.L, self.D, self.dtype, self.device = Hkv, L, D, dtype, device
         self.Hq = Hq
+        # constants of the geometry every launch of the batch restates: bytes per payload element, the layout of the ids
+        # in the position cache ([3, 1, n] M-RoPE ids or [1, n]) and the 16-bit format intermediate results are rounded to
+        # (the library's dtype code is c.dtype below)
+        self.esize = 4 if dtype == torch.float32 else 2
+        self.pos_ndim = 3 if P == 3 else 2
+        self.round_mode = nv.round_mode(dtype)
+        self.defer_select = L >= 512   # the chip-wide selection kernels; smaller chunks select inside update
         self.keep_idx = torch.arange(keep, dtype=torch.int64, device=device).repeat(slots, 1) if keep_all \
             else torch.empty((slots, keep), dtype=torch.int64, device=device)
         self.pos_new = torch.empty((P, slots, keep), dtype=torch.int64, device=device) if P else None
@@ -331,6 +356,7 @@ class _Batch:
         self.rotary_emb_fn = None
         self.rot: Optional[_Rotary] = None
         self.mrope_section = None
+        self.sec = None            # ... as the ctypes array the launches take (written by PivotKVCache._bind_rotary)
         self.x_like = None
         self.mask_obj = None       # the last key-patch mask tensor that passed validation, and its address
         self.mask_ptr = None
@@ -360,7 +386,7 @@ class _Batch:
         c.Hq, c.Hkv, c.L, c.D, c.keep, c.P, c.slots = Hq, Hkv, L, D, keep, P, slots
         c.dtype = nv.RTK_BF16 if dtype == torch.bfloat16 else (nv.RTK_F16 if dtype == torch.float16 else nv.RTK_F32)
         c.score_dtype, c.prep_dtype = self.score_dt, self.prep_dt
-        c.reforge, c.keep_all, c.round_mode = int(reforge), int(keep_all), nv.round_mode(dtype)
+        c.reforge, c.keep_all, c.round_mode = int(reforge), int(keep_all), self.round_mode
         c.rs_n, c.skip_masked, c.batched_passes = self.rs_n.value, int(skip_masked), int(self.batched_passes)
         c.partial_floats = self.part_floats
         c.keep_idx = self.keep_idx.data_ptr()
@@ -668,7 +694,7 @@ class PivotKVCache(DynamicCache):
         self._layers: List[_LayerStore] = []
         self._batch: Optional[_Batch] = None
         self._last_slot = None
-        self._pos_layers = 0
+        self._pos_layers = 0          # len(position_cache) of the reference (skipped layers are padded with [])
         self._kview = _CacheView(self, "k")
         self._vview = _CacheView(self, "v")
         super().__init__()
@@ -759,11 +785,9 @@ class PivotKVCache(DynamicCache):
             raise ValueError("flush_every_layers must be >= 0")
         self._sides: List[_Side] = []
         self._side_rr = 0
-        self._pos_layers = 0          # len(position_cache) of the reference (skipped layers are padded with [])
         self.num_evicted_tokens: List[int] = []
         self.keypatches_mask_chunk = None
         self._ws: Dict[str, torch.Tensor] = {}
-        self._batch: Optional[_Batch] = None
         self._warned = False
         # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it): "hip" makes the attention
         # patches call `attention` below instead of torch / flash_attn; None (default) leaves them exactly as they are
@@ -1205,13 +1229,12 @@ class PivotKVCache(DynamicCache):
         self._rotaries[id(rotary_emb_fn)] = (rotary_emb_fn, entry, _inv_stamp(rotary_emb_fn))
         return entry
 
-    def _rope_tables(self, cos_t, sin_t, rotary_emb_fn, x_like, pos2d, pos_ld, ndim, mrope_section, n, D):
+    def _rope_tables(self, cos_t, sin_t, rotary_emb_fn, x_like, pos2d, pos_ld, ndim, sec, n, D):
         """fp32 [n, D] cos/sin tables of the ids pos2d [P, n] (row stride pos_ld), section-merged
-        (reference :249 / :298 + :68-74), written into cos_t / sin_t."""
+        (reference :249 / :298 + :68-74; `sec`: the batch's M-RoPE sections array or None), into cos_t / sin_t."""
         dev = x_like.device
         P = pos2d.shape[0]
-        sec = (C.c_int * len(mrope_section))(*mrope_section) if mrope_section else None
-        nsec = len(mrope_section) if mrope_section else 0
+        nsec = len(sec) if sec is not None else 0
         s = nv.stream()
         rot = self._rotary(rotary_emb_fn, dev)
         if rot is not None:
@@ -1288,23 +1311,233 @@ class PivotKVCache(DynamicCache):
             for l in layers:
                 st = L_[l]
                 if st.c.pos_len + b.keep > st.c.pos_cap:
-                    self._pos_reserve(st, b.P, 3 if b.P == 3 else 2, b.keep, b.device)
+                    self._pos_reserve(st, b.P, b.pos_ndim, b.keep, b.device)
                 elif st.pos_ndim == 0:
-                    st.pos_ndim = 3 if b.P == 3 else 2
+                    st.pos_ndim = b.pos_ndim
         states = (C.c_void_p * n)(*[L_[l].cref for l in layers])
         slots = (C.c_int32 * n)(*[b.slot(l) for l in layers])
         idx = b.dev_index
         self._order_compaction(b)
-        if nv.current_device() == idx:
-            rc = nv.lib.rtk_pivotkv_flush(b.cref, states, slots, n, nv.raw_stream(idx))
-        else:
-            with torch.cuda.device(b.device):
-                rc = nv.lib.rtk_pivotkv_flush(b.cref, states, slots, n, nv.raw_stream(idx))
+        rc = _on_device(idx, nv.lib.rtk_pivotkv_flush, b.cref, states, slots, n, nv.raw_stream(idx))
         if rc == nv.RTK_EUNSUPPORTED:
             return False
         if rc:
             self._reset_compaction(b)
         nv.check(rc, "rtk_pivotkv_flush")
+        self._end_flush(b, layers)
+        return True
+
+    def _flush_general(self, b: _Batch):
+        """The same chain launched stage by stage (reference :260-318, top to bottom): worker streams, small chunks
+        (selection inside update), rotary modules that have to be called for the new ids' tables, the fp8 archive."""
+        # taken off the batch first: the id shift below finds the last layer's chunk pending and re-enters _flush
+        layers, b.pending = b.pending, []
+        # slot of a layer: the layer itself, or (flush_every_layers) layer mod slots - within one flush slots ascend with the
+        # layers, so the offset is one number (the score runs and the range of the new-id tables rely on it)
+        assert all(b.slot(l) - l == b.slot(layers[0]) - layers[0] for l in layers)
+        fp8 = self.kv_cache_dtype is not None
+        with torch.cuda.device(b.device):
+            self._wait_workers(layers)
+            self._shift_pending_ids(b, layers[-1])
+            self._score_unscored(b, layers)
+            self._select_unselected(b, layers)
+            # reforge: K is re-rotated at the NEW ids (reference :297-306).  With the native RoPE the scan's kernel
+            # computes their cos/sin itself; a third-party rotary module is called once for every pending slot and its
+            # section-merged fp32 tables are handed over.
+            rot = self._rotary(b.rotary_emb_fn, b.device) if (b.reforge and b.P and not b.defer) else None
+            if b.reforge and rot is None and not b.defer and not fp8:
+                self._new_id_tables(b, layers)
+            if fp8:   # the kept rows go to the archive (keep-all chunks included), the 16-bit tail is left to the next chunk
+                self._archive(b, layers, rot)
+            elif b.compact_sync is not None and not b.keep_all and (rot is not None or b.defer or not b.reforge):
+                self._compact(b, layers, rot)
+            else:
+                self._evict_staged(b, layers, rot)
+        # rtk_pivotkv_flush does exactly this itself for its units (pivotkv_update.hip:646-654, 730-738)
+        self._advance_layers(b, layers, fp8)
+        self._end_flush(b, layers)
+
+    def _wait_workers(self, layers):
+        """The current stream waits for the layers whose chunk was scored on a worker stream (overlap_streams > 0)."""
+        main = torch.cuda.current_stream()
+        for l in layers:
+            st = self._layers[l]
+            if st.pending_event is not None:
+                main.wait_event(st.pending_event)
+                st.pending_event = None
+
+    def _shift_pending_ids(self, b: _Batch, last_layer: int):
+        """Pre-RoPE units: the caller's ids tensor takes the last layer's continuity shift now (qwen2_vl.py:73; what the
+        reference's layer loop leaves behind) - before the flush appends that layer's new ids."""
+        if b.shift_ids is not None:
+            ids, b.shift_ids = b.shift_ids, None
+            b.c.shift_row = None
+            self._shift_row(ids, last_layer)
+
+    def _score_unscored(self, b: _Batch, layers):
+        """The two matrix passes (reference :260-268) of the units `update` left unscored: every run of consecutive
+        slots whose queries live alike in one launch per kernel.  (Keep-all units are never scored: `update` marks them.)"""
+        unscored = sorted(l for l in layers if l not in b.scored)
+        if not unscored:
+            return
+        off = b.slot(layers[0]) - layers[0]   # (one number: see _flush_general)
+
+        def qkey(l):   # queries scored where they lie (prologue route) carry their strides; packed ones None
+            t = b.q_keep[l + off]
+            return None if t is None else t.stride()
+
+        D, Hkv = b.D, b.Hkv
+        i = 0
+        while i < len(unscored):
+            j = i
+            while j + 1 < len(unscored) and unscored[j + 1] == unscored[j] + 1 and qkey(unscored[j + 1]) == qkey(unscored[i]):
+                j += 1
+            l0, n = unscored[i], j - i + 1
+            mptr = [b.masks.get(l) for l in range(l0, l0 + n)]
+            l0 += off     # from here on: the run's first SLOT
+            km = (C.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in mptr]) \
+                if self.skip_masked_columns and any(m is not None for m in mptr) else None
+            qk = [b.q_keep[l] for l in range(l0, l0 + n)]
+            qu, qsh, qsl = None, 0, 0
+            if qk[0] is not None:   # units of the prologue route whose queries are scored in place
+                qu = (C.c_void_p * n)(*[t.data_ptr() for t in qk])
+                qsh, qsl = qk[0].stride(1), qk[0].stride(2)
+            nv.check(nv.lib.rtk_pivotkv_score_passes_batched_q(
+                C.c_void_p(b.score_ws_base + l0 * b.ws_stride), b.ws_stride,
+                nv.ptr(b.k_unrot[l0]) if b.reforge else None, b.L * D * Hkv * b.esize,
+                nv.ptr(b.partials[l0]), b.part_floats, n, b.Hq, Hkv, b.L, D, b.score_dt,
+                km, nv.ptr(b.key_index[l0]) if km is not None else None, qu, qsh, qsl, nv.stream()),
+                "rtk_pivotkv_score_passes_batched")
+            i = j + 1
+
+    def _select_unselected(self, b: _Batch, layers):
+        """Mask override + top-k + id gather / rescale (reference :269-295) of the units not selected inside `update`,
+        in one launch.  Keep-all batches: the selection is the identity (keep_idx is set once per batch) and the units
+        of the one-call path carry their ids in pos_old only: ids x 1.0 = the ids (:288-292)."""
+        todo = [l for l in layers if l not in b.selected]
+        if not todo:
+            return
+        P, keep = b.P, b.keep
+        if b.keep_all:
+            if P:
+                for l in todo:
+                    b.pos_new[:, b.slot(l)].copy_(b.pos_old[b.slot(l)])
+            return
+        su = (nv.SelectUnit * len(todo))()
+        for u, l in zip(su, todo):
+            sl = b.slot(l)
+            u.partial = b.partials[sl].data_ptr()
+            u.score = b.score[sl].data_ptr()
+            m = b.masks.get(l)
+            u.mask = m.data_ptr() if m is not None else None
+            u.pos = b.pos_old[sl].data_ptr() if P else None
+            u.keep_idx = b.keep_idx[sl].data_ptr()
+            u.rank = None
+            u.pos_out = (b.pos_new.data_ptr() + sl * keep * 8) if P else None
+            u.workspace = b.sel_ws[sl].data_ptr()
+        nv.check(nv.lib.rtk_pivotkv_select_batched(su, len(todo), b.Hkv, b.rs_n.value, b.Hq // b.Hkv, b.L, keep, P,
+                                                   int(b.reforge), b.slots * keep, b.score_dt, nv.stream()),
+                 "rtk_pivotkv_select_batched")
+
+    def _new_id_tables(self, b: _Batch, layers):
+        """Section-merged fp32 cos / sin tables of the NEW ids of every pending slot, from a rotary module that has
+        to be called (reference :298), for the staged scan."""
+        b.ensure_tables()
+        keep, P = b.keep, b.P
+        lo, hi = b.slot(min(layers)), b.slot(max(layers))
+        n = (hi - lo + 1) * keep
+        pos2d = b.pos_new[:, lo:hi + 1].reshape(P, n)   # a copy when the slot range is partial
+        self._rope_tables(b.cos_new[lo * keep:], b.sin_new[lo * keep:], b.rotary_emb_fn, b.x_like, pos2d, n, b.pos_ndim,
+                          b.sec, n, b.D)
+
+    def _scan_unit(self, b: _Batch, l: int, u):
+        """What the three scans share of layer l's unit.  Fills the fields every unit type names alike - the K source
+        (the slot's un-rotated rows with reforge, else the tail), keep_idx, and the position-id bookkeeping (reference
+        :308-309; the layer's id buffer is grown first) - and returns (layer store, slot, K tail, V tail, their head
+        stride in elements); the tail is where the append put the chunk: rows [length, length + L) of the buffers."""
+        st, sl = self._layers[l], b.slot(l)
+        keep, D = b.keep, b.D
+        tail, stride_h = st.length * D * b.esize, st.k.shape[2] * D
+        k_tail, v_tail = st.k.data_ptr() + tail, st.v.data_ptr() + tail
+        if b.reforge:
+            u.k_src, u.k_src_stride_h = b.k_unrot[sl].data_ptr(), b.L * D
+        else:
+            u.k_src, u.k_src_stride_h = k_tail, stride_h
+        u.keep_idx = b.keep_idx[sl].data_ptr()
+        if b.reforge and b.P:
+            self._pos_reserve(st, b.P, b.pos_ndim, keep, b.device)
+            u.pos_src, u.pos_src_stride = b.pos_new.data_ptr() + sl * keep * 8, b.slots * keep
+            u.pos_dst, u.pos_dst_stride = st.pos.data_ptr() + st.pos_len * 8, st.pos.shape[1]
+        else:
+            u.pos_src = u.pos_dst = None
+        return st, sl, k_tail, v_tail, stride_h
+
+    def _evict_staged(self, b: _Batch, layers, rot):
+        """The eviction scan of the pending layers as two launches (reference :278-318): the evict launch
+        (rtk_pivotkv_evict_batched[_rope]) gathers the kept rows - K re-rotated at the new ids straight into the cache with reforge, else K and V into
+        the staging rows - and rtk_pivotkv_place_batched puts the staged rows at the head of the tail."""
+        keep, D, Hkv, es, dt = b.keep, b.D, b.Hkv, b.esize, b.c.dtype
+        tables = b.reforge and rot is None and not b.defer   # of a called rotary module (_new_id_tables)
+        if not b.keep_all:
+            b.ensure_staging()
+        units = (nv.EvictUnit * len(layers))()
+        places = (nv.PlaceUnit * (0 if b.keep_all else len(layers) * (1 if b.reforge else 2)))()
+        nc = 0
+        for u, l in zip(units, layers):
+            st, sl, k_tail, v_tail, stride_h = self._scan_unit(b, l, u)
+            staged = []   # (staging rows, tail) of this unit: K unless it goes straight into the cache, V
+            if b.reforge:
+                if tables:
+                    u.cos_new = b.cos_new.data_ptr() + sl * keep * D * 4
+                    u.sin_new = b.sin_new.data_ptr() + sl * keep * D * 4
+                u.k_dst, u.k_dst_stride_h = k_tail, stride_h  # straight into the cache
+            elif not b.keep_all:
+                u.k_dst, u.k_dst_stride_h = b.k_stage[sl].data_ptr(), keep * D
+                staged.append((u.k_dst, k_tail))
+            u.v_src, u.v_src_stride_h = v_tail, stride_h
+            if not b.keep_all:   # (keep-all: every row already sits where the append put it)
+                u.v_dst, u.v_dst_stride_h = b.v_stage[sl].data_ptr(), keep * D
+                staged.append((u.v_dst, v_tail))
+            for stage, tail in staged:
+                p = places[nc]
+                p.stage, p.stage_stride_h_bytes = stage, keep * D * es
+                p.tail, p.tail_stride_h_bytes = tail, stride_h * es
+                p.keep_idx = u.keep_idx
+                nc += 1
+        s = nv.stream()
+        if rot is not None:
+            nv.check(nv.lib.rtk_pivotkv_evict_batched_rope(units, len(layers), Hkv, D, keep, b.P, dt, nv.ptr(rot.inv),
+                                                           rot.scaling, b.sec, b.c.nsec, b.round_mode, 1, s),
+                     "rtk_pivotkv_evict_batched_rope")
+        elif b.reforge or not b.keep_all:   # (deferred re-rotation: every kept un-rotated K row is copied, bit 1)
+            nv.check(nv.lib.rtk_pivotkv_evict_batched(units, len(layers), Hkv, D, keep, b.P if b.reforge else 0, dt,
+                                                      3 if b.defer else 1, s), "rtk_pivotkv_evict_batched")
+        # kept rows -> head of the tail: in place, except the ~ratio of them whose source lies inside the destination
+        # range (parked in the staging rows by the launch above) - reference :313-318 without a full second copy
+        if nc:
+            nv.check(nv.lib.rtk_pivotkv_place_batched(places, nc, Hkv, keep, D, dt, s), "rtk_pivotkv_place_batched")
+
+    def _advance_layers(self, b: _Batch, layers, fp8: bool):
+        """The layers' numbers after a stage-by-stage flush: the kept rows are committed (to the archive with fp8 rows),
+        nothing is pending."""
+        keep, ids = b.keep, b.reforge and b.P
+        for l in layers:
+            st = self._layers[l]
+            b.q_units[b.slot(l)] = None
+            if fp8:
+                st.len8 += keep
+            else:
+                st.length += keep
+            st.pending = 0
+            st.pending_keep = 0
+            st.c.mask = None
+            if ids:
+                st.pos_len += keep
+
+    def _end_flush(self, b: _Batch, layers):
+        """The batch's own bookkeeping of a completed flush, whichever route ran it: nothing is pending, what `update`
+        noted per unit (masks, scored / selected marks, the ids tensor to shift, queries kept alive) is dropped, and
+        the position cache covers the flushed layers (reference :308-309)."""
         b.pending = []
         b.c_pending = 0
         b.masks.clear()
@@ -1314,189 +1547,7 @@ class PivotKVCache(DynamicCache):
         for l in layers:
             b.q_keep[b.slot(l)] = None
         if b.reforge and b.P:
-            self._pos_layers = max(self._pos_layers, layers[-1] + 1)
-        return True
-
-    def _flush_general(self, b: _Batch):
-        """The same chain launched stage by stage: worker streams, small chunks (selection inside update), rotary
-        modules that have to be called for the tables of the new ids."""
-        layers, b.pending = b.pending, []
-        b.c_pending = 0
-        # slot of a layer: the layer itself, or (flush_every_layers) layer mod slots - within one flush slots ascend with the
-        # layers, so the offset is one number
-        off = b.slot(layers[0]) - layers[0]
-        assert all(b.slot(l) == l + off for l in layers)
-        if b.shift_ids is not None:   # pre-RoPE units: the caller's ids tensor takes the last layer's shift now
-            ids, b.shift_ids = b.shift_ids, None
-            b.c.shift_row = None
-            self._shift_row(ids, layers[-1])
-        if not b.keep_all:
-            b.ensure_scoring()
-        keep, D, Hkv, P = b.keep, b.D, b.Hkv, b.P
-        if b.keep_all:   # units of the one-call path carry their ids in pos_old only: ids x 1.0 = the ids (:288-292)
-            for l in layers:
-                if l not in b.selected:
-                    if P:
-                        b.pos_new[:, l + off].copy_(b.pos_old[l + off])
-                    b.selected.add(l)
-                    b.scored.add(l)
-        es = 4 if b.dtype == torch.float32 else 2
-        dt = nv.RTK_BF16 if b.dtype == torch.bfloat16 else (nv.RTK_F16 if b.dtype == torch.float16 else nv.RTK_F32)
-        with torch.cuda.device(b.device):
-            main = torch.cuda.current_stream()
-            for l in layers:
-                st = self._layers[l]
-                if st.pending_event is not None:  # scored on a worker stream
-                    main.wait_event(st.pending_event)
-                    st.pending_event = None
-            unscored = sorted(l for l in layers if l not in b.scored)
-            i = 0
-            def qkey(l):   # queries scored where they lie (prologue route) carry their strides; packed ones None
-                t = b.q_keep[l + off]
-                return None if t is None else t.stride()
-
-            while i < len(unscored):  # the matrix passes of every run of consecutive slots whose queries live alike
-                j = i                   # in one launch per kernel (:260-268)
-                while j + 1 < len(unscored) and unscored[j + 1] == unscored[j] + 1 and qkey(unscored[j + 1]) == qkey(unscored[i]):
-                    j += 1
-                l0, n = unscored[i], j - i + 1
-                mptr = [b.masks.get(l) for l in range(l0, l0 + n)]
-                l0 += off     # from here on: the run's first SLOT
-                km = (C.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in mptr]) \
-                    if self.skip_masked_columns and any(m is not None for m in mptr) else None
-                qk = [b.q_keep[l] for l in range(l0, l0 + n)]
-                qu, qsh, qsl = None, 0, 0
-                if qk[0] is not None:   # units of the prologue route whose queries are scored in place
-                    qu = (C.c_void_p * n)(*[t.data_ptr() for t in qk])
-                    qsh, qsl = qk[0].stride(1), qk[0].stride(2)
-                nv.check(nv.lib.rtk_pivotkv_score_passes_batched_q(
-                    C.c_void_p(b.score_ws_base + l0 * b.ws_stride), b.ws_stride,
-                    nv.ptr(b.k_unrot[l0]) if b.reforge else None, b.L * D * Hkv * es,
-                    nv.ptr(b.partials[l0]), b.part_floats, n, b.Hq, Hkv, b.L, D, b.score_dt,
-                    km, nv.ptr(b.key_index[l0]) if km is not None else None, qu, qsh, qsl, nv.stream()),
-                    "rtk_pivotkv_score_passes_batched")
-                i = j + 1
-            b.scored.clear()
-            todo = [l for l in layers if l not in b.selected]
-            if todo:  # mask override + top-k + id gather / rescale of every layer of the chunk (reference :269-295)
-                su = (nv.SelectUnit * len(todo))()
-                for i, l in enumerate(todo):
-                    u = su[i]
-                    sl = l + off
-                    u.partial = b.partials[sl].data_ptr()
-                    u.score = b.score[sl].data_ptr()
-                    m = b.masks.get(l)
-                    u.mask = m.data_ptr() if m is not None else None
-                    u.pos = b.pos_old[sl].data_ptr() if P else None
-                    u.keep_idx = b.keep_idx[sl].data_ptr()
-                    u.rank = None
-                    u.pos_out = (b.pos_new.data_ptr() + sl * keep * 8) if P else None
-                    u.workspace = b.sel_ws[sl].data_ptr()
-                nv.check(nv.lib.rtk_pivotkv_select_batched(su, len(todo), Hkv, b.rs_n.value, b.Hq // Hkv, b.L, keep, P,
-                                                           int(b.reforge), b.slots * keep, b.score_dt, nv.stream()),
-                         "rtk_pivotkv_select_batched")
-            b.selected.clear()
-            b.masks.clear()
-            lo, hi = min(layers) + off, max(layers) + off      # slots
-            # reforge: K is re-rotated at the NEW ids (reference :297-306).  With the native RoPE the eviction kernel
-            # computes their cos/sin itself; a third-party rotary module is called once for every pending slot and its
-            # section-merged fp32 tables are handed over.
-            defer = bool(getattr(b, "defer", False))
-            rot = self._rotary(b.rotary_emb_fn, b.device) if (b.reforge and P and not defer) else None
-            rope_in_kernel = rot is not None
-            if b.reforge and not rope_in_kernel and not defer and self.kv_cache_dtype is None:
-                b.ensure_tables()
-                n = (hi - lo + 1) * keep
-                pos2d, ld = b.pos_new[:, lo:hi + 1].reshape(P, n), n  # a copy when the slot range is partial
-                self._rope_tables(b.cos_new[lo * keep:], b.sin_new[lo * keep:], b.rotary_emb_fn, b.x_like, pos2d, ld,
-                                  3 if P == 3 else 2, b.mrope_section, n, D)
-            fp8 = self.kv_cache_dtype is not None
-            if fp8:   # the kept rows go to the archive (keep-all chunks included), the 16-bit tail is left to the next chunk
-                self._archive(b, layers, rot, dt)
-                layers_done, layers = layers, []
-            elif b.compact_sync is not None and not b.keep_all and (rope_in_kernel or defer or not b.reforge):
-                self._compact(b, layers, rot, defer, dt, es)
-                layers_done, layers = layers, []
-            else:
-                layers_done = layers
-                if not b.keep_all:
-                    b.ensure_staging()
-            units = (nv.EvictUnit * max(1, len(layers)))()
-            places = (nv.PlaceUnit * max(1, len(layers) * (1 if b.reforge else 2)))()
-            nc = 0
-            for i, l in enumerate(layers):
-                st = self._layers[l]
-                sl = l + off
-                cap = st.k.shape[2]
-                tail = st.length * D * es
-                u = units[i]
-                if b.reforge:
-                    u.k_src, u.k_src_stride_h = b.k_unrot[sl].data_ptr(), b.L * D
-                    if rope_in_kernel or defer:
-                        u.cos_new = u.sin_new = None
-                    else:
-                        u.cos_new = b.cos_new.data_ptr() + sl * keep * D * 4
-                        u.sin_new = b.sin_new.data_ptr() + sl * keep * D * 4
-                    u.k_dst, u.k_dst_stride_h = st.k.data_ptr() + tail, cap * D  # straight into the cache
-                elif b.keep_all:   # every row already sits where the append put it
-                    u.k_src, u.k_src_stride_h = st.k.data_ptr() + tail, cap * D
-                    u.cos_new = u.sin_new = u.k_dst = None
-                else:
-                    u.k_src, u.k_src_stride_h = st.k.data_ptr() + tail, cap * D
-                    u.cos_new = u.sin_new = None
-                    u.k_dst, u.k_dst_stride_h = b.k_stage[sl].data_ptr(), keep * D
-                    places[nc].stage, places[nc].stage_stride_h_bytes = b.k_stage[sl].data_ptr(), keep * D * es
-                    places[nc].tail, places[nc].tail_stride_h_bytes = st.k.data_ptr() + tail, cap * D * es
-                    places[nc].keep_idx = b.keep_idx[sl].data_ptr()
-                    nc += 1
-                u.v_src, u.v_src_stride_h = st.v.data_ptr() + tail, cap * D
-                if b.keep_all:
-                    u.v_dst = None
-                else:
-                    u.v_dst, u.v_dst_stride_h = b.v_stage[sl].data_ptr(), keep * D
-                    places[nc].stage, places[nc].stage_stride_h_bytes = b.v_stage[sl].data_ptr(), keep * D * es
-                    places[nc].tail, places[nc].tail_stride_h_bytes = st.v.data_ptr() + tail, cap * D * es
-                    places[nc].keep_idx = b.keep_idx[sl].data_ptr()
-                    nc += 1
-                u.keep_idx = b.keep_idx[sl].data_ptr()
-                if b.reforge and P:  # bookkeeping (reference :308-309)
-                    self._pos_reserve(st, P, 3 if P == 3 else 2, keep, b.device)
-                    u.pos_src, u.pos_src_stride = b.pos_new.data_ptr() + sl * keep * 8, b.slots * keep
-                    u.pos_dst, u.pos_dst_stride = st.pos.data_ptr() + st.pos_len * 8, st.pos.shape[1]
-                else:
-                    u.pos_src = u.pos_dst = None
-            s = nv.stream()
-            if not layers:
-                pass
-            elif rope_in_kernel:
-                sec = (C.c_int * len(b.mrope_section))(*b.mrope_section) if b.mrope_section else None
-                nv.check(nv.lib.rtk_pivotkv_evict_batched_rope(units, len(layers), Hkv, D, keep, P, dt, nv.ptr(rot.inv),
-                                                               rot.scaling, sec,
-                                                               len(b.mrope_section) if b.mrope_section else 0,
-                                                               nv.round_mode(b.x_like.dtype), 1, s),
-                         "rtk_pivotkv_evict_batched_rope")
-            elif b.reforge or not b.keep_all:   # (deferred re-rotation: every kept un-rotated K row is copied, bit 1)
-                nv.check(nv.lib.rtk_pivotkv_evict_batched(units, len(layers), Hkv, D, keep, P if b.reforge else 0, dt,
-                                                          3 if defer else 1, s), "rtk_pivotkv_evict_batched")
-            # kept rows -> head of the tail: in place, except the ~ratio of them whose source lies inside the destination
-            # range (parked in the staging rows by the launch above) - reference :313-318 without a full second copy
-            if nc:
-                nv.check(nv.lib.rtk_pivotkv_place_batched(places, nc, Hkv, keep, D, dt, s), "rtk_pivotkv_place_batched")
-            layers = layers_done
-        for l in layers:
-            st = self._layers[l]
-            b.q_keep[l + off] = None
-            b.q_units[l + off] = None
-            if self.kv_cache_dtype is not None:
-                st.len8 += keep
-            else:
-                st.length += keep
-            st.pending = 0
-            st.pending_keep = 0
-            st.c.mask = None
-            if b.reforge and P:
-                st.pos_len += keep
-                self._pos_layers = max(self._pos_layers, l + 1)
+            self._pos_layers = max(self._pos_layers, max(layers) + 1)
 
     def _order_compaction(self, b: _Batch):
         """The in-place compaction's tickets and flags (batch.compact_sync) serve ONE launch at a time: flushes of a batch
@@ -1517,81 +1568,57 @@ class PivotKVCache(DynamicCache):
             except Exception:  # noqa: BLE001  (a device-side abort leaves the context unusable; the first error is what is raised)
                 pass
 
-    def _archive(self, b: _Batch, layers, rot, dt):
+    def _archive(self, b: _Batch, layers, rot):
         """The eviction scan of the pending layers into their fp8 archives, one launch (rtk_pivotkv_archive_batched;
         reference :278-310): kept K re-rotated at the new ids and rounded to the model dtype as the compaction does (taken
         from the tail as it is without reforge), kept V from the tail, both quantised per (kv head, row) into rows
         [len8, len8 + keep) of the archive; ids to the position cache.  The 16-bit length does not advance."""
-        keep, D, Hkv, P = b.keep, b.D, b.Hkv, b.P
-        if b.reforge and (rot is None or not P or getattr(b, "defer", False)):
+        keep, D, Hkv = b.keep, b.D, b.Hkv
+        if b.reforge and (rot is None or not b.P or b.defer):
             raise NotImplementedError("kv_cache_dtype='fp8_e4m3' with pos_embed_reforge needs position ids and the native RoPE, "
                                       "and no deferred re-rotation")
         units = (nv.ArchiveUnit * len(layers))()
-        for i, l in enumerate(layers):
+        for u, l in zip(units, layers):
             st = self._layers[l]
-            sl = b.slot(l)
-            cap = st.k.shape[2]
-            tail = st.length * D * 2
             self._archive_reserve(st, keep, Hkv, D, b.device)
             if st.archive_at < 0:
                 st.archive_at = st.length
-            u = units[i]
-            if b.reforge:
-                u.k_src, u.k_src_stride_h = b.k_unrot[sl].data_ptr(), b.L * D
-            else:
-                u.k_src, u.k_src_stride_h = st.k.data_ptr() + tail, cap * D
-            u.v_src, u.v_src_stride_h = st.v.data_ptr() + tail, cap * D
-            u.keep_idx = None if b.keep_all else b.keep_idx[sl].data_ptr()
-            if b.reforge and P:  # bookkeeping (reference :308-309)
-                self._pos_reserve(st, P, 3 if P == 3 else 2, keep, b.device)
-                u.pos_src, u.pos_src_stride = b.pos_new.data_ptr() + sl * keep * 8, b.slots * keep
-                u.pos_dst, u.pos_dst_stride = st.pos.data_ptr() + st.pos_len * 8, st.pos.shape[1]
-            else:
-                u.pos_src = u.pos_dst = None
+            _, _, _, v_tail, stride_h = self._scan_unit(b, l, u)
+            u.v_src, u.v_src_stride_h = v_tail, stride_h
+            if b.keep_all:
+                u.keep_idx = None
             cap8 = st.k8.shape[2]
             u.k8, u.v8, u.dst_stride_h = st.k8.data_ptr() + st.len8 * D, st.v8.data_ptr() + st.len8 * D, cap8 * D
             u.k_scale, u.v_scale, u.scale_stride_h = st.ks8.data_ptr() + st.len8 * 4, st.vs8.data_ptr() + st.len8 * 4, cap8
         mode = nv.COMPACT_K_ROTATE if b.reforge else nv.COMPACT_K_COPY
-        sec = (C.c_int * len(b.mrope_section))(*b.mrope_section) if (b.mrope_section and b.reforge) else None
+        sec = b.sec if b.reforge else None
         nv.check(nv.lib.rtk_pivotkv_archive_batched(
-            units, len(layers), Hkv, D, keep, P if b.reforge else 0, dt, mode, nv.ptr(rot.inv) if b.reforge else None,
-            rot.scaling if b.reforge else 1.0, sec, len(sec) if sec is not None else 0,
-            nv.round_mode(b.x_like.dtype) if b.x_like is not None else nv.round_mode(b.dtype), nv.stream()),
+            units, len(layers), Hkv, D, keep, b.P if b.reforge else 0, b.c.dtype, mode,
+            nv.ptr(rot.inv) if b.reforge else None, rot.scaling if b.reforge else 1.0,
+            sec, len(sec) if sec is not None else 0, b.round_mode, nv.stream()),
             "rtk_pivotkv_archive_batched")
 
-    def _compact(self, b: _Batch, layers, rot, defer, dt, es):
+    def _compact(self, b: _Batch, layers, rot):
         """The eviction scan of the pending layers as one in-place launch (rtk_pivotkv_compact_batched; reference
         :278-318): kept K re-rotated at the new ids (or copied un-rotated when the rotation is deferred; compacted in
         place without reforge), V compacted inside the tail, ids to the position cache."""
-        keep, D, Hkv, P = b.keep, b.D, b.Hkv, b.P
         units = (nv.CompactUnit * len(layers))()
-        for i, l in enumerate(layers):
-            st = self._layers[l]
-            sl = b.slot(l)
-            cap = st.k.shape[2]
-            tail = st.length * D * es
-            u = units[i]
-            if b.reforge:
-                u.k_src, u.k_src_stride_h = b.k_unrot[sl].data_ptr(), b.L * D
-            else:
+        for u, l in zip(units, layers):
+            _, _, k_tail, v_tail, stride_h = self._scan_unit(b, l, u)
+            u.k_tail, u.k_tail_stride_h = k_tail, stride_h
+            u.v_tail, u.v_tail_stride_h = v_tail, stride_h
+            if not b.reforge:   # K is compacted inside its tail like V: no separate source
                 u.k_src, u.k_src_stride_h = None, 0
-            u.k_tail, u.k_tail_stride_h = st.k.data_ptr() + tail, cap * D
-            u.v_tail, u.v_tail_stride_h = st.v.data_ptr() + tail, cap * D
-            u.keep_idx = b.keep_idx[sl].data_ptr()
-            if b.reforge and P:  # bookkeeping (reference :308-309)
-                self._pos_reserve(st, P, 3 if P == 3 else 2, keep, b.device)
-                u.pos_src, u.pos_src_stride = b.pos_new.data_ptr() + sl * keep * 8, b.slots * keep
-                u.pos_dst, u.pos_dst_stride = st.pos.data_ptr() + st.pos_len * 8, st.pos.shape[1]
-            else:
-                u.pos_src = u.pos_dst = None
-        mode = nv.COMPACT_K_INPLACE if not b.reforge else (nv.COMPACT_K_COPY if defer else nv.COMPACT_K_ROTATE)
-        sec = (C.c_int * len(b.mrope_section))(*b.mrope_section) if (b.mrope_section and mode == nv.COMPACT_K_ROTATE) else None
+        mode = nv.COMPACT_K_INPLACE if not b.reforge else (nv.COMPACT_K_COPY if b.defer else nv.COMPACT_K_ROTATE)
+        rotate = mode == nv.COMPACT_K_ROTATE
+        sec = b.sec if rotate else None
         self._order_compaction(b)
         nv.check(nv.lib.rtk_pivotkv_compact_batched(
-            units, len(layers), Hkv, D, keep, P if b.reforge else 0, dt, mode,
-            nv.ptr(rot.inv) if mode == nv.COMPACT_K_ROTATE else None, rot.scaling if mode == nv.COMPACT_K_ROTATE else 1.0,
-            sec, len(sec) if sec is not None else 0, nv.round_mode(b.x_like.dtype) if b.x_like is not None else nv.round_mode(b.dtype),
-            b.c.compact_sync, b.c.compact_sync_ints, nv.stream()), "rtk_pivotkv_compact_batched")
+            units, len(layers), b.Hkv, b.D, b.keep, b.P if b.reforge else 0, b.c.dtype, mode,
+            nv.ptr(rot.inv) if rotate else None, rot.scaling if rotate else 1.0,
+            sec, len(sec) if sec is not None else 0, b.round_mode, b.c.compact_sync, b.c.compact_sync_ints,
+            nv.stream()),
+            "rtk_pivotkv_compact_batched")
 
     # ---- the hot path ---------------------------------------------------------------------------
     def update(
@@ -1654,7 +1681,7 @@ class PivotKVCache(DynamicCache):
                 and nv.current_device() == idx):
             return None
         L, P = b.L, b.P
-        if pos.dtype is not torch.int64 or pos.shape[-1] != L or pos.shape[0] != P or pos.ndim != (3 if P == 3 else 2) \
+        if pos.dtype is not torch.int64 or pos.shape[-1] != L or pos.shape[0] != P or pos.ndim != b.pos_ndim \
                 or pos.stride(-1) != 1 or (pos.ndim == 3 and (pos.shape[1] != 1 or pos.stride(0) < L)):
             return None   # (ids whose rows alias - `.expand(3, ..)` - take the stage-by-stage route)
         mask = self.keypatches_mask_chunk
@@ -1729,9 +1756,8 @@ class PivotKVCache(DynamicCache):
             nv.check(rc, "rtk_pivotkv_update")
         if io.flags & nv.RTK_UPDATE_SHIFT_NEXT:
             self._preshifted = (weakref.ref(pos), _version_of(pos), layer_idx + 1, stream)
-        if not self._warned:  # the reference's logger.warning_once (:232)
-            self._warned = True
-            _warn_once("Enable PivotKVCache compression: length after compression %.2f" % (self.compression_ratio))
+        if not self._warned:
+            self._warn_compression()
         if not pre:  # the reference's cache_kwargs protocol (:235, :241-243)
             ck.pop("position_ids", None)
             ck.pop("query_states", None)
@@ -1750,9 +1776,7 @@ class PivotKVCache(DynamicCache):
         if mask is not None:
             b.masks[layer_idx] = mask
         b.q_keep[slot] = q if q_in_place else None
-        if b.keep_all:
-            b.scored.add(layer_idx)
-        elif not b.batched_passes:
+        if b.keep_all or not b.batched_passes:   # nothing to score, or scored inside the call
             b.scored.add(layer_idx)
         b.pending.append(layer_idx)
         b.c_pending += 1
@@ -1811,9 +1835,7 @@ class PivotKVCache(DynamicCache):
             return None
         L = key_states.shape[2]
         b = self._batch
-        hit = self._rotaries.get(id(rotary_emb))
-        if b is None or b.L != L or not b.c_capable or hit is None or hit[0] is not rotary_emb or hit[1] is None \
-                or hit[1] is not b.rot or hit[2] != _inv_stamp(rotary_emb) \
+        if b is None or b.L != L or not b.c_capable or not self._bound_rotary(b, rotary_emb) \
                 or (layer_idx >= b.slots and not b.wrap) or layer_idx >= len(self._layers) \
                 or self._layers[layer_idx].c.length + L > self._layers[layer_idx].c.cap:
             # not the steady state: find / build the batch of this geometry, bind the rotary, make room
@@ -1910,6 +1932,17 @@ class PivotKVCache(DynamicCache):
         m = st.c.length
         return q, st._k.narrow(2, 0, m), st._v.narrow(2, 0, m)
 
+    def _warn_compression(self):
+        """The reference's logger.warning_once (:232): a log line on stderr, once per process."""
+        self._warned = True
+        _warn_once("Enable PivotKVCache compression: length after compression %.2f" % (self.compression_ratio))
+
+    def _bound_rotary(self, b: _Batch, rotary_emb_fn) -> bool:
+        """Is `rotary_emb_fn` the batch's bound rotary module, natively served and unchanged since its snapshot?"""
+        hit = self._rotaries.get(id(rotary_emb_fn))
+        return hit is not None and hit[0] is rotary_emb_fn and hit[1] is not None and hit[1] is b.rot \
+            and hit[2] == _inv_stamp(rotary_emb_fn)
+
     def _bind_rotary(self, b: _Batch, rotary_emb_fn, mrope_section, rot: Optional[_Rotary]):
         """The rotary module / M-RoPE sections the batch's pending units were (and its next units will be) rotated
         with; units of different rotaries never share a flush."""
@@ -1925,28 +1958,14 @@ class PivotKVCache(DynamicCache):
                 raise ValueError("mrope_section has more than 8 entries")
             for i in range(c.nsec):
                 c.sections[i] = int(mrope_section[i])
+            b.sec = (C.c_int * c.nsec)(*b.mrope_section) if c.nsec else None
             c.inv_freq = rot.inv.data_ptr() if rot is not None else None
             c.attention_scaling = rot.scaling if rot is not None else 1.0
 
-    def _update_general(
-        self,
-        key_states: torch.Tensor,
-        value_states: torch.Tensor,
-        layer_idx: int,
-        cache_kwargs: Optional[Dict[str, Any]] = None,
-    ) -> Tuple[torch.Tensor, torch.Tensor]:
-        """
-        Input
-            query_states: [bsz, num_heads, q_len, d]      (cache_kwargs['query_states'], post-RoPE)
-            key_states:   [bsz, num_key_value_heads, q_len, d]
-            position_ids: [3, bsz, q_len] / [bsz, q_len]  (cache_kwargs['position_ids'])
-        Output
-            key_states_output, value_states_output: the layer's UNCOMPRESSED keys/values
-            ([prefix | whole current chunk]) for this layer's self attention (reference :217-323).
-        """
-        if not self._warned:  # the reference's logger.warning_once (:232): a log line on stderr, once per process
-            self._warned = True
-            _warn_once("Enable PivotKVCache compression: length after compression %.2f" % (self.compression_ratio))
+    def _update_general(self, key_states, value_states, layer_idx, cache_kwargs=None):
+        """`update` stage by stage (inputs and outputs: see its docstring)."""
+        if not self._warned:
+            self._warn_compression()
         cache_kwargs = cache_kwargs if cache_kwargs is not None else {}
         position_ids = cache_kwargs.pop("position_ids", None)
         cache_kwargs.pop("shift_next_position_ids", None)   # (the build's own key: only the one-call route acts on it)
@@ -1968,26 +1987,51 @@ class PivotKVCache(DynamicCache):
                 self.update_position_ids(position_ids, layer_idx)
             return st.k[:, :, :st.length], st.v[:, :, :st.length]
 
+        u = self._bind_update(key_states, value_states, layer_idx, cache_kwargs, position_ids)
+        b, st, dev = u.b, u.st, key_states.device
+        with torch.cuda.device(dev):
+            side = self._next_side(dev)
+            if side is None:
+                u.pos_in = self._ids_2d(u, False)
+                prepared = self._fused_prepare(u, self._ws)
+                if not prepared:
+                    self._append_tail(u)
+                self._run_stages(u, self._ws, prepared)
+            else:
+                self._append_tail(u)   # on the caller's stream: all this layer's attention needs
+                u.pos_in = self._ids_2d(u, True)
+                self._run_on_worker(u, side)
+        self.update_num_evicted_tokens(n_new - b.keep, layer_idx)  # reference :310
+        st.pending = n_new
+        st.pending_keep = b.keep
+        b.pending.append(layer_idx)
+        self._last_slot = (b, u.slot)
+        return st.k[:, :, :st.length + n_new], st.v[:, :, :st.length + n_new]
+
+    def _bind_update(self, key_states, value_states, layer_idx, cache_kwargs, position_ids) -> _Update:
+        """The argument handling of a compressed `_update_general` call: pops the rest of the cache_kwargs protocol
+        (reference :235, :241-243), checks the operands, finds / builds the batch of the chunk's geometry, binds the
+        rotary, claims the layer's slot and makes room for the chunk."""
         query_states = cache_kwargs.pop("query_states")
         rotary_emb_fn = cache_kwargs.pop("rotary_emb")
         mrope_section = cache_kwargs.pop("mrope_section", None)  # M-RoPE only
-        bsz, num_heads, q_len, head_dim = query_states.shape
-        num_key_value_heads, k_len = key_states.shape[1:3]
+        bsz, Hq, L, D = query_states.shape
+        Hkv = key_states.shape[1]
         assert bsz == 1
         nv.require_device(query_states)
-        dev, dt = key_states.device, nv.dtype_code(key_states)
-        D, L, Hkv, Hq = head_dim, q_len, num_key_value_heads, num_heads
+        dev = key_states.device
+        nv.dtype_code(key_states)   # (raises for a dtype the kernels do not serve)
         for t in (query_states, key_states, value_states):
             if t.stride(-1) != 1:
                 raise ValueError("q/k/v must be contiguous along head_dim")
-        keep_len = max(1, int(self.compression_ratio * q_len))  # evict new tokens only (reference :263)
-        if keep_len > q_len:   # compression_ratio > 1: the reference's topk refuses it (:276)
-            raise RuntimeError(f"PivotKVCache.update: selected index k out of range (keep {keep_len} of {q_len} tokens)")
+        keep_len = max(1, int(self.compression_ratio * L))  # evict new tokens only (reference :263)
+        if keep_len > L:   # compression_ratio > 1: the reference's topk refuses it (:276)
+            raise RuntimeError(f"PivotKVCache.update: selected index k out of range (keep {keep_len} of {L} tokens)")
         reforge = bool(self.pos_embed_reforge)
-        self._fp8_refuse(key_states.dtype, D, reforge, self._rotary(rotary_emb_fn, dev) if reforge else None,
-                         position_ids is not None)
+        rot = self._rotary(rotary_emb_fn, dev) if reforge else None
+        self._fp8_refuse(key_states.dtype, D, reforge, rot, position_ids is not None)
 
-        mask = getattr(self, "keypatches_mask_chunk", None)
+        mask = self.keypatches_mask_chunk
         if mask is not None:
             nv.require_device(mask)
             if mask.dtype != torch.bool or not mask.is_contiguous():
@@ -1997,169 +2041,151 @@ class PivotKVCache(DynamicCache):
         if position_ids is not None:
             nv.require_device(position_ids)
             Pn = 3 if position_ids.ndim == 3 else 1
-        batch = self._get_batch(layer_idx, Hq, Hkv, L, D, keep_len, Pn, key_states.dtype, dev)
-        rot = self._rotary(rotary_emb_fn, dev) if reforge else None
-        self._bind_rotary(batch, rotary_emb_fn, mrope_section, rot)
-        if batch.pending and batch.c.pre_rope:   # units of the prologue route are flushed among themselves
+        b = self._get_batch(layer_idx, Hq, Hkv, L, D, keep_len, Pn, key_states.dtype, dev)
+        self._bind_rotary(b, rotary_emb_fn, mrope_section, rot)
+        if b.pending and b.c.pre_rope:   # units of the prologue route are flushed among themselves
             self._flush()
-        batch.c.pre_rope = 0
-        slot = self._claim_slot(batch, layer_idx)
-        batch.x_like = value_states[:, :, :1]
-        st = self.reserve(layer_idx, n_new, key_states)
-        P0 = st.length
-        cap = st.k.shape[2]
-        esz = st.k.element_size()
+        b.c.pre_rope = 0
+        u = _Update()
+        u.b, u.layer, u.slot = b, layer_idx, self._claim_slot(b, layer_idx)
+        u.q, u.k, u.v, u.ids, u.mask = query_states, key_states, value_states, position_ids, mask
+        b.x_like = value_states[:, :, :1]
+        u.st = st = self.reserve(layer_idx, key_states.shape[2], key_states)
+        tail = st.length * D * st.k.element_size()
+        u.k_tail, u.v_tail = C.c_void_p(st.k.data_ptr() + tail), C.c_void_p(st.v.data_ptr() + tail)
+        u.a_scale = float(getattr(rotary_emb_fn, "attention_scaling", 1.0)) if reforge else 1.0
+        u.pos_in = u.cos = u.sin = None
+        return u
 
-        a_scale = float(getattr(rotary_emb_fn, "attention_scaling", 1.0)) if reforge else 1.0
-        ws_bytes = batch.ws_bytes
-        sel_bytes = nv.lib.rtk_pivotkv_select_workspace_bytes(L)
-        keep_idx = batch.keep_idx[slot]
-        shared = {}   # values handed from one stage to the next
+    def _ids_2d(self, u: _Update, snapshot: bool):
+        if u.ids is None:
+            return None
+        p2 = u.ids.reshape(u.b.P, u.b.L)
+        # worker streams read the ids later than the caller's stream runs on: the attention patch shifts the
+        # SAME ids tensor in place for the next layer (qwen2_vl.py:73), so they get a private copy
+        return p2.clone() if snapshot else (p2 if p2.is_contiguous() else p2.contiguous())
 
-        defer_select = L >= 512   # the chip-wide selection kernels; smaller chunks select inside update
+    def _run_stages(self, u: _Update, ws, prepared: bool):
+        """The launch stages of one update on the CURRENT stream: un-rotate / pack (unless the fused prepare launch has
+        done it), the chunk's ids into the slot, the matrix passes, the selection."""
+        if not prepared:
+            self._stage_pre(u, ws)
+            if u.b.defer_select and u.pos_in is not None:
+                u.b.pos_old[u.slot].copy_(u.pos_in)
+        self._stage_passes(u, ws)
+        self._stage_post(u, ws)
 
-        def ws_pointer(ws):
-            if batch.batched_passes:   # the slot's own workspace: q~ must survive until the batched passes of the flush
-                return batch.score_ws_base + slot * batch.ws_stride
-            wsb = self._buf("score_ws", (ws_bytes + 256,), torch.uint8, dev, ws)
-            return (wsb.data_ptr() + 255) & ~255
+    def _run_on_worker(self, u: _Update, side: _Side):
+        """`_run_stages` on a worker stream (overlap_streams > 0): it starts after what the caller's stream has queued
+        so far, and the layer's flush waits for its completion event."""
+        main = torch.cuda.current_stream()
+        ready = torch.cuda.Event()
+        ready.record(main)
+        for t in (u.q, u.k, u.v, u.pos_in, u.mask):
+            if t is not None:
+                t.record_stream(side.stream)
+        with torch.cuda.stream(side.stream):
+            side.stream.wait_event(ready)
+            self._run_stages(u, side.ws, False)
+            done = torch.cuda.Event()
+            done.record(side.stream)
+        u.st.pending_event = done
 
-        def score_stage(ws, stages):
-            ws_ptr = ws_pointer(ws)
-            score = batch.score[slot]
-            k_unrot = batch.k_unrot[slot] if reforge else None
-            # the matrix passes of a per-update launch know the chunk's key-patch mask: pass 2 skips the columns the
-            # selection overwrites with 1.0 anyway (reference :272-274)
-            live = mask if (stages & nv.SCORE_PASSES) and self.skip_masked_columns else None
-            kidx = self._buf("key_index", (L + 1,), torch.int32, dev, ws) if live is not None else None
-            nv.check(nv.lib.rtk_pivotkv_score_stages_masked(
-                nv.ptr(query_states), query_states.stride(1), query_states.stride(2),
-                nv.ptr(key_states), key_states.stride(1), key_states.stride(2),
-                Hq, Hkv, L, D, batch.score_dt, nv.ptr(shared.get("cos")), nv.ptr(shared.get("sin")), a_scale,
-                nv.ptr(score), nv.ptr(k_unrot), C.c_void_p(ws_ptr), ws_bytes, stages, nv.ptr(batch.partials[slot]),
-                nv.ptr(live), nv.ptr(kidx), nv.stream()), "rtk_pivotkv_score")
-            return score
+    def _score_ws_pointer(self, u: _Update, ws):
+        b = u.b
+        if b.batched_passes:   # the slot's own workspace: q~ must survive until the batched passes of the flush
+            return b.score_ws_base + u.slot * b.ws_stride
+        wsb = self._buf("score_ws", (b.ws_bytes + 256,), torch.uint8, b.device, ws)
+        return (wsb.data_ptr() + 255) & ~255
 
-        def stage_pre(ws, pos_in):
-            """RoPE tables of the chunk's ids + un-rotate / pack (reference :248-259), on the CURRENT stream."""
-            batch.ensure_scoring()
-            if reforge:
-                cos_t = self._buf("old_cos", (L, D), torch.float32, dev, ws)
-                sin_t = self._buf("old_sin", (L, D), torch.float32, dev, ws)
-                self._rope_tables(cos_t, sin_t, rotary_emb_fn, value_states, pos_in, L, position_ids.ndim, mrope_section,
-                                  L, D)
-                shared["cos"], shared["sin"] = cos_t, sin_t
-            score_stage(ws, nv.SCORE_PREPARE)
+    def _score_stage(self, u: _Update, ws, stages):
+        b, q, k = u.b, u.q, u.k
+        score = b.score[u.slot]
+        k_unrot = b.k_unrot[u.slot] if b.reforge else None
+        # the matrix passes of a per-update launch know the chunk's key-patch mask: pass 2 skips the columns the
+        # selection overwrites with 1.0 anyway (reference :272-274)
+        live = u.mask if (stages & nv.SCORE_PASSES) and self.skip_masked_columns else None
+        kidx = self._buf("key_index", (b.L + 1,), torch.int32, b.device, ws) if live is not None else None
+        nv.check(nv.lib.rtk_pivotkv_score_stages_masked(
+            nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), k.stride(1), k.stride(2),
+            b.Hq, b.Hkv, b.L, b.D, b.score_dt, nv.ptr(u.cos), nv.ptr(u.sin), u.a_scale,
+            nv.ptr(score), nv.ptr(k_unrot), C.c_void_p(self._score_ws_pointer(u, ws)), b.ws_bytes, stages,
+            nv.ptr(b.partials[u.slot]), nv.ptr(live), nv.ptr(kidx), nv.stream()), "rtk_pivotkv_score")
+        return score
 
-        def stage_big(ws):
-            """the two matrix passes (reference :260-268): deferred to the flush (all layers of the chunk in one
-            launch per kernel) whenever the batched form supports the shape"""
-            if batch.keep_all:         # nothing to choose: no scores
-                batch.scored.add(layer_idx)
-                return
-            if batch.batched_passes:
-                return
-            score_stage(ws, nv.SCORE_PASSES)
-            batch.scored.add(layer_idx)
+    def _stage_pre(self, u: _Update, ws):
+        """RoPE tables of the chunk's ids + un-rotate / pack (reference :248-259), on the CURRENT stream."""
+        b = u.b
+        b.ensure_scoring()
+        if b.reforge:
+            L, D = b.L, b.D
+            u.cos = self._buf("old_cos", (L, D), torch.float32, b.device, ws)
+            u.sin = self._buf("old_sin", (L, D), torch.float32, b.device, ws)
+            self._rope_tables(u.cos, u.sin, b.rotary_emb_fn, u.v, u.pos_in, L, u.ids.ndim, b.sec, L, D)
+        self._score_stage(u, ws, nv.SCORE_PREPARE)
 
-        def stage_post(ws, pos_in):
-            """small chunks only: column-mass reduction, mask override + top-k + position ids (reference :269-295)
-            right away; larger chunks leave this to the batched selection of the flush"""
-            if batch.keep_all:         # keep_idx is the identity (set once per batch); ids x 1.0 = the ids (:288-292)
-                if pos_in is not None:
-                    batch.pos_new[:, slot].copy_(pos_in)
-                batch.selected.add(layer_idx)
-                return
-            if defer_select:
-                batch.masks[layer_idx] = mask
-                return
-            score = score_stage(ws, nv.SCORE_FINALIZE)
-            rank = self._buf("rank", (L,), torch.int32, dev, ws)
-            pos_out = batch.pos_new[:, slot] if pos_in is not None else None
-            sel_ws = self._buf("select_ws", (sel_bytes,), torch.uint8, dev, ws)
-            nv.check(nv.lib.rtk_pivotkv_select(nv.ptr(score), nv.ptr(mask), L, keep_len, nv.ptr(pos_in), Pn,
-                                               int(reforge), nv.ptr(keep_idx), nv.ptr(rank), nv.ptr(pos_out),
-                                               batch.slots * keep_len, nv.ptr(sel_ws), sel_bytes, nv.stream()),
-                     "rtk_pivotkv_select")
-            batch.selected.add(layer_idx)
+    def _stage_passes(self, u: _Update, ws):
+        """the two matrix passes (reference :260-268): deferred to the flush (all layers of the chunk in one
+        launch per kernel) whenever the batched form supports the shape"""
+        b = u.b
+        if b.keep_all:         # nothing to choose: no scores
+            b.scored.add(u.layer)
+            return
+        if b.batched_passes:
+            return
+        self._score_stage(u, ws, nv.SCORE_PASSES)
+        b.scored.add(u.layer)
 
-        def pos_2d(snapshot: bool):
-            if position_ids is None:
-                return None
-            p2 = position_ids.reshape(Pn, L)
-            # worker streams read the ids later than the caller's stream runs on: the attention patch shifts the
-            # SAME ids tensor in place for the next layer (qwen2_vl.py:73), so they get a private copy
-            return p2.clone() if snapshot else (p2 if p2.is_contiguous() else p2.contiguous())
+    def _stage_post(self, u: _Update, ws):
+        """small chunks only: column-mass reduction, mask override + top-k + position ids (reference :269-295)
+        right away; larger chunks leave this to the batched selection of the flush"""
+        b, slot, pos_in = u.b, u.slot, u.pos_in
+        if b.keep_all:         # keep_idx is the identity (set once per batch); ids x 1.0 = the ids (:288-292)
+            if pos_in is not None:
+                b.pos_new[:, slot].copy_(pos_in)
+            b.selected.add(u.layer)
+            return
+        if b.defer_select:
+            b.masks[u.layer] = u.mask
+            return
+        score = self._score_stage(u, ws, nv.SCORE_FINALIZE)
+        L, dev = b.L, b.device
+        rank = self._buf("rank", (L,), torch.int32, dev, ws)
+        pos_out = b.pos_new[:, slot] if pos_in is not None else None
+        sel_ws = self._buf("select_ws", (b.sel_bytes,), torch.uint8, dev, ws)
+        nv.check(nv.lib.rtk_pivotkv_select(nv.ptr(score), nv.ptr(u.mask), L, b.keep, nv.ptr(pos_in), b.P,
+                                           int(b.reforge), nv.ptr(b.keep_idx[slot]), nv.ptr(rank), nv.ptr(pos_out),
+                                           b.slots * b.keep, nv.ptr(sel_ws), b.sel_bytes, nv.stream()),
+                 "rtk_pivotkv_select")
+        b.selected.add(u.layer)
 
-        k_tail = C.c_void_p(st.k.data_ptr() + P0 * D * esz)
-        v_tail = C.c_void_p(st.v.data_ptr() + P0 * D * esz)
+    def _append_tail(self, u: _Update):
+        """reference :238 - the uncompressed view this layer's attention reads"""
+        b, k, v = u.b, u.k, u.v
+        nv.check(nv.lib.rtk_pivotkv_append(
+            nv.ptr(k), k.stride(1), k.stride(2), nv.ptr(v), v.stride(1), v.stride(2), b.Hkv, b.L, b.D, b.c.dtype,
+            u.k_tail, u.v_tail, u.st.k.shape[2] * b.D, nv.stream()), "rtk_pivotkv_append")
 
-        def append_tail():   # reference :238 — the uncompressed view this layer's attention reads
-            nv.check(nv.lib.rtk_pivotkv_append(
-                nv.ptr(key_states), key_states.stride(1), key_states.stride(2),
-                nv.ptr(value_states), value_states.stride(1), value_states.stride(2), Hkv, L, D, dt,
-                k_tail, v_tail, cap * D, nv.stream()), "rtk_pivotkv_append")
-
-        def fused_prepare(ws, pos_in) -> bool:
-            """append + native RoPE tables + un-rotate in ONE launch (k read once); False if the shape needs the
-            separate kernels."""
-            if not (reforge and rot is not None and pos_in is not None):
-                return False
-            inv = rot.inv
-            # keep-all chunks are not scored: no q~, no score workspace (any aligned address will do)
-            k_only = batch.keep_all and batch.partials is None
-            ws_ptr = batch.c.score_ws if k_only else ws_pointer(ws)
-            sec = (C.c_int * len(mrope_section))(*mrope_section) if mrope_section else None
-            rc = nv.lib.rtk_pivotkv_prepare(
-                nv.ptr(query_states), query_states.stride(1), query_states.stride(2),
-                nv.ptr(key_states), key_states.stride(1), key_states.stride(2),
-                nv.ptr(value_states), value_states.stride(1), value_states.stride(2),
-                Hq, Hkv, L, D, batch.prep_dt | (nv.RTK_PREPARE_K_ONLY if k_only else 0), nv.ptr(pos_in), L, Pn,
-                nv.ptr(inv), a_scale, sec,
-                len(mrope_section) if mrope_section else 0, nv.round_mode(key_states.dtype),
-                nv.ptr(batch.k_unrot[slot]), C.c_void_p(ws_ptr), ws_bytes, k_tail, v_tail, cap * D,
-                nv.ptr(batch.pos_old[slot]) if defer_select else None, nv.stream())
-            if rc == nv.RTK_EUNSUPPORTED:
-                return False
-            nv.check(rc, "rtk_pivotkv_prepare")
-            return True
-
-        with torch.cuda.device(dev):
-            side = self._next_side(dev)
-            if side is None:
-                pos_in = pos_2d(False)
-                if not fused_prepare(self._ws, pos_in):
-                    append_tail()
-                    stage_pre(self._ws, pos_in)
-                    if defer_select and pos_in is not None:
-                        batch.pos_old[slot].copy_(pos_in)
-                stage_big(self._ws)
-                stage_post(self._ws, pos_in)
-            else:
-                append_tail()   # on the caller's stream: all this layer's attention needs
-                main = torch.cuda.current_stream()
-                pos_in = pos_2d(True)
-                ready = torch.cuda.Event()
-                ready.record(main)
-                for t in (query_states, key_states, value_states, pos_in, mask):
-                    if t is not None:
-                        t.record_stream(side.stream)
-                with torch.cuda.stream(side.stream):
-                    side.stream.wait_event(ready)
-                    stage_pre(side.ws, pos_in)
-                    if defer_select and pos_in is not None:
-                        batch.pos_old[slot].copy_(pos_in)
-                    stage_big(side.ws)
-                    stage_post(side.ws, pos_in)
-                    done = torch.cuda.Event()
-                    done.record(side.stream)
-                st.pending_event = done
-        self.update_num_evicted_tokens(k_len - keep_len, layer_idx)  # reference :310
-        st.pending = n_new
-        st.pending_keep = keep_len
-        batch.pending.append(layer_idx)
-        self._last_slot = (batch, slot)
-        return st.k[:, :, :P0 + n_new], st.v[:, :, :P0 + n_new]
+    def _fused_prepare(self, u: _Update, ws) -> bool:
+        """append + native RoPE tables + un-rotate in ONE launch (k read once); False if the shape needs the
+        separate kernels."""
+        b, q, k, v, pos_in = u.b, u.q, u.k, u.v, u.pos_in
+        if not (b.reforge and b.rot is not None and pos_in is not None):
+            return False
+        # keep-all chunks are not scored: no q~, no score workspace (any aligned address will do)
+        k_only = b.keep_all and b.partials is None
+        ws_ptr = b.c.score_ws if k_only else self._score_ws_pointer(u, ws)
+        rc = nv.lib.rtk_pivotkv_prepare(
+            nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), k.stride(1), k.stride(2),
+            nv.ptr(v), v.stride(1), v.stride(2),
+            b.Hq, b.Hkv, b.L, b.D, b.prep_dt | (nv.RTK_PREPARE_K_ONLY if k_only else 0), nv.ptr(pos_in), b.L, b.P,
+            nv.ptr(b.rot.inv), u.a_scale, b.sec, b.c.nsec, b.round_mode,
+            nv.ptr(b.k_unrot[u.slot]), C.c_void_p(ws_ptr), b.ws_bytes, u.k_tail, u.v_tail, u.st.k.shape[2] * b.D,
+            nv.ptr(b.pos_old[u.slot]) if b.defer_select else None, nv.stream())
+        if rc == nv.RTK_EUNSUPPORTED:
+            return False
+        nv.check(rc, "rtk_pivotkv_prepare")
+        return True
 
 
 def _kv_cache_dtype_of(config):

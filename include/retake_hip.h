@@ -24,15 +24,14 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (62 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (59 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
  *   §C  "MA-LLM / MA-LLM-hard merges"   rtk_adjacent_cosine, rtk_mallm_argmax, rtk_mallm_merge, rtk_mallm_hard_chain
  *   §D  "RoPE tables"                   rtk_rope_merge, rtk_rope_table, rtk_rope_rotate_rows, rtk_rope_shift(_segments)
  *   §E  "PivotKV" (one unit, by stage)  rtk_pivotkv_score(_stages, _stages_masked, _passes_batched(_q), _partials),
- *                                       rtk_pivotkv_prepare, rtk_pivotkv_select(_batched), rtk_pivotkv_evict,
- *                                       rtk_pivotkv_commit, rtk_copy_rows, *_workspace_bytes
+ *                                       rtk_pivotkv_prepare, rtk_pivotkv_select(_batched), *_workspace_bytes
  *   §F  "Chunk-batched cache maintenance"  rtk_pivotkv_append, rtk_pivotkv_evict_batched(_rope), _commit_batched,
  *                                       _place_batched, rtk_pivotkv_compact_batched (+ _compact_sync_ints)
  *   §G  "One-call update and one-call flush"  rtk_pivotkv_update, rtk_pivotkv_flush, rtk_pivotkv_append_rope,
@@ -225,7 +224,7 @@ size_t rtk_pivotkv_score_workspace_bytes(int Hq, int Hkv, int L, int D, int dtyp
  *   un-rotated, x~ = ((x*cos) - (rotate_half(x)*sin)) / attention_scaling^2   (:76-78, :109-111).
  *   score [L] fp32 = mean_g mean_{h in g} sum_i softmax_j(q~_h,i . k~_g,j / sqrt(D))  — keys are the
  *   current chunk only, no causal mask (:264-270).
- *   k_unrot (optional, may be NULL): receives k~ [Hkv,L,D] contiguous in `dtype` for rtk_pivotkv_evict.
+ *   k_unrot (optional, may be NULL): receives k~ [Hkv,L,D] contiguous in `dtype` for rtk_pivotkv_evict_batched.
  * The [Hq,L,L] probability tensor is never materialised. */
 int rtk_pivotkv_score(const void* q, int64_t q_stride_h, int64_t q_stride_l,
                       const void* k, int64_t k_stride_h, int64_t k_stride_l,
@@ -349,39 +348,6 @@ int rtk_pivotkv_select_batched(const rtk_select_unit* units, int n_units, int Hk
 /* Layout of the column partials rtk_pivotkv_score_stages(RTK_SCORE_PASSES) produces for these sizes: returns the
  * number of floats (Hkv * RS * L) and writes RS (row splits actually used) to *rs_out. */
 size_t rtk_pivotkv_score_partials(int Hq, int Hkv, int L, int D, int dtype, int* rs_out);
-
-/* P1, P8, P11, P13  longvideo_cache.py:238, :278-280, :297-306, :313-318 — the eviction scan.
- * One launch over the chunk's K and V rows:
- *   every row l is appended to the cache tail   k_tail/v_tail[h][l]      (the uncompressed view the
- *                                                current layer's attention reads, :238)
- *   row keep_idx[r] is also written to          k_kept/v_kept[h][r]      (the compacted cache, :313-318)
- *   keep_idx [keep] int64 ascending, as produced by rtk_pivotkv_select
- * With reforge (cos_new != NULL) the kept K row is taken from k_unrot (un-rotated, as produced by
- * rtk_pivotkv_score) and rotated forward with the fp32 [keep,D] tables of its NEW position:
- *   k' = (k~*cos_new) + (rotate_half(k~)*sin_new)          (:80-81, :113-114)
- * otherwise it is a plain copy of k.  V rows are plain copies.
- * k_tail/v_tail may be NULL (no append wanted).  Destinations: element (h,r,d) at
- * h*stride_h + r*D + d. */
-int rtk_pivotkv_evict(const void* k, int64_t k_stride_h, int64_t k_stride_l,
-                      const void* v, int64_t v_stride_h, int64_t v_stride_l,
-                      const void* k_unrot, int Hkv, int L, int D, int dtype,
-                      const int64_t* keep_idx, int keep,
-                      const float* cos_new, const float* sin_new,
-                      void* k_tail, void* v_tail, int64_t tail_stride_h,
-                      void* k_kept, void* v_kept, int64_t kept_stride_h,
-                      rtk_stream_t stream);
-
-/* P13 (second half)  longvideo_cache.py:313-318: commits the staged kept K and V rows of one layer over
- * the head of the uncompressed tail, once the layer's attention has consumed that view.  One launch:
- * dst[h][r][:] = stage[h][r][:], r < rows, for both tensors. */
-int rtk_pivotkv_commit(const void* k_stage, const void* v_stage, int64_t stage_stride_h,
-                       void* k_dst, void* v_dst, int64_t dst_stride_h,
-                       int H, int rows, int D, int dtype, rtk_stream_t stream);
-
-/* Row-block copy used to commit staged kept rows into the cache after the layer's attention has
- * consumed the uncompressed view: dst[h][r][:] = src[h][r][:], r < rows. */
-int rtk_copy_rows(const void* src, int64_t src_stride_h, void* dst, int64_t dst_stride_h,
-                  int H, int rows, int D, int dtype, rtk_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Chunk-batched cache maintenance.  The reference rebuilds every layer's cache with two torch.cat per

@@ -86,7 +86,7 @@ def test_new_entry_points_are_declared_exported_and_bound(tmp_path):
         assert s in syms, f"{s} not declared in retake_hip.h"
         assert hasattr(lib, s), f"{s} not exported"
         assert s in nv.EXPORTS, f"{s} not bound"
-    assert nv.lib.rtk_version() == nv.ABI_VERSION == 17
+    assert nv.lib.rtk_version() == nv.ABI_VERSION == 18
     # rtk_archive_unit: the ctypes mirror has the layout gcc gives the header's struct
     st, cname = nv.ArchiveUnit, "rtk_archive_unit"
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "retake_hip.h"', "int main(void) {",

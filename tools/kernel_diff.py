@@ -51,8 +51,8 @@ def elf_kernels(path):
             cur = body.setdefault(m.group(1), [])
         elif cur is not None and line.strip() not in ("", "..."):   # ("...": zero padding after a section's last kernel)
             cur.append(re.sub(r"\s*//.*$", "", line).strip())
-    for lines in body.values():   # alignment padding after the last instruction
-        while lines and lines[-1].split()[0] in ("s_nop", "s_code_end"):
+    for lines in body.values():   # alignment padding after the last instruction (a lone zero dword decodes as a v_cndmask)
+        while lines and (lines[-1].split()[0] in ("s_nop", "s_code_end") or lines[-1].startswith("v_cndmask_b32_e32 v0, s0, v0")):
             lines.pop()
     names = sorted(kd)
     dem = run("c++filt", *names).splitlines() if names else []

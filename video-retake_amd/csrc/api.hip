@@ -28,7 +28,7 @@ int hip_fail(hipError_t e, const char* what) {
 namespace rtk {
 static const char* const kKernelNames[KID_COUNT] = {"dpselect_dis", "dpselect_select", "gather_frames", "rope_table",
                                                     "unrotate_pack", "score_pass1", "score_pass2", "score_finalize",
-                                                    "pivotkv_select", "evict_scan", "copy_rows", "append",
+                                                    "pivotkv_select", "append",
                                                     "evict_batched", "commit_batched", "position_shift", "pivotkv_emit",
                                                     "prologue", "compact_units", "archive_units"};
 struct ProfRec { int kid; hipEvent_t a, b; };
@@ -138,6 +138,6 @@ extern "C" int rtk_profile_copy(void* dst, const void* src, size_t bytes, rtk_st
     return RTK_OK;
 }
 
-extern "C" int rtk_version(void) { return 17; }
+extern "C" int rtk_version(void) { return 18; }
 extern "C" const char* rtk_last_error(void) { return rtk::g_err; }
 extern "C" const char* rtk_arch(void) { return "gfx950"; }

@@ -86,6 +86,19 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
     return v;
 }
+// v = minimum of v over a workgroup of NW waves, in every thread; red: NW words of LDS (one barrier inside).  Updated in
+// place: the by-value form (noundef argument and result) compiles the callers to different code than the loops it replaces
+template <int NW>
+__device__ __forceinline__ void block_min_ll(long long& v, long long* red) {
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long t = __shfl_xor(v, o, WAVE);
+        v = min(v, t);
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[threadIdx.x / WAVE] = v;
+    __syncthreads();
+    v = red[0];
+    for (int w = 1; w < NW; ++w) v = min(v, red[w]);
+}
 
 // order-preserving map float -> uint32 (larger float <=> larger key); -0 < +0 is harmless here
 __device__ __forceinline__ uint32_t f2key(float f) {
@@ -376,6 +389,23 @@ inline bool fits_buffer_offsets(int64_t H, int64_t L, int64_t D, int64_t sh, int
     return last < (1ull << 31);
 }
 
+// RTK_F32 / RTK_BF16 / RTK_F16 payload -> bytes per element and elements per 16-byte vector; false for any other code
+inline bool payload_dims(int dtype, int& es, int& ve) {
+    es = dtype != RTK_F32 ? 2 : 4;
+    ve = 16 / es;
+    return dtype == RTK_F32 || dtype == RTK_BF16 || dtype == RTK_F16;
+}
+
+// n >= 1 units of a HOST array as the by-value argument of a batched launch (Units = struct { unit u[MAX]; }, grid.y = n);
+// the slots past n repeat the last unit and are never read
+template <typename Units, typename Unit>
+inline Units pad_units(const Unit* units, int n) {
+    Units o;
+    constexpr int MAX = (int)(sizeof(o.u) / sizeof(o.u[0]));
+    for (int i = 0; i < MAX; ++i) o.u[i] = units[i < n ? i : n - 1];
+    return o;
+}
+
 inline int make_rowsel(RowSel& rs, int P, int D, const int* sections, int nsec, const char* who) {
     if (D > 256 || (D & 1)) {
         set_error("%s: head_dim %d unsupported (must be even and <= 256)", who, D);
@@ -405,8 +435,8 @@ inline int make_rowsel(RowSel& rs, int P, int D, const int* sections, int nsec, 
 // ---- optional per-kernel HIP-event timing (rtk_profile_*), used by bench.py ------------------------
 namespace rtk {
 enum KernelId {
-    KID_DIS = 0, KID_DPSEL, KID_GATHER, KID_ROPE, KID_UNROT, KID_PASS1, KID_PASS2, KID_FINALIZE, KID_PSEL, KID_EVICT,
-    KID_COPY, KID_APPEND, KID_EVICTB, KID_COMMITB, KID_SHIFT, KID_PEMIT, KID_PROLOGUE, KID_COMPACT, KID_ARCHIVE, KID_COUNT
+    KID_DIS = 0, KID_DPSEL, KID_GATHER, KID_ROPE, KID_UNROT, KID_PASS1, KID_PASS2, KID_FINALIZE, KID_PSEL, KID_APPEND,
+    KID_EVICTB, KID_COMMITB, KID_SHIFT, KID_PEMIT, KID_PROLOGUE, KID_COMPACT, KID_ARCHIVE, KID_COUNT
 };
 bool profile_on(int kid);
 void profile_begin(int kid, hipStream_t st);

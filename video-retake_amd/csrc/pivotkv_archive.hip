@@ -171,8 +171,7 @@ extern "C" int rtk_pivotkv_archive_batched(const rtk_archive_unit* units, int n_
     const int nb = (keep + ARC_R - 1) / ARC_R;
     for (int b = 0; b < n_units; b += RTK_ARCHIVE_MAX_UNITS) {
         const int n = std::min(RTK_ARCHIVE_MAX_UNITS, n_units - b);
-        ArchiveUnits au;
-        for (int i = 0; i < RTK_ARCHIVE_MAX_UNITS; ++i) au.u[i] = units[b + std::min(i, n - 1)];
+        const ArchiveUnits au = pad_units<ArchiveUnits>(units + b, n);
 #define RTK_LAUNCH_ARC(DTV, ROT)                                                                                          \
     RTK_LAUNCH(KID_ARCHIVE, (archive_units_kernel<DTV, ROT>), dim3(nb, n), dim3(ARC_BLOCK), 0, st, au, Hkv, keep, P, inv_freq, \
                attention_scaling, rs, round_mode)

@@ -195,7 +195,8 @@ extern "C" int rtk_pivotkv_compact_batched(const rtk_compact_unit* units, int n_
                                            size_t sync_ws_ints, rtk_stream_t stream) {
     RTK_CHECK_ARG(units && n_units >= 1, "rtk_pivotkv_compact_batched: no units");
     RTK_CHECK_ARG(Hkv >= 1 && keep >= 1 && D >= 2, "rtk_pivotkv_compact_batched: bad shape");
-    RTK_CHECK_ARG(dtype == RTK_F32 || dtype == RTK_BF16 || dtype == RTK_F16, "rtk_pivotkv_compact_batched: unsupported dtype %d", dtype);
+    int es, ve;
+    RTK_CHECK_ARG(payload_dims(dtype, es, ve), "rtk_pivotkv_compact_batched: unsupported dtype %d", dtype);
     RTK_CHECK_ARG(k_mode == RTK_COMPACT_K_ROTATE || k_mode == RTK_COMPACT_K_COPY || k_mode == RTK_COMPACT_K_INPLACE,
                   "rtk_pivotkv_compact_batched: k_mode %d", k_mode);
     RTK_CHECK_ARG(P == 0 || P == 1 || P == 3, "rtk_pivotkv_compact_batched: P must be 0, 1 or 3, got %d", P);
@@ -207,7 +208,6 @@ extern "C" int rtk_pivotkv_compact_batched(const rtk_compact_unit* units, int n_
         set_error("rtk_pivotkv_compact_batched: head_dim %d unsupported for this dtype", D);
         return RTK_EUNSUPPORTED;
     }
-    const int es = dtype != RTK_F32 ? 2 : 4;
     const int HG = (Hkv + CMP_HU - 1) / CMP_HU;
     const size_t stride = (size_t)((CMP_HDR + nb + 31) / 32) * 32;
     if (sync_ws_ints < (size_t)n_units * HG * stride) {
@@ -238,8 +238,7 @@ extern "C" int rtk_pivotkv_compact_batched(const rtk_compact_unit* units, int n_
     hipStream_t st = (hipStream_t)stream;
     for (int b = 0; b < n_units; b += RTK_COMPACT_MAX_UNITS) {
         const int n = std::min(RTK_COMPACT_MAX_UNITS, n_units - b);
-        CompactUnits cu;
-        for (int i = 0; i < RTK_COMPACT_MAX_UNITS; ++i) cu.u[i] = units[b + std::min(i, n - 1)];
+        const CompactUnits cu = pad_units<CompactUnits>(units + b, n);
         int32_t* sy = sync_ws + (size_t)b * HG * stride;
 #define RTK_LAUNCH_CMP(DTV, KM)                                                                                              \
     RTK_LAUNCH(KID_COMPACT, (compact_units_kernel<DTV, KM>), dim3(nb, n * HG), dim3(CMP_BLOCK), 0, st, cu, Hkv, HG, D, keep, \

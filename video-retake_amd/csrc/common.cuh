@@ -3,6 +3,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+#include <type_traits>
+
 #include "retake_hip.h"
 
 namespace rtk {
@@ -62,6 +65,18 @@ template <> struct H16<RTK_F16> {
         return __builtin_amdgcn_fdot2(__builtin_bit_cast(rtk_f16x2, a), __builtin_bit_cast(rtk_f16x2, b), acc, false);
     }
 };
+// halves of a packed bf16 pair as fp32
+__device__ __forceinline__ float bf_lo(uint32_t p) { return __uint_as_float(p << 16); }
+__device__ __forceinline__ float bf_hi(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
+// RTK_BF16_FAST operands: the un-rotated bf16 values re-encoded as fp16 for v_mfma_f32_32x32x16_f16.  A bf16 value has 8
+// significant bits, fp16 holds 11: k~ converts EXACTLY (inside fp16's range; saturated to +-65504 beyond it, 24-bit
+// subnormals below 6e-5), and q~ * log2(e)/sqrt(D) is rounded once, to 11 bits (relative 2^-12), so the matrix pipe
+// delivers the base-2 logits directly and the softmax needs no multiply.
+__device__ __forceinline__ uint32_t pack2_f16(float lo, float hi) {
+    const rtk_f32x2 v = {__builtin_fminf(__builtin_fmaxf(lo, -65504.f), 65504.f),
+                         __builtin_fminf(__builtin_fmaxf(hi, -65504.f), 65504.f)};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, rtk_f16x2));   // v_cvt_f16_f32: round to nearest even
+}
 // A wave-uniform int the compiler keeps in a scalar register (readfirstlane makes the uniformity provable): the head index
 // of the per-update kernels, whose row offsets then travel in the soffset operand of buffer loads / stores (buf_load).
 __device__ __forceinline__ int uniform_int(int x) { return __builtin_amdgcn_readfirstlane(x); }
@@ -211,17 +226,26 @@ template <> struct Vec16<RTK_F16> {
     }
 };
 
-// (x*cos) + (rotate_half(x)*sin) for one 16-byte chunk `lo` of the first half of a row and its partner `hi` in the second
-// half - apply_rotary_pos_emb's op chain with one rounding per torch op and no fma contraction.  16-bit payloads round
-// through the packed converts (H16<DT>::pack2: one instruction per pair); rotate_half(x)[d] = -x2,
-// rotate_half(x)[d + D/2] = x1.  c1 / s1: tables of the channels of `lo`, c2 / s2: of `hi`.
-template <int DT>
-__device__ __forceinline__ void rotate_chunk_pair(const u32x4& lo, const u32x4& hi, const float* c1, const float* s1,
-                                                  const float* c2, const float* s2, u32x4& olo, u32x4& ohi) {
+// NW 32-bit words of a row as one aligned load / store (the narrow-chunk forms of the per-update kernels)
+template <int NW> struct alignas(4 * NW) WV {
+    uint32_t w[NW];
+    __device__ __forceinline__ uint32_t& operator[](int i) { return w[i]; }   // (indexed like the native u32x4)
+    __device__ __forceinline__ const uint32_t& operator[](int i) const { return w[i]; }
+};
+
+// The RoPE arithmetic of every kernel that restates the reference's torch op chains, for NW words `lo` of the first half of
+// a row and their rotation partners `hi` in the second half (16-bit payloads: 2 NW channels each; fp32: NW).  c1 / s1:
+// tables of the channels of `lo`, c2 / s2: of `hi`.  One rounding per torch op and no fma contraction; 16-bit payloads
+// round through the packed converts (H16<DT>::pack2: one instruction per pair).  rotate_half(x)[d] = -x2,
+// rotate_half(x)[d + D/2] = x1.
+// rotate_words: (x*cos) + (rotate_half(x)*sin) - apply_rotary_pos_emb (longvideo_cache.py:28-32, :80-81)
+template <int DT, int NW, class Words>   // Words: WV<NW>, or the native u32x4 (NW = 4)
+__device__ __forceinline__ void rotate_words(const Words& lo, const Words& hi, const float* c1, const float* s1,
+                                             const float* c2, const float* s2, Words& olo, Words& ohi) {
     if constexpr (DT != RTK_F32) {
         using Hh = H16<DT>;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) {
+        for (int w = 0; w < NW; ++w) {
             const float x1a = Hh::lo(lo[w]), x1b = Hh::hi(lo[w]), x2a = Hh::lo(hi[w]), x2b = Hh::hi(hi[w]);
             const int e = 2 * w;
             const uint32_t p1 = Hh::pack2(x1a * c1[e], x1b * c1[e + 1]);
@@ -233,12 +257,70 @@ __device__ __forceinline__ void rotate_chunk_pair(const u32x4& lo, const u32x4& 
         }
     } else {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
+        for (int e = 0; e < NW; ++e) {
             const float x1 = __uint_as_float(lo[e]), x2 = __uint_as_float(hi[e]);
             olo[e] = __float_as_uint(__fadd_rn(__fmul_rn(x1, c1[e]), __fmul_rn(-x2, s1[e])));
             ohi[e] = __float_as_uint(__fadd_rn(__fmul_rn(x2, c2[e]), __fmul_rn(x1, s2[e])));
         }
     }
+}
+// ... of one 16-byte chunk pair held as native vectors (rope / compact / archive / evict)
+template <int DT>
+__device__ __forceinline__ void rotate_chunk_pair(const u32x4& lo, const u32x4& hi, const float* c1, const float* s1,
+                                                  const float* c2, const float* s2, u32x4& olo, u32x4& ohi) {
+    rotate_words<DT, 4>(lo, hi, c1, s1, c2, s2, olo, ohi);
+}
+// unrotate_words: ((x*cos) - (rotate_half(x)*sin)) / a^2 - pos_embed_reforge's un-rotation (longvideo_cache.py:76-78).
+// div: 0 = no division (attention_scaling^2 == 1), 1 = multiply by rcp_a2 (bf16 only; the host has verified over all 65536
+// bf16 inputs that bf16(x * rcp_a2) == bf16(x / a2): bf16_rcp_is_exact), 2 = IEEE division.  Div is an int (chosen at run
+// time, wave-uniform) or a std::integral_constant<int, DIV> (chosen at compile time): one text serves both.
+template <int DT, int NW, class Div>
+__device__ __forceinline__ void unrotate_words(const WV<NW>& lo, const WV<NW>& hi, const float* c1, const float* s1,
+                                               const float* c2, const float* s2, float a2, float rcp_a2, Div div,
+                                               WV<NW>& olo, WV<NW>& ohi) {
+    if constexpr (DT != RTK_F32) {   // bf16 / fp16: every torch op rounds to the tensor dtype
+        using Hh = H16<DT>;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const float x1a = Hh::lo(lo.w[w]), x1b = Hh::hi(lo.w[w]), x2a = Hh::lo(hi.w[w]), x2b = Hh::hi(hi.w[w]);
+            const int e = 2 * w;
+            const uint32_t p1 = Hh::pack2(x1a * c1[e], x1b * c1[e + 1]);          // x1*cos
+            const uint32_t n1 = Hh::pack2(x2a * s1[e], x2b * s1[e + 1]);          // -(rotate_half(x)*sin) = x2*sin
+            const uint32_t p2 = Hh::pack2(x2a * c2[e], x2b * c2[e + 1]);          // x2*cos
+            const uint32_t n2 = Hh::pack2(x1a * s2[e], x1b * s2[e + 1]);          // rotate_half(x)*sin = x1*sin
+            uint32_t t1 = Hh::pack2(Hh::lo(p1) + Hh::lo(n1), Hh::hi(p1) + Hh::hi(n1));
+            uint32_t t2 = Hh::pack2(Hh::lo(p2) - Hh::lo(n2), Hh::hi(p2) - Hh::hi(n2));
+            if (div == 1) {
+                t1 = Hh::pack2(Hh::lo(t1) * rcp_a2, Hh::hi(t1) * rcp_a2);
+                t2 = Hh::pack2(Hh::lo(t2) * rcp_a2, Hh::hi(t2) * rcp_a2);
+            } else if (div == 2) {
+                t1 = Hh::pack2(__fdiv_rn(Hh::lo(t1), a2), __fdiv_rn(Hh::hi(t1), a2));
+                t2 = Hh::pack2(__fdiv_rn(Hh::lo(t2), a2), __fdiv_rn(Hh::hi(t2), a2));
+            }
+            olo.w[w] = t1;
+            ohi.w[w] = t2;
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < NW; ++e) {
+            const float x1 = __uint_as_float(lo.w[e]), x2 = __uint_as_float(hi.w[e]);
+            float o1 = __fsub_rn(__fmul_rn(x1, c1[e]), __fmul_rn(-x2, s1[e]));
+            float o2 = __fsub_rn(__fmul_rn(x2, c2[e]), __fmul_rn(x1, s2[e]));
+            if (div != 0) {
+                o1 = __fdiv_rn(o1, a2);
+                o2 = __fdiv_rn(o2, a2);
+            }
+            olo.w[e] = __float_as_uint(o1);
+            ohi.w[e] = __float_as_uint(o2);
+        }
+    }
+}
+// bf16 pairs -> fp16 pairs of (value * scale): the RTK_BF16_FAST operands (pack2_f16)
+template <int NW> __device__ __forceinline__ WV<NW> bf16_to_f16_words(const WV<NW>& x, float scale) {
+    WV<NW> o;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) o.w[w] = pack2_f16(bf_lo(x.w[w]) * scale, bf_hi(x.w[w]) * scale);
+    return o;
 }
 
 // Shape of the per-update kernels (fused prepare, attention prologue) - A/B: profiles/r12_ab_prologue_shape.txt
@@ -247,9 +329,6 @@ constexpr int PREP_NW = 1;        // 16-bit dtypes: 32-bit words per thread and 
 constexpr int PREP_HU = 7;        // query heads whose rows are requested together (register batch)
 constexpr int PREP_YSPLIT = 2;    // the query heads are split over this many workgroups per token range (k and v go to the
                                   // first and the last)
-
-// NW 32-bit words of a row as one aligned load / store (the narrow-chunk forms of the per-update kernels)
-template <int NW> struct alignas(4 * NW) WV { uint32_t w[NW]; };
 
 // NW-dword accesses through a buffer descriptor: address = descriptor base + soff (SGPR: the head's offset) + voff (VGPR: the
 // thread's offset inside a head, computed once) + a compile-time immediate - no vector ALU work per access (the per-update
@@ -286,6 +365,25 @@ template <int NW, int IMM = 0> __device__ __forceinline__ void buf_store(const W
         __builtin_amdgcn_raw_buffer_store_b128(u4{x.w[0], x.w[1], x.w[2], x.w[3]}, r, voff + IMM, soff, 0);
     }
 }
+
+// The head-batch walk of the per-update kernels.  A row's address = descriptor (tensor base) + soffset (the head: wave-uniform,
+// a scalar multiply) + voffset (the thread's byte offset inside a head, computed once).
+__device__ __forceinline__ uint32_t head_soff(int h, uint32_t head_stride_bytes) {
+    return (uint32_t)uniform_int((int)((uint32_t)h * head_stride_bytes));
+}
+// request the chunk pairs (off, off2) of heads hb .. hb + N - 1 (clamped to hlast: a short last batch repeats its last head)
+template <int NW, int N>
+__device__ __forceinline__ void load_heads(WV<NW>* a, WV<NW>* b, __amdgpu_buffer_rsrc_t r, uint32_t off, uint32_t off2,
+                                           uint32_t head_stride_bytes, int hb, int hlast) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+        const uint32_t so = head_soff(min(hb + u, hlast), head_stride_bytes);
+        a[u] = buf_load<NW>(r, off, so);
+        b[u] = buf_load<NW>(r, off2, so);
+    }
+}
+// (The pipeline's hand-over of the requested batch - lo[u] = lon[u], hi[u] = hin[u] - stays a loop in each kernel: behind a
+// function the compiler schedules those kernels differently.)
 
 }  // namespace rtk
 
@@ -371,14 +469,23 @@ bool bf16_rcp_is_exact(float a2);
 int score_unrotate(int payload, const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, int64_t k_stride_h,
                    int64_t k_stride_l, int Hq, int Hkv, int L, int D, const float* cosv, const float* sinv,
                    float attention_scaling, char* q_out, char* k_out, char* k_f16, hipStream_t st);
-// rtk_pivotkv_prepare with the next layer's id shift in the launch (pivotkv_prepare.hip; used by rtk_pivotkv_update)
-int pivotkv_prepare_shift(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, int64_t k_stride_h,
-                          int64_t k_stride_l, const void* v, int64_t v_stride_h, int64_t v_stride_l, int Hq, int Hkv, int L,
-                          int D, int dtype, const int64_t* pos, int64_t pos_stride, int P, const float* inv_freq,
-                          float attention_scaling, const int* sections_host, int nsec, int round_bf16, void* k_unrot,
-                          void* workspace, size_t workspace_bytes, void* k_tail, void* v_tail, int64_t tail_stride_h,
-                          int64_t* pos_copy, int64_t* shift_row, const int64_t* next_prev, int32_t* ticket,
-                          int64_t ticket_ints, int32_t* status, rtk_stream_t stream);
+// The arguments of rtk_pivotkv_prepare (include/retake_hip.h) as one block, plus the next layer's continuity shift riding in
+// the launch (rtk_pivotkv_update's RTK_UPDATE_SHIFT_NEXT): shift_row != NULL is the temporal row of `pos` itself, ticket
+// the rtk_pivotkv_shift_ticket_ints zeroed device words, status (optional, host-visible) counts a bounded wait that ran out.
+struct PrepareArgs {
+    const void* q; int64_t q_stride_h, q_stride_l;
+    const void* k; int64_t k_stride_h, k_stride_l;
+    const void* v; int64_t v_stride_h, v_stride_l;
+    int Hq, Hkv, L, D, dtype;
+    const int64_t* pos; int64_t pos_stride; int P;
+    const float* inv_freq; float attention_scaling;
+    const int* sections_host; int nsec, round_bf16;
+    void *k_unrot, *workspace; size_t workspace_bytes;
+    void *k_tail, *v_tail; int64_t tail_stride_h;
+    int64_t* pos_copy;
+    int64_t* shift_row; const int64_t* next_prev; int32_t* ticket; int64_t ticket_ints; int32_t* status;
+};
+int pivotkv_prepare_shift(PrepareArgs a, rtk_stream_t stream);   // (pivotkv_prepare.hip; also behind rtk_pivotkv_update)
 
 // The per-update kernels address rows as (descriptor base + 32-bit head offset + 32-bit thread offset): every byte of a
 // [H, L, D] operand with element strides (sh, sl, 1) must lie below 2 GiB from its base, strides non-negative.
@@ -389,11 +496,44 @@ inline bool fits_buffer_offsets(int64_t H, int64_t L, int64_t D, int64_t sh, int
     return last < (1ull << 31);
 }
 
+// One [H, L, D] operand of a buffer-addressed kernel (prepare_native_kernel, prologue_kernel), element strides (stride_h, stride_l, 1)
+struct BufOperand {
+    const void* p;
+    int64_t H, stride_h, stride_l;
+};
+// THE operand rules of the buffer-addressed kernels, for elements of `es` bytes: 16-byte aligned pointers and strides, a row
+// half that is whole 16-byte vectors, head_dim <= 256 (RowSel), and every operand inside 32-bit offsets.  Declines with
+// RTK_EUNSUPPORTED under the caller's name: callers fall back to the stage-by-stage route.
+inline int check_buffer_operands(const char* who, int es, int D, int L, std::initializer_list<BufOperand> ops) {
+    const int ve = 16 / es;
+    bool aligned = D % (2 * ve) == 0 && D <= 256;
+    for (const BufOperand& o : ops)
+        aligned = aligned && ((uintptr_t)o.p & 15) == 0 && (o.stride_h * es) % 16 == 0 && (o.stride_l * es) % 16 == 0;
+    if (!aligned) {
+        set_error("%s: needs 16-byte aligned pointers / strides and head_dim a multiple of %d", who, 2 * ve);
+        return RTK_EUNSUPPORTED;
+    }
+    for (const BufOperand& o : ops)
+        if (!fits_buffer_offsets(o.H, L, D, o.stride_h, o.stride_l, (size_t)es)) {
+            set_error("%s: an operand spans 2 GiB or more (or has a negative stride): 32-bit row offsets do not reach", who);
+            return RTK_EUNSUPPORTED;
+        }
+    return RTK_OK;
+}
+
 // RTK_F32 / RTK_BF16 / RTK_F16 payload -> bytes per element and elements per 16-byte vector; false for any other code
 inline bool payload_dims(int dtype, int& es, int& ve) {
     es = dtype != RTK_F32 ? 2 : 4;
     ve = 16 / es;
     return dtype == RTK_F32 || dtype == RTK_BF16 || dtype == RTK_F16;
+}
+
+// f(std::integral_constant<int, DT>) for the payload of a dtype code: RTK_F32, RTK_F16, or bf16 (RTK_BF16 and the score
+// arithmetics that stand on it)
+template <class F> inline int with_payload(int dtype, F&& f) {
+    if (dtype == RTK_F32) return f(std::integral_constant<int, RTK_F32>{});
+    if (dtype == RTK_F16) return f(std::integral_constant<int, RTK_F16>{});
+    return f(std::integral_constant<int, RTK_BF16>{});
 }
 
 // n >= 1 units of a HOST array as the by-value argument of a batched launch (Units = struct { unit u[MAX]; }, grid.y = n);

@@ -7,6 +7,8 @@
 //   prepare_native_kernel   the per-update form (rtk_pivotkv_prepare, rtk_pivotkv_update): tables built in registers
 //                           from the position ids, k and v appended to the cache tail in the same pass, and optionally
 //                           the next layer's continuity shift of the ids riding in the launch
+// The un-rotation itself is written once, in common.cuh (unrotate_words), for these kernels and the attention prologue
+// (pivotkv_update.hip); only the scalar fallback below spells it per element.
 #include <algorithm>
 #include <type_traits>
 #include <cmath>
@@ -100,53 +102,16 @@ __global__ __launch_bounds__(256) void unrotate_pack_vec_kernel(const char* __re
             *(u32x4*)(orow + (size_t)(d + h2) * ES) = hi[u];
             continue;
         }
-        // rotate_half(x)[d] = -x2, rotate_half(x)[d+h2] = x1   (longvideo_cache.py:28-32)
-        // x~ = ((x*cos) - (rotate_half(x)*sin)) / a^2, one rounding per torch op (:76-78)
-        if constexpr (DT != RTK_F32) {   // bf16 / fp16: every torch op rounds to the tensor dtype
-            using Hh = H16<DT>;
-            const uint32_t wl[4] = {lo[u].x, lo[u].y, lo[u].z, lo[u].w}, wh[4] = {hi[u].x, hi[u].y, hi[u].z, hi[u].w};
-            uint32_t r1[4], r2[4];
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const float x1a = Hh::lo(wl[w]), x1b = Hh::hi(wl[w]), x2a = Hh::lo(wh[w]), x2b = Hh::hi(wh[w]);
-                const int e = 2 * w;
-                const uint32_t p1 = Hh::pack2(x1a * c1[e], x1b * c1[e + 1]);          // x1*cos
-                const uint32_t n1 = Hh::pack2(x2a * s1[e], x2b * s1[e + 1]);          // -(rotate_half(x)*sin) = x2*sin
-                const uint32_t p2 = Hh::pack2(x2a * c2[e], x2b * c2[e + 1]);          // x2*cos
-                const uint32_t n2 = Hh::pack2(x1a * s2[e], x1b * s2[e + 1]);          // rotate_half(x)*sin = x1*sin
-                uint32_t t1 = Hh::pack2(Hh::lo(p1) + Hh::lo(n1), Hh::hi(p1) + Hh::hi(n1));
-                uint32_t t2 = Hh::pack2(Hh::lo(p2) - Hh::lo(n2), Hh::hi(p2) - Hh::hi(n2));
-                if constexpr (DIV == 1) {
-                    t1 = Hh::pack2(Hh::lo(t1) * rcp_a2, Hh::hi(t1) * rcp_a2);
-                    t2 = Hh::pack2(Hh::lo(t2) * rcp_a2, Hh::hi(t2) * rcp_a2);
-                } else if constexpr (DIV == 2) {
-                    t1 = Hh::pack2(__fdiv_rn(Hh::lo(t1), a2), __fdiv_rn(Hh::hi(t1), a2));
-                    t2 = Hh::pack2(__fdiv_rn(Hh::lo(t2), a2), __fdiv_rn(Hh::hi(t2), a2));
-                }
-                r1[w] = t1;
-                r2[w] = t2;
-            }
-            if constexpr (FAST) {
-                store_fast(u32x4{r1[0], r1[1], r1[2], r1[3]}, u32x4{r2[0], r2[1], r2[2], r2[3]});
-            } else {
-                *(u32x4*)(orow + (size_t)d * ES) = u32x4{r1[0], r1[1], r1[2], r1[3]};
-                *(u32x4*)(orow + (size_t)(d + h2) * ES) = u32x4{r2[0], r2[1], r2[2], r2[3]};
-            }
+        // x~ = ((x*cos) - (rotate_half(x)*sin)) / a^2, one rounding per torch op (:76-78): unrotate_words on the chunk pair
+        WV<4> r1, r2;
+        unrotate_words<DT, 4>(WV<4>{{lo[u].x, lo[u].y, lo[u].z, lo[u].w}}, WV<4>{{hi[u].x, hi[u].y, hi[u].z, hi[u].w}}, c1, s1, c2,
+                              s2, a2, rcp_a2, std::integral_constant<int, DIV>{}, r1, r2);
+        const u32x4 o1 = {r1.w[0], r1.w[1], r1.w[2], r1.w[3]}, o2 = {r2.w[0], r2.w[1], r2.w[2], r2.w[3]};
+        if constexpr (FAST) {
+            store_fast(o1, o2);
         } else {
-            float x1[VE], x2[VE], o1[VE], o2[VE];
-            V::unpack(lo[u], x1);
-            V::unpack(hi[u], x2);
-#pragma unroll
-            for (int e = 0; e < VE; ++e) {
-                o1[e] = __fsub_rn(__fmul_rn(x1[e], c1[e]), __fmul_rn(-x2[e], s1[e]));
-                o2[e] = __fsub_rn(__fmul_rn(x2[e], c2[e]), __fmul_rn(x1[e], s2[e]));
-                if constexpr (DIV != 0) {
-                    o1[e] = __fdiv_rn(o1[e], a2);
-                    o2[e] = __fdiv_rn(o2[e], a2);
-                }
-            }
-            *(u32x4*)(orow + (size_t)d * ES) = V::pack(o1);
-            *(u32x4*)(orow + (size_t)(d + h2) * ES) = V::pack(o2);
+            *(u32x4*)(orow + (size_t)d * ES) = o1;
+            *(u32x4*)(orow + (size_t)(d + h2) * ES) = o2;
         }
     }
 }
@@ -288,24 +253,8 @@ __global__ __launch_bounds__(PREP_BLOCK) void prepare_native_kernel(const char* 
                                  r_tail = buf_rsrc(tail), r_kf = buf_rsrc(k_fast);
     const uint32_t hs_q = (uint32_t)(q_sh * ES), hs_kv = (uint32_t)(sh * ES), hs_o = (uint32_t)((int64_t)L * D * ES),
                    hs_t = (uint32_t)(tail_sh * ES);
-    auto load_q = [&](W* a, W* b, int hb) {
-#pragma unroll
-        for (int u = 0; u < HU; ++u) {
-            const int h = min(hb + u, qe - 1);
-            const uint32_t so = (uint32_t)uniform_int((int)((uint32_t)h * hs_q));
-            a[u] = buf_load<NW>(r_q, off_q, so);
-            b[u] = buf_load<NW>(r_q, off_q2, so);
-        }
-    };
-    auto load_kv = [&](W* a, W* b, int hb) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int h = min(hb + u, Hkv - 1);
-            const uint32_t so = (uint32_t)uniform_int((int)((uint32_t)h * hs_kv));
-            a[u] = buf_load<NW>(r_src, off_kv, so);
-            b[u] = buf_load<NW>(r_src, off_kv2, so);
-        }
-    };
+    auto load_q = [&](W* a, W* b, int hb) { load_heads<NW, HU>(a, b, r_q, off_q, off_q2, hs_q, hb, qe - 1); };
+    auto load_kv = [&](W* a, W* b, int hb) { load_heads<NW, 4>(a, b, r_src, off_kv, off_kv2, hs_kv, hb, Hkv - 1); };
     float pid[3];   // the token's ids (t / h / w rows; a 1-D id fills all three)
 #pragma unroll
     for (int p = 0; p < 3; ++p) pid[p] = (float)pos[(size_t)min(p, P - 1) * pos_ld + l];
@@ -321,49 +270,7 @@ __global__ __launch_bounds__(PREP_BLOCK) void prepare_native_kernel(const char* 
     }
     // x~ = ((x*cos) - (rotate_half(x)*sin)) / a^2 for one head's chunk pair, one rounding per torch op (:76-78)
     auto unrot = [&](const W& lo, const W& hi, W& olo, W& ohi) {
-        if constexpr (DT != RTK_F32) {
-            using Hh = H16<DT>;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) {
-                const float x1a = Hh::lo(lo.w[w]), x1b = Hh::hi(lo.w[w]), x2a = Hh::lo(hi.w[w]), x2b = Hh::hi(hi.w[w]);
-                const int e = 2 * w;
-                const uint32_t p1 = Hh::pack2(x1a * c1[e], x1b * c1[e + 1]);
-                const uint32_t n1 = Hh::pack2(x2a * s1[e], x2b * s1[e + 1]);
-                const uint32_t p2 = Hh::pack2(x2a * c2[e], x2b * c2[e + 1]);
-                const uint32_t n2 = Hh::pack2(x1a * s2[e], x1b * s2[e + 1]);
-                uint32_t t1 = Hh::pack2(Hh::lo(p1) + Hh::lo(n1), Hh::hi(p1) + Hh::hi(n1));
-                uint32_t t2 = Hh::pack2(Hh::lo(p2) - Hh::lo(n2), Hh::hi(p2) - Hh::hi(n2));
-                if constexpr (DIV == 1) {
-                    t1 = Hh::pack2(Hh::lo(t1) * rcp_a2, Hh::hi(t1) * rcp_a2);
-                    t2 = Hh::pack2(Hh::lo(t2) * rcp_a2, Hh::hi(t2) * rcp_a2);
-                } else if constexpr (DIV == 2) {
-                    t1 = Hh::pack2(__fdiv_rn(Hh::lo(t1), a2), __fdiv_rn(Hh::hi(t1), a2));
-                    t2 = Hh::pack2(__fdiv_rn(Hh::lo(t2), a2), __fdiv_rn(Hh::hi(t2), a2));
-                }
-                olo.w[w] = t1;
-                ohi.w[w] = t2;
-            }
-        } else {
-            float o1[VE], o2[VE];
-#pragma unroll
-            for (int e = 0; e < VE; ++e) {
-                const float x1 = __uint_as_float(lo.w[e]), x2 = __uint_as_float(hi.w[e]);
-                o1[e] = __fsub_rn(__fmul_rn(x1, c1[e]), __fmul_rn(-x2, s1[e]));
-                o2[e] = __fsub_rn(__fmul_rn(x2, c2[e]), __fmul_rn(x1, s2[e]));
-                if constexpr (DIV != 0) {
-                    o1[e] = __fdiv_rn(o1[e], a2);
-                    o2[e] = __fdiv_rn(o2[e], a2);
-                }
-                olo.w[e] = __float_as_uint(o1[e]);
-                ohi.w[e] = __float_as_uint(o2[e]);
-            }
-        }
-    };
-    auto to_f16 = [&](const W& x, float scale) {   // bf16 pairs -> fp16 pairs of (value * scale)
-        W o;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) o.w[w] = pack2_f16(bf_lo(x.w[w]) * scale, bf_hi(x.w[w]) * scale);
-        return o;
+        unrotate_words<DT, NW>(lo, hi, c1, s1, c2, s2, a2, rcp_a2, std::integral_constant<int, DIV>{}, olo, ohi);
     };
     for (int hb = qb; hb < qe; hb += HU) {
         if (hb + HU < qe) load_q(lon, hin, hb + HU);
@@ -375,10 +282,10 @@ __global__ __launch_bounds__(PREP_BLOCK) void prepare_native_kernel(const char* 
             W olo, ohi;
             unrot(lo[u], hi[u], olo, ohi);
             if constexpr (FAST) {   // the score's A / B operand: fp16(q~ * log2(e)/sqrt(D))
-                olo = to_f16(olo, qscale);
-                ohi = to_f16(ohi, qscale);
+                olo = bf16_to_f16_words<NW>(olo, qscale);
+                ohi = bf16_to_f16_words<NW>(ohi, qscale);
             }
-            const uint32_t so = (uint32_t)uniform_int((int)((uint32_t)h * hs_o));
+            const uint32_t so = head_soff(h, hs_o);
             buf_store<NW>(olo, r_qo, off_o, so);
             buf_store<NW>(ohi, r_qo, off_o2, so);
         }
@@ -394,18 +301,18 @@ __global__ __launch_bounds__(PREP_BLOCK) void prepare_native_kernel(const char* 
         for (int u = 0; u < 4; ++u) {
             const int h = hb + u;
             if (h >= nkv) break;
-            const uint32_t sot = (uint32_t)uniform_int((int)((uint32_t)h * hs_t));
+            const uint32_t sot = head_soff(h, hs_t);
             buf_store<NW>(lo[u], r_tail, off_o, sot);
             buf_store<NW>(hi[u], r_tail, off_o2, sot);
             if (blockIdx.y == 0) {
                 W olo, ohi;
                 unrot(lo[u], hi[u], olo, ohi);
-                const uint32_t so = (uint32_t)uniform_int((int)((uint32_t)h * hs_o));
+                const uint32_t so = head_soff(h, hs_o);
                 buf_store<NW>(olo, r_ko, off_o, so);
                 buf_store<NW>(ohi, r_ko, off_o2, so);
                 if constexpr (FAST) {   // the same k~ as fp16 for the score passes (exact re-encoding)
-                    buf_store<NW>(to_f16(olo, 1.f), r_kf, off_o, so);
-                    buf_store<NW>(to_f16(ohi, 1.f), r_kf, off_o2, so);
+                    buf_store<NW>(bf16_to_f16_words<NW>(olo, 1.f), r_kf, off_o, so);
+                    buf_store<NW>(bf16_to_f16_words<NW>(ohi, 1.f), r_kf, off_o2, so);
                 }
             }
         }
@@ -417,7 +324,8 @@ __global__ __launch_bounds__(PREP_BLOCK) void prepare_native_kernel(const char* 
     }
 }
 
-// scalar fallback (any even head_dim, any alignment)
+// scalar fallback (any even head_dim, any alignment): one thread per channel pair, so there is no packed pair to round
+// through - it keeps the per-element form of the same op chain (H16<DT>::rnd after every torch op) instead of unrotate_words
 template <int DT>
 __global__ __launch_bounds__(256) void unrotate_pack_kernel(const void* __restrict__ xv, int64_t stride_h,
                                                             int64_t stride_l, int H, int L, int D,
@@ -561,34 +469,30 @@ int score_unrotate(int payload, const void* q, int64_t q_stride_h, int64_t q_str
         return unrotate_impl<decltype(dt)::value>(q, q_stride_h, q_stride_l, k, k_stride_h, k_stride_l, Hq, Hkv, L, D, cosv, sinv,
                                                   attention_scaling, q_out, k_out, k_f16, st);
     };
-    if (payload == RTK_F32) return call(std::integral_constant<int, RTK_F32>{});
-    if (payload == RTK_F16) return call(std::integral_constant<int, RTK_F16>{});
-    return call(std::integral_constant<int, RTK_BF16>{});
+    return with_payload(payload, call);
 }
 
+// one prepare_native_kernel launch: qt / k_fast are q~ and (RTK_BF16_FAST) the fp16 k~ inside a.workspace
 template <int DT>
-static int prepare_impl(const void* q, int64_t qsh, int64_t qsl, const void* k, int64_t ksh, int64_t ksl, const void* v,
-                        int64_t vsh, int64_t vsl, int Hq, int Hkv, int L, int D, const int64_t* pos, int64_t pos_stride,
-                        const float* inv_freq, float a, const RowSel& rs, int round_bf16, char* qt, char* kt, void* k_tail,
-                        void* v_tail, int64_t tail_sh, int P, int64_t* pos_copy, hipStream_t st, char* k_fast = nullptr,
-                        int64_t* shift_row = nullptr, const int64_t* next_prev = nullptr, int* ticket = nullptr,
-                        int* status = nullptr) {
-    const float a2 = (float)((double)a * (double)a);
+static int prepare_impl(const PrepareArgs& a, const RowSel& rs, char* qt, char* k_fast, hipStream_t st) {
+    const float a2 = (float)((double)a.attention_scaling * (double)a.attention_scaling);
     const float rcp = 1.0f / a2;
     // 16-bit dtypes: 4-byte chunks per thread - four times the waves of the 16-byte form, a quarter of the instruction
     // stream each (same-box A/B, profiles/r11_ab_prepare_chunk_width.txt: 20.0 -> 16.1 us at L = 2304, 29.6 -> 28.4 at 6272)
     constexpr int NW = DT != RTK_F32 ? PREP_NW : 4;   // 32-bit words per thread and row half
     constexpr int VE = NW * 4 / (DT == RTK_F32 ? 4 : 2);
-    const int threads = L * (D / 2 / VE);
+    const int threads = a.L * (a.D / 2 / VE);
     static_assert(PREP_YSPLIT >= 2, "the first y-slice takes k and the LAST one v: one slice would never append v");
     // (+ one column of workgroups when the next layer's id shift rides along: its last one does the shift)
-    const dim3 grid((threads + PREP_BLOCK - 1) / PREP_BLOCK + (shift_row ? 1 : 0), PREP_YSPLIT);
+    const dim3 grid((threads + PREP_BLOCK - 1) / PREP_BLOCK + (a.shift_row ? 1 : 0), PREP_YSPLIT);
     // k_fast (RTK_BF16_FAST): q~ as fp16(q~ * log2(e)/sqrt(D)), k~ as bf16 (eviction) and as fp16 at k_fast (scoring)
-    const float qscale = k_fast ? 1.4426950408889634f / sqrtf((float)D) : 1.f;
+    const float qscale = k_fast ? 1.4426950408889634f / sqrtf((float)a.D) : 1.f;
     auto launch = [&](auto kern) {
-        RTK_LAUNCH(KID_UNROT, kern, grid, dim3(PREP_BLOCK), 0, st, (const char*)q, qsh, qsl, (const char*)k, ksh, ksl, (const char*)v,
-                   vsh, vsl, Hq, Hkv, L, D, pos, pos_stride, inv_freq, a, rs, round_bf16, a2, rcp, qt, kt, (char*)k_tail,
-                   (char*)v_tail, tail_sh, P, pos_copy, k_fast, qscale, shift_row, next_prev, ticket, status);
+        RTK_LAUNCH(KID_UNROT, kern, grid, dim3(PREP_BLOCK), 0, st, (const char*)a.q, a.q_stride_h, a.q_stride_l, (const char*)a.k,
+                   a.k_stride_h, a.k_stride_l, (const char*)a.v, a.v_stride_h, a.v_stride_l, a.Hq, a.Hkv, a.L, a.D, a.pos,
+                   a.pos_stride, a.inv_freq, a.attention_scaling, rs, a.round_bf16, a2, rcp, qt, (char*)a.k_unrot,
+                   (char*)a.k_tail, (char*)a.v_tail, a.tail_stride_h, a.P, a.pos_copy, k_fast, qscale, a.shift_row, a.next_prev,
+                   a.ticket, a.status);
     };
     with_div<DT>(pick_div<DT>(true, a2), [&](auto div) {
         constexpr int DIV = decltype(div)::value;
@@ -612,10 +516,10 @@ extern "C" int rtk_pivotkv_prepare(const void* q, int64_t q_stride_h, int64_t q_
                                    const int* sections_host, int nsec, int round_bf16, void* k_unrot, void* workspace,
                                    size_t workspace_bytes, void* k_tail, void* v_tail, int64_t tail_stride_h,
                                    int64_t* pos_copy, rtk_stream_t stream) {
-    return rtk::pivotkv_prepare_shift(q, q_stride_h, q_stride_l, k, k_stride_h, k_stride_l, v, v_stride_h, v_stride_l, Hq, Hkv,
-                                      L, D, dtype, pos, pos_stride, P, inv_freq, attention_scaling, sections_host, nsec,
-                                      round_bf16, k_unrot, workspace, workspace_bytes, k_tail, v_tail, tail_stride_h, pos_copy,
-                                      nullptr, nullptr, nullptr, 0, nullptr, stream);
+    return pivotkv_prepare_shift({q, q_stride_h, q_stride_l, k, k_stride_h, k_stride_l, v, v_stride_h, v_stride_l, Hq, Hkv, L, D,
+                                  dtype, pos, pos_stride, P, inv_freq, attention_scaling, sections_host, nsec, round_bf16,
+                                  k_unrot, workspace, workspace_bytes, k_tail, v_tail, tail_stride_h, pos_copy,
+                                  nullptr, nullptr, nullptr, 0, nullptr}, stream);
 }
 
 // words of rtk_update_io.ticket: the launch count (word 0) and the run-out latch (word 31) in the first cache line, then
@@ -625,70 +529,45 @@ extern "C" size_t rtk_pivotkv_shift_ticket_ints(int L, int D) {
     return (size_t)RTK_SHIFT_STRIDE * (1 + RTK_SHIFT_COUNTERS);
 }
 
-// rtk_pivotkv_prepare + (shift_row != NULL) the next layer's continuity shift in the same launch: rtk_pivotkv_update's
-// RTK_UPDATE_SHIFT_NEXT.  shift_row is the temporal row of `pos` itself, ticket the zeroed device words (counters left zero);
-// status (optional, host-visible memory) is incremented if the watcher's bounded wait runs out (see the kernel).
-int rtk::pivotkv_prepare_shift(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, int64_t k_stride_h,
-                               int64_t k_stride_l, const void* v, int64_t v_stride_h, int64_t v_stride_l, int Hq, int Hkv,
-                               int L, int D, int dtype, const int64_t* pos, int64_t pos_stride, int P,
-                               const float* inv_freq, float attention_scaling, const int* sections_host, int nsec,
-                               int round_bf16, void* k_unrot, void* workspace, size_t workspace_bytes, void* k_tail,
-                               void* v_tail, int64_t tail_stride_h, int64_t* pos_copy, int64_t* shift_row,
-                               const int64_t* next_prev, int32_t* ticket, int64_t ticket_ints, int32_t* status,
-                               rtk_stream_t stream) {
-    RTK_CHECK_ARG(!shift_row || (ticket && ticket_ints >= (int64_t)rtk_pivotkv_shift_ticket_ints(L, D)),
+// rtk_pivotkv_prepare + (a.shift_row != NULL) the next layer's continuity shift in the same launch (PrepareArgs, common.cuh)
+int rtk::pivotkv_prepare_shift(PrepareArgs a, rtk_stream_t stream) {
+    RTK_CHECK_ARG(!a.shift_row || (a.ticket && a.ticket_ints >= (int64_t)rtk_pivotkv_shift_ticket_ints(a.L, a.D)),
                   "rtk_pivotkv_prepare: the in-launch id shift needs rtk_pivotkv_shift_ticket_ints(L, D) zeroed device words");
-    const bool k_only = (dtype & RTK_PREPARE_K_ONLY) != 0;   // keep-all chunk: no q~
-    dtype &= ~RTK_PREPARE_K_ONLY;
-    const int dtype_full = dtype;              // may carry RTK_SCORE_MANY_UNITS: the workspace layout follows the split policy
-    dtype &= ~RTK_SCORE_MANY_UNITS;
-    RTK_CHECK_ARG(q && k && v && pos && inv_freq && k_unrot && workspace && k_tail && v_tail, "rtk_pivotkv_prepare: NULL pointer");
-    RTK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && L >= 1 && D >= 2, "rtk_pivotkv_prepare: bad shape");
+    const bool k_only = (a.dtype & RTK_PREPARE_K_ONLY) != 0;   // keep-all chunk: no q~
+    a.dtype &= ~RTK_PREPARE_K_ONLY;
+    const int dtype_full = a.dtype;            // may carry RTK_SCORE_MANY_UNITS: the workspace layout follows the split policy
+    const int dtype = a.dtype &= ~RTK_SCORE_MANY_UNITS;
+    const int L = a.L, D = a.D;
+    RTK_CHECK_ARG(a.q && a.k && a.v && a.pos && a.inv_freq && a.k_unrot && a.workspace && a.k_tail && a.v_tail,
+                  "rtk_pivotkv_prepare: NULL pointer");
+    RTK_CHECK_ARG(a.Hq >= 1 && a.Hkv >= 1 && L >= 1 && D >= 2, "rtk_pivotkv_prepare: bad shape");
     RTK_CHECK_ARG(dtype == RTK_F32 || dtype == RTK_BF16 || dtype == RTK_BF16_FAST || dtype == RTK_F16,
                   "rtk_pivotkv_prepare: unsupported dtype %d", dtype);
-    RTK_CHECK_ARG(pos_stride >= L, "rtk_pivotkv_prepare: pos_stride %lld < L %d", (long long)pos_stride, L);
+    RTK_CHECK_ARG(a.pos_stride >= L, "rtk_pivotkv_prepare: pos_stride %lld < L %d", (long long)a.pos_stride, L);
     const bool fast = dtype == RTK_BF16_FAST && !k_only;
     if (fast && D != HD) {
         set_error("rtk_pivotkv_prepare: RTK_BF16_FAST needs head_dim %d", HD);
         return RTK_EUNSUPPORTED;
     }
-    RTK_CHECK_ARG(((uintptr_t)workspace & 255) == 0, "rtk_pivotkv_prepare: workspace must be 256-byte aligned");
-    const ScoreWs w = score_ws(Hq, Hkv, L, D, dtype_full);
-    if (!k_only && workspace_bytes < w.total) {
-        set_error("rtk_pivotkv_prepare: workspace %zu < required %zu bytes", workspace_bytes, w.total);
+    RTK_CHECK_ARG(((uintptr_t)a.workspace & 255) == 0, "rtk_pivotkv_prepare: workspace must be 256-byte aligned");
+    const ScoreWs w = score_ws(a.Hq, a.Hkv, L, D, dtype_full);
+    if (!k_only && a.workspace_bytes < w.total) {
+        set_error("rtk_pivotkv_prepare: workspace %zu < required %zu bytes", a.workspace_bytes, w.total);
         return RTK_EWORKSPACE;
     }
-    if (k_only) Hq = 0;   // the kernel's query loop is empty; k / v take the same path
-    const int ve = dtype != RTK_F32 ? 8 : 4, es = dtype != RTK_F32 ? 2 : 4;
-    const bool ok = (D % (2 * ve) == 0) && D <= 256 && (q_stride_h * es) % 16 == 0 && (q_stride_l * es) % 16 == 0 &&
-                    (k_stride_h * es) % 16 == 0 && (k_stride_l * es) % 16 == 0 && (v_stride_h * es) % 16 == 0 &&
-                    (v_stride_l * es) % 16 == 0 && (tail_stride_h * es) % 16 == 0 &&
-                    (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)k_unrot | (uintptr_t)k_tail | (uintptr_t)v_tail) & 15) == 0;
-    if (!ok) {
-        set_error("rtk_pivotkv_prepare: needs 16-byte aligned pointers / strides and head_dim a multiple of %d", 2 * ve);
-        return RTK_EUNSUPPORTED;   // callers fall back to rtk_rope_table + rtk_pivotkv_score + rtk_pivotkv_append
-    }
-    if (!(fits_buffer_offsets(Hq, L, D, q_stride_h, q_stride_l, es) && fits_buffer_offsets(Hkv, L, D, k_stride_h, k_stride_l, es) &&
-          fits_buffer_offsets(Hkv, L, D, v_stride_h, v_stride_l, es) && fits_buffer_offsets(Hkv, L, D, tail_stride_h, D, es) &&
-          fits_buffer_offsets(Hq > Hkv ? Hq : Hkv, L, D, (int64_t)L * D, D, es))) {
-        set_error("rtk_pivotkv_prepare: an operand spans 2 GiB or more (or has a negative stride): 32-bit row offsets do not reach");
-        return RTK_EUNSUPPORTED;
-    }
-    RowSel rs;
-    int rc = make_rowsel(rs, P, D, sections_host, nsec, "rtk_pivotkv_prepare");
+    if (k_only) a.Hq = 0;   // the kernel's query loop is empty; k / v take the same path
+    const int Hq = a.Hq, Hkv = a.Hkv, es = dtype != RTK_F32 ? 2 : 4;
+    char* qt = (char*)a.workspace + w.q_off;
+    // (declined: callers fall back to rtk_rope_table + rtk_pivotkv_score + rtk_pivotkv_append)
+    int rc = check_buffer_operands("rtk_pivotkv_prepare", es, D, L,
+                                   {{a.q, Hq, a.q_stride_h, a.q_stride_l}, {a.k, Hkv, a.k_stride_h, a.k_stride_l},
+                                    {a.v, Hkv, a.v_stride_h, a.v_stride_l}, {a.k_tail, Hkv, a.tail_stride_h, D},
+                                    {a.v_tail, Hkv, a.tail_stride_h, D},
+                                    {qt, Hq, (int64_t)L * D, D}, {a.k_unrot, Hkv, (int64_t)L * D, D}});   // the packed q~ and k~
     if (rc) return rc;
-    char* qt = (char*)workspace + w.q_off;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RTK_F16)
-        return prepare_impl<RTK_F16>(q, q_stride_h, q_stride_l, k, k_stride_h, k_stride_l, v, v_stride_h, v_stride_l, Hq, Hkv, L,
-                                     D, pos, pos_stride, inv_freq, attention_scaling, rs, round_bf16, qt, (char*)k_unrot, k_tail,
-                                     v_tail, tail_stride_h, P, pos_copy, st, nullptr, shift_row, next_prev, ticket, status);
-    if (dtype != RTK_F32)
-        return prepare_impl<RTK_BF16>(q, q_stride_h, q_stride_l, k, k_stride_h, k_stride_l, v, v_stride_h, v_stride_l, Hq, Hkv,
-                                      L, D, pos, pos_stride, inv_freq, attention_scaling, rs, round_bf16, qt, (char*)k_unrot,
-                                      k_tail, v_tail, tail_stride_h, P, pos_copy, st,
-                                      fast ? (char*)workspace + w.k_off : nullptr, shift_row, next_prev, ticket, status);
-    return prepare_impl<RTK_F32>(q, q_stride_h, q_stride_l, k, k_stride_h, k_stride_l, v, v_stride_h, v_stride_l, Hq, Hkv, L,
-                                 D, pos, pos_stride, inv_freq, attention_scaling, rs, round_bf16, qt, (char*)k_unrot, k_tail,
-                                 v_tail, tail_stride_h, P, pos_copy, st, nullptr, shift_row, next_prev, ticket, status);
+    RowSel rs;
+    rc = make_rowsel(rs, a.P, D, a.sections_host, a.nsec, "rtk_pivotkv_prepare");
+    if (rc) return rc;
+    char* k_fast = fast ? (char*)a.workspace + w.k_off : nullptr;
+    return with_payload(dtype, [&](auto dt) { return prepare_impl<decltype(dt)::value>(a, rs, qt, k_fast, (hipStream_t)stream); });
 }

@@ -19,22 +19,8 @@ constexpr int REG_ROWS = 128; // rows held in registers per workgroup (32 per wa
 constexpr int SC_BLOCK = 256;
 constexpr int NXCD = 8;      // MI355X: 8 XCDs, workgroup b is dispatched to XCD b % 8
 
-using f32x2_t = __attribute__((ext_vector_type(2))) float;
-// halves of a packed bf16 pair as fp32
-__device__ __forceinline__ float bf_lo(uint32_t p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
-
-// RTK_BF16_FAST operands: the un-rotated bf16 values re-encoded as fp16 for v_mfma_f32_32x32x16_f16.  A bf16 value has 8
-// significant bits, fp16 holds 11: k~ converts EXACTLY (inside fp16's range; saturated to +-65504 beyond it, 24-bit
-// subnormals below 6e-5), and q~ * log2(e)/sqrt(D) is rounded once, to 11 bits (relative 2^-12), so the matrix pipe
-// delivers the base-2 logits directly and the softmax needs no multiply.
-using f16x2_t = __attribute__((ext_vector_type(2))) _Float16;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-__device__ __forceinline__ uint32_t pack2_f16(float lo, float hi) {
-    const f32x2_t v = {__builtin_fminf(__builtin_fmaxf(lo, -65504.f), 65504.f),
-                       __builtin_fminf(__builtin_fmaxf(hi, -65504.f), 65504.f)};
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));   // v_cvt_f16_f32: round to nearest even
-}
+// RTK_BF16_FAST operands of a 16-byte chunk (bf_lo / bf_hi / pack2_f16: common.cuh)
 __device__ __forceinline__ u32x4 bf16x8_to_f16x8(const u32x4& v, float scale) {
     return u32x4{pack2_f16(bf_lo(v.x) * scale, bf_hi(v.x) * scale), pack2_f16(bf_lo(v.y) * scale, bf_hi(v.y) * scale),
                  pack2_f16(bf_lo(v.z) * scale, bf_hi(v.z) * scale), pack2_f16(bf_lo(v.w) * scale, bf_hi(v.w) * scale)};

@@ -198,14 +198,17 @@ int rtk_rope_rotate_rows(void* k, int64_t stride_layer, int64_t stride_h, int la
  * that are already rotated: k [H, n, D] with head stride `stride_h`, delta = one int64 in device
  * memory.  Used by the multi-GPU sharding (retake/sharded.py): ranks compress their chunks at
  * provisional temporal ids; once the global offsets are known, R(p + delta) = R(delta) R(p)
- * (longvideo_cache.py:80-81 composed with the continuity shift of qwen2_vl.py:68-73). */
+ * (longvideo_cache.py:80-81 composed with the continuity shift of qwen2_vl.py:68-73).
+ * rtk_rope_shift and rtk_rope_shift_segments are NOT called by the package any more (finalize keeps the kept keys
+ * un-rotated and rotates them once with rtk_rope_rotate_rows); they stay in the ABI and are tested on their own against
+ * float64 (tests/test_rope_gpu.py). */
 int rtk_rope_shift(void* k, int64_t stride_h, int H, int n, int D, int dtype, const int64_t* delta_dev,
                    const float* inv_freq, int P, const int* sections_host, int nsec, rtk_stream_t stream);
 
 /* The same for a whole assembled cache in one launch: k [layers, H, world * seg, D] (element strides stride_layer,
  * stride_h; rows contiguous), the segment of rank r in layer l rotated by table_dev[r * layers + l] temporal steps
- * (table_dev: device int64 [world, layers], what retake/sharded.exchange_temporal_offsets returns).  Replaces
- * layers x world calls of rtk_rope_shift in ShardedPivotKV.finalize. */
+ * (table_dev: device int64 [world, layers], what retake/sharded.exchange_temporal_offsets returns): the arithmetic of
+ * layers x world calls of rtk_rope_shift, bit for bit. */
 int rtk_rope_shift_segments(void* k, int64_t stride_layer, int64_t stride_h, int layers, int H, int world, int seg, int D,
                             int dtype, const int64_t* table_dev, const float* inv_freq, int P,
                             const int* sections_host, int nsec, rtk_stream_t stream);

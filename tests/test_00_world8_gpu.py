@@ -87,6 +87,26 @@ def test_sharded_prefill_8_ranks_collective_code_path_host_staged():
     assert "chunks 64 on 8 rank(s)" in r.stdout and "chunks 65 on 8 rank(s)" in r.stdout
 
 
+def test_sharded_plain_rope_prefill_8_ranks_over_p2p():
+    """The plain-RoPE (LLaVA protocol, ids [1, L]) sharded prefill at world size 8 over p2p (tests/mp_sharded_gpu.py
+    plain_rope_blocks): 16 chunks (per-chunk pushes), 17 (ragged) and 7 - the eighth rank's block is empty - in fp32 and bf16;
+    assembled video rows == sequential cache on every rank, bit for bit."""
+    _fresh_parent()
+    r = _launch_ranks("mp_sharded_gpu.py", 8, env={"RETAKE_TEST_TRANSPORT": "p2p", "RETAKE_TEST_ONE_GPU": "1",
+                                                   "RETAKE_TEST_ONLY_MORE_CASES": "1", "RETAKE_TEST_PLAIN_ROPE": "1"})
+    assert r.returncode == 0 and "MP_SHARDED_PLAIN_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    assert r.stdout.count("plain RoPE") == 6 and "chunks 7 on 8 rank(s)" in r.stdout
+
+
+def test_sharded_plain_rope_prefill_8_ranks_collective_code_path_host_staged():
+    """The same through the collective-transport code path, every exchange staged through the host over gloo."""
+    _fresh_parent()
+    r = _launch_ranks("mp_sharded_gpu.py", 8, env={"RETAKE_TEST_TRANSPORT": "host", "RETAKE_TEST_ONE_GPU": "1",
+                                                   "RETAKE_TEST_ONLY_MORE_CASES": "1", "RETAKE_TEST_PLAIN_ROPE": "1"})
+    assert r.returncode == 0 and "MP_SHARDED_PLAIN_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    assert r.stdout.count("plain RoPE") == 6 and "chunks 7 on 8 rank(s)" in r.stdout
+
+
 def test_bench_eight_ranks_share_one_gpu_p2p(tmp_path):
     """`bench.py --gpus 8 --transport p2p` end to end with all eight ranks on GPU 0 (RETAKE_BENCH_SHARE_GPU=1) on a 512-frame /
     2-layer video (16 chunks: blocks of 2): world size 8 through rank start-up, halo frames, the in-process

@@ -1504,6 +1504,97 @@ def _single_rank_group():
         dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev())
 
 
+@pytest.mark.parametrize("route,dtype", [("pre_rope", torch.float32), ("pre_rope", torch.bfloat16), ("update", torch.float32)])
+def test_sharded_blocks_reproduce_sequential_cache_plain_rope(route, dtype):
+    """The LLaVA protocol (plain RoPE, ids [1, L], no mrope_section; tests/mp_sharded_gpu.py's plain_rope_* geometry: L 640,
+    keep 63 at the non-dyadic ratio 0.0996, key-patch masks at a rate of 0.05): five chunks compressed as two blocks (2, 3)
+    from provisional id 0 and finalized at first_start = 19 / block 0's last id + 1 must equal the video rows of one cache
+    that saw a 19-token text segment and then all chunks in order.  Through the attention prologue on pre-RoPE projections
+    (fp32, bf16): ids, V and K bit-equal - the contract verify_sharded_equals_sequential states for M-RoPE; through `update`
+    on rotated fp32 tensors: ids and V exact, K within 1e-5 (the M-RoPE twin's bar).  The sequential ids are also compared
+    with rope_ref's reforging formula on the kept indices, so the comparison is not purely self-referential."""
+    import mp_sharded_gpu as mp
+    import rope_ref as rr
+    from retake import sharded
+
+    _single_rank_group()
+    d = dev()
+    rot = mp.plain_rope_rotary(d)
+    inv = torch.from_numpy(synth.inv_freq(mp.PLAIN_D))
+    extra = {"native_rope": False} if route == "update" else {}
+    L, keep, text, last_layer = mp.PLAIN_L, mp.PLAIN_KEEP, mp.PLAIN_TEXT, mp.PLAIN_LAYERS - 1
+    kept = []     # the last layer's kept indices, per chunk
+    seq = mp.plain_rope_sequential(5, dtype, d, rot, route,
+                                   after_chunk=lambda cache, c: kept.append(cache.last_keep_indices.cpu().long()), **extra)
+    assert seq.position_cache[0].shape == (1, text + 5 * keep)
+    # independent: the last layer's ids are the reforged ids of the kept tokens of consecutive ids continuing the previous chunk
+    start = text
+    for c, idx in enumerate(kept):
+        assert idx.numel() == keep and bool((idx[1:] > idx[:-1]).all())
+        want = rr.reforge_ids(start + idx, keep, L)
+        got = seq.position_cache[last_layer][0, text + c * keep:text + (c + 1) * keep].cpu()
+        assert torch.equal(got, want), (c, got.tolist(), want.tolist())
+        start = int(want[-1]) + 1
+    a = sharded.ShardedPivotKV(mp.plain_rope_config(**extra), first_start=text)
+    mp.plain_rope_feed(a.cache, [0, 1], dtype, d, rot, route)
+    ka, va, pa = a.finalize(inv, None, assemble=False)
+    b = sharded.ShardedPivotKV(mp.plain_rope_config(**extra), first_start=torch.stack([p[0, -1] for p in pa]) + 1)
+    mp.plain_rope_feed(b.cache, [2, 3, 4], dtype, d, rot, route)
+    kb, vb, pb = b.finalize(inv, None, assemble=False)
+    for l in range(mp.PLAIN_LAYERS):
+        k_all, v_all, p_all = torch.cat([ka[l], kb[l]], dim=2), torch.cat([va[l], vb[l]], dim=2), torch.cat([pa[l], pb[l]], dim=-1)
+        assert p_all.shape == (1, 5 * keep) and torch.equal(p_all, seq.position_cache[l][:, text:])
+        assert torch.equal(v_all, seq.value_cache[l][:, :, text:])
+        if route == "pre_rope":
+            assert torch.equal(k_all, seq.key_cache[l][:, :, text:])
+        else:
+            assert (k_all - seq.key_cache[l][:, :, text:]).abs().max().item() <= 1e-5
+
+
+def test_sharded_overlapped_assembly_equals_assembly_at_the_end_plain_rope():
+    """The plain-RoPE twin of test_sharded_overlapped_assembly_equals_assembly_at_the_end (3 chunks, bf16, first_start 57):
+    gather_chunk + finalize(assemble=True) - ONE launch of rtk_rope_rotate_rows over the assembled cache with P = 1 - must
+    return, bit for bit, the cache finalize() assembles at the end."""
+    import mp_sharded_gpu as mp
+    from retake import sharded
+
+    _single_rank_group()
+    d = dev()
+    rot = mp.plain_rope_rotary(d)
+    inv = torch.from_numpy(synth.inv_freq(mp.PLAIN_D))
+
+    def run(overlap):
+        sh = sharded.ShardedPivotKV(mp.plain_rope_config(), first_start=57)
+        mp.plain_rope_feed(sh.cache, range(3), torch.bfloat16, d, rot, after_chunk=(lambda cache, c: sh.gather_chunk()) if overlap else None)
+        if overlap:
+            assert sh._gather is not None and sh._gather.rows() == 3 * mp.PLAIN_KEEP
+        return sh.finalize(inv, None, assemble=True)
+
+    ka, va, pa = run(False)
+    kb, vb, pb = run(True)
+    for l in range(mp.PLAIN_LAYERS):
+        assert ka[l].shape == kb[l].shape == (1, mp.PLAIN_HKV, 3 * mp.PLAIN_KEEP, mp.PLAIN_D) and torch.equal(ka[l], kb[l])
+        assert torch.equal(va[l], vb[l]) and torch.equal(pa[l], pb[l])
+        # the first stored id is the block's start + the index of the first kept token (reforging keeps the minimum)
+        assert pa[l].shape == (1, 3 * mp.PLAIN_KEEP) and 57 <= int(pa[l][0, 0]) < 57 + mp.PLAIN_L
+        assert bool((pa[l][0, 1:] >= pa[l][0, :-1]).all())
+
+
+def test_sharded_finalize_of_a_block_that_saw_no_chunk():
+    """A rank whose block is empty (a video with fewer chunks than ranks) holds a cache that never saw an update: `finalize`
+    must not raise on it - at world size 1 there is nobody to learn the geometry from and the result is an empty cache."""
+    import mp_sharded_gpu as mp
+    from retake import sharded
+
+    _single_rank_group()
+    inv = torch.from_numpy(synth.inv_freq(mp.PLAIN_D))
+    for assemble in (False, True):
+        sh = sharded.ShardedPivotKV(mp.plain_rope_config(), first_start=7)
+        keys, values, pos = sh.finalize(inv, None, assemble=assemble)
+        assert len(keys) == len(values) == len(pos)
+        assert all(t.shape[-2] == 0 for t in list(keys) + list(values)) and all(p.shape[-1] == 0 for p in pos)
+
+
 @pytest.mark.parametrize("sync", [True, False])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_dpselect_sharded_ratio_below_one_matches_single_gpu(sync, dtype):
@@ -2313,6 +2404,36 @@ def test_sharded_ranks_over_p2p(world):
     tests/test_00_world8_gpu.py.)"""
     r = _launch_ranks("mp_sharded_gpu.py", world, env={"RETAKE_TEST_TRANSPORT": "p2p", "RETAKE_TEST_ONE_GPU": "1"})
     assert r.returncode == 0 and "MP_SHARDED_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+
+
+@pytest.mark.parametrize("world", [2, 3])
+def test_sharded_plain_rope_ranks_over_p2p(world):
+    """The plain-RoPE (LLaVA protocol, ids [1, L]) sharded prefill at world size 2 and 3 over the p2p transport, all ranks on
+    GPU 0 (tests/mp_sharded_gpu.py plain_rope_blocks): even blocks with per-chunk pushes, ragged blocks with the padded
+    assembly, and world - 1 chunks - one rank's block is empty and takes part in every exchange with zero rows; assembled
+    video rows == sequential cache on every rank, bit for bit, fp32 and bf16."""
+    r = _launch_ranks("mp_sharded_gpu.py", world, env={"RETAKE_TEST_TRANSPORT": "p2p", "RETAKE_TEST_ONE_GPU": "1",
+                                                       "RETAKE_TEST_ONLY_MORE_CASES": "1", "RETAKE_TEST_PLAIN_ROPE": "1"})
+    assert r.returncode == 0 and "MP_SHARDED_PLAIN_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    assert r.stdout.count("plain RoPE") == 6 and f"chunks {world - 1} on {world} rank(s)" in r.stdout
+
+
+def test_sharded_plain_rope_two_ranks_collective_code_path_host_staged():
+    """The same at world size 2 through the COLLECTIVE-transport code path (`ChunkGather`, `all_gather_caches`,
+    `all_gather_ids` with [1, n] ids, `exchange_temporal_offsets` with a -1 row), every exchange staged through the host."""
+    r = _launch_ranks("mp_sharded_gpu.py", 2, env={"RETAKE_TEST_TRANSPORT": "host", "RETAKE_TEST_ONE_GPU": "1",
+                                                   "RETAKE_TEST_ONLY_MORE_CASES": "1", "RETAKE_TEST_PLAIN_ROPE": "1"})
+    assert r.returncode == 0 and "MP_SHARDED_PLAIN_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    assert r.stdout.count("plain RoPE") == 6 and "chunks 1 on 2 rank(s)" in r.stdout
+    assert "overlapped gathers True" in r.stdout and "overlapped gathers False" in r.stdout
+
+
+def test_sharded_plain_rope_multi_rank_rccl():
+    """... and on min(2, visible GPUs) ranks over RCCL (world size 1 on a 1-GPU box: the path through the collectives)."""
+    world = min(2, torch.cuda.device_count())
+    r = _launch_ranks("mp_sharded_gpu.py", world, env={"RETAKE_TEST_ONLY_MORE_CASES": "1", "RETAKE_TEST_PLAIN_ROPE": "1"})
+    assert r.returncode == 0 and "MP_SHARDED_PLAIN_OK" in r.stdout, (r.stdout[-2000:], r.stderr[-3000:])
+    assert r.stdout.count("plain RoPE") == (6 if world >= 2 else 4)
 
 
 def test_p2p_across_gpus():

@@ -266,6 +266,36 @@ def test_ragged_blocks_are_padded_and_trimmed():
         assert pcol == [1, 2, 3, 4, 5, 1001, 1002, 1003, 2001, 2002, 2003]
 
 
+def _plain_ids_with_an_empty_rank(rank, world):
+    """Plain-RoPE ids [1, n] and a middle rank that kept nothing (what `ShardedPivotKV.finalize` hands these helpers for an
+    empty block: zero-row tensors, last id -1)."""
+    from retake import sharded
+
+    n = [4, 0, 2][rank]
+    last = torch.tensor([[6, 9], [-1, -1], [3, 3]][rank], dtype=torch.int64)
+    table = sharded.exchange_temporal_offsets(last, first_start=19, all_ranks=True)
+    mine = sharded.exchange_temporal_offsets(last, first_start=19)
+    layers, Hkv, D = 2, 2, 4
+    keys = [torch.full((1, Hkv, n, D), float(10 * rank + l)) + torch.arange(n)[None, None, :, None] for l in range(layers)]
+    vals = [k + 0.5 for k in keys]
+    pos = [torch.arange(n)[None] + 1000 * rank + l for l in range(layers)]        # [1, n]
+    ids = sharded.all_gather_ids(pos)
+    K, V, P = sharded.all_gather_caches(keys, vals, pos)
+    return (table.tolist(), mine.tolist(), [tuple(p.shape) for p in ids], ids[1][0].tolist(), [tuple(k.shape) for k in K],
+            K[1][0, 1, :, 2].tolist(), V[0][0, 0, :, 0].tolist(), [tuple(p.shape) for p in P], P[0][0].tolist())
+
+
+def test_plain_rope_ids_and_an_empty_block_through_the_gather_helpers():
+    for rank, (table, mine, ishapes, icol, kshapes, kcol, vcol, pshapes, pcol) in enumerate(
+            _spawn("_plain_ids_with_an_empty_rank", world=3)):
+        assert table == [[19, 19], [26, 29], [26, 29]]     # the empty block spans nothing: its successor starts where it would
+        assert mine == table[rank]
+        assert ishapes == [(1, 6), (1, 6)] and icol == [1, 2, 3, 4, 2001, 2002]
+        assert kshapes == [(1, 2, 6, 4)] * 2 and kcol == [1, 2, 3, 4, 21, 22]
+        assert vcol == [0.5, 1.5, 2.5, 3.5, 20.5, 21.5]
+        assert pshapes == [(1, 6), (1, 6)] and pcol == [0, 1, 2, 3, 2000, 2001]
+
+
 def test_phase_timer_sums_spans_between_marks_per_step():
     """PhaseTimer on the host clock (its form under gloo): a phase is the span up to its mark, the two orders in which
     `finalize` marks rotate / assembly both add up, `step` is start -> last mark, means are per recorded step."""

@@ -603,9 +603,35 @@ class ShardedPivotKV:
 
         cache = self.cache
         cache.after_forward()
-        n_layers = len(cache.position_cache)
-        dev = cache.position_cache[0].device
-        last = torch.stack([pc.reshape(-1, pc.shape[-1])[0, -1] for pc in cache.position_cache])   # [layers]
+        pcs = cache.position_cache
+        # A rank whose block is empty (fewer chunks than ranks: `shard_chunks` hands out (c, c) blocks) holds a cache that
+        # never saw an update - no layers, no device, no dtype.  It still takes part in EVERY exchange below, with zero
+        # rows: the ranks first tell each other (layers, Hkv, D, dtype, id rank) in one small all-gather - the first
+        # collective of `finalize` on every rank - and an empty rank adopts the geometry of the first rank that has rows.
+        if pcs:
+            dev = pcs[0].device
+            k0 = cache.key_cache[0]
+            mine = [len(pcs), k0.shape[1], k0.shape[3], nv.dtype_code(k0), pcs[0].ndim]
+        else:
+            p2p = _P2P.get(self.group)
+            dev = p2p.device if p2p is not None else torch.device("cuda", torch.cuda.current_device())
+            mine = [0, 0, 0, -1, 0]
+        geo = _gather_stack(torch.tensor(mine, dtype=torch.int64, device=dev), self.group).tolist()
+        have = [g_ for g_ in geo if g_[0] > 0]
+        if not have:       # nobody kept a row (the same answer on every rank): an empty cache, nothing to exchange
+            self._gather = None
+            return [], [], []
+        if any(g_ != have[0] for g_ in have):
+            raise RuntimeError(f"sharded finalize: the ranks' caches disagree on (layers, Hkv, D, dtype, id rank): {geo}")
+        n_layers, Hkv_, D_, dcode, id_ndim = have[0]
+        empty = not pcs
+        if empty:
+            dt = {nv.RTK_F32: torch.float32, nv.RTK_BF16: torch.bfloat16, nv.RTK_F16: torch.float16}[dcode]
+            pcs = [torch.empty((3, 1, 0) if id_ndim == 3 else (1, 0), dtype=torch.int64, device=dev) for _ in range(n_layers)]
+            kv0 = [torch.empty((1, Hkv_, 0, D_), dtype=dt, device=dev) for _ in range(n_layers)]
+            last = torch.full((n_layers,), -1, dtype=torch.int64, device=dev)     # "-1 if the block kept nothing"
+        else:
+            last = torch.stack([pc.reshape(-1, pc.shape[-1])[0, -1] for pc in pcs])               # [layers]
         table = exchange_temporal_offsets(last, self.first_start, self.group, all_ranks=True)      # [world, layers]
         delta = table[dist.get_rank(self.group)]                                                   # [layers]
         _mark(phases, "offsets")
@@ -621,8 +647,8 @@ class ShardedPivotKV:
             st = nv.stream()
             inv = inv_freq.to(device=dev, dtype=torch.float32).contiguous()
             for layer in range(n_layers):
-                k, v = cache.key_cache[layer], cache.value_cache[layer]
-                pc = cache.position_cache[layer]
+                k, v = (kv0[layer], kv0[layer]) if empty else (cache.key_cache[layer], cache.value_cache[layer])
+                pc = pcs[layer]
                 if pc.ndim == 3:
                     pc[0] += delta[layer]
                 else:
@@ -633,7 +659,7 @@ class ShardedPivotKV:
 
             def rotate_own():
                 """this rank's kept rows of every layer, in place in the layers' cache buffers, at their final ids"""
-                for layer in range(n_layers):
+                for layer in range(0 if empty else n_layers):
                     st_l = cache._layers[layer]
                     kbuf, k = st_l.k, keys[layer]
                     P = 3 if pos[layer].ndim == 3 else 1

@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (59 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (63 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -39,10 +39,12 @@
  *                                       package calls per update / per chunk / per decode step
  *   §H  "Direct peer-to-peer all-gather over xGMI"  rtk_p2p_alloc / _free / _export / _open / _close / _push / _wait
  *   §I  "Chunk attention"               rtk_attention_forward (+ rtk_attention_workspace_bytes): the chunk's queries over
- *                                       [compressed prefix | current chunk], opt-in (attention_kernel="hip")
+ *                                       [compressed prefix | current chunk], opt-in (attention_kernel="hip");
+ *                                       rtk_attention_decode (+ _workspace_bytes): the same function for few query
+ *                                       rows, GQA-packed, opt-in (decode_attention="packed")
  *   §J  "Measurement support"           rtk_profile_* (off by default)
  *   §K  "FP8 rows of the compressed cache"  rtk_pivotkv_archive_batched, rtk_attention_forward_fp8kv (+ _workspace_bytes_fp8kv),
- *                                       rtk_fp8kv_dequant: opt-in (kv_cache_dtype="fp8_e4m3" with attention_kernel="hip")
+ *                                       rtk_attention_decode_fp8kv (+ _workspace_bytes_fp8kv), rtk_fp8kv_dequant: opt-in (kv_cache_dtype="fp8_e4m3" with attention_kernel="hip")
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -717,6 +719,29 @@ int rtk_attention_forward(const void* q, int64_t q_stride_h, int64_t q_stride_l,
                           int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
                           int D, int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
 
+/* rtk_attention_forward for FEW query rows (decode steps, short trailing text), GQA-packed: the same function, the same
+ * arguments, another kernel.  Envelope: RTK_BF16 / RTK_F16, D == 128 and R = (Hq / Hkv) * Lq <= 16 packed rows - Lq <= 2 at
+ * 7 or 8 query heads per kv head, up to Lq 16 at one.  One workgroup serves one kv head and one key range: the R rows
+ * (g, i) of the kv head - row i of query head hkv * (Hq / Hkv) + g - are the columns of one MFMA operand, so every K and V
+ * byte is fetched once per call, not once per query head.  The range's key tiles of T = 32 keys go to the workgroup's four
+ * waves round robin; each wave keeps its own (max, sum, acc), the four are folded in wave order, and the workgroup leaves
+ * one un-normalised partial per row, which the second launch of rtk_attention_forward folds in split order.  No atomics.
+ * The plan is a function of (Hkv, K) alone, K = Lk keys:
+ *     n0     = max(1, min(ceil(512 / Hkv), ceil(K / 128)))
+ *     kps    = 128 * ceil(ceil(K / n0) / 128)                      keys per split
+ *     nsplit = ceil(K / kps)                                       split s takes keys [s * kps, min(K, (s + 1) * kps))
+ * (no split is empty; a split wholly above a row's diagonal leaves that row's partial empty and the fold skips it), so
+ * results are bit-reproducible and stream-independent.  They are NOT the bits of rtk_attention_forward: the fp32 sums are
+ * grouped differently.  The partials ALWAYS live in `workspace`, laid out [nsplit][Hq][Lq][D] fp32 accumulators followed
+ * by [nsplit][Hq][Lq][2] fp32 (max, sum): rtk_attention_decode_workspace_bytes() = nsplit * Hq * Lq * (D + 2) * 4 bytes
+ * (0, with the message set, for arguments rtk_attention_decode would reject), 16-byte aligned.
+ * Errors, all before any launch: those of rtk_attention_forward, same codes and messages; RTK_EUNSUPPORTED, naming the
+ * reason, for RTK_F32, D != 128 and (Hq / Hkv) * Lq > 16 - the caller then makes the rtk_attention_forward call. */
+size_t rtk_attention_decode_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int D, int dtype);
+int rtk_attention_decode(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                         int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                         int D, int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement support (bench.py).  When enabled, every kernel launch of this library is bracketed
  * by two hipEvents recorded on the launch stream; rtk_profile_collect() waits for them and folds
@@ -805,6 +830,18 @@ int rtk_attention_forward_fp8kv(const void* q, int64_t q_stride_h, int64_t q_str
                                 const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
                                 int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
                                 int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+
+/* rtk_attention_decode over [archive | 16-bit rows]: the arguments of rtk_attention_forward_fp8kv, the envelope, errors and
+ * workspace layout of rtk_attention_decode.  The plan is that of rtk_attention_decode with K = Lk + L8 rounded up to a
+ * multiple of the key tile T = 32: the archive comes first, padded to whole tiles, so a tile is of one kind.  Archive rows
+ * are dequantised by rule 5 on their way into the operands, and whenever L8 % 32 == 0 the result equals, bit for bit,
+ * rtk_attention_decode over [dequantised archive | 16-bit rows] with q_offset + L8.  L8 == 0 IS rtk_attention_decode. */
+size_t rtk_attention_decode_workspace_bytes_fp8kv(int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype);
+int rtk_attention_decode_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                               int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                               const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                               int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
+                               int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,19 @@ the ratio sdpa / native.  One JSON document; a markdown table on stdout.
 The same shapes with the first P0 keys as fp8 rows (kv_cache_dtype="fp8_e4m3"): the two-segment call
 (rtk_attention_forward_fp8kv: e4m3 archive + 16-bit tail) against the 16-bit kernel on [dequantised archive | tail], same
 process, same timing; whether the two outputs are bit-equal (they must be when P0 % 64 == 0) is recorded per shape.
+
+    python tools/bench_attention.py --decode [--fp8kv] [--out profiles/[fp8kv_]decode_attention_bench.json]
+
+The few-row shapes of generation - Lq 1 and 2 over Lk 4 000, 25 088 and 100 352 (bf16, and fp16 once) - through the
+GQA-packed kernel (rtk_attention_decode) and through rtk_attention_forward, the call it replaces, on the same tensors in
+this same process, beside the SDPA route.  Both native entry points are called directly with a resident output and
+workspace (the host cost of chunk_attention, tens of microseconds, would otherwise be most of a packed call), DECODE_INNER
+calls back to back between one pair of HIP events, the time divided by DECODE_INNER; the median of `reps` such samples.
+Reported per shape: the K/V bytes one call reads once, what fraction of 8 TB/s and of the calibration copy
+(rtk_profile_copy over a 2 GiB buffer, read + write bytes) the packed call reaches on them, and the milliseconds per
+generated token (x 28 layers).  --fp8kv: all but the last Lq keys as fp8 rows - the packed two-segment call, the packed
+16-bit call on [dequantised archive | tail] (their ratio, and whether the outputs are bit-equal: they must be when
+L8 % 32 == 0), and rtk_attention_forward_fp8kv.
 """
 from __future__ import annotations
 
@@ -40,6 +53,10 @@ PEAK_FLOPS = 2.5e15
 HQ, HKV, D = 28, 4, 128
 CHUNK_SHAPES = [(2304, 0), (2304, 3456), (2304, 7488), (6272, 0), (6272, 50176), (6272, 98784)]
 FEW_ROW_SHAPES = [(5, 100352 - 5), (1, 100352 - 1)]   # text segment / decode step over Lk 100 352
+DECODE_SHAPES = [(Lq, Lk - Lq) for Lk in (4000, 25088, 100352) for Lq in (1, 2)]
+DECODE_INNER = 10     # launches per timed sample of --decode
+LAYERS = 28           # attention calls per generated token
+HBM_PEAK = 8e12
 
 
 def flop(Lq, P0):
@@ -126,9 +143,138 @@ def main_fp8kv(args):
               f"{r['ratio_fp8kv_over_dense16']:.2f} | {r['kv_bytes_fp8kv'] / r['kv_bytes_16bit']:.2f} | {r['bit_equal']} |")
 
 
+def copy_rate(dev):
+    """bytes / s (read + write) of rtk_profile_copy over a 2 GiB buffer: the calibration of bench.py's hbm_achievable."""
+    import retake._native as nv
+
+    n = 1 << 31
+    src = torch.empty(n, dtype=torch.uint8, device=dev).random_()
+    dst = torch.empty_like(src)
+    fn = lambda: nv.check(nv.lib.rtk_profile_copy(nv.ptr(dst), nv.ptr(src), n, nv.stream()), "rtk_profile_copy")   # noqa: E731
+    fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return 2 * n * 5 / (e0.elapsed_time(e1) * 1e-3)
+
+
+def main_decode(args):
+    import retake._native as nv
+    import retake.longvideo_cache as lc
+
+    dev = torch.device("cuda:0")
+    G = HQ // HKV
+    copy = copy_rate(dev)
+    torch.cuda.empty_cache()
+    cases = [(s, torch.bfloat16) for s in DECODE_SHAPES] + [(DECODE_SHAPES[-2], torch.float16)]
+    rows = []
+    for (Lq, P0), dtype in cases:
+        q, k, v, mask = make(Lq, P0, dtype, dev)
+        Lk, code, stream = P0 + Lq, nv.dtype_code(q), nv.stream()
+        out = torch.empty((1, Lq, HQ, D), dtype=dtype, device=dev)
+        scale = D ** -0.5
+        L8 = P0 // 32 * 32 if args.fp8kv else 0     # whole key tiles: the two packed calls must then agree bit for bit
+        kd, vd = k, v
+        if args.fp8kv:
+            ak, sk = lc.fp8_quantize_rows(k[:, :, :L8].contiguous())
+            av, sv = lc.fp8_quantize_rows(v[:, :, :L8].contiguous())
+            kd, vd = k.clone(), v.clone()               # [dequantised archive | tail]
+            lc.fp8_dequantize_rows(ak, sk, dtype, kd[:, :, :L8])
+            lc.fp8_dequantize_rows(av, sv, dtype, vd[:, :, :L8])
+            kt, vt = k[:, :, L8:], v[:, :, L8:]
+            a8 = (nv.ptr(ak), nv.ptr(av), nv.ptr(sk), nv.ptr(sv), L8, ak.stride(1), sk.stride(1))
+
+        def direct(fn, kk, vv, archive=()):
+            """DECODE_INNER back-to-back calls of one entry point on (q, kk, vv), resident output and workspace."""
+            sfx = "_fp8kv" if archive else ""
+            n8 = archive[4] if archive else 0
+            shape = (HQ, HKV, Lq, kk.shape[2]) + ((n8,) if archive else ()) + (D, code)
+            need = getattr(nv.lib, fn + "_workspace_bytes" + sfx)(*shape)
+            ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+            call = getattr(nv.lib, fn + sfx)
+            a = (nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(kk), nv.ptr(vv), kk.stride(1), kk.stride(2)) + tuple(archive) + \
+                (nv.ptr(out), HQ, HKV, Lq, kk.shape[2], kk.shape[2] - Lq, D, code, scale, nv.ptr(ws), need, stream)
+
+            def run():
+                for _ in range(DECODE_INNER):
+                    nv.check(call(*a), fn + sfx)
+                return out
+            return run
+
+        def sdpa():
+            for _ in range(DECODE_INNER):
+                kk, vv = lc.repeat_kv(kd, G), lc.repeat_kv(vd, G)
+                qc, kc, vc = (t.contiguous() for t in (q, kk, vv))
+                o = torch.nn.functional.scaled_dot_product_attention(qc, kc, vc, attn_mask=mask, dropout_p=0.0, is_causal=False)
+                o = o.transpose(1, 2).contiguous()
+            return o
+
+        if args.fp8kv:
+            routes = (("packed_fp8kv", direct("rtk_attention_decode", kt, vt, a8)),
+                      ("packed_dense16", direct("rtk_attention_decode", kd, vd)),
+                      ("forward_fp8kv", direct("rtk_attention_forward", kt, vt, a8)))
+            kv_bytes = 2 * HKV * (L8 * (D + 4) + (Lk - L8) * D * 2)
+        else:
+            routes = (("packed", direct("rtk_attention_decode", k, v)), ("forward", direct("rtk_attention_forward", k, v)),
+                      ("sdpa", sdpa))
+            kv_bytes = 2 * HKV * Lk * D * 2
+        row = {"Lq": Lq, "P0": P0, "Lk": Lk, "Hq": HQ, "Hkv": HKV, "D": D, "dtype": str(dtype)[6:], "reps": args.reps,
+               "inner": DECODE_INNER, "kv_bytes": kv_bytes, "copy_bytes_per_s": copy}
+        if args.fp8kv:
+            row["L8"] = L8
+        outs = {}
+        for name, fn in routes:
+            us, _, o = timed(fn, args.reps, args.warmup)
+            outs[name] = o.clone()   # (the native routes share one resident output)
+            row[name] = {"us": us / DECODE_INNER, "ms_per_token": us / DECODE_INNER * LAYERS * 1e-3}
+        first = routes[0][0]
+        t = row[first]["us"] * 1e-6
+        row[first].update({"fraction_of_8_TBps": kv_bytes / t / HBM_PEAK, "fraction_of_copy": kv_bytes / t / copy})
+        if args.fp8kv:
+            row["ratio_fp8kv_over_dense16"] = row["packed_fp8kv"]["us"] / row["packed_dense16"]["us"]
+            row["ratio_forward_fp8kv_over_packed_fp8kv"] = row["forward_fp8kv"]["us"] / row["packed_fp8kv"]["us"]
+            row["bit_equal"] = bool(torch.equal(outs["packed_fp8kv"], outs["packed_dense16"]))
+        else:
+            row["ratio_forward_over_packed"] = row["forward"]["us"] / row["packed"]["us"]
+            row["ratio_sdpa_over_packed"] = row["sdpa"]["us"] / row["packed"]["us"]
+            row["max_abs_diff_packed_vs_forward"] = (outs["packed"].float() - outs["forward"].float()).abs().max().item()
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        del q, k, v, kd, vd, mask, outs, routes
+        torch.cuda.empty_cache()
+    doc = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "hbm_peak_bytes_per_s": HBM_PEAK,
+           "copy_bytes_per_s": copy, "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    if args.fp8kv:
+        print("\n| dtype | Lq | L8 | packed fp8kv us | packed 16-bit on dequantised rows us | fp8kv / 16-bit | rtk_attention_forward_fp8kv us "
+              "| K/V MB | of 8 TB/s | of the copy | ms / token | bit-equal |")
+        print("|---|---|---|---|---|---|---|---|---|---|---|---|")
+        for r in rows:
+            p = r["packed_fp8kv"]
+            print(f"| {r['dtype']} | {r['Lq']} | {r['L8']} | {p['us']:.1f} | {r['packed_dense16']['us']:.1f} | "
+                  f"{r['ratio_fp8kv_over_dense16']:.2f} | {r['forward_fp8kv']['us']:.1f} | {r['kv_bytes'] / 1e6:.1f} | "
+                  f"{p['fraction_of_8_TBps']:.3f} | {p['fraction_of_copy']:.3f} | {p['ms_per_token']:.2f} | {r['bit_equal']} |")
+        return
+    print("\n| dtype | Lq | Lk | packed us | rtk_attention_forward us | forward / packed | SDPA route us | K/V MB | of 8 TB/s "
+          "| of the copy | packed ms / token | forward ms / token |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        p = r["packed"]
+        print(f"| {r['dtype']} | {r['Lq']} | {r['Lk']} | {p['us']:.1f} | {r['forward']['us']:.1f} | {r['ratio_forward_over_packed']:.2f} | "
+              f"{r['sdpa']['us']:.1f} | {r['kv_bytes'] / 1e6:.1f} | {p['fraction_of_8_TBps']:.3f} | {p['fraction_of_copy']:.3f} | "
+              f"{p['ms_per_token']:.2f} | {r['forward']['ms_per_token']:.2f} |")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fp8kv", action="store_true", help="the two-segment fp8 call against the 16-bit kernel on dequantised rows")
+    ap.add_argument("--decode", action="store_true", help="the GQA-packed few-row kernel against the call it replaces")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -138,7 +284,10 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_attention.py needs the GPU: a CPU run measures nothing")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "fp8kv_attention_bench.json" if args.fp8kv else "attention_bench.json")
+        args.out = os.path.join(ROOT, "profiles", ("fp8kv_" if args.fp8kv else "") + ("decode_" if args.decode else "") +
+                                "attention_bench.json")
+    if args.decode:
+        return main_decode(args)
     if args.fp8kv:
         return main_fp8kv(args)
     import retake.longvideo_cache as lc

@@ -25,9 +25,7 @@
 // Few query rows — both kernels take a key range per blockIdx "split" and leave un-normalised (m, l, acc) partials in
 // the caller's workspace; attn_combine_kernel folds them split 0, 1, 2 ... in that fixed order (no atomics).  The
 // number of splits is a function of the shape alone.
-#include <cmath>
-
-#include "fp8kv.cuh"
+#include "attention_shared.cuh"
 
 namespace rtk {
 namespace {
@@ -54,29 +52,9 @@ template <int DT> __device__ __forceinline__ void mma16(f32x16& acc, const u32x4
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
 }
 
-// descriptor over `bytes` bytes from a wave-uniform base: loads beyond it return zero
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t bounded_rsrc(const void* p, uint32_t bytes) {
-    const unsigned long long a = (unsigned long long)p;
-    const unsigned long long u = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
-                                 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a);
-    return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ u32x4 load16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0);
-    return u32x4{v[0], v[1], v[2], v[3]};
-}
 // row r of the accumulator register `reg` in lane half `hf` of a 32x32 MFMA result
 __device__ __forceinline__ int acc_row(int reg, int hf) { return (reg & 3) + 8 * (reg >> 2) + 4 * hf; }
 __device__ __forceinline__ int swz(int row) { return ((row & 3) << 2) | ((row >> 2) & 3); }
-__device__ __forceinline__ float safe_max(float m) { return m == -INFINITY ? 0.f : m; }
-
-// The e4m3 archive that precedes the 16-bit keys (retake_hip.h "FP8 rows of the compressed cache"): L8 rows per kv head.
-struct Archive8 {
-    const char *k8, *v8;        // codes, row (h, r) at h * sh8 + r * 128 bytes
-    const float *ks, *vs;       // scales, row (h, r) at h * shs + r
-    int64_t sh8, shs;
-    int L8;
-};
 
 // The body of both kernels is attention_d128_body.inc, included once each with FP8 false / true - a function the two
 // kernels share compiles the existing instantiations differently (tools/kernel_diff.py), the same text does not.
@@ -104,15 +82,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_d128_fp8kv_kernel(
     int keys_per_split, Archive8 a8) {
     constexpr bool FP8 = true;
 #include "attention_d128_body.inc"
-}
-
-template <int DT> __device__ __forceinline__ float ld_elem(const void* p, size_t i) {
-    if constexpr (DT == RTK_F32) return ((const float*)p)[i];
-    else return H16<DT>::ld(p, i);
-}
-template <int DT> __device__ __forceinline__ void st_elem(void* p, size_t i, float x) {
-    if constexpr (DT == RTK_F32) ((float*)p)[i] = x;
-    else H16<DT>::st(p, i, x);
 }
 
 // One wave per (query row, head, key split).  Per step of 64 keys: lane j computes the logit of key j0 + j (fp32 FMA
@@ -195,30 +164,6 @@ __global__ __launch_bounds__(256) void attn_fwd_general_kernel(const char* __res
     }
 }
 
-// out[row, h, d] from the key splits' (m, l, acc) partials, folded in split order 0, 1, 2, ...
-template <int DT>
-__global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restrict__ part_acc, const float* __restrict__ part_ml,
-                                                           char* __restrict__ out, int Hq, int Lq, int D, int nsplit) {
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x, total = (size_t)Lq * Hq * D;
-    if (idx >= total) return;
-    const int d = (int)(idx % D);
-    const size_t rh = idx / D;   // row * Hq + h
-    const int h = (int)(rh % Hq);
-    const size_t row = rh / Hq;
-    float mg = -INFINITY;
-    for (int s = 0; s < nsplit; ++s) mg = fmaxf(mg, part_ml[2 * (((size_t)s * Hq + h) * Lq + row)]);
-    float num = 0.f, den = 0.f;
-    for (int s = 0; s < nsplit; ++s) {
-        const size_t prow = ((size_t)s * Hq + h) * Lq + row;
-        const float ms = part_ml[2 * prow];
-        if (ms == -INFINITY) continue;   // a split wholly above this row's diagonal
-        const float w = __builtin_amdgcn_exp2f(ms - mg);
-        num = __builtin_fmaf(w, part_acc[prow * D + d], num);
-        den = __builtin_fmaf(w, part_ml[2 * prow + 1], den);
-    }
-    st_elem<DT>(out, idx, num / den);
-}
-
 struct AttnPlan {
     bool fast;
     int nsplit, keys_per_split;
@@ -245,25 +190,6 @@ AttnPlan attn_plan(int Hq, int Lq, int Lk, int D, int dtype) {
     p.keys_per_split = (int)kps;
     p.ws_bytes = ns > 1 ? (size_t)ns * Hq * Lq * ((size_t)D + 2) * sizeof(float) : 0;
     return p;
-}
-
-int attn_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int D, int dtype) {
-    RTK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && Lq >= 1 && Lk >= 1, "%s: Hq, Hkv, Lq and Lk must be positive", who);
-    RTK_CHECK_ARG(Hq % Hkv == 0, "%s: Hq %d is not a multiple of Hkv %d", who, Hq, Hkv);
-    RTK_CHECK_ARG(Lk >= Lq, "%s: Lk %d < Lq %d (the queries are the last Lq rows of the keys)", who, Lk, Lq);
-    if (dtype != RTK_F32 && dtype != RTK_BF16 && dtype != RTK_F16) {
-        set_error("%s: unsupported dtype code %d (RTK_F32, RTK_BF16 or RTK_F16)", who, dtype);
-        return RTK_EUNSUPPORTED;
-    }
-    if (D < 8 || D > 256 || D % 8 != 0) {
-        set_error("%s: unsupported head_dim %d (a multiple of 8 up to 256)", who, D);
-        return RTK_EUNSUPPORTED;
-    }
-    if (Hq > 65535) {
-        set_error("%s: unsupported Hq %d (at most 65535)", who, Hq);
-        return RTK_EUNSUPPORTED;
-    }
-    return RTK_OK;
 }
 
 template <int DT>
@@ -339,6 +265,28 @@ int attn_launch_fp8kv(const AttnPlan& pl, const void* q, int64_t q_sh, int64_t q
 // the archive padded to whole key tiles: the key count the split plan of an fp8kv call is made for
 inline long long fp8kv_keys(int Lk, int L8) { return (long long)Lk + ((long long)L8 + AT_KT - 1) / AT_KT * AT_KT; }
 
+}  // namespace
+
+// (declared in attention_shared.cuh: the packed decode entry points run the same checks)
+int attn_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int D, int dtype) {
+    RTK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && Lq >= 1 && Lk >= 1, "%s: Hq, Hkv, Lq and Lk must be positive", who);
+    RTK_CHECK_ARG(Hq % Hkv == 0, "%s: Hq %d is not a multiple of Hkv %d", who, Hq, Hkv);
+    RTK_CHECK_ARG(Lk >= Lq, "%s: Lk %d < Lq %d (the queries are the last Lq rows of the keys)", who, Lk, Lq);
+    if (dtype != RTK_F32 && dtype != RTK_BF16 && dtype != RTK_F16) {
+        set_error("%s: unsupported dtype code %d (RTK_F32, RTK_BF16 or RTK_F16)", who, dtype);
+        return RTK_EUNSUPPORTED;
+    }
+    if (D < 8 || D > 256 || D % 8 != 0) {
+        set_error("%s: unsupported head_dim %d (a multiple of 8 up to 256)", who, D);
+        return RTK_EUNSUPPORTED;
+    }
+    if (Hq > 65535) {
+        set_error("%s: unsupported Hq %d (at most 65535)", who, Hq);
+        return RTK_EUNSUPPORTED;
+    }
+    return RTK_OK;
+}
+
 int fp8kv_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype) {
     const int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
     if (rc != RTK_OK) return rc;
@@ -354,7 +302,42 @@ int fp8kv_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, 
     return RTK_OK;
 }
 
-}  // namespace
+int attn_check_operands(const char* who, const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                        int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8, const float* k_scale,
+                        const float* v_scale, int64_t stride8_h, int64_t scale_stride_h, const void* out, int Lq, int Lk,
+                        int q_offset, int D, int dtype, float scale, int q_slack, int kv_slack) {
+    RTK_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
+    RTK_CHECK_ARG(q_offset >= Lk - Lq && q_offset <= 0x3fffffff,
+                  "%s: q_offset %d < Lk - Lq = %d (the last keys would be visible to no row)", who, q_offset, Lk - Lq);
+    const size_t es = dtype == RTK_F32 ? 4 : 2;
+    // 16-byte row chunks, and per-head extents (the head offset is folded into the descriptor base) that fit the 31-bit
+    // buffer offsets with a tile of slack rows
+    const bool aligned = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)k8 | (uintptr_t)v8) & 15) == 0 &&
+                         (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3) == 0 && stride8_h % 16 == 0 &&
+                         (q_stride_h * (int64_t)es) % 16 == 0 && (q_stride_l * (int64_t)es) % 16 == 0 &&
+                         (kv_stride_h * (int64_t)es) % 16 == 0 && (kv_stride_l * (int64_t)es) % 16 == 0;
+    if (!aligned || q_stride_l < D || kv_stride_l < D || q_stride_h < 0 || kv_stride_h < 0 || stride8_h < 0 || scale_stride_h < 0) {
+        set_error("%s: unsupported layout (16-byte aligned pointers and strides, row strides >= head_dim)", who);
+        return RTK_EUNSUPPORTED;
+    }
+    if (!fits_buffer_offsets(1, (int64_t)Lq + q_slack, D, 0, q_stride_l, es) ||
+        !fits_buffer_offsets(1, (int64_t)Lk + kv_slack, D, 0, kv_stride_l, es)) {
+        set_error("%s: unsupported extent: one head of q or k / v spans 2 GiB or more", who);
+        return RTK_EUNSUPPORTED;
+    }
+    return RTK_OK;
+}
+
+int attn_check_workspace(const char* who, const char* query, size_t need, const void* workspace, size_t workspace_bytes) {
+    if (!need) return RTK_OK;
+    if (!workspace || workspace_bytes < need) {
+        set_error("%s: workspace too small (%zu < %zu bytes; query %s)", who, workspace ? workspace_bytes : (size_t)0, need, query);
+        return RTK_EWORKSPACE;
+    }
+    RTK_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    return RTK_OK;
+}
+
 }  // namespace rtk
 
 using namespace rtk;
@@ -370,35 +353,14 @@ extern "C" int rtk_attention_forward(const void* q, int64_t q_stride_h, int64_t 
                                      rtk_stream_t stream) {
     const char* who = "rtk_attention_forward";
     RTK_CHECK_ARG(q && k && v && out, "%s: NULL q / k / v / out pointer", who);
-    const int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
+    int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
     if (rc != RTK_OK) return rc;
-    RTK_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    RTK_CHECK_ARG(q_offset >= Lk - Lq && q_offset <= 0x3fffffff,
-                  "%s: q_offset %d < Lk - Lq = %d (the last keys would be visible to no row)", who, q_offset, Lk - Lq);
-    const size_t es = dtype == RTK_F32 ? 4 : 2;
-    // 16-byte row chunks, and per-head extents (the head offset is folded into the descriptor base) that fit the 31-bit
-    // buffer offsets with a tile of slack rows
-    const bool aligned = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0 &&
-                         (q_stride_h * (int64_t)es) % 16 == 0 && (q_stride_l * (int64_t)es) % 16 == 0 &&
-                         (kv_stride_h * (int64_t)es) % 16 == 0 && (kv_stride_l * (int64_t)es) % 16 == 0;
-    if (!aligned || q_stride_l < D || kv_stride_l < D || q_stride_h < 0 || kv_stride_h < 0) {
-        set_error("%s: unsupported layout (16-byte aligned pointers and strides, row strides >= head_dim)", who);
-        return RTK_EUNSUPPORTED;
-    }
-    if (!fits_buffer_offsets(1, (int64_t)Lq + AT_QB, D, 0, q_stride_l, es) ||
-        !fits_buffer_offsets(1, (int64_t)Lk + AT_KT, D, 0, kv_stride_l, es)) {
-        set_error("%s: unsupported extent: one head of q or k / v spans 2 GiB or more", who);
-        return RTK_EUNSUPPORTED;
-    }
+    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, nullptr, nullptr, nullptr, nullptr,
+                             0, 0, out, Lq, Lk, q_offset, D, dtype, scale, AT_QB, AT_KT);
+    if (rc != RTK_OK) return rc;
     const AttnPlan pl = attn_plan(Hq, Lq, Lk, D, dtype);
-    if (pl.ws_bytes) {
-        if (!workspace || workspace_bytes < pl.ws_bytes) {
-            set_error("%s: workspace too small (%zu < %zu bytes; query rtk_attention_workspace_bytes)", who,
-                      workspace ? workspace_bytes : (size_t)0, pl.ws_bytes);
-            return RTK_EWORKSPACE;
-        }
-        RTK_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    }
+    rc = attn_check_workspace(who, "rtk_attention_workspace_bytes", pl.ws_bytes, workspace, workspace_bytes);
+    if (rc != RTK_OK) return rc;
     const float c2 = scale * 1.44269504088896340736f;   // the kernels exponentiate in base 2
     hipStream_t st = (hipStream_t)stream;
     void* ws = pl.ws_bytes ? workspace : nullptr;
@@ -422,38 +384,18 @@ extern "C" int rtk_attention_forward_fp8kv(const void* q, int64_t q_stride_h, in
                                            rtk_stream_t stream) {
     const char* who = "rtk_attention_forward_fp8kv";
     RTK_CHECK_ARG(q && k && v && out, "%s: NULL q / k / v / out pointer", who);
-    const int rc = fp8kv_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype);
+    int rc = fp8kv_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype);
     if (rc != RTK_OK) return rc;
     if (L8 == 0)   // no archive yet: the 16-bit call itself
         return rtk_attention_forward(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset,
                                      D, dtype, scale, workspace, workspace_bytes, stream);
     RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
-    RTK_CHECK_ARG(scale > 0.f && std::isfinite(scale), "%s: scale must be positive and finite", who);
-    RTK_CHECK_ARG(q_offset >= Lk - Lq && q_offset <= 0x3fffffff,
-                  "%s: q_offset %d < Lk - Lq = %d (the last keys would be visible to no row)", who, q_offset, Lk - Lq);
-    const size_t es = 2;
-    const bool aligned = (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)k8 | (uintptr_t)v8) & 15) == 0 &&
-                         (((uintptr_t)k_scale | (uintptr_t)v_scale) & 3) == 0 && stride8_h % 16 == 0 &&
-                         (q_stride_h * (int64_t)es) % 16 == 0 && (q_stride_l * (int64_t)es) % 16 == 0 &&
-                         (kv_stride_h * (int64_t)es) % 16 == 0 && (kv_stride_l * (int64_t)es) % 16 == 0;
-    if (!aligned || q_stride_l < D || kv_stride_l < D || q_stride_h < 0 || kv_stride_h < 0 || stride8_h < 0 || scale_stride_h < 0) {
-        set_error("%s: unsupported layout (16-byte aligned pointers and strides, row strides >= head_dim)", who);
-        return RTK_EUNSUPPORTED;
-    }
-    if (!fits_buffer_offsets(1, (int64_t)Lq + AT_QB, D, 0, q_stride_l, es) ||
-        !fits_buffer_offsets(1, (int64_t)Lk + AT_KT, D, 0, kv_stride_l, es)) {
-        set_error("%s: unsupported extent: one head of q or k / v spans 2 GiB or more", who);
-        return RTK_EUNSUPPORTED;
-    }
+    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, k8, v8, k_scale, v_scale,
+                             stride8_h, scale_stride_h, out, Lq, Lk, q_offset, D, dtype, scale, AT_QB, AT_KT);
+    if (rc != RTK_OK) return rc;
     const AttnPlan pl = attn_plan(Hq, Lq, (int)fp8kv_keys(Lk, L8), D, dtype);
-    if (pl.ws_bytes) {
-        if (!workspace || workspace_bytes < pl.ws_bytes) {
-            set_error("%s: workspace too small (%zu < %zu bytes; query rtk_attention_workspace_bytes_fp8kv)", who,
-                      workspace ? workspace_bytes : (size_t)0, pl.ws_bytes);
-            return RTK_EWORKSPACE;
-        }
-        RTK_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    }
+    rc = attn_check_workspace(who, "rtk_attention_workspace_bytes_fp8kv", pl.ws_bytes, workspace, workspace_bytes);
+    if (rc != RTK_OK) return rc;
     const float c2 = scale * 1.44269504088896340736f;
     const Archive8 a8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
     void* ws = pl.ws_bytes ? workspace : nullptr;

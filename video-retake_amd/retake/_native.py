@@ -155,11 +155,17 @@ _SIGNATURES = {
     "rtk_attention_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "rtk_attention_forward": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz,
                                     _vp]),
+    "rtk_attention_decode_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz,
+                                   _vp]),
     "rtk_pivotkv_archive_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _i, _i, _vp]),
     "rtk_fp8kv_dequant": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _i, _vp]),
     "rtk_attention_workspace_bytes_fp8kv": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "rtk_attention_forward_fp8kv": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp,
                                           _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "rtk_attention_decode_workspace_bytes_fp8kv": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_fp8kv": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp,
+                                         _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),
     "rtk_p2p_free": (C.c_int, [_vp]),
     "rtk_p2p_export": (C.c_int, [_vp, _vp, C.POINTER(_sz)]),

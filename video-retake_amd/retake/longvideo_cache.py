@@ -499,7 +499,8 @@ class _CacheView:
             self._o._adopt(len(self._o._layers) - 1, self._w, value)
 
 
-def chunk_attention(query_states, key_states, value_states, scaling=None, workspace=None, query_offset=None, archive=None):
+def chunk_attention(query_states, key_states, value_states, scaling=None, workspace=None, query_offset=None, archive=None,
+                    packed_gqa=False, route=None):
     """Attention of a chunk's queries over [compressed prefix | current chunk] in one HIP launch (rtk_attention_forward):
     what the reference's attention patches hand to torch / flash_attn after the cache update (qwen2_vl.py:88-117,
     :188-219, :303-358; llava_onevision.py:118-139).
@@ -517,7 +518,12 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
     archive: optional (k8, v8, k_scale, v_scale) - e4m3 codes uint8 [1, Hkv, L8, D] and fp32 scales [1, Hkv, L8] of rows that
     PRECEDE key_states / value_states in the sequence (kv_cache_dtype="fp8_e4m3"; rtk_attention_forward_fp8kv, bf16 / fp16
     with head_dim 128 only).  Every query row sees all of them; query_offset then counts over the L8 + Lk keys (default
-    L8 + Lk - Lq)."""
+    L8 + Lk - Lq).
+
+    packed_gqa: try the GQA-packed few-row kernel first (rtk_attention_decode, or rtk_attention_decode_fp8kv with an
+    archive: bf16 / fp16, head_dim 128, (Hq / Hkv) * Lq <= 16).  A shape it declines (RTK_EUNSUPPORTED) takes the call above
+    in this same invocation, so it returns the bits the default returns.  Its partials are kept in `workspace` under a key
+    of their own.  route: optional list; the call appends "packed" or "chunk", whichever kernel produced the result."""
     nv.require_device(query_states, key_states, value_states)
     if query_states.dim() != 4 or key_states.dim() != 4 or value_states.dim() != 4 or query_states.shape[0] != 1:
         raise ValueError("chunk_attention takes [1, H, L, D] tensors (one unpadded sequence)")
@@ -548,36 +554,42 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
             raise ValueError("archive rows must be dense (D codes per row, one scale per row)")
         L8 = k8.shape[2]
     q_off = L8 + Lk - Lq if query_offset is None else int(query_offset)
-    if archive is not None:
-        need = nv.lib.rtk_attention_workspace_bytes_fp8kv(Hq, Hkv, Lq, Lk, L8, D, code)
-    else:
-        need = nv.lib.rtk_attention_workspace_bytes(Hq, Hkv, Lq, Lk, D, code)
     stream = nv.raw_stream(query_states.device.index)
-    ws = None
-    if need:
-        key = ("attention_ws", query_states.device.index, stream)   # per stream: calls on two streams may overlap
+    out = torch.empty((1, Lq, Hq, D), dtype=query_states.dtype, device=query_states.device)
+
+    def scratch(tag, need):   # per stream: calls on two streams may overlap
+        if not need:
+            return None
+        key = (tag, query_states.device.index, stream)
         ws = None if workspace is None else workspace.get(key)
         if ws is None or ws.numel() < need:
             ws = torch.empty(need, dtype=torch.uint8, device=query_states.device)
             if workspace is not None:
                 workspace[key] = ws
-    out = torch.empty((1, Lq, Hq, D), dtype=query_states.dtype, device=query_states.device)
+        return ws
+
+    qkv = (nv.ptr(query_states), query_states.stride(1), query_states.stride(2), nv.ptr(key_states), nv.ptr(value_states),
+           key_states.stride(1), key_states.stride(2))
     if archive is not None:   # (an empty archive included: the library then runs the 16-bit call itself)
-        rc = nv.lib.rtk_attention_forward_fp8kv(
-            nv.ptr(query_states), query_states.stride(1), query_states.stride(2), nv.ptr(key_states), nv.ptr(value_states),
-            key_states.stride(1), key_states.stride(2), nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), L8, k8.stride(1),
-            ks8.stride(1), nv.ptr(out), Hq, Hkv, Lq, Lk, q_off - L8, D, code, scale, nv.ptr(ws), need, stream)
+        qkv += (nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), L8, k8.stride(1), ks8.stride(1))
+        shape = (Hq, Hkv, Lq, Lk, L8, D, code)
+        sfx = "_fp8kv"
+    else:
+        shape = (Hq, Hkv, Lq, Lk, D, code)
+        sfx = ""
+    routes = (("packed", "rtk_attention_decode", "rtk_attention_decode_workspace_bytes", "attention_decode_ws"),) \
+        if packed_gqa else ()
+    for tag, fn, query, ws_tag in routes + (("chunk", "rtk_attention_forward", "rtk_attention_workspace_bytes", "attention_ws"),):
+        need = getattr(nv.lib, query + sfx)(*shape)
+        ws = scratch(ws_tag, need)
+        rc = getattr(nv.lib, fn + sfx)(*qkv, nv.ptr(out), Hq, Hkv, Lq, Lk, q_off - L8, D, code, scale, nv.ptr(ws), need, stream)
         if rc == nv.RTK_EUNSUPPORTED:
-            return None
-        nv.check(rc, "rtk_attention_forward_fp8kv")
+            continue
+        nv.check(rc, fn + sfx)
+        if route is not None:
+            route.append(tag)
         return out
-    rc = nv.lib.rtk_attention_forward(nv.ptr(query_states), query_states.stride(1), query_states.stride(2),
-                                      nv.ptr(key_states), nv.ptr(value_states), key_states.stride(1), key_states.stride(2),
-                                      nv.ptr(out), Hq, Hkv, Lq, Lk, q_off, D, code, scale, nv.ptr(ws), need, stream)
-    if rc == nv.RTK_EUNSUPPORTED:
-        return None
-    nv.check(rc, "rtk_attention_forward")
-    return out
+    return None
 
 
 def fp8_quantize_rows(x: torch.Tensor):
@@ -799,6 +811,10 @@ class PivotKVCache(DynamicCache):
         # and leaves the 16-bit length where it was.  Lossy, not in the reference; needs attention_kernel="hip".
         self.kv_cache_dtype = None
         self.attention_calls = 0      # native attention launches so far (tests count them)
+        # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it): "packed" makes `attention` try
+        # the GQA-packed few-row kernel first (chunk_attention(packed_gqa=True)); None (default): exactly as without it
+        self.decode_attention = None
+        self.decode_attention_calls = 0   # ... of which took the packed kernel
         self._attn_ws: Dict[Any, torch.Tensor] = {}
 
     def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None, layer_idx=None):
@@ -811,10 +827,13 @@ class PivotKVCache(DynamicCache):
             if layer_idx is None:
                 raise ValueError("PivotKVCache.attention needs layer_idx when kv_cache_dtype is set")
             archive = self.archive(layer_idx)
+        route = []
         out = chunk_attention(query_states, key_states, value_states, scaling=scaling, workspace=self._attn_ws,
-                              query_offset=query_offset, archive=archive)
+                              query_offset=query_offset, archive=archive, packed_gqa=self.decode_attention == "packed",
+                              route=route)
         if out is not None:
             self.attention_calls += 1
+            self.decode_attention_calls += route == ["packed"]
         elif self.kv_cache_dtype is not None:
             raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r}: the native chunk attention refuses this shape "
                                       f"({nv.lib.rtk_last_error().decode(errors='replace')}) and no other route reads the fp8 rows")
@@ -2188,6 +2207,13 @@ class PivotKVCache(DynamicCache):
         return True
 
 
+def _decode_attention_of(config):
+    kind = config.longvideo_kwargs.get("decode_attention", None)
+    if kind not in (None, "packed"):
+        raise ValueError(f"decode_attention must be None or 'packed', got {kind!r}")
+    return kind
+
+
 def _kv_cache_dtype_of(config):
     kind = config.longvideo_kwargs.get("kv_cache_dtype", None)
     if kind not in KV_CACHE_DTYPES:
@@ -2205,6 +2231,9 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
         cache = PivotKVCache(config, reserve_tokens=reserve_tokens, reserve_archive_tokens=reserve_archive_tokens)
         cache.attention_kernel = _attention_kernel_of(config)
         cache.kv_cache_dtype = _kv_cache_dtype_of(config)
+        cache.decode_attention = _decode_attention_of(config)
+        if cache.decode_attention is not None and cache.attention_kernel != "hip":
+            raise ValueError("decode_attention='packed' needs attention_kernel='hip': it is a kernel of the native attention")
         if cache.kv_cache_dtype is not None:
             if cache.attention_kernel != "hip":
                 raise ValueError("kv_cache_dtype='fp8_e4m3' needs attention_kernel='hip': the third-party attention routes "

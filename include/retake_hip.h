@@ -308,6 +308,28 @@ int rtk_pivotkv_score_passes_batched_q(void* workspace0, size_t workspace_stride
                                        const void* const* q_units_host, int64_t q_stride_h, int64_t q_stride_l,
                                        rtk_stream_t stream);
 
+/* Prompt-guided scoring (kvcache_compression_kwargs["prompt_guided_scoring"]; NOT in the reference, whose
+ * PivotKVCache.before_forward ignores prompt_length): the chunk's L rows are Lv = L - Lp video rows followed by the Lp rows
+ * of the appended prompt, and the video keys are scored by the prompt's queries alone -
+ *   score[j] = mean_g mean_{h in g} (1/Lp) sum_{i in [Lv,L)} softmax_{j' in [0,Lv)}(q~[h,i] . k~[g,j'] / sqrt(D))[j]
+ * for j < Lv: softmax over the video keys only, no causal mask, prompt keys never read; every score is < 1.  Arithmetic of
+ * the RTK_F32 / RTK_BF16 / RTK_F16 codes (exact products, fp32 accumulation, softmax and sums; RTK_EUNSUPPORTED for the
+ * other codes).  One call serves 1 .. 28 (layer, chunk) units laid out as for rtk_pivotkv_score_passes_batched_q: the units'
+ * score workspaces (q~ [Hq, L, D] at offset 0 from RTK_SCORE_PREPARE / rtk_pivotkv_prepare / rtk_pivotkv_update), their k~
+ * [Hkv, L, D] (k_unrot0 == NULL: inside the workspaces), optionally the queries read in place through q_units_host +
+ * element strides (workspace0 may then be NULL when k_unrot0 is given).  Reads rows [Lv, L) of q~ and rows [0, Lv) of k~;
+ * writes the FINAL score[0 .. Lv) of unit u at score0 + u * score_stride_floats (entries >= Lv are not touched).
+ * scratch0: rtk_pivotkv_score_prompt_workspace_bytes per unit, units scratch_stride bytes apart, 256-byte aligned (the
+ * rows' log-sum-exps between the two launches).  bf16 / fp16 with head_dim 128: MFMA kernels whose row operand packs the
+ * G * Lp query rows of a KV group into 32-row blocks (pivotkv_score_prompt.hip); fp32 or any other head_dim: plain FMA,
+ * the parity path.  No atomics; every sum runs in an order fixed by the shape, so two runs give the same bits. */
+size_t rtk_pivotkv_score_prompt_workspace_bytes(int Hq, int Hkv, int L, int Lp, int D, int dtype);
+int rtk_pivotkv_score_prompt_batched(void* workspace0, size_t workspace_stride, void* k_unrot0, size_t k_unrot_stride,
+                                     float* score0, size_t score_stride_floats, void* scratch0, size_t scratch_stride,
+                                     int n_units, int Hq, int Hkv, int L, int Lp, int D, int dtype,
+                                     const void* const* q_units_host, int64_t q_stride_h, int64_t q_stride_l,
+                                     rtk_stream_t stream);
+
 /* P6-P7, P9-P10  longvideo_cache.py:272-277, :283-295.
  *   score [L] fp32: entries with mask != 0 are overwritten with 1.0 IN PLACE (masked_fill_, :274);
  *   mask may be NULL.

@@ -64,6 +64,7 @@ class ArchiveUnit(C.Structure):
 
 COMPACT_K_ROTATE, COMPACT_K_COPY, COMPACT_K_INPLACE = 0, 1, 2
 ARCHIVE_MAX_UNITS = 28
+PROMPT_SCORE_MAX_UNITS = 28   # units per rtk_pivotkv_score_prompt_batched call
 P2P_MAX_RANKS, IPC_HANDLE_BYTES = 16, 64
 
 
@@ -134,6 +135,9 @@ _SIGNATURES = {
     "rtk_pivotkv_score_passes_batched": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_pivotkv_score_passes_batched_q": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i64,
                                                      _i64, _vp]),
+    "rtk_pivotkv_score_prompt_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "rtk_pivotkv_score_prompt_batched": (C.c_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp, _i64,
+                                                   _i64, _vp]),
     "rtk_pivotkv_score_partials": (C.c_size_t, [_i, _i, _i, _i, _i, C.POINTER(C.c_int)]),
     "rtk_pivotkv_select_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _vp]),
     "rtk_pivotkv_prepare": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _i64, _i,

@@ -300,8 +300,11 @@ class _Batch:
     """Per-chunk batch of pending evictions: slot = layer index.  All units share the chunk geometry."""
 
     def __init__(self, key, slots, Hq, Hkv, L, D, keep, P, reforge, dtype, device, refround=False, fast=False,
-                 keep_all=False, skip_masked=True, in_place_compaction=True):
+                 keep_all=False, skip_masked=True, in_place_compaction=True, prompt=0):
         self.key, self.slots, self.keep, self.P, self.reforge = key, slots, keep, P, reforge
+        # prompt-guided scoring: the chunk's last `prompt` rows are the appended prompt; they score the Lv video keys, the
+        # selection runs over those Lv columns and no prompt row is cached (0: an ordinary chunk)
+        self.prompt, self.Lv = int(prompt), L - int(prompt)
         self.wrap = False          # flush_every_layers: slot = layer % slots (else slot == layer)
         self.keep_all = keep_all   # keep == L and no scoring asked for: the selection is the identity
         # dtype code of the scoring entry points: bf16 payloads with the reference's bf16 rounding chain, or through the
@@ -313,6 +316,8 @@ class _Batch:
         self.batched_passes = dtype in (torch.bfloat16, torch.float16) and D == 128 and L >= 512
         if self.batched_passes:   # all layers of a chunk per launch: splits chosen for the stream length (same flag everywhere)
             self.score_dt |= nv.RTK_SCORE_MANY_UNITS
+        if self.prompt:   # scored at the flush whatever the shape (rtk_pivotkv_score_prompt_batched): q~ waits in the slot's workspace
+            self.batched_passes = True
         # what rtk_pivotkv_prepare is told: the payload dtype (the reference-rounding mode prepares like plain bf16)
         self.prep_dt = ((nv.RTK_BF16 if dtype == torch.bfloat16 else nv.RTK_F16) if refround else self.score_dt & 0xFF) \
             | (self.score_dt & ~0xFF)
@@ -324,7 +329,7 @@ class _Batch:
         self.esize = 4 if dtype == torch.float32 else 2
         self.pos_ndim = 3 if P == 3 else 2
         self.round_mode = nv.round_mode(dtype)
-        self.defer_select = L >= 512   # the chip-wide selection kernels; smaller chunks select inside update
+        self.defer_select = L >= 512 or bool(self.prompt)   # the chip-wide selection kernels; smaller chunks select inside update
         self.keep_idx = torch.arange(keep, dtype=torch.int64, device=device).repeat(slots, 1) if keep_all \
             else torch.empty((slots, keep), dtype=torch.int64, device=device)
         self.pos_new = torch.empty((P, slots, keep), dtype=torch.int64, device=device) if P else None
@@ -342,6 +347,11 @@ class _Batch:
         self.ws_bytes = nv.lib.rtk_pivotkv_score_workspace_bytes(Hq, Hkv, L, D, self.score_dt)
         self.ws_stride = (self.ws_bytes + 255) & ~255
         self.partials = self.score = self.sel_ws = self.score_ws = self.key_index = None
+        # prompt-guided units: per-slot scratch of the thin score kernels and the video rows' ids as dense [P, Lv] blocks
+        self.prompt_bytes = nv.lib.rtk_pivotkv_score_prompt_workspace_bytes(Hq, Hkv, L, self.prompt, D, self.score_dt) \
+            if self.prompt else 0
+        self.prompt_ws = self.pos_video = None
+        self.prompt_ws_base = 0
         self.score_ws_base = 0
         self.v_stage = None
         if reforge:  # kept K is re-rotated from the un-rotated copy straight into the cache: no K staging
@@ -436,6 +446,10 @@ class _Batch:
         c.sel_ws_stride = self.sel_bytes
         c.score_ws, c.score_ws_stride, c.score_ws_bytes = self.score_ws_base, self.ws_stride, self.ws_bytes
         c.key_index = self.key_index.data_ptr()
+        if self.prompt:
+            self.prompt_ws = torch.empty(slots * self.prompt_bytes + 256, dtype=torch.uint8, device=device)
+            self.prompt_ws_base = (self.prompt_ws.data_ptr() + 255) & ~255
+            self.pos_video = torch.empty((slots, self.P, self.Lv), dtype=torch.int64, device=device) if self.P else None
 
     def ensure_staging(self):
         if self.v_stage is None:
@@ -793,6 +807,14 @@ class PivotKVCache(DynamicCache):
         # does not).  This key is the kill switch: False = every layer's shift is its own launch, whatever the caller says.
         self.shift_next_in_update = bool(kv_compression_kwargs.get("shift_next_in_update", True))
         self._preshifted = None       # (ids tensor, its version, layer, stream) an update launch has already shifted for
+        # MI355X build option (not in the reference, which leaves `prompt_guided_compression` unfinished: its before_forward
+        # ignores prompt_length): True makes a chunk that follows before_forward(prompt_length=Lp), 0 < Lp < L, a
+        # PROMPT-GUIDED unit - its last Lp rows are the appended prompt, the Lv = L - Lp video keys are scored by the prompt's
+        # queries alone (softmax over the video keys, no mask, mean over rows / heads / groups: every score < 1), the
+        # selection keeps max(1, int(ratio * Lv)) of the VIDEO rows and the prompt rows are not cached.  What the layer's
+        # attention sees is unchanged.  False (default): nothing changes anywhere, prompt_length is ignored as in the reference
+        self.prompt_guided_scoring = bool(kv_compression_kwargs.get("prompt_guided_scoring", False))
+        self._prompt_len = 0          # prompt rows of the chunk in flight (before_forward .. after_forward), 0 = none
         if self.flush_every_layers < 0:
             raise ValueError("flush_every_layers must be >= 0")
         self._sides: List[_Side] = []
@@ -904,7 +926,9 @@ class PivotKVCache(DynamicCache):
         """Scores of the most recent compressed update; None if it kept its whole chunk without scoring it."""
         b, l = self._last_slot
         self._flush()
-        return None if b.keep_all else b.score[l]
+        if b.keep_all:
+            return None
+        return b.score[l, :b.Lv] if b.prompt else b.score[l]
 
     @property
     def last_keep_indices(self):
@@ -949,8 +973,8 @@ class PivotKVCache(DynamicCache):
         if b is not None:
             out["k_unrotated"] = nbytes(b.k_unrot)
             out["score_operands"] = nbytes(b.score_ws)
-            out["score_partials"] = nbytes(b.partials) + nbytes(b.score) + nbytes(b.key_index)
-            out["selection"] = (nbytes(b.keep_idx) + nbytes(b.pos_new) + nbytes(b.pos_old) + nbytes(b.sel_ws)
+            out["score_partials"] = nbytes(b.partials) + nbytes(b.score) + nbytes(b.key_index) + nbytes(b.prompt_ws)
+            out["selection"] = (nbytes(b.keep_idx) + nbytes(b.pos_new) + nbytes(b.pos_old) + nbytes(b.sel_ws) + nbytes(b.pos_video)
                                 + nbytes(b.compact_sync) + nbytes(b.cos_new) + nbytes(b.sin_new))
             out["staging"] = nbytes(b.v_stage) + nbytes(b.k_stage)
             seen = set()
@@ -1061,10 +1085,18 @@ class PivotKVCache(DynamicCache):
 
     # ---- hooks (reference :146-150): after_forward is where deferred compaction is flushed -------
     def before_forward(self, **kwargs):
-        pass
+        if self.prompt_guided_scoring:   # (off: the reference's `pass`)
+            n = kwargs.get("prompt_length")
+            self._prompt_len = int(n) if n is not None and int(n) > 0 else 0
 
     def after_forward(self, **kwargs):
         self._flush()
+        self._prompt_len = 0
+
+    def _prompt_rows(self, L: int) -> int:
+        """Prompt rows of a chunk of L rows arriving now: the recorded prompt_length if 0 < Lp < L, else 0 (an ordinary chunk)."""
+        n = self._prompt_len
+        return n if 0 < n < L else 0
 
     # ---- bookkeeping lists (reference :152-215) ------------------------------------------------
     def update_num_evicted_tokens(self, num_tokens: int, layer_idx: int):
@@ -1273,7 +1305,7 @@ class PivotKVCache(DynamicCache):
                                        nv.ptr(sin_t), s), "rtk_rope_merge")
 
     # ---- deferred eviction -----------------------------------------------------------------------
-    def _get_batch(self, layer_idx, Hq, Hkv, L, D, keep, P, dtype, device) -> _Batch:
+    def _get_batch(self, layer_idx, Hq, Hkv, L, D, keep, P, dtype, device, prompt=0) -> _Batch:
         refround = self.score_rounding == "reference" and dtype in (torch.bfloat16, torch.float16)
         if refround and D != 128:
             raise NotImplementedError("score_rounding='reference' needs head_dim 128")
@@ -1281,7 +1313,7 @@ class PivotKVCache(DynamicCache):
         fast = self.score_rounding == "fast" and dtype == torch.bfloat16 and D == 128
         keep_all = keep == L and not self.score_when_keeping_all
         defer = bool(self.defer_rerotation and self.pos_embed_reforge)
-        key = (Hq, Hkv, L, D, keep, P, bool(self.pos_embed_reforge), dtype, device, refround, fast, keep_all, defer)
+        key = (Hq, Hkv, L, D, keep, P, bool(self.pos_embed_reforge), dtype, device, refround, fast, keep_all, defer, prompt)
         b = self._batch
         wrap = self.flush_every_layers > 0
         if b is not None and b.key == key and (layer_idx < b.slots or b.wrap) and b.wrap == wrap:
@@ -1293,7 +1325,7 @@ class PivotKVCache(DynamicCache):
             slots = max(int(self.num_hidden_layers), layer_idx + 1, b.slots if b is not None and b.key == key else 0)
         self._batch = None  # release the old buffers before allocating the new ones
         self._batch = _Batch(key, slots, Hq, Hkv, L, D, keep, P, bool(self.pos_embed_reforge), dtype, device, refround, fast,
-                             keep_all, self.skip_masked_columns, self.in_place_compaction)
+                             keep_all, self.skip_masked_columns, self.in_place_compaction, prompt)
         self._batch.wrap = wrap
         self._batch.defer = defer
         self._batch.c.defer_rot = int(defer)
@@ -1315,7 +1347,7 @@ class PivotKVCache(DynamicCache):
             self._shift_failed(b)
         if b is None or not b.pending:
             return
-        if self.kv_cache_dtype is None and b.c_pending == len(b.pending) and self._flush_c(b):
+        if self.kv_cache_dtype is None and b.c_pending == len(b.pending) and not b.prompt and self._flush_c(b):
             return
         self._flush_general(b)
 
@@ -1421,6 +1453,10 @@ class PivotKVCache(DynamicCache):
             if qk[0] is not None:   # units of the prologue route whose queries are scored in place
                 qu = (C.c_void_p * n)(*[t.data_ptr() for t in qk])
                 qsh, qsl = qk[0].stride(1), qk[0].stride(2)
+            if b.prompt:   # prompt-guided units: the prompt's rows score the video keys, final scores, no partials
+                self._score_prompt_run(b, l0, n, qk, qsh, qsl)
+                i = j + 1
+                continue
             nv.check(nv.lib.rtk_pivotkv_score_passes_batched_q(
                 C.c_void_p(b.score_ws_base + l0 * b.ws_stride), b.ws_stride,
                 nv.ptr(b.k_unrot[l0]) if b.reforge else None, b.L * D * Hkv * b.esize,
@@ -1428,6 +1464,51 @@ class PivotKVCache(DynamicCache):
                 km, nv.ptr(b.key_index[l0]) if km is not None else None, qu, qsh, qsl, nv.stream()),
                 "rtk_pivotkv_score_passes_batched")
             i = j + 1
+
+    def _score_prompt_run(self, b: _Batch, l0: int, n: int, qk, qsh: int, qsl: int):
+        """rtk_pivotkv_score_prompt_batched for the n consecutive slots from l0 (up to 28 units per call): rows [Lv, L) of
+        the slots' q~ (packed, or qk's tensors where they lie) against rows [0, Lv) of their k~ -> b.score[slot, :Lv]."""
+        D, Hkv = b.D, b.Hkv
+        for u0 in range(0, n, nv.PROMPT_SCORE_MAX_UNITS):
+            m, s0 = min(nv.PROMPT_SCORE_MAX_UNITS, n - u0), l0 + u0
+            qu = (C.c_void_p * m)(*[t.data_ptr() for t in qk[u0:u0 + m]]) if qk[0] is not None else None
+            nv.check(nv.lib.rtk_pivotkv_score_prompt_batched(
+                C.c_void_p(b.score_ws_base + s0 * b.ws_stride), b.ws_stride,
+                nv.ptr(b.k_unrot[s0]) if b.reforge else None, b.L * D * Hkv * b.esize,
+                nv.ptr(b.score[s0]), b.L, C.c_void_p(b.prompt_ws_base + s0 * b.prompt_bytes), b.prompt_bytes, m,
+                b.Hq, Hkv, b.L, b.prompt, D, b.score_dt, qu, qsh, qsl, nv.stream()), "rtk_pivotkv_score_prompt_batched")
+
+    def _select_prompt_units(self, b: _Batch, todo):
+        """The selection of prompt-guided units: mask override + top-k + id gather / rescale over the Lv VIDEO columns
+        (the existing kernels called with L = Lv: keep of Lv, temporal ids rescaled by keep / Lv).  Their ids are handed
+        over as dense [P, Lv] blocks; a key-patch mask is read up to Lv."""
+        P, keep, Lv = b.P, b.keep, b.Lv
+        slots = [b.slot(l) for l in todo]
+        if P:
+            lo, hi = min(slots), max(slots) + 1
+            b.pos_video[lo:hi].copy_(b.pos_old[lo:hi, :, :Lv])
+        su = (nv.SelectUnit * len(todo))()
+        for u, l, sl in zip(su, todo, slots):
+            u.partial = None           # the scores are final
+            u.score = b.score[sl].data_ptr()
+            m = b.masks.get(l)
+            u.mask = m.data_ptr() if m is not None else None
+            u.pos = b.pos_video[sl].data_ptr() if P else None
+            u.keep_idx = b.keep_idx[sl].data_ptr()
+            u.rank = None
+            u.pos_out = (b.pos_new.data_ptr() + sl * keep * 8) if P else None
+            u.workspace = b.sel_ws[sl].data_ptr()
+        rc = nv.lib.rtk_pivotkv_select_batched(su, len(todo), 0, 0, 0, Lv, keep, P, int(b.reforge), b.slots * keep, b.score_dt,
+                                               nv.stream())
+        if rc != nv.RTK_EUNSUPPORTED:
+            nv.check(rc, "rtk_pivotkv_select_batched")
+            return
+        # few video rows (a video's tail chunk): outside the chip-wide kernels, one workgroup per unit
+        rank = self._buf("rank", (Lv,), torch.int32, b.device)
+        for u in su:
+            nv.check(nv.lib.rtk_pivotkv_select(u.score, u.mask, Lv, keep, u.pos, P, int(b.reforge), u.keep_idx, nv.ptr(rank),
+                                               u.pos_out, b.slots * keep, u.workspace, b.sel_bytes, nv.stream()),
+                     "rtk_pivotkv_select")
 
     def _select_unselected(self, b: _Batch, layers):
         """Mask override + top-k + id gather / rescale (reference :269-295) of the units not selected inside `update`,
@@ -1442,6 +1523,8 @@ class PivotKVCache(DynamicCache):
                 for l in todo:
                     b.pos_new[:, b.slot(l)].copy_(b.pos_old[b.slot(l)])
             return
+        if b.prompt:
+            return self._select_prompt_units(b, todo)
         su = (nv.SelectUnit * len(todo))()
         for u, l in zip(su, todo):
             sl = b.slot(l)
@@ -1671,7 +1754,7 @@ class PivotKVCache(DynamicCache):
         if b is not None and b.shift_latch is not None and b.shift_latch[0]:
             self._shift_failed(b)
         if b is not None and b.c_capable and cache_kwargs is not None and self.kvcache_compression \
-                and self.overlap_streams <= 0 and self.one_call_update:
+                and self.overlap_streams <= 0 and self.one_call_update and b.prompt == self._prompt_rows(b.L):
             out = self._update_c(b, key_states, value_states, layer_idx, cache_kwargs, None)
             if out is not None:
                 return out
@@ -1709,8 +1792,8 @@ class PivotKVCache(DynamicCache):
         elif mask is b.mask_obj:
             mptr = b.mask_ptr
         else:
-            if not (mask.is_cuda and mask.dtype is torch.bool and mask.numel() == L and mask.is_contiguous()
-                    and mask.get_device() == idx):
+            if not (mask.is_cuda and mask.dtype is torch.bool and mask.numel() in (L, b.Lv) and mask.is_contiguous()
+                    and mask.get_device() == idx):   # (prompt-guided units: the mask may cover the video rows only)
                 return None
             b.mask_obj, b.mask_ptr = mask, mask.data_ptr()
             mptr = b.mask_ptr
@@ -1854,13 +1937,14 @@ class PivotKVCache(DynamicCache):
             return None
         L = key_states.shape[2]
         b = self._batch
-        if b is None or b.L != L or not b.c_capable or not self._bound_rotary(b, rotary_emb) \
+        lp = self._prompt_rows(L)
+        if b is None or b.L != L or b.prompt != lp or not b.c_capable or not self._bound_rotary(b, rotary_emb) \
                 or (layer_idx >= b.slots and not b.wrap) or layer_idx >= len(self._layers) \
                 or self._layers[layer_idx].c.length + L > self._layers[layer_idx].c.cap:
             # not the steady state: find / build the batch of this geometry, bind the rotary, make room
             dev = key_states.device
             rot = self._rotary(rotary_emb, dev)
-            keep_len = max(1, int(self.compression_ratio * L))
+            keep_len = max(1, int(self.compression_ratio * (L - lp)))
             if rot is None or L < 512 or keep_len > L or (self.score_rounding == "reference"
                                                          and self.prologue_operands != "reference"
                                                          and key_states.dtype in (torch.bfloat16, torch.float16)):
@@ -1868,7 +1952,7 @@ class PivotKVCache(DynamicCache):
             Hq, D = query_states.shape[1], query_states.shape[3]
             self._fp8_refuse(key_states.dtype, D, True, rot)
             b = self._get_batch(layer_idx, Hq, key_states.shape[1], L, D, keep_len, 3 if position_ids.ndim == 3 else 1,
-                                key_states.dtype, dev)
+                                key_states.dtype, dev, lp)
             if not b.c_capable:
                 return None
             self._bind_rotary(b, rotary_emb, mrope_section, rot)
@@ -2043,11 +2127,15 @@ class PivotKVCache(DynamicCache):
         for t in (query_states, key_states, value_states):
             if t.stride(-1) != 1:
                 raise ValueError("q/k/v must be contiguous along head_dim")
-        keep_len = max(1, int(self.compression_ratio * L))  # evict new tokens only (reference :263)
-        if keep_len > L:   # compression_ratio > 1: the reference's topk refuses it (:276)
+        lp = self._prompt_rows(L)   # prompt-guided unit: the last lp rows are the appended prompt, keep counts video rows
+        keep_len = max(1, int(self.compression_ratio * (L - lp)))  # evict new tokens only (reference :263)
+        if keep_len > L - lp:   # compression_ratio > 1: the reference's topk refuses it (:276)
             raise RuntimeError(f"PivotKVCache.update: selected index k out of range (keep {keep_len} of {L} tokens)")
         reforge = bool(self.pos_embed_reforge)
         rot = self._rotary(rotary_emb_fn, dev) if reforge else None
+        if lp and reforge and rot is None:
+            raise ValueError("prompt_guided_scoring with pos_embed_reforge needs a rotary module of the static inv_freq * "
+                             "position kind and native_rope=True: a rotary module that has to be called is not served")
         self._fp8_refuse(key_states.dtype, D, reforge, rot, position_ids is not None)
 
         mask = self.keypatches_mask_chunk
@@ -2055,12 +2143,12 @@ class PivotKVCache(DynamicCache):
             nv.require_device(mask)
             if mask.dtype != torch.bool or not mask.is_contiguous():
                 mask = mask.to(torch.bool).contiguous()
-            assert mask.numel() == L, "keypatches_mask_chunk must have one entry per chunk token"
+            assert mask.numel() in (L, L - lp), "keypatches_mask_chunk must have one entry per chunk token"
         Pn = 0
         if position_ids is not None:
             nv.require_device(position_ids)
             Pn = 3 if position_ids.ndim == 3 else 1
-        b = self._get_batch(layer_idx, Hq, Hkv, L, D, keep_len, Pn, key_states.dtype, dev)
+        b = self._get_batch(layer_idx, Hq, Hkv, L, D, keep_len, Pn, key_states.dtype, dev, lp)
         self._bind_rotary(b, rotary_emb_fn, mrope_section, rot)
         if b.pending and b.c.pre_rope:   # units of the prologue route are flushed among themselves
             self._flush()
@@ -2240,5 +2328,16 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
                                  "cannot read the fp8 rows")
             if cache.defer_rerotation:
                 raise ValueError("kv_cache_dtype='fp8_e4m3' does not serve defer_rerotation (the sharded prefill)")
+        if cache.prompt_guided_scoring:   # what the mode does not serve: refused here, never a silent fallback
+            for key, value, served in (("score_rounding", cache.score_rounding, "fp32"),
+                                       ("kv_cache_dtype", cache.kv_cache_dtype, None),
+                                       ("defer_rerotation", cache.defer_rerotation, False),
+                                       ("overlap_streams", cache.overlap_streams, 0),
+                                       ("flush_every_layers", cache.flush_every_layers, 0),
+                                       ("native_rope", cache.native_rope, True)):
+                if value != served:
+                    raise ValueError(f"prompt_guided_scoring=True does not serve {key}={value!r} (only {key}={served!r}): "
+                                     "the prompt-guided scores are defined for the default fp32 score arithmetic, 16-bit cache "
+                                     "rows, one flush per chunk on the caller's stream and the native RoPE")
         return cache
     raise NotImplementedError

@@ -518,7 +518,11 @@ int rtk_pivotkv_compact_batched(const rtk_compact_unit* units, int n_units, int 
  *                         rtk_pivotkv_place_batched) for the pending layers
  * ------------------------------------------------------------------------------------------- */
 
-/* One layer's pre-allocated cache (longvideo_cache.py: key_cache[l] / value_cache[l] / position_cache[l]). */
+/* One layer's pre-allocated cache (longvideo_cache.py: key_cache[l] / value_cache[l] / position_cache[l]).
+ * Rewinding (a follow-up question on the same video; PivotKVCache.mark / rewind): the rows below `length` / `pos_len` are
+ * never rewritten by later calls - a compressed chunk compacts inside its own tail, rtk_pivotkv_append_rope appends at
+ * `length` - so a foreign host goes back to an earlier state by restoring `length` and `pos_len` (with nothing pending)
+ * and its own count of archived fp8 rows; no call into the library, no copy. */
 typedef struct rtk_layer_state {
     void* k;                 /* [1, Hkv, cap, D] keys   (element (h, r, d) at (h*cap + r)*D + d) */
     void* v;                 /* [1, Hkv, cap, D] values */

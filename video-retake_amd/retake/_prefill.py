@@ -72,19 +72,47 @@ def prompt_guided(config) -> bool:
     return bool(comp.get("prompt_guided_compression", False) and comp.get("compression_ratio", 1) < 1.0)
 
 
+def followup_position_ids(mark, n: int, device=None) -> torch.Tensor:
+    """Position ids of `n` text rows appended where the video ended (not in the reference, which prefills the video again
+    for every question): `mark.resume_position_ids + arange(n)` on every row, as [3, 1, n] (M-RoPE) or [1, n] int64 on
+    `device` - the ids a fresh prefill would have given n text rows at that place.  `mark` is `cache.video_end` after a
+    chunked prefill.  The attention patches then shift the temporal row by their continuity rule, as for any segment."""
+    resume = getattr(mark, "resume_position_ids", None)
+    if resume is None:
+        raise ValueError("followup_position_ids: the mark carries no resume_position_ids (it is not the `video_end` of a "
+                         "chunked prefill whose video was followed by text)")
+    P = resume.numel()
+    if P not in (1, 3):
+        raise ValueError(f"followup_position_ids: resume_position_ids must hold 1 or 3 ids, got {P}")
+    ids = resume.to(torch.int64).reshape(P, 1) + torch.arange(int(n), dtype=torch.int64)
+    ids = ids.reshape(3, 1, int(n)) if P == 3 else ids
+    return ids if device is None else ids.to(device)
+
+
 def run_chunked_prefill(segments: List[Segment], chunk_size: int, cache, keypatches_mask,
-                        run_text: Callable[[int, int], object], run_video_chunk: Callable[[int, int], object]):
+                        run_text: Callable[[int, int], object], run_video_chunk: Callable[[int, int], object],
+                        position_ids: Optional[torch.Tensor] = None):
     """The prefill driver (reference: qwen2_vl.py:670-720).
 
     Text segments are prefilled in one call with compression off; each video segment is cut into
     `chunk_size`-token chunks, the cache gets the chunk's key-patch mask (the callback fires the
     `before_forward` / `after_forward` hooks around the model call), and compression is switched off
     again afterwards so that decoding appends normally.  Returns the last model output.
+
+    position_ids (not in the reference): the forward's ids of the whole prompt, [3, 1, S] or [1, S].  Before the text
+    segment that follows the last video run is prefilled, the ids of its first row - as the forward computed them, before
+    the attention patch shifts them - are noted on `cache.video_end` (a cache with `mark` only; followup_position_ids).
     """
     compression_on = getattr(cache, "kvcache_compression", False)
     outputs = None
-    for (s, e, kind) in segments:
+    last_video = max((i for i, seg in enumerate(segments) if seg[2] == "video"), default=None)
+    for i, (s, e, kind) in enumerate(segments):
         if kind == "text":
+            # (with visual compression the reference segments the prompt BEFORE the video tokens are dropped: the runs then
+            # do not line up with the ids, the trailing text is prefilled inside the last "video" chunks, nothing is noted)
+            if last_video is not None and i == last_video + 1 and position_ids is not None and hasattr(cache, "mark") \
+                    and cache.video_end is not None and s < e and segments[-1][1] == position_ids.shape[-1]:
+                cache.set_resume_position_ids(position_ids[..., s])
             cache.kvcache_compression = False
             outputs = run_text(s, e)
         elif kind == "video":

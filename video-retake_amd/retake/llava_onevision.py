@@ -323,7 +323,7 @@ def retake_LlavaOnevisionForConditionalGeneration_forward(
             return out
 
         outputs = _prefill.run_chunked_prefill(modality_segments, chunk_size, cache, keypatches_mask, run_text,
-                                               run_video_chunk)
+                                               run_video_chunk, position_ids=position_ids)
     else:
         common["use_cache"] = use_cache
         outputs = self.language_model(attention_mask=attention_mask, position_ids=position_ids,

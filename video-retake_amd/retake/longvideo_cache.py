@@ -26,6 +26,7 @@ evictions into one bandwidth-bound launch.  `memory_footprint()` says what all o
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import sys
@@ -51,7 +52,7 @@ def _warn_once(msg: str):
 
 
 __all__ = ["repeat_kv", "rotate_half", "apply_multimodal_rotary_pos_emb", "apply_rotary_pos_emb", "PivotKVCache",
-           "build_kvcache", "DynamicCache"]
+           "CacheMark", "build_kvcache", "DynamicCache"]
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -706,8 +707,65 @@ def _attention_kernel_of(config):
     return kind
 
 
+# one layer's numbers at a mark.  has_kv / has_pos: did the layer own K / V and id buffers (a skipped layer owns none)
+_LayerMark = collections.namedtuple("_LayerMark", "length pos_len pos_ndim len8 archive_at num_evicted has_kv has_pos")
+
+
+class CacheMark:
+    """A restore point of one PivotKVCache (`PivotKVCache.mark`): the host-side numbers that say which rows of the layers'
+    buffers are in use - no tensor of the cache, no copy of a row.  `PivotKVCache.rewind` puts them back; the rows below a
+    mark are never rewritten by later work (a compressed chunk compacts inside its own tail, text and decode rows append
+    at `length`, the fp8 archive appends at `len8`), so that restores the cache.  Immutable.
+
+      serial, epoch   the cache's mark counter / buffer epoch when the mark was taken (rewind checks both)
+      layers          per layer, skipped ones included: (length, pos_len, pos_ndim, len8, archive_at, num_evicted, ..)
+      n_layers, pos_layers, n_evicted   len(cache._layers), len(position_cache), len(num_evicted_tokens)
+      seen_tokens     the base class's `_seen_tokens`, None when the installed base class keeps none
+      resume_position_ids   CPU int64 [P], None unless the prefill glue set it: the ids a fresh prefill gave the first text
+                      row after the video (`_prefill.followup_position_ids` continues from them)"""
+
+    __slots__ = ("_ref", "serial", "epoch", "layers", "n_layers", "pos_layers", "n_evicted", "seen_tokens", "flushes",
+                 "compressed", "video_end", "resume_position_ids", "__weakref__")
+
+    def __init__(self, ref, serial, epoch, layers, n_layers, pos_layers, n_evicted, seen_tokens, flushes, compressed,
+                 video_end, resume_position_ids=None):
+        for name, value in (("_ref", ref), ("serial", serial), ("epoch", epoch), ("layers", layers),
+                            ("n_layers", n_layers), ("pos_layers", pos_layers), ("n_evicted", n_evicted),
+                            ("seen_tokens", seen_tokens), ("flushes", flushes), ("compressed", compressed),
+                            ("video_end", video_end), ("resume_position_ids", resume_position_ids)):
+            object.__setattr__(self, name, value)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"CacheMark is immutable (cannot set {name!r})")
+
+    def __delattr__(self, name):
+        raise AttributeError(f"CacheMark is immutable (cannot delete {name!r})")
+
+    @property
+    def cache(self):
+        """The cache the mark belongs to, None once it has been released."""
+        return self._ref()
+
+    def _with_resume(self, ids):
+        """The same restore point (same serial) carrying `ids` as resume_position_ids."""
+        return CacheMark(self._ref, self.serial, self.epoch, self.layers, self.n_layers, self.pos_layers, self.n_evicted,
+                         self.seen_tokens, self.flushes, self.compressed, self.video_end, ids)
+
+    def __repr__(self):
+        return (f"CacheMark(serial={self.serial}, epoch={self.epoch}, layers={self.n_layers}, "
+                f"rows={[m.length + m.len8 for m in self.layers]})")
+
+
 class PivotKVCache(DynamicCache):
     """Drop-in for the reference's PivotKVCache (longvideo_cache.py:119-323)."""
+
+    # mark / rewind (not in the reference).  Class-level defaults: the base class's __init__ already goes through the setters
+    _epoch = 0                    # bumped wherever a layer's buffers are replaced or rewritten wholesale
+    _mark_serial = 0              # marks taken so far
+    _dead_marks = ()              # (lo, hi] serial ranges a rewind / crop has invalidated, lo ascending
+    _flushes = 0                  # identity of the most recent compressed flush whose rows the cache holds
+    _compressed_in_forward = False
+    last_compressed_mark = None   # the mark `after_forward` took after the most recent forward that compressed a chunk
 
     def __init__(self, config, reserve_tokens: Optional[int] = None, reserve_archive_tokens: Optional[int] = None) -> None:
         """reserve_tokens (not in the reference): tokens per layer this cache is expected to hold at most - compressed
@@ -987,6 +1045,156 @@ class PivotKVCache(DynamicCache):
         out["total"] = sum(out.values())
         return out
 
+    # ---- mark / rewind / crop (not in the reference) ------------------------------------------------
+    def _take_mark(self, compressed: bool) -> CacheMark:
+        nev = self.num_evicted_tokens
+        layers = tuple(_LayerMark(st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at,
+                                  nev[l] if l < len(nev) else 0, st._k is not None, st._pos is not None)
+                       for l, st in enumerate(self._layers))
+        self._mark_serial += 1
+        return CacheMark(weakref.ref(self), self._mark_serial, self._epoch, layers, len(self._layers), self._pos_layers, len(nev),
+                         getattr(self, "_seen_tokens", None), self._flushes, compressed,
+                         None if compressed else self.last_compressed_mark)
+
+    def mark(self) -> CacheMark:
+        """A restore point of the cache as it stands (see CacheMark).  Like reading `position_cache` it first flushes
+        deferred work (the flush waits for the worker streams), so a mark taken between an `update` and `after_forward`
+        equals the one taken after it.  O(layers) on the host; launches nothing besides that flush."""
+        if self.defer_rerotation:
+            raise NotImplementedError("PivotKVCache.mark: a cache with defer_rerotation (the sharded prefill's block caches) "
+                                      "holds un-rotated keys and provisional ids until `finalize`; it has no restore points")
+        self._flush()
+        return self._take_mark(False)
+
+    @property
+    def video_end(self) -> Optional[CacheMark]:
+        """`last_compressed_mark`: the restore point after the most recent forward that compressed a chunk - after a chunked
+        prefill, the end of the video (None: nothing has been compressed).  The prefill glue attaches the ids of the first
+        text row that followed (CacheMark.resume_position_ids)."""
+        return self.last_compressed_mark
+
+    def set_resume_position_ids(self, position_ids: torch.Tensor):
+        """The prefill glue's note on `video_end`: the ids ([3, 1] / [1], any device) the forward computed for the first text
+        row after the video, before the attention patch shifted them."""
+        m = self.last_compressed_mark
+        if m is not None:
+            self.last_compressed_mark = m._with_resume(position_ids.detach().reshape(-1).to("cpu", torch.int64).clone())
+
+    def _mark_is_dead(self, serial: int) -> bool:
+        return any(lo < serial <= hi for lo, hi in self._dead_marks)
+
+    def _kill_marks_after(self, serial: int):
+        """Every mark taken after `serial` so far is invalid from now on (its rows are about to be overwritten)."""
+        if serial < self._mark_serial:   # (ranges that start at or above `serial` lie inside the new one)
+            self._dead_marks = tuple(r for r in self._dead_marks if r[0] < serial) + ((serial, self._mark_serial),)
+
+    def _check_mark(self, mark: CacheMark):
+        if not isinstance(mark, CacheMark):
+            raise ValueError(f"PivotKVCache.rewind takes a CacheMark (PivotKVCache.mark), got {type(mark).__name__}")
+        if mark.cache is not self:
+            raise ValueError("PivotKVCache.rewind: the mark belongs to another cache")
+        if self._mark_is_dead(mark.serial):
+            raise ValueError("PivotKVCache.rewind: the mark has been invalidated - the cache was rewound or cropped to an "
+                             "earlier point since, and the rows the mark names have been given up")
+        if mark.epoch != self._epoch:
+            raise ValueError("PivotKVCache.rewind: buffers of the cache were replaced or rewritten wholesale after the mark was "
+                             "taken (key_cache / value_cache / position_cache assigned, or stored rows rotated in place)")
+        nev = self.num_evicted_tokens
+        if len(self._layers) < mark.n_layers or self._pos_layers < mark.pos_layers or len(nev) < mark.n_evicted:
+            raise ValueError("PivotKVCache.rewind: the cache holds fewer layers than the mark records")
+        for l, m in enumerate(mark.layers):
+            st = self._layers[l]
+            if st.c.length < m.length or st.c.pos_len < m.pos_len or st.len8 < m.len8 or (m.has_kv and st._k is None) \
+                    or (m.has_pos and st._pos is None) or (m.archive_at >= 0 and st.archive_at != m.archive_at):
+                raise ValueError(f"PivotKVCache.rewind: layer {l} is shorter than the mark says")
+
+    def rewind(self, mark: CacheMark) -> None:
+        """Back to the state `mark` recorded: the follow-up question's way of not prefilling the video again (rewind to
+        `video_end`, append the next question).  O(layers) on the host: the numbers are restored, layers / id lists /
+        eviction counts that did not exist at the mark are dropped, `_prompt_len` / the pre-shift memo are cleared.  Nothing
+        is launched, copied, freed or reallocated - every buffer that existed at the mark keeps its address -, and
+        `kvcache_compression`, `keypatches_mask_chunk`, the batch and the scratch are left alone.  Every mark taken after
+        `mark` is invalid afterwards.  ValueError, before anything changes: a mark of another cache, an invalidated one,
+        one from before the buffers were replaced (the epoch), or a cache that is shorter than the mark says."""
+        self._flush()
+        self._shift_latch_check()
+        self._check_mark(mark)
+        for st, m in zip(self._layers, mark.layers):
+            st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at = m.length, m.pos_len, m.pos_ndim, m.len8, m.archive_at
+            if not m.has_kv and st._k is not None:    # a layer that was skipped at the mark owns nothing again
+                st.k = st.v = None
+            if not m.has_pos and st._pos is not None:
+                st.pos = None
+        del self._layers[mark.n_layers:]
+        self._pos_layers = mark.pos_layers
+        nev = self.num_evicted_tokens
+        del nev[mark.n_evicted:]
+        for l in range(mark.n_evicted):
+            nev[l] = mark.layers[l].num_evicted
+        if mark.seen_tokens is not None:
+            self._seen_tokens = mark.seen_tokens
+        self._after_rewind(mark.serial)
+        self._flushes = mark.flushes
+        self._compressed_in_forward = False
+        lcm = self.last_compressed_mark
+        if lcm is not None and lcm.serial > mark.serial:   # video_end as it was at the mark
+            self.last_compressed_mark = mark if mark.compressed else mark.video_end
+
+    def _after_rewind(self, serial: int):
+        self._prompt_len = 0
+        self._preshifted = None
+        self._kill_marks_after(serial)
+
+    def _crop_floor(self):
+        """Rows per layer a crop may not go below: the boundary after the most recent compressed flush, as
+        `last_compressed_mark` recorded it - or None when the cache holds compressed rows and no such record of them."""
+        m = self.last_compressed_mark
+        if m is not None and m.epoch == self._epoch and m.flushes == self._flushes:
+            return [m.layers[l].length + m.layers[l].len8 if l < m.n_layers else 0 for l in range(len(self._layers))]
+        if self._flushes == 0 and not any(self.num_evicted_tokens):
+            return [0] * len(self._layers)
+        return None
+
+    def crop(self, max_length: int):
+        """transformers' DynamicCache.crop on this cache: keep the first `max_length` rows of every layer (negative: drop
+        that many trailing rows; at or above the current length: nothing happens).  Assisted and prompt-lookup generation
+        call it to give up rejected candidate tokens.  Served down to the boundary after the most recent compressed flush
+        only: below it a length alone cannot say what `num_evicted_tokens` or the archive split were - ValueError, and
+        the cache stays as it was.  Like `rewind` it moves numbers only.  Every mark taken after `video_end` is invalid
+        afterwards (which of them name dropped rows is not tracked)."""
+        self._flush()
+        self._shift_latch_check()
+        cur = self.get_seq_length()
+        if max_length < 0:
+            max_length = cur - abs(max_length)
+        if cur <= max_length:
+            return
+        if max_length < 0:
+            raise ValueError(f"PivotKVCache.crop: cannot drop more rows than the cache holds ({cur})")
+        if self.defer_rerotation:
+            raise NotImplementedError("PivotKVCache.crop: not served with defer_rerotation (see PivotKVCache.mark)")
+        floor = self._crop_floor()
+        drops = []
+        for l, st in enumerate(self._layers):
+            total = st.c.length + st.len8 if st._k is not None else 0
+            drop = max(0, total - max_length)
+            if drop and (floor is None or total - drop < floor[l]):
+                raise ValueError(
+                    f"PivotKVCache.crop({max_length}): layer {l} would be cut inside its compressed video rows "
+                    f"({'no boundary is recorded' if floor is None else f'they end at row {floor[l]}'}): a length alone cannot "
+                    "restore num_evicted_tokens or the archive split there - rewind to a mark instead")
+            if drop and st.c.pos_len not in (0, total):
+                raise ValueError(f"PivotKVCache.crop: layer {l} keeps ids for {st.c.pos_len} of its {total} rows")
+            drops.append(drop)
+        for st, drop in zip(self._layers, drops):
+            st.c.length -= drop
+            if st.c.pos_len:
+                st.c.pos_len -= drop
+        if hasattr(self, "_seen_tokens"):
+            self._seen_tokens = max_length
+        m = self.last_compressed_mark
+        self._after_rewind(m.serial if m is not None else 0)
+
     # ---- list views --------------------------------------------------------------------------
     @property
     def key_cache(self):
@@ -995,6 +1203,7 @@ class PivotKVCache(DynamicCache):
     @key_cache.setter
     def key_cache(self, value):  # the base class assigns [] in __init__
         self._flush()
+        self._epoch += 1
         self._layers = []
         for v in value:
             self._kview.append(v)
@@ -1005,6 +1214,7 @@ class PivotKVCache(DynamicCache):
 
     @value_cache.setter
     def value_cache(self, value):
+        self._epoch += 1
         for i, v in enumerate(value):
             if i >= len(self._layers):
                 self._layers.append(_LayerStore())
@@ -1018,6 +1228,7 @@ class PivotKVCache(DynamicCache):
         st = self._layers[i]
         if st.pending:
             self._flush()
+        self._epoch += 1
         if isinstance(value, list) and len(value) == 0:
             st.k = st.v = None
             st.length = 0
@@ -1063,6 +1274,7 @@ class PivotKVCache(DynamicCache):
     @position_cache.setter
     def position_cache(self, value):
         self._flush()
+        self._epoch += 1
         self._pos_layers = len(value)
         for i, t in enumerate(value):
             st = self._store(i)
@@ -1092,6 +1304,10 @@ class PivotKVCache(DynamicCache):
     def after_forward(self, **kwargs):
         self._flush()
         self._prompt_len = 0
+        if self._compressed_in_forward:   # the work is flushed: a few tuples per chunk
+            self._compressed_in_forward = False
+            if not self.defer_rerotation:
+                self.last_compressed_mark = self._take_mark(True)
 
     def _prompt_rows(self, L: int) -> int:
         """Prompt rows of a chunk of L rows arriving now: the recorded prompt_length if 0 < Lp < L, else 0 (an ordinary chunk)."""
@@ -1642,6 +1858,7 @@ class PivotKVCache(DynamicCache):
         the position cache covers the flushed layers (reference :308-309)."""
         b.pending = []
         b.c_pending = 0
+        self._flushes += 1
         b.masks.clear()
         b.scored.clear()
         b.selected.clear()
@@ -1882,6 +2099,7 @@ class PivotKVCache(DynamicCache):
             b.scored.add(layer_idx)
         b.pending.append(layer_idx)
         b.c_pending += 1
+        self._compressed_in_forward = True
         self._last_slot = (b, slot)
         n = P0 + L
         return st._k.narrow(2, 0, n), st._v.narrow(2, 0, n)
@@ -2108,6 +2326,7 @@ class PivotKVCache(DynamicCache):
         st.pending = n_new
         st.pending_keep = b.keep
         b.pending.append(layer_idx)
+        self._compressed_in_forward = True
         self._last_slot = (b, u.slot)
         return st.k[:, :, :st.length + n_new], st.v[:, :, :st.length + n_new]
 

@@ -445,7 +445,7 @@ def retake_Qwen2VLForConditionalGeneration_forward(
             return out
 
         outputs = _prefill.run_chunked_prefill(modality_segments, chunk_size, cache, keypatches_mask, run_text,
-                                               run_video_chunk)
+                                               run_video_chunk, position_ids=position_ids)
     else:  # decode / ordinary prefill
         common["use_cache"] = use_cache
         outputs = self.model(position_ids=position_ids, attention_mask=attention_mask,

@@ -659,6 +659,7 @@ class ShardedPivotKV:
 
             def rotate_own():
                 """this rank's kept rows of every layer, in place in the layers' cache buffers, at their final ids"""
+                cache._epoch += 1   # stored rows are rewritten: restore points taken before this are void (PivotKVCache.rewind)
                 for layer in range(0 if empty else n_layers):
                     st_l = cache._layers[layer]
                     kbuf, k = st_l.k, keys[layer]

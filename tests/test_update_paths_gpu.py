@@ -350,8 +350,8 @@ def test_qwen_attention_patch_takes_the_prologue():
 
 
 def test_layer_state_block_tracks_the_store():
-    """rtk_layer_state mirrors _LayerStore: the library sees the buffers only when both are dense blocks of one capacity,
-    and the numbers Python reads are the ones the library advanced."""
+    """rtk_layer_state mirrors _LayerStore (retake/_cache_state.py): the library sees the buffers only when both are dense
+    blocks of one capacity, and the numbers Python reads are the ones the library advanced."""
     import retake.longvideo_cache as lc
 
     L = 640

@@ -5,7 +5,7 @@
                                     [--routes native,sdpa,fa2]      (--routes native: the run to put under rocprofv3)
 
 Per shape (Hq 28 / Hkv 4 / D 128; bf16, and fp16 once), inputs resident on the device (gaussian, tests/synth.py scale):
-  native   PivotKVCache.attention's call (retake.longvideo_cache.chunk_attention) on the patches' own tensors: q the
+  native   PivotKVCache.attention's call (retake.native_attention.chunk_attention) on the patches' own tensors: q the
            transposed view of [1, Lq, Hq*D], k / v the [:P0 + Lq] view of a [1, Hkv, capacity, D] cache buffer;
   sdpa     what retake_Qwen2VLSdpaAttention_forward does with the same tensors when the switch is off: repeat_kv,
            .contiguous(), scaled_dot_product_attention with the [1, 1, Lq, Lk] additive mask, transpose + contiguous;

@@ -23,12 +23,16 @@ once (`after_forward`, which the reference calls after every video chunk; or the
 pending layer; or any access to `key_cache` / `value_cache` / `position_cache`; or, with `flush_every_layers: N`, every N
 layers).  This removes the reference's two O(cache) torch.cat rebuilds per (layer, chunk) and turns 28 launch-bound
 evictions into one bandwidth-bound launch.  `memory_footprint()` says what all of it costs in bytes.
+
+Where the rest lives (the names are re-exported here, and the other modules of the package import them from here):
+    _rope_torch       repeat_kv, rotate_half, apply_rotary_pos_emb, apply_multimodal_rotary_pos_emb
+    _hf_cache         DynamicCache: which class PivotKVCache subclasses, and why
+    _cache_state      what a layer and a slot of the batch own (_LayerStore, _Batch, ...), the list views, CacheMark
+    native_attention  chunk_attention, native_attention (causal offset from the HF mask), the fp8 row helpers
 """
 from __future__ import annotations
 
-import collections
 import ctypes as C
-import math
 import sys
 import weakref
 from typing import Any, Dict, List, Optional, Tuple
@@ -36,11 +40,12 @@ from typing import Any, Dict, List, Optional, Tuple
 import torch
 
 from . import _native as nv
-
-try:  # the HF classes are third-party; they only matter for isinstance checks inside `generate`
-    from transformers.cache_utils import DynamicCache as _HFDynamicCache
-except Exception:  # noqa: BLE001
-    _HFDynamicCache = None
+from ._cache_state import (CacheMark, _Batch, _CacheView, _LayerMark, _LayerStore, _Rotary, _Side, _Update,  # noqa: F401
+                           _inv_stamp, _on_device, _version_of)
+from ._hf_cache import DynamicCache, _hf_dynamic_cache_is_legacy, _ListDynamicCache  # noqa: F401
+from ._rope_torch import _rotate, apply_multimodal_rotary_pos_emb, apply_rotary_pos_emb, repeat_kv, rotate_half  # noqa: F401
+from .native_attention import (ATTENTION_KERNELS, KV_CACHE_DTYPES, chunk_attention, fp8_dequantize_rows,  # noqa: F401
+                               fp8_quantize_rows, native_attention)
 
 _WARNED = set()
 
@@ -55,705 +60,12 @@ __all__ = ["repeat_kv", "rotate_half", "apply_multimodal_rotary_pos_emb", "apply
            "CacheMark", "build_kvcache", "DynamicCache"]
 
 
-# ---------------------------------------------------------------------------------------------------
-# small torch helpers of the reference surface (longvideo_cache.py:16-116); used by the attention
-# patch on the current chunk, not by the cache's hot path
-# ---------------------------------------------------------------------------------------------------
-def repeat_kv(hidden_states: torch.Tensor, n_rep: int) -> torch.Tensor:
-    """[B, Hkv, L, D] -> [B, Hkv*n_rep, L, D]  (longvideo_cache.py:16-25)."""
-    b, h, s, d = hidden_states.shape
-    if n_rep == 1:
-        return hidden_states
-    return hidden_states[:, :, None, :, :].expand(b, h, n_rep, s, d).reshape(b, h * n_rep, s, d)
-
-
-def rotate_half(x):
-    """cat(-x[D/2:], x[:D/2])  (longvideo_cache.py:28-32)."""
-    half = x.shape[-1] // 2
-    return torch.cat((-x[..., half:], x[..., :half]), dim=-1)
-
-
-def _rotate(q, k, cos, sin, reverse, attention_scaling):
-    if reverse:  # rotate towards the opposite direction (longvideo_cache.py:76-78)
-        q_embed = ((q * cos) - (rotate_half(q) * sin)) / attention_scaling ** 2
-        k_embed = ((k * cos) - (rotate_half(k) * sin)) / attention_scaling ** 2
-    else:
-        q_embed = (q * cos) + (rotate_half(q) * sin) if q is not None else None
-        k_embed = (k * cos) + (rotate_half(k) * sin) if k is not None else None
-    return q_embed, k_embed
-
-
-def apply_multimodal_rotary_pos_emb(q, k, cos, sin, mrope_section, unsqueeze_dim=1, reverse=False,
-                                    attention_scaling=1):
-    """M-RoPE with the reference's extra `reverse` / `attention_scaling` arguments (longvideo_cache.py:35-83)."""
-    sections = mrope_section * 2
-    cos = torch.cat([m[i % 3] for i, m in enumerate(cos.split(sections, dim=-1))], dim=-1).unsqueeze(unsqueeze_dim)
-    sin = torch.cat([m[i % 3] for i, m in enumerate(sin.split(sections, dim=-1))], dim=-1).unsqueeze(unsqueeze_dim)
-    return _rotate(q, k, cos, sin, reverse, attention_scaling)
-
-
-def apply_rotary_pos_emb(q, k, cos, sin, position_ids=None, unsqueeze_dim=1, reverse=False, attention_scaling=1):
-    """1-D RoPE with `reverse` / `attention_scaling` (longvideo_cache.py:86-116)."""
-    return _rotate(q, k, cos.unsqueeze(unsqueeze_dim), sin.unsqueeze(unsqueeze_dim), reverse, attention_scaling)
-
-
-# ---------------------------------------------------------------------------------------------------
-# cache base with transformers==4.48 DynamicCache public behaviour (key_cache / value_cache lists)
-# ---------------------------------------------------------------------------------------------------
-def _hf_dynamic_cache_is_legacy() -> bool:
-    if _HFDynamicCache is None:
-        return False
-    try:
-        return hasattr(_HFDynamicCache(), "key_cache")
-    except Exception:  # noqa: BLE001
-        return False
-
-
-class _ListDynamicCache:
-    """Minimal stand-in used when the installed transformers no longer has the 4.48 list-based
-    DynamicCache the reference subclasses (third-party API, restated from its documentation)."""
-
-    def __init__(self, *args, **kwargs) -> None:
-        self.key_cache: List[torch.Tensor] = []
-        self.value_cache: List[torch.Tensor] = []
-        self._seen_tokens = 0
-
-    def update(self, key_states, value_states, layer_idx, cache_kwargs=None):
-        if layer_idx == 0:
-            self._seen_tokens += key_states.shape[-2]
-        if len(self.key_cache) <= layer_idx:
-            for _ in range(len(self.key_cache), layer_idx):
-                self.key_cache.append([])
-                self.value_cache.append([])
-            self.key_cache.append(key_states)
-            self.value_cache.append(value_states)
-        elif len(self.key_cache[layer_idx]) == 0:
-            self.key_cache[layer_idx] = key_states
-            self.value_cache[layer_idx] = value_states
-        else:
-            self.key_cache[layer_idx] = torch.cat([self.key_cache[layer_idx], key_states], dim=-2)
-            self.value_cache[layer_idx] = torch.cat([self.value_cache[layer_idx], value_states], dim=-2)
-        return self.key_cache[layer_idx], self.value_cache[layer_idx]
-
-    def get_seq_length(self, layer_idx: int = 0) -> int:
-        if len(self.key_cache) <= layer_idx or len(self.key_cache[layer_idx]) == 0:
-            return 0
-        return self.key_cache[layer_idx].shape[-2]
-
-    def get_max_cache_shape(self):
-        return None
-
-    def get_max_length(self):
-        return None
-
-    def __len__(self):
-        return len(self.key_cache)
-
-    def __getitem__(self, layer_idx):
-        return self.key_cache[layer_idx], self.value_cache[layer_idx]
-
-    def __iter__(self):
-        for i in range(len(self)):
-            yield self.key_cache[i], self.value_cache[i]
-
-
-DynamicCache = _HFDynamicCache if _hf_dynamic_cache_is_legacy() else _ListDynamicCache
-
-
-class _LayerStore:
-    """One layer's pre-allocated K/V buffers [1, Hkv, cap, D] and position ids [P, cap].  The numbers live in a
-    rtk_layer_state block (`c`) the library reads and advances itself (rtk_pivotkv_update / rtk_pivotkv_flush)."""
-
-    __slots__ = ("c", "cref", "_k", "_v", "_pos", "pending_event", "pos_ndim", "k8", "v8", "ks8", "vs8", "len8", "archive_at")
-
-    def __init__(self):
-        self.c = nv.LayerState()
-        self.cref = C.addressof(self.c)
-        self._k = self._v = self._pos = None
-        self.pending_event = None  # worker-stream completion of this layer's scoring (overlap_streams > 0)
-        self.pos_ndim = 0          # 3: ids are [3, 1, n] (M-RoPE), 2: [1, n]
-        # kv_cache_dtype="fp8_e4m3": the archive of the kept video rows - e4m3 codes uint8 [1, Hkv, cap8, D], one fp32
-        # scale per (kv head, row) [1, Hkv, cap8], rows in use, and the 16-bit `length` at the first archive write
-        self.k8 = self.v8 = self.ks8 = self.vs8 = None
-        self.len8 = 0
-        self.archive_at = -1
-
-    def _sync(self):
-        k, v, c = self._k, self._v, self.c
-        c.k = k.data_ptr() if k is not None else None
-        c.v = v.data_ptr() if v is not None else None
-        # the library may only use the buffers when both are dense [1, Hkv, cap, D] blocks of one capacity
-        ok = (k is not None and v is not None and k.ndim == 4 and k.shape == v.shape and k.is_contiguous()
-              and v.is_contiguous())
-        c.cap = k.shape[2] if ok else 0
-
-    @property
-    def k(self):
-        return self._k
-
-    @k.setter
-    def k(self, t):
-        self._k = t
-        self._sync()
-
-    @property
-    def v(self):
-        return self._v
-
-    @v.setter
-    def v(self, t):
-        self._v = t
-        self._sync()
-
-    @property
-    def pos(self):           # int64 [P, cap]: position ids of the cached tokens (pos_embed_reforge)
-        return self._pos
-
-    @pos.setter
-    def pos(self, t):
-        self._pos = t
-        self.c.pos = t.data_ptr() if t is not None else None
-        self.c.pos_cap = t.shape[1] if t is not None else 0
-
-    @property
-    def length(self):        # committed tokens
-        return self.c.length
-
-    @length.setter
-    def length(self, n):
-        self.c.length = n
-
-    @property
-    def pending(self):       # uncompressed chunk tokens sitting at [length, length + pending)
-        return self.c.pending
-
-    @pending.setter
-    def pending(self, n):
-        self.c.pending = n
-
-    @property
-    def pending_keep(self):
-        return self.c.pending_keep
-
-    @pending_keep.setter
-    def pending_keep(self, n):
-        self.c.pending_keep = n
-
-    @property
-    def pos_len(self):
-        return self.c.pos_len
-
-    @pos_len.setter
-    def pos_len(self, n):
-        self.c.pos_len = n
-
-
-class _Side:
-    """A worker stream with its own scratch buffers (overlap_streams > 0)."""
-
-    def __init__(self, device):
-        self.stream = torch.cuda.Stream(device=device)
-        self.ws: Dict[str, torch.Tensor] = {}
-
-
-class _Update:
-    """One stage-by-stage update (PivotKVCache._update_general), handed from stage to stage: the batch, the layer with
-    its slot and store, the operands, the chunk's tail in the layer's buffers, and what the stages make."""
-
-    __slots__ = ("b", "layer", "slot", "st",
-                 "q", "k", "v", "ids", "mask", "a_scale", "k_tail", "v_tail",
-                 "pos_in", "cos", "sin")   # ids as [P, L]; cos / sin tables of the chunk's ids
-
-
-class _Rotary:
-    """What the kernels need of an inv_freq * position rotary module (native RoPE): its inv_freq on the device and
-    attention_scaling.  HF builds one rotary module per attention layer; modules with equal contents share an entry."""
-
-    __slots__ = ("inv", "scaling", "device")
-
-    def __init__(self, inv, scaling, device):
-        self.inv, self.scaling, self.device = inv, scaling, device
-
-
-def _version_of(t: torch.Tensor):
-    """The tensor's version counter, None for tensors that do not keep one (created under torch.inference_mode()): for
-    those a shift the previous layer's launch has already applied is simply applied again (it is idempotent)."""
-    return None if t.is_inference() else t._version
-
-
-def _on_device(index: int, fn, *args):
-    """fn(*args) with device `index` current: entered through torch.cuda.device only when it is not already (the usual
-    case on the per-layer paths, where the context manager would cost more than the call)."""
-    if nv.current_device() == index:
-        return fn(*args)
-    with torch.cuda.device(index):
-        return fn(*args)
-
-
-def _inv_stamp(rotary_emb_fn):
-    """Identity + write counter of a rotary module's inv_freq: the native-RoPE snapshot of the module (_Rotary) is only
-    valid while this is unchanged (a module whose inv_freq is re-assigned or modified in place is snapshotted again)."""
-    inv = getattr(rotary_emb_fn, "inv_freq", None)
-    return (inv.data_ptr(), _version_of(inv)) if isinstance(inv, torch.Tensor) else None
-
-
-class _Batch:
-    """Per-chunk batch of pending evictions: slot = layer index.  All units share the chunk geometry."""
-
-    def __init__(self, key, slots, Hq, Hkv, L, D, keep, P, reforge, dtype, device, refround=False, fast=False,
-                 keep_all=False, skip_masked=True, in_place_compaction=True, prompt=0):
-        self.key, self.slots, self.keep, self.P, self.reforge = key, slots, keep, P, reforge
-        # prompt-guided scoring: the chunk's last `prompt` rows are the appended prompt; they score the Lv video keys, the
-        # selection runs over those Lv columns and no prompt row is cached (0: an ordinary chunk)
-        self.prompt, self.Lv = int(prompt), L - int(prompt)
-        self.wrap = False          # flush_every_layers: slot = layer % slots (else slot == layer)
-        self.keep_all = keep_all   # keep == L and no scoring asked for: the selection is the identity
-        # dtype code of the scoring entry points: bf16 payloads with the reference's bf16 rounding chain, or through the
-        # fp16 matrix instruction with pre-scaled queries (score_rounding="fast"), on request
-        self.score_dt = ((nv.RTK_BF16_REFROUND if refround else (nv.RTK_BF16_FAST if fast else nv.RTK_BF16))
-                         if dtype == torch.bfloat16 else
-                         ((nv.RTK_F16_REFROUND if refround else nv.RTK_F16) if dtype == torch.float16 else nv.RTK_F32))
-        self.fast = self.score_dt == nv.RTK_BF16_FAST
-        self.batched_passes = dtype in (torch.bfloat16, torch.float16) and D == 128 and L >= 512
-        if self.batched_passes:   # all layers of a chunk per launch: splits chosen for the stream length (same flag everywhere)
-            self.score_dt |= nv.RTK_SCORE_MANY_UNITS
-        if self.prompt:   # scored at the flush whatever the shape (rtk_pivotkv_score_prompt_batched): q~ waits in the slot's workspace
-            self.batched_passes = True
-        # what rtk_pivotkv_prepare is told: the payload dtype (the reference-rounding mode prepares like plain bf16)
-        self.prep_dt = ((nv.RTK_BF16 if dtype == torch.bfloat16 else nv.RTK_F16) if refround else self.score_dt & 0xFF) \
-            | (self.score_dt & ~0xFF)
-        self.Hkv, self.L, self.D, self.dtype, self.device = Hkv, L, D, dtype, device
-        self.Hq = Hq
-        # constants of the geometry every launch of the batch restates: bytes per payload element, the layout of the ids
-        # in the position cache ([3, 1, n] M-RoPE ids or [1, n]) and the 16-bit format intermediate results are rounded to
-        # (the library's dtype code is c.dtype below)
-        self.esize = 4 if dtype == torch.float32 else 2
-        self.pos_ndim = 3 if P == 3 else 2
-        self.round_mode = nv.round_mode(dtype)
-        self.defer_select = L >= 512 or bool(self.prompt)   # the chip-wide selection kernels; smaller chunks select inside update
-        self.keep_idx = torch.arange(keep, dtype=torch.int64, device=device).repeat(slots, 1) if keep_all \
-            else torch.empty((slots, keep), dtype=torch.int64, device=device)
-        self.pos_new = torch.empty((P, slots, keep), dtype=torch.int64, device=device) if P else None
-        # deferred selection (flushed for all layers at once): per-slot column partials of the scoring passes, the
-        # final score, a private copy of the chunk's position ids (the caller shifts its tensor in place for the next
-        # layer), the key-patch mask of the update and the selection scratch
-        self.rs_n = C.c_int(0)
-        self.part_floats = nv.lib.rtk_pivotkv_score_partials(Hq, Hkv, L, D, self.score_dt, C.byref(self.rs_n))
-        self.pos_old = torch.empty((slots, P, L), dtype=torch.int64, device=device) if P else None
-        self.sel_bytes = nv.lib.rtk_pivotkv_select_workspace_bytes(L)
-        self.masks: Dict[int, Optional[torch.Tensor]] = {}
-        self.selected = set()      # layers whose selection already ran inside update (small chunks)
-        self.scored = set()        # layers whose matrix passes already ran inside update
-        # one score workspace per slot (q~, lse partials): the matrix passes of all layers run in one launch each
-        self.ws_bytes = nv.lib.rtk_pivotkv_score_workspace_bytes(Hq, Hkv, L, D, self.score_dt)
-        self.ws_stride = (self.ws_bytes + 255) & ~255
-        self.partials = self.score = self.sel_ws = self.score_ws = self.key_index = None
-        # prompt-guided units: per-slot scratch of the thin score kernels and the video rows' ids as dense [P, Lv] blocks
-        self.prompt_bytes = nv.lib.rtk_pivotkv_score_prompt_workspace_bytes(Hq, Hkv, L, self.prompt, D, self.score_dt) \
-            if self.prompt else 0
-        self.prompt_ws = self.pos_video = None
-        self.prompt_ws_base = 0
-        self.score_ws_base = 0
-        self.v_stage = None
-        if reforge:  # kept K is re-rotated from the un-rotated copy straight into the cache: no K staging
-            self.k_unrot = torch.empty((slots, Hkv, L, D), dtype=dtype, device=device)
-            self.k_stage = None
-        else:
-            self.k_unrot = None
-            self.k_stage = None if (keep_all or in_place_compaction) else torch.empty((slots, Hkv, keep, D), dtype=dtype, device=device)
-        self.cos_new = self.sin_new = None   # tables of a third-party rotary module, allocated when one is used
-        self.pending: List[int] = []
-        self.c_pending = 0         # how many of them were appended by rtk_pivotkv_update (the one-call path)
-        self.rotary_emb_fn = None
-        self.rot: Optional[_Rotary] = None
-        self.mrope_section = None
-        self.sec = None            # ... as the ctypes array the launches take (written by PivotKVCache._bind_rotary)
-        self.x_like = None
-        self.mask_obj = None       # the last key-patch mask tensor that passed validation, and its address
-        self.mask_ptr = None
-        self.shift_ids = None      # pre-RoPE units: the caller's ids tensor, shifted in place by the flush
-        self.defer = False         # deferred re-rotation (PivotKVCache.defer_rerotation)
-        self.qshape, self.kshape = torch.Size((1, Hq, L, D)), torch.Size((1, Hkv, L, D))
-        self.dev_index = device.index if device.index is not None else torch.cuda.current_device()
-        # the one-call path (rtk_pivotkv_update / rtk_pivotkv_flush): argument blocks bound once per batch
-        self.c = nv.PivotKVBatch()
-        self.cref = C.addressof(self.c)
-        self.io = nv.UpdateIO()
-        self.ioref = C.addressof(self.io)
-        # RTK_UPDATE_SHIFT_NEXT's words (launch count + arrival counters of the prepare launch), zeroed once
-        self.shift_ticket = torch.zeros(max(1, nv.lib.rtk_pivotkv_shift_ticket_ints(L, D)), dtype=torch.int32, device=device)
-        self.io.ticket, self.io.ticket_ints = self.shift_ticket.data_ptr(), self.shift_ticket.numel()
-        # ... and a word of PINNED HOST memory the watching workgroup increments if its bounded wait ever runs out (it then
-        # shifts nothing): the host reads it without a device synchronisation (PivotKVCache._shift_latch_check raises)
-        self.shift_status = torch.zeros(1, dtype=torch.int32, pin_memory=True) if device.type == "cuda" else None
-        self.shift_latch = self.shift_status.numpy() if self.shift_status is not None else None
-        self.io.status = self.shift_status.data_ptr() if self.shift_status is not None else None
-        self.shift_stream = None   # the stream of the batch's last RTK_UPDATE_SHIFT_NEXT launch (the words serve one stream at a time)
-        # prologue route: queries that are scored where they lie (no packed copy) - the pointers the library reads at
-        # the flush, and the tensors themselves, kept alive until then
-        self.q_units = (C.c_void_p * slots)()
-        self.q_keep: List[Optional[torch.Tensor]] = [None] * slots
-        c = self.c
-        c.Hq, c.Hkv, c.L, c.D, c.keep, c.P, c.slots = Hq, Hkv, L, D, keep, P, slots
-        c.dtype = nv.RTK_BF16 if dtype == torch.bfloat16 else (nv.RTK_F16 if dtype == torch.float16 else nv.RTK_F32)
-        c.score_dtype, c.prep_dtype = self.score_dt, self.prep_dt
-        c.reforge, c.keep_all, c.round_mode = int(reforge), int(keep_all), self.round_mode
-        c.rs_n, c.skip_masked, c.batched_passes = self.rs_n.value, int(skip_masked), int(self.batched_passes)
-        c.partial_floats = self.part_floats
-        c.keep_idx = self.keep_idx.data_ptr()
-        c.pos_new = self.pos_new.data_ptr() if P else None
-        c.pos_old = self.pos_old.data_ptr() if P else None
-        c.k_unrot = self.k_unrot.data_ptr() if reforge else None
-        c.k_stage = self.k_stage.data_ptr() if self.k_stage is not None else None
-        c.q_units = C.addressof(self.q_units)
-        # the one-call path serves the deferred chip-wide selection (L >= 512) of reforging caches with position ids
-        self.c_capable = bool(reforge and P and L >= 512)
-        # rtk_pivotkv_flush compacts the tails in place in one launch (rtk_pivotkv_compact_batched): tickets and flags
-        # of its workgroups live here, zeroed once; the staging rows are then only allocated by the stage-by-stage route
-        self.compact_sync = None
-        self.sync_stream = None    # the stream the batch's last in-place compaction was launched on
-        if in_place_compaction and not keep_all:
-            n_ints = nv.lib.rtk_pivotkv_compact_sync_ints(slots, Hkv, keep, D, c.dtype)
-            if n_ints:
-                self.compact_sync = torch.zeros(n_ints, dtype=torch.int32, device=device)
-                c.compact_sync, c.compact_sync_ints = self.compact_sync.data_ptr(), n_ints
-        if not keep_all:
-            self.ensure_scoring()
-            if self.compact_sync is None:
-                self.ensure_staging()
-        else:  # nothing is scored or staged: the scratch is allocated only if a route that needs it comes along
-            self._dummy = torch.empty(512, dtype=torch.uint8, device=device)
-            c.score_ws = (self._dummy.data_ptr() + 255) & ~255
-            c.score_ws_stride, c.score_ws_bytes = 0, 0
-
-    def slot(self, layer_idx: int) -> int:
-        return layer_idx % self.slots if self.wrap else layer_idx
-
-    def ensure_scoring(self):
-        """Scoring scratch of every slot (q~ / lse workspace, column partials, scores, selection scratch, live-key
-        lists); keep-all batches get it only on the routes that still un-rotate the queries."""
-        if self.partials is not None:
-            return
-        slots, L, device, c = self.slots, self.L, self.device, self.c
-        self.partials = torch.empty((slots, self.part_floats), dtype=torch.float32, device=device)
-        self.score = torch.empty((slots, L), dtype=torch.float32, device=device)
-        self.sel_ws = torch.empty((slots, self.sel_bytes), dtype=torch.uint8, device=device)
-        self.score_ws = torch.empty(slots * self.ws_stride + 256, dtype=torch.uint8, device=device)
-        self.score_ws_base = (self.score_ws.data_ptr() + 255) & ~255
-        # pass 2's live-key lists (the unmasked tokens of every slot + their count): the columns the mask override
-        # discards (reference :272-274) are not computed
-        self.key_index = torch.empty((slots, L + 1), dtype=torch.int32, device=device)
-        c.partials, c.score, c.sel_ws = self.partials.data_ptr(), self.score.data_ptr(), self.sel_ws.data_ptr()
-        c.sel_ws_stride = self.sel_bytes
-        c.score_ws, c.score_ws_stride, c.score_ws_bytes = self.score_ws_base, self.ws_stride, self.ws_bytes
-        c.key_index = self.key_index.data_ptr()
-        if self.prompt:
-            self.prompt_ws = torch.empty(slots * self.prompt_bytes + 256, dtype=torch.uint8, device=device)
-            self.prompt_ws_base = (self.prompt_ws.data_ptr() + 255) & ~255
-            self.pos_video = torch.empty((slots, self.P, self.Lv), dtype=torch.int64, device=device) if self.P else None
-
-    def ensure_staging(self):
-        if self.v_stage is None:
-            self.v_stage = torch.empty((self.slots, self.Hkv, self.keep, self.D), dtype=self.dtype, device=self.device)
-            self.c.v_stage = self.v_stage.data_ptr()
-            if not self.reforge and self.k_stage is None:
-                self.k_stage = torch.empty_like(self.v_stage)
-                self.c.k_stage = self.k_stage.data_ptr()
-
-    def ensure_tables(self):
-        if self.cos_new is None:
-            self.cos_new = torch.empty((self.slots * self.keep, self.D), dtype=torch.float32, device=self.device)
-            self.sin_new = torch.empty((self.slots * self.keep, self.D), dtype=torch.float32, device=self.device)
-
-
-class _CacheView:
-    """List-like view handed out as `key_cache` / `value_cache`: indexing flushes pending compaction
-    first, so readers always see the compacted cache exactly like the reference's lists."""
-
-    def __init__(self, owner: "PivotKVCache", which: str):
-        # a weak reference: the cache owns its views, not the other way round - with a strong one the pair is a reference
-        # cycle and a dropped cache (gigabytes of device memory) lives on until the garbage collector happens to run
-        self._ref, self._w = weakref.ref(owner), which
-
-    @property
-    def _o(self) -> "PivotKVCache":
-        o = self._ref()
-        if o is None:
-            raise ReferenceError("the PivotKVCache this view belongs to has been released")
-        return o
-
-    def __len__(self):
-        return len(self._o._layers)
-
-    def __getitem__(self, i):
-        if isinstance(i, slice):
-            return [self[j] for j in range(*i.indices(len(self)))]
-        if i < 0:
-            i += len(self)
-        st = self._o._layers[i]
-        if st.k is None:
-            return []
-        if st.pending:
-            self._o._flush()
-        if st.len8:
-            return self._o._dense(st, self._w)
-        buf = st.k if self._w == "k" else st.v
-        return buf[:, :, :st.length]
-
-    def __setitem__(self, i, value):
-        # external writers (e.g. HF crop / reorder utilities) replace a layer wholesale
-        self._o._adopt(i, self._w, value)
-
-    def __iter__(self):
-        for i in range(len(self)):
-            yield self[i]
-
-    def append(self, value):
-        self._o._layers.append(_LayerStore())
-        if not (isinstance(value, list) and len(value) == 0):
-            self._o._adopt(len(self._o._layers) - 1, self._w, value)
-
-
-def chunk_attention(query_states, key_states, value_states, scaling=None, workspace=None, query_offset=None, archive=None,
-                    packed_gqa=False, route=None):
-    """Attention of a chunk's queries over [compressed prefix | current chunk] in one HIP launch (rtk_attention_forward):
-    what the reference's attention patches hand to torch / flash_attn after the cache update (qwen2_vl.py:88-117,
-    :188-219, :303-358; llava_onevision.py:118-139).
-
-    query_states [1, Hq, Lq, D], key_states / value_states [1, Hkv, Lk, D] with a contiguous head_dim and any head / row
-    strides - they are read where they are (the transposed projection output, the `[:P0 + L]` view of the cache buffer):
-    no repeat_kv, no .contiguous(), no mask.  One unpadded sequence; query row i sees keys j <= query_offset + i.  The
-    default, Lk - Lq, is bottom-right causal: the queries are the last Lq of the Lk positions (what flash-attn computes).  A
-    larger offset restates the 4-D additive mask HF builds over the UNCOMPRESSED positions, which the patches slice to the
-    keys the compressed cache holds: its width T gives query_offset = T - Lq (see native_attention).  Returns [1, Lq, Hq, D] (contiguous: `reshape(1, Lq, -1)` feeds o_proj), or None - nothing was
-    touched, take the existing route - when the library declines the shape (RTK_EUNSUPPORTED).
-
-    workspace: optional dict the key-split scratch is kept in between calls (PivotKVCache.attention passes its own).
-
-    archive: optional (k8, v8, k_scale, v_scale) - e4m3 codes uint8 [1, Hkv, L8, D] and fp32 scales [1, Hkv, L8] of rows that
-    PRECEDE key_states / value_states in the sequence (kv_cache_dtype="fp8_e4m3"; rtk_attention_forward_fp8kv, bf16 / fp16
-    with head_dim 128 only).  Every query row sees all of them; query_offset then counts over the L8 + Lk keys (default
-    L8 + Lk - Lq).
-
-    packed_gqa: try the GQA-packed few-row kernel first (rtk_attention_decode, or rtk_attention_decode_fp8kv with an
-    archive: bf16 / fp16, head_dim 128, (Hq / Hkv) * Lq <= 16).  A shape it declines (RTK_EUNSUPPORTED) takes the call above
-    in this same invocation, so it returns the bits the default returns.  Its partials are kept in `workspace` under a key
-    of their own.  route: optional list; the call appends "packed" or "chunk", whichever kernel produced the result."""
-    nv.require_device(query_states, key_states, value_states)
-    if query_states.dim() != 4 or key_states.dim() != 4 or value_states.dim() != 4 or query_states.shape[0] != 1:
-        raise ValueError("chunk_attention takes [1, H, L, D] tensors (one unpadded sequence)")
-    if key_states.shape != value_states.shape or key_states.stride() != value_states.stride():
-        raise ValueError("key_states and value_states must share shape and strides")
-    if not (query_states.dtype == key_states.dtype == value_states.dtype):
-        raise ValueError("query, key and value states must share a dtype")
-    _, Hq, Lq, D = query_states.shape
-    _, Hkv, Lk, Dk = key_states.shape
-    if Dk != D:
-        raise ValueError("query and key head_dim differ")
-    if query_states.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return None
-    if query_states.stride(3) != 1 or key_states.stride(3) != 1:
-        return None
-    code = nv.dtype_code(query_states)
-    scale = float(D) ** -0.5 if scaling is None else float(scaling)
-    L8 = 0
-    if archive is not None:
-        k8, v8, ks8, vs8 = archive
-        nv.require_device(k8, v8, ks8, vs8)
-        if k8.dtype != torch.uint8 or v8.dtype != torch.uint8 or ks8.dtype != torch.float32 or vs8.dtype != torch.float32:
-            raise ValueError("archive = (codes uint8, codes uint8, scales float32, scales float32)")
-        if k8.dim() != 4 or k8.shape[:2] != (1, Hkv) or k8.shape[3] != D or v8.shape != k8.shape or v8.stride() != k8.stride() \
-                or ks8.shape != k8.shape[:3] or vs8.shape != ks8.shape or vs8.stride() != ks8.stride():
-            raise ValueError("archive codes must be [1, Hkv, L8, D] and scales [1, Hkv, L8], K and V laid out alike")
-        if k8.stride(3) != 1 or k8.stride(2) != D or ks8.stride(2) != 1:
-            raise ValueError("archive rows must be dense (D codes per row, one scale per row)")
-        L8 = k8.shape[2]
-    q_off = L8 + Lk - Lq if query_offset is None else int(query_offset)
-    stream = nv.raw_stream(query_states.device.index)
-    out = torch.empty((1, Lq, Hq, D), dtype=query_states.dtype, device=query_states.device)
-
-    def scratch(tag, need):   # per stream: calls on two streams may overlap
-        if not need:
-            return None
-        key = (tag, query_states.device.index, stream)
-        ws = None if workspace is None else workspace.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=query_states.device)
-            if workspace is not None:
-                workspace[key] = ws
-        return ws
-
-    qkv = (nv.ptr(query_states), query_states.stride(1), query_states.stride(2), nv.ptr(key_states), nv.ptr(value_states),
-           key_states.stride(1), key_states.stride(2))
-    if archive is not None:   # (an empty archive included: the library then runs the 16-bit call itself)
-        qkv += (nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), L8, k8.stride(1), ks8.stride(1))
-        shape = (Hq, Hkv, Lq, Lk, L8, D, code)
-        sfx = "_fp8kv"
-    else:
-        shape = (Hq, Hkv, Lq, Lk, D, code)
-        sfx = ""
-    routes = (("packed", "rtk_attention_decode", "rtk_attention_decode_workspace_bytes", "attention_decode_ws"),) \
-        if packed_gqa else ()
-    for tag, fn, query, ws_tag in routes + (("chunk", "rtk_attention_forward", "rtk_attention_workspace_bytes", "attention_ws"),):
-        need = getattr(nv.lib, query + sfx)(*shape)
-        ws = scratch(ws_tag, need)
-        rc = getattr(nv.lib, fn + sfx)(*qkv, nv.ptr(out), Hq, Hkv, Lq, Lk, q_off - L8, D, code, scale, nv.ptr(ws), need, stream)
-        if rc == nv.RTK_EUNSUPPORTED:
-            continue
-        nv.check(rc, fn + sfx)
-        if route is not None:
-            route.append(tag)
-        return out
-    return None
-
-
-def fp8_quantize_rows(x: torch.Tensor):
-    """x [1, Hkv, L, 128] (bf16 / fp16, dense rows, any head stride) -> (codes uint8 [1, Hkv, L, 128], scales fp32
-    [1, Hkv, L]) by the rule of include/retake_hip.h "FP8 rows of the compressed cache", on the device
-    (rtk_pivotkv_archive_batched in copy mode with the identity selection).  Tools and diagnostics; the cache's flush
-    fills its archive with the same kernel."""
-    nv.require_device(x)
-    if x.dim() != 4 or x.shape[0] != 1 or x.stride(3) != 1 or x.stride(2) != x.shape[3]:
-        raise ValueError("fp8_quantize_rows takes [1, Hkv, L, D] with dense rows")
-    _, H, L, D = x.shape
-    codes = torch.empty((1, H, L, D), dtype=torch.uint8, device=x.device)
-    scales = torch.empty((1, H, L), dtype=torch.float32, device=x.device)
-    if L == 0:
-        return codes, scales
-    dummy_c, dummy_s = torch.empty_like(codes), torch.empty_like(scales)   # (the kernel archives a K and a V per unit)
-    units = (nv.ArchiveUnit * 1)()
-    u = units[0]
-    u.k_src, u.k_src_stride_h, u.v_src, u.v_src_stride_h = x.data_ptr(), x.stride(1), x.data_ptr(), x.stride(1)
-    u.k8, u.v8, u.dst_stride_h = codes.data_ptr(), dummy_c.data_ptr(), L * D
-    u.k_scale, u.v_scale, u.scale_stride_h = scales.data_ptr(), dummy_s.data_ptr(), L
-    with torch.cuda.device(x.device):
-        nv.check(nv.lib.rtk_pivotkv_archive_batched(units, 1, H, D, L, 0, nv.dtype_code(x), nv.COMPACT_K_COPY, None, 1.0, None, 0,
-                                                    nv.round_mode(x.dtype), nv.stream()), "rtk_pivotkv_archive_batched")
-    return codes, scales
-
-
-def fp8_dequantize_rows(codes: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype, out: Optional[torch.Tensor] = None):
-    """codes uint8 [1, Hkv, L, 128] + scales fp32 [1, Hkv, L] (dense rows, any head stride) -> [1, Hkv, L, 128] of `dtype`
-    (rtk_fp8kv_dequant), written into `out` (dense rows, any head stride) when given."""
-    nv.require_device(codes, scales)
-    _, H, L, D = codes.shape
-    if out is None:
-        out = torch.empty((1, H, L, D), dtype=dtype, device=codes.device)
-    if L:
-        with torch.cuda.device(codes.device):
-            nv.check(nv.lib.rtk_fp8kv_dequant(nv.ptr(codes), codes.stride(1), nv.ptr(scales), scales.stride(1), nv.ptr(out),
-                                              out.stride(1), H, L, D, nv.dtype_code(out), nv.stream()), "rtk_fp8kv_dequant")
-    return out
-
-
-def native_attention(module, cache, query_states, key_states, value_states, attention_mask, *, output_attentions=False,
-                     scaling=None):
-    """What the attention patches call after the prologue / cache update: the chunk's attention through `cache.attention`
-    iff the cache was built with attention_kernel="hip", the batch is one sequence on the GPU, no dropout is active, no
-    attention weights are wanted and the layer has no active sliding window.  [1, Lq, Hq, D], or None = take the patch's
-    existing route (nothing was touched).
-
-    attention_mask: the patch's additive mask [1, 1, Lq, T >= Lk], or "causal" for the flash-attn patch (no mask operand,
-    bottom-right causal).  The mask's VALUES are not read: the switch asserts one unpadded sequence - the only case the
-    reference supports (`assert bsz == 1`, longvideo_cache.py:246) - whose HF mask is 0 where j <= (T - Lq) + i and -inf
-    elsewhere (every recorded mask is: tests/test_attention_cpu.py).  Its WIDTH is: HF builds it over the uncompressed
-    positions and the patches slice it to the keys of the compressed cache, so row i sees keys j <= (T - Lq) + i, which for
-    T > Lk is more than bottom-right causal over the Lk keys - the native route returns what the patch's own route would.
-    A missing or differently shaped mask means something else on each patch's route: that call is declined."""
-    if getattr(cache, "attention_kernel", None) != "hip":
-        return None
-    fp8 = getattr(cache, "kv_cache_dtype", None) is not None
-
-    def decline(why):
-        # with fp8 rows the patch's own route would read the 16-bit rows only and silently miss the archive
-        if fp8:
-            raise NotImplementedError(f"kv_cache_dtype={cache.kv_cache_dtype!r}: the native chunk attention is the only "
-                                      f"route that reads the fp8 rows, and it does not serve this call: {why}")
-        return None
-
-    if output_attentions:
-        return decline("attention weights are wanted (output_attentions)")
-    if query_states.shape[0] != 1 or not query_states.is_cuda:
-        return decline("a padded batch or CPU tensors (one unpadded sequence on the GPU only)")
-    if module.training and getattr(module, "attention_dropout", 0.0):
-        return decline("attention dropout is active")
-    cfg = getattr(module, "config", None)
-    if (getattr(cfg, "use_sliding_window", False) and getattr(cfg, "sliding_window", None) is not None
-            and module.layer_idx >= getattr(cfg, "max_window_layers", 0)):
-        return decline("the layer has an active sliding window")
-    layer_idx = getattr(module, "layer_idx", None)
-    Lq = query_states.shape[2]
-    Lk = key_states.shape[2] + (cache.archive_len(layer_idx) if fp8 else 0)   # keys of the whole sequence
-    if isinstance(attention_mask, str):
-        if attention_mask != "causal":
-            return decline(f"attention mask {attention_mask!r}")
-        offset = Lk - Lq
-    else:
-        if attention_mask is None or attention_mask.dim() != 4 or tuple(attention_mask.shape[:3]) != (1, 1, Lq) \
-                or attention_mask.shape[3] < Lk:
-            return decline("a missing attention mask, or one that is not [1, 1, Lq, T >= Lk] (a padded batch)")
-        offset = attention_mask.shape[3] - Lq
-    return cache.attention(query_states, key_states, value_states, scaling=scaling, query_offset=offset, layer_idx=layer_idx)
-
-
-ATTENTION_KERNELS = (None, "hip")
-KV_CACHE_DTYPES = (None, "fp8_e4m3")
-
-
-def _attention_kernel_of(config):
-    kind = config.longvideo_kwargs.get("attention_kernel", None)
-    if kind not in ATTENTION_KERNELS:
-        raise ValueError(f"attention_kernel must be None or 'hip', got {kind!r}")
-    return kind
-
-
-# one layer's numbers at a mark.  has_kv / has_pos: did the layer own K / V and id buffers (a skipped layer owns none)
-_LayerMark = collections.namedtuple("_LayerMark", "length pos_len pos_ndim len8 archive_at num_evicted has_kv has_pos")
-
-
-class CacheMark:
-    """A restore point of one PivotKVCache (`PivotKVCache.mark`): the host-side numbers that say which rows of the layers'
-    buffers are in use - no tensor of the cache, no copy of a row.  `PivotKVCache.rewind` puts them back; the rows below a
-    mark are never rewritten by later work (a compressed chunk compacts inside its own tail, text and decode rows append
-    at `length`, the fp8 archive appends at `len8`), so that restores the cache.  Immutable.
-
-      serial, epoch   the cache's mark counter / buffer epoch when the mark was taken (rewind checks both)
-      layers          per layer, skipped ones included: (length, pos_len, pos_ndim, len8, archive_at, num_evicted, ..)
-      n_layers, pos_layers, n_evicted   len(cache._layers), len(position_cache), len(num_evicted_tokens)
-      seen_tokens     the base class's `_seen_tokens`, None when the installed base class keeps none
-      resume_position_ids   CPU int64 [P], None unless the prefill glue set it: the ids a fresh prefill gave the first text
-                      row after the video (`_prefill.followup_position_ids` continues from them)"""
-
-    __slots__ = ("_ref", "serial", "epoch", "layers", "n_layers", "pos_layers", "n_evicted", "seen_tokens", "flushes",
-                 "compressed", "video_end", "resume_position_ids", "__weakref__")
-
-    def __init__(self, ref, serial, epoch, layers, n_layers, pos_layers, n_evicted, seen_tokens, flushes, compressed,
-                 video_end, resume_position_ids=None):
-        for name, value in (("_ref", ref), ("serial", serial), ("epoch", epoch), ("layers", layers),
-                            ("n_layers", n_layers), ("pos_layers", pos_layers), ("n_evicted", n_evicted),
-                            ("seen_tokens", seen_tokens), ("flushes", flushes), ("compressed", compressed),
-                            ("video_end", video_end), ("resume_position_ids", resume_position_ids)):
-            object.__setattr__(self, name, value)
-
-    def __setattr__(self, name, value):
-        raise AttributeError(f"CacheMark is immutable (cannot set {name!r})")
-
-    def __delattr__(self, name):
-        raise AttributeError(f"CacheMark is immutable (cannot delete {name!r})")
-
-    @property
-    def cache(self):
-        """The cache the mark belongs to, None once it has been released."""
-        return self._ref()
-
-    def _with_resume(self, ids):
-        """The same restore point (same serial) carrying `ids` as resume_position_ids."""
-        return CacheMark(self._ref, self.serial, self.epoch, self.layers, self.n_layers, self.pos_layers, self.n_evicted,
-                         self.seen_tokens, self.flushes, self.compressed, self.video_end, ids)
-
-    def __repr__(self):
-        return (f"CacheMark(serial={self.serial}, epoch={self.epoch}, layers={self.n_layers}, "
-                f"rows={[m.length + m.len8 for m in self.layers]})")
+def _fill_io(io, q, qs, k, ks, v, vs, pos):
+    """The operands of a rtk_update_io block (qs, ks, vs: the tensors' .stride()); the callers check them, each by its rules."""
+    io.q, io.q_stride_h, io.q_stride_l = q.data_ptr(), qs[1], qs[2]
+    io.k, io.k_stride_h, io.k_stride_l = k.data_ptr(), ks[1], ks[2]
+    io.v, io.v_stride_h, io.v_stride_l = v.data_ptr(), vs[1], vs[2]
+    io.pos, io.pos_stride = pos.data_ptr(), pos.stride(0)
 
 
 class PivotKVCache(DynamicCache):
@@ -1694,6 +1006,22 @@ class PivotKVCache(DynamicCache):
                 nv.ptr(b.score[s0]), b.L, C.c_void_p(b.prompt_ws_base + s0 * b.prompt_bytes), b.prompt_bytes, m,
                 b.Hq, Hkv, b.L, b.prompt, D, b.score_dt, qu, qsh, qsl, nv.stream()), "rtk_pivotkv_score_prompt_batched")
 
+    def _select_units(self, b: _Batch, todo, partials, ids):
+        """rtk_select_unit blocks of the layers `todo`; `partials` (None: the scores are final) and `ids` are indexed by slot."""
+        su = (nv.SelectUnit * len(todo))()
+        for u, l in zip(su, todo):
+            sl = b.slot(l)
+            u.partial = partials[sl].data_ptr() if partials is not None else None
+            u.score = b.score[sl].data_ptr()
+            m = b.masks.get(l)
+            u.mask = m.data_ptr() if m is not None else None
+            u.pos = ids[sl].data_ptr() if b.P else None
+            u.keep_idx = b.keep_idx[sl].data_ptr()
+            u.rank = None
+            u.pos_out = (b.pos_new.data_ptr() + sl * b.keep * 8) if b.P else None
+            u.workspace = b.sel_ws[sl].data_ptr()
+        return su
+
     def _select_prompt_units(self, b: _Batch, todo):
         """The selection of prompt-guided units: mask override + top-k + id gather / rescale over the Lv VIDEO columns
         (the existing kernels called with L = Lv: keep of Lv, temporal ids rescaled by keep / Lv).  Their ids are handed
@@ -1703,17 +1031,7 @@ class PivotKVCache(DynamicCache):
         if P:
             lo, hi = min(slots), max(slots) + 1
             b.pos_video[lo:hi].copy_(b.pos_old[lo:hi, :, :Lv])
-        su = (nv.SelectUnit * len(todo))()
-        for u, l, sl in zip(su, todo, slots):
-            u.partial = None           # the scores are final
-            u.score = b.score[sl].data_ptr()
-            m = b.masks.get(l)
-            u.mask = m.data_ptr() if m is not None else None
-            u.pos = b.pos_video[sl].data_ptr() if P else None
-            u.keep_idx = b.keep_idx[sl].data_ptr()
-            u.rank = None
-            u.pos_out = (b.pos_new.data_ptr() + sl * keep * 8) if P else None
-            u.workspace = b.sel_ws[sl].data_ptr()
+        su = self._select_units(b, todo, None, b.pos_video)   # (no partials: the scores are final)
         rc = nv.lib.rtk_pivotkv_select_batched(su, len(todo), 0, 0, 0, Lv, keep, P, int(b.reforge), b.slots * keep, b.score_dt,
                                                nv.stream())
         if rc != nv.RTK_EUNSUPPORTED:
@@ -1741,18 +1059,7 @@ class PivotKVCache(DynamicCache):
             return
         if b.prompt:
             return self._select_prompt_units(b, todo)
-        su = (nv.SelectUnit * len(todo))()
-        for u, l in zip(su, todo):
-            sl = b.slot(l)
-            u.partial = b.partials[sl].data_ptr()
-            u.score = b.score[sl].data_ptr()
-            m = b.masks.get(l)
-            u.mask = m.data_ptr() if m is not None else None
-            u.pos = b.pos_old[sl].data_ptr() if P else None
-            u.keep_idx = b.keep_idx[sl].data_ptr()
-            u.rank = None
-            u.pos_out = (b.pos_new.data_ptr() + sl * keep * 8) if P else None
-            u.workspace = b.sel_ws[sl].data_ptr()
+        su = self._select_units(b, todo, b.partials, b.pos_old)
         nv.check(nv.lib.rtk_pivotkv_select_batched(su, len(todo), b.Hkv, b.rs_n.value, b.Hq // b.Hkv, b.L, keep, P,
                                                    int(b.reforge), b.slots * keep, b.score_dt, nv.stream()),
                  "rtk_pivotkv_select_batched")
@@ -2033,10 +1340,7 @@ class PivotKVCache(DynamicCache):
             return None
         io = b.io
         stream = nv.raw_stream(idx)
-        io.q, io.q_stride_h, io.q_stride_l = q.data_ptr(), qs[1], qs[2]
-        io.k, io.k_stride_h, io.k_stride_l = key_states.data_ptr(), ks[1], ks[2]
-        io.v, io.v_stride_h, io.v_stride_l = value_states.data_ptr(), vs[1], vs[2]
-        io.pos, io.pos_stride = pos.data_ptr(), pos.stride(0)
+        _fill_io(io, q, qs, key_states, ks, value_states, vs, pos)
         q_in_place = False
         if pre:
             rt = nv.RTK_UPDATE_ROUNDTRIP if roundtrip else 0
@@ -2236,10 +1540,7 @@ class PivotKVCache(DynamicCache):
         if st.c.pos_len != st.c.length + st.len8:   # a cache whose earlier rows carry no ids (filled without reforging): not ours
             return None
         io = self._aio
-        io.q, io.q_stride_h, io.q_stride_l = q.data_ptr(), qs[1], qs[2]
-        io.k, io.k_stride_h, io.k_stride_l = k.data_ptr(), ks[1], ks[2]
-        io.v, io.v_stride_h, io.v_stride_l = v.data_ptr(), vs[1], vs[2]
-        io.pos, io.pos_stride = pos.data_ptr(), pos.stride(0)
+        _fill_io(io, q, qs, k, ks, v, vs, pos)
         io.q_rot, io.qr_stride_h, io.qr_stride_l, io.flags = io.q, qs[1], qs[2], 0
         nsec = len(mrope_section) if mrope_section else 0
         sec = (C.c_int * nsec)(*mrope_section) if nsec else None
@@ -2514,17 +1815,11 @@ class PivotKVCache(DynamicCache):
         return True
 
 
-def _decode_attention_of(config):
-    kind = config.longvideo_kwargs.get("decode_attention", None)
-    if kind not in (None, "packed"):
-        raise ValueError(f"decode_attention must be None or 'packed', got {kind!r}")
-    return kind
-
-
-def _kv_cache_dtype_of(config):
-    kind = config.longvideo_kwargs.get("kv_cache_dtype", None)
-    if kind not in KV_CACHE_DTYPES:
-        raise ValueError(f"kv_cache_dtype must be None or 'fp8_e4m3', got {kind!r}")
+def _option_of(config, key: str, allowed):
+    """longvideo_kwargs[key] (a top-level key, default None) if it is one of `allowed`, else ValueError."""
+    kind = config.longvideo_kwargs.get(key, None)
+    if kind not in allowed:
+        raise ValueError(f"{key} must be {' or '.join(map(repr, allowed))}, got {kind!r}")
     return kind
 
 
@@ -2536,9 +1831,9 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
     compression_method = config.longvideo_kwargs["kvcache_compression_kwargs"]["compression_method"]
     if compression_method.lower() == "pivotkv":
         cache = PivotKVCache(config, reserve_tokens=reserve_tokens, reserve_archive_tokens=reserve_archive_tokens)
-        cache.attention_kernel = _attention_kernel_of(config)
-        cache.kv_cache_dtype = _kv_cache_dtype_of(config)
-        cache.decode_attention = _decode_attention_of(config)
+        cache.attention_kernel = _option_of(config, "attention_kernel", ATTENTION_KERNELS)
+        cache.kv_cache_dtype = _option_of(config, "kv_cache_dtype", KV_CACHE_DTYPES)
+        cache.decode_attention = _option_of(config, "decode_attention", (None, "packed"))
         if cache.decode_attention is not None and cache.attention_kernel != "hip":
             raise ValueError("decode_attention='packed' needs attention_kernel='hip': it is a kernel of the native attention")
         if cache.kv_cache_dtype is not None:

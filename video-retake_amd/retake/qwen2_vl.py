@@ -149,6 +149,13 @@ def retake_Qwen2VLFlashAttention2_forward(self, hidden_states, attention_mask=No
     helper for the kernel (third-party; present when flash-attn for ROCm is installed)."""
     from transformers.modeling_flash_attention_utils import _flash_attention_forward  # third-party
 
+    def half_dtype():   # what fp32 states are cast to: autocast's dtype, else the pre-quantization dtype, else the weight dtype
+        if torch.is_autocast_enabled():
+            return torch.get_autocast_gpu_dtype()
+        if hasattr(self.config, "_pre_quantization_dtype"):
+            return self.config._pre_quantization_dtype
+        return self.q_proj.weight.dtype
+
     bsz, q_len, _ = hidden_states.size()
     if past_key_value is not None and getattr(self.config, "use_sliding_window", False) \
             and getattr(self.config, "sliding_window", None) is not None:
@@ -181,12 +188,7 @@ def retake_Qwen2VLFlashAttention2_forward(self, hidden_states, attention_mask=No
         # so that it returns what the flash-attn route would; None = declined, the route below
         native_qkv = (query_states, key_states, value_states)
         if query_states.dtype == torch.float32:
-            if torch.is_autocast_enabled():
-                native_dtype = torch.get_autocast_gpu_dtype()
-            elif hasattr(self.config, "_pre_quantization_dtype"):
-                native_dtype = self.config._pre_quantization_dtype
-            else:
-                native_dtype = self.q_proj.weight.dtype
+            native_dtype = half_dtype()
             native_qkv = tuple(t.to(native_dtype) for t in native_qkv)
         native = native_attention(self, past_key_value, *native_qkv, "causal")
         if native is not None:
@@ -196,12 +198,7 @@ def retake_Qwen2VLFlashAttention2_forward(self, hidden_states, attention_mask=No
     dropout_rate = 0.0 if not self.training else self.attention_dropout
     input_dtype = query_states.dtype
     if input_dtype == torch.float32:  # flash-attn wants half precision (reference :318-333)
-        if torch.is_autocast_enabled():
-            target_dtype = torch.get_autocast_gpu_dtype()
-        elif hasattr(self.config, "_pre_quantization_dtype"):
-            target_dtype = self.config._pre_quantization_dtype
-        else:
-            target_dtype = self.q_proj.weight.dtype
+        target_dtype = half_dtype()
         query_states, key_states, value_states = (t.to(target_dtype) for t in (query_states, key_states, value_states))
     query_states, key_states, value_states = (t.transpose(1, 2) for t in (query_states, key_states, value_states))
     sliding_window = None

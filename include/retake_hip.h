@@ -45,6 +45,8 @@
  *   §J  "Measurement support"           rtk_profile_* (off by default)
  *   §K  "FP8 rows of the compressed cache"  rtk_pivotkv_archive_batched, rtk_attention_forward_fp8kv (+ _workspace_bytes_fp8kv),
  *                                       rtk_attention_decode_fp8kv (+ _workspace_bytes_fp8kv), rtk_fp8kv_dequant: opt-in (kv_cache_dtype="fp8_e4m3" with attention_kernel="hip")
+ *   §L  "Shared 16-bit rows"            rtk_attention_forward_shared, rtk_attention_decode_shared (+ _workspace_bytes_shared):
+ *                                       the keys are [archive | rows of another buffer | own rows] (PivotKVCache.fork)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -868,6 +870,42 @@ int rtk_attention_decode_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stri
                                const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
                                int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
                                int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+
+/* rtk_attention_forward_fp8kv / rtk_attention_decode_fp8kv with ONE MORE key segment: Ls 16-bit rows ks / vs of the model
+ * dtype that live in another buffer (head stride s_stride_h, row stride s_stride_l, elements) and sit between the archive
+ * and k / v in sequence order: [archive L8 | shared Ls | own Lk].  A fork of a PivotKVCache reads its parent's rows this
+ * way, where they lie.  Every archive row and every shared row is visible to every query row; own row r is visible to
+ * query row i iff r <= q_offset + i, so Lk, q_offset (>= Lk - Lq) and Lk >= Lq describe the own rows alone (the caller
+ * passes the offset of the whole sequence minus L8 + Ls).  The archive may be empty (L8 == 0: k8 .. v_scale are not read).
+ * Key tiles are counted in the padded index space of the _fp8kv calls with one more segment: the archive takes
+ * [0, L8p), the shared rows [L8p, L8p + Lsp), own row r sits at L8p + Lsp + r, L8p / Lsp = L8 / Ls rounded up to a whole
+ * key tile T (64 in rtk_attention_forward_shared, 32 in rtk_attention_decode_shared).  A tile is of one kind; rows past
+ * the end of a segment are zero-filled by the descriptor's bounds and masked; the split plan and the diagonal arithmetic
+ * are those of a 16-bit call over the padded total, the workspace layout that of the corresponding existing call.
+ * Hence, bit for bit:
+ *   Ls == 0              IS the _fp8kv call (ks / vs are not read), and with L8 == 0 as well the plain call;
+ *   Ls % T == 0, any L8  equals the _fp8kv call over (archive, [shared | own] concatenated in one buffer) with
+ *                        q_offset + Ls - with L8 == 0 the plain call over the concatenation;
+ * and the _workspace_bytes_shared functions agree with their counterparts in the same way.  Otherwise the own rows start
+ * a new key tile, i.e. the fp32 sums are grouped differently.
+ * RTK_BF16 / RTK_F16 with D == 128 only, rtk_attention_decode_shared with (Hq / Hkv) * Lq <= 16 besides
+ * (RTK_EUNSUPPORTED otherwise, with the reason in rtk_last_error()).  Errors, all before any launch: those of the _fp8kv
+ * call, plus RTK_EINVAL for Ls < 0 or NULL ks / vs with Ls > 0, RTK_EUNSUPPORTED for ks / vs or shared strides that are
+ * not multiples of 16 bytes, a shared row stride below D, or a shared head of 2 GiB or more. */
+size_t rtk_attention_workspace_bytes_shared(int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype);
+int rtk_attention_forward_shared(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                 int64_t kv_stride_h, int64_t kv_stride_l, const void* ks, const void* vs, int Ls,
+                                 int64_t s_stride_h, int64_t s_stride_l, const void* k8, const void* v8,
+                                 const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                 int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
+                                 int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+size_t rtk_attention_decode_workspace_bytes_shared(int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype);
+int rtk_attention_decode_shared(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                int64_t kv_stride_h, int64_t kv_stride_l, const void* ks, const void* vs, int Ls,
+                                int64_t s_stride_h, int64_t s_stride_l, const void* k8, const void* v8,
+                                const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
+                                int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -58,6 +58,7 @@ __device__ __forceinline__ int swz(int row) { return ((row & 3) << 2) | ((row >>
 
 // The body of both kernels is attention_d128_body.inc, included once each with FP8 false / true - a function the two
 // kernels share compiles the existing instantiations differently (tools/kernel_diff.py), the same text does not.
+// SHARED adds a third kind of tile in the same way: [archive | shared 16-bit rows | 16-bit rows], each segment padded.
 // FP8: the keys are [archive | 16-bit rows].  Key tiles are counted in a padded index space - the archive takes
 // [0, L8p), L8p = L8 rounded up to a whole tile, the 16-bit row r sits at L8p + r - so a tile is of one kind, the split
 // plan and the diagonal arithmetic are those of a 16-bit call over L8p + Lk keys, and with L8 % 64 == 0 every fp32 sum
@@ -68,8 +69,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_d128_kernel(
     const char* __restrict__ v, int64_t kv_sh, uint32_t kv_row_bytes, uint32_t kv_bytes, char* __restrict__ out,
     float* __restrict__ part_acc, float* __restrict__ part_ml, int Hq, int G, int Lq, int Lk, int off, float c2,
     int keys_per_split) {
-    constexpr bool FP8 = false;
+    constexpr bool FP8 = false, SHARED = false;
     const Archive8 a8{};
+    const Shared16 s16{};
 #include "attention_d128_body.inc"
 }
 
@@ -80,7 +82,19 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_d128_fp8kv_kernel(
     const char* __restrict__ v, int64_t kv_sh, uint32_t kv_row_bytes, uint32_t kv_bytes, char* __restrict__ out,
     float* __restrict__ part_acc, float* __restrict__ part_ml, int Hq, int G, int Lq, int Lk, int off, float c2,
     int keys_per_split, Archive8 a8) {
-    constexpr bool FP8 = true;
+    constexpr bool FP8 = true, SHARED = false;
+    const Shared16 s16{};
+#include "attention_d128_body.inc"
+}
+
+// the same body over [e4m3 archive (may be empty) | shared 16-bit rows | own 16-bit rows]: Lk and off describe the own rows
+template <int DT, bool SPLIT>
+__global__ __launch_bounds__(256, 2) void attn_fwd_d128_shared_kernel(
+    const char* __restrict__ q, int64_t q_sh, uint32_t q_row_bytes, uint32_t q_bytes, const char* __restrict__ k,
+    const char* __restrict__ v, int64_t kv_sh, uint32_t kv_row_bytes, uint32_t kv_bytes, char* __restrict__ out,
+    float* __restrict__ part_acc, float* __restrict__ part_ml, int Hq, int G, int Lq, int Lk, int off, float c2,
+    int keys_per_split, Archive8 a8, Shared16 s16) {
+    constexpr bool FP8 = true, SHARED = true;
 #include "attention_d128_body.inc"
 }
 
@@ -262,6 +276,35 @@ int attn_launch_fp8kv(const AttnPlan& pl, const void* q, int64_t q_sh, int64_t q
     return RTK_OK;
 }
 
+template <int DT>
+int attn_launch_shared(const AttnPlan& pl, const void* q, int64_t q_sh, int64_t q_sl, const void* k, const void* v, int64_t kv_sh,
+                       int64_t kv_sl, const Archive8& a8, const Shared16& s16, void* out, int Hq, int Hkv, int Lq, int Lk, int off,
+                       float c2, void* ws, hipStream_t st) {
+    constexpr int D = 128;
+    constexpr size_t es = 2;
+    float* part_acc = (float*)ws;
+    float* part_ml = part_acc ? part_acc + (size_t)pl.nsplit * Hq * Lq * D : nullptr;
+    const uint32_t q_bytes = (uint32_t)(((size_t)(Lq - 1) * q_sl + D) * es);
+    const uint32_t kv_bytes = (uint32_t)(((size_t)(Lk - 1) * kv_sl + D) * es);
+    const dim3 grid((unsigned)(Hq * ((Lq + AT_QB - 1) / AT_QB)), (unsigned)pl.nsplit);
+    if (pl.nsplit > 1)
+        hipLaunchKernelGGL((attn_fwd_d128_shared_kernel<DT, true>), grid, dim3(256), 0, st, (const char*)q, q_sh,
+                           (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * es),
+                           kv_bytes, (char*)out, part_acc, part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8, s16);
+    else
+        hipLaunchKernelGGL((attn_fwd_d128_shared_kernel<DT, false>), grid, dim3(256), 0, st, (const char*)q, q_sh,
+                           (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * es),
+                           kv_bytes, (char*)out, part_acc, part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8, s16);
+    RTK_LAUNCH_CHECK("attn_fwd_d128_shared_kernel");
+    if (pl.nsplit > 1) {
+        const size_t total = (size_t)Lq * Hq * D;
+        hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc,
+                           part_ml, (char*)out, Hq, Lq, D, pl.nsplit);
+        RTK_LAUNCH_CHECK("attn_combine_kernel");
+    }
+    return RTK_OK;
+}
+
 // the archive padded to whole key tiles: the key count the split plan of an fp8kv call is made for
 inline long long fp8kv_keys(int Lk, int L8) { return (long long)Lk + ((long long)L8 + AT_KT - 1) / AT_KT * AT_KT; }
 
@@ -297,6 +340,32 @@ int fp8kv_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, 
     }
     if (fp8kv_keys(Lk, L8) > 0x3fffffff || (long long)L8 * 128 >= (1ll << 31) - AT_KT * 128) {
         set_error("%s: unsupported extent: %d archive rows + %d keys", who, L8, Lk);
+        return RTK_EUNSUPPORTED;
+    }
+    return RTK_OK;
+}
+
+int shared_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype, int tile) {
+    const int rc = fp8kv_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG(Ls >= 0, "%s: Ls %d is negative", who, Ls);
+    if (shared_keys(Lk, L8, Ls, tile) > 0x3fffffff) {
+        set_error("%s: unsupported extent: %d archive rows + %d shared rows + %d keys", who, L8, Ls, Lk);
+        return RTK_EUNSUPPORTED;
+    }
+    return RTK_OK;
+}
+
+int shared_check_operands(const char* who, const void* ks, const void* vs, int Ls, int64_t s_stride_h, int64_t s_stride_l, int D,
+                          int slack) {
+    RTK_CHECK_ARG(ks && vs, "%s: NULL shared pointer with Ls = %d", who, Ls);
+    if ((((uintptr_t)ks | (uintptr_t)vs) & 15) != 0 || (s_stride_h * 2) % 16 != 0 || (s_stride_l * 2) % 16 != 0 ||
+        s_stride_l < D || s_stride_h < 0) {
+        set_error("%s: unsupported layout of the shared rows (16-byte aligned pointers and strides, row stride >= head_dim)", who);
+        return RTK_EUNSUPPORTED;
+    }
+    if (!fits_buffer_offsets(1, (int64_t)Ls + slack, D, 0, s_stride_l, 2)) {
+        set_error("%s: unsupported extent: one head of the shared rows spans 2 GiB or more", who);
         return RTK_EUNSUPPORTED;
     }
     return RTK_OK;
@@ -405,4 +474,49 @@ extern "C" int rtk_attention_forward_fp8kv(const void* q, int64_t q_stride_h, in
                                            q_offset, c2, ws, st);
     return attn_launch_fp8kv<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, out, Hq, Hkv, Lq, Lk,
                                       q_offset, c2, ws, st);
+}
+
+extern "C" size_t rtk_attention_workspace_bytes_shared(int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype) {
+    if (shared_check_shape("rtk_attention_workspace_bytes_shared", Hq, Hkv, Lq, Lk, L8, Ls, D, dtype, AT_KT) != RTK_OK) return 0;
+    return attn_plan(Hq, Lq, (int)shared_keys(Lk, L8, Ls, AT_KT), D, dtype).ws_bytes;
+}
+
+extern "C" int rtk_attention_forward_shared(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                            int64_t kv_stride_h, int64_t kv_stride_l, const void* ks, const void* vs, int Ls,
+                                            int64_t s_stride_h, int64_t s_stride_l, const void* k8, const void* v8,
+                                            const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                            int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                                            int D, int dtype, float scale, void* workspace, size_t workspace_bytes,
+                                            rtk_stream_t stream) {
+    const char* who = "rtk_attention_forward_shared";
+    RTK_CHECK_ARG(q && k && v && out, "%s: NULL q / k / v / out pointer", who);
+    int rc = shared_check_shape(who, Hq, Hkv, Lq, Lk, L8, Ls, D, dtype, AT_KT);
+    if (rc != RTK_OK) return rc;
+    if (Ls == 0)   // no shared rows: the two-segment call itself
+        return rtk_attention_forward_fp8kv(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, k8, v8, k_scale, v_scale, L8,
+                                           stride8_h, scale_stride_h, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype, scale, workspace,
+                                           workspace_bytes, stream);
+    rc = shared_check_operands(who, ks, vs, Ls, s_stride_h, s_stride_l, D, AT_KT);
+    if (rc != RTK_OK) return rc;
+    Archive8 a8{};
+    if (L8 > 0) {
+        RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
+        a8 = Archive8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
+    }
+    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8.k8, a8.v8, a8.ks, a8.vs, a8.sh8,
+                             a8.shs, out, Lq, Lk, q_offset, D, dtype, scale, AT_QB, AT_KT);
+    if (rc != RTK_OK) return rc;
+    const AttnPlan pl = attn_plan(Hq, Lq, (int)shared_keys(Lk, L8, Ls, AT_KT), D, dtype);
+    rc = attn_check_workspace(who, "rtk_attention_workspace_bytes_shared", pl.ws_bytes, workspace, workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    const float c2 = scale * 1.44269504088896340736f;
+    const Shared16 s16{(const char*)ks, (const char*)vs, s_stride_h, (uint32_t)(s_stride_l * 2),
+                       (uint32_t)(((size_t)(Ls - 1) * s_stride_l + D) * 2), Ls};
+    void* ws = pl.ws_bytes ? workspace : nullptr;
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RTK_BF16)
+        return attn_launch_shared<RTK_BF16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, s16, out, Hq, Hkv, Lq,
+                                            Lk, q_offset, c2, ws, st);
+    return attn_launch_shared<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, s16, out, Hq, Hkv, Lq, Lk,
+                                       q_offset, c2, ws, st);
 }

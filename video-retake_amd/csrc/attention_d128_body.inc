@@ -1,5 +1,6 @@
-// attention_d128_body.inc - the body of attn_fwd_d128_kernel / attn_fwd_d128_fp8kv_kernel (attention.hip), which include
-// it with `constexpr bool FP8` and `Archive8 a8` in scope, besides their common parameters.
+// attention_d128_body.inc - the body of attn_fwd_d128_kernel / attn_fwd_d128_fp8kv_kernel / attn_fwd_d128_shared_kernel
+// (attention.hip), which include it with `constexpr bool FP8, SHARED`, `Archive8 a8` and `Shared16 s16` in scope, besides
+// their common parameters.
     using Hh = H16<DT>;
     __shared__ __attribute__((aligned(16))) char lds[4 * AT_TILE];   // [buffer][K | V]
     // FP8: from here on Lk and off count in the padded key space (see attention.hip)
@@ -7,6 +8,12 @@
     if constexpr (FP8) {
         Lk += L8p;
         off += L8p;
+    }
+    // SHARED: one more padded segment, [L8p, L8p + Lsp), between the archive and the kernel's own rows
+    const int Ls = SHARED ? s16.Ls : 0, Lsp = (Ls + AT_KT - 1) / AT_KT * AT_KT;
+    if constexpr (SHARED) {
+        Lk += Lsp;
+        off += Lsp;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = uniform_int(tid >> 6);
     const int r = lane & 31, hf = lane >> 5;
@@ -26,6 +33,11 @@
     const __amdgpu_buffer_rsrc_t rq = bounded_rsrc(q + (int64_t)hq * q_sh * 2, q_bytes);
     const __amdgpu_buffer_rsrc_t rk = bounded_rsrc(k + (int64_t)hkv * kv_sh * 2, kv_bytes);
     const __amdgpu_buffer_rsrc_t rv = bounded_rsrc(v + (int64_t)hkv * kv_sh * 2, kv_bytes);
+    __amdgpu_buffer_rsrc_t rsk = rk, rsv = rk;
+    if constexpr (SHARED) {
+        rsk = bounded_rsrc(s16.k + (int64_t)hkv * s16.sh * 2, s16.bytes);
+        rsv = bounded_rsrc(s16.v + (int64_t)hkv * s16.sh * 2, s16.bytes);
+    }
     // archive tiles: thread -> rows arow, arow + 32, codes 16 acc_ .. 16 acc_ + 15 (the row's chunks 2 acc_, 2 acc_ + 1).
     // Consecutive 8-lane groups take rows r, r + 4, r + 1, r + 5, ...: the swizzle's parity alternates, so the 16 lanes of
     // an LDS write hold the even chunks of one row and the odd chunks of another - every bank once.
@@ -70,6 +82,18 @@
                 return;
             }
             kbase -= L8p;
+        }
+        if constexpr (SHARED) {
+            if (kbase < Lsp) {   // rows >= Ls of the last shared tile read as zero
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const uint32_t o = (uint32_t)(kbase + srow + 16 * u) * s16.row_bytes + 16u * sch;
+                    kst[u] = load16(rsk, o);
+                    vst[u] = load16(rsv, o);
+                }
+                return;
+            }
+            kbase -= Lsp;
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -144,6 +168,9 @@
             int vis_w = min(off + wrow0, Lk - 1), vis_r = min(off + qrow, Lk - 1);
             if constexpr (FP8) {
                 if (kbase < L8p) vis_w = vis_r = L8 - 1;
+            }
+            if constexpr (SHARED) {   // likewise a shared tile: the last shared row
+                if (kbase >= L8p && kbase < L8p + Lsp) vis_w = vis_r = L8p + Ls - 1;
             }
             if (kbase + AT_KT - 1 > vis_w) {   // the tile straddles one of them
                 const int lim = vis_r - kbase;

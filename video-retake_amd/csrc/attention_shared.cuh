@@ -31,6 +31,15 @@ struct Archive8 {
     int L8;
 };
 
+// 16-bit rows of ANOTHER buffer that sit between the archive and k / v in sequence order (rtk_attention_forward_shared: a
+// fork reads its parent's rows where they lie).  Ls rows per kv head, every one visible to every query row.
+struct Shared16 {
+    const char *k, *v;          // element (h, l, d) at (h * sh + d) * 2 + l * row_bytes bytes
+    int64_t sh;                 // head stride, elements
+    uint32_t row_bytes, bytes;  // row stride; extent of one head: the descriptor's bound
+    int Ls;
+};
+
 template <int DT> __device__ __forceinline__ float ld_elem(const void* p, size_t i) {
     if constexpr (DT == RTK_F32) return ((const float*)p)[i];
     else return H16<DT>::ld(p, i);
@@ -75,6 +84,15 @@ int attn_check_operands(const char* who, const void* q, int64_t q_stride_h, int6
                         int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8, const float* k_scale,
                         const float* v_scale, int64_t stride8_h, int64_t scale_stride_h, const void* out, int Lq, int Lk,
                         int q_offset, int D, int dtype, float scale, int q_slack, int kv_slack);
+// the shared rows (rtk_attention_*_shared): fp8kv_check_shape plus Ls and the padded total; `tile`: 64 (chunk) or 32 (decode)
+int shared_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype, int tile);
+// NULL pointers (RTK_EINVAL), 16-byte layout and the 2 GiB head extent of the shared rows, with `slack` rows past the last
+int shared_check_operands(const char* who, const void* ks, const void* vs, int Ls, int64_t s_stride_h, int64_t s_stride_l, int D,
+                          int slack);
+// keys of the padded index space [archive | shared | own]: each of the first two rounded up to whole tiles
+inline long long shared_keys(int Lk, int L8, int Ls, int tile) {
+    return (long long)Lk + ((long long)L8 + tile - 1) / tile * tile + ((long long)Ls + tile - 1) / tile * tile;
+}
 // RTK_EWORKSPACE unless `workspace` holds `need` bytes (need 0: nothing is checked); `query`: the entry point that sizes it
 int attn_check_workspace(const char* who, const char* query, size_t need, const void* workspace, size_t workspace_bytes);
 

@@ -23,7 +23,8 @@ class _LayerStore:
     """One layer's pre-allocated K/V buffers [1, Hkv, cap, D] and position ids [P, cap].  The numbers live in a
     rtk_layer_state block (`c`) the library reads and advances itself (rtk_pivotkv_update / rtk_pivotkv_flush)."""
 
-    __slots__ = ("c", "cref", "_k", "_v", "_pos", "pending_event", "pos_ndim", "k8", "v8", "ks8", "vs8", "len8", "archive_at")
+    __slots__ = ("c", "cref", "_k", "_v", "_pos", "pending_event", "pos_ndim", "k8", "v8", "ks8", "vs8", "len8", "archive_at",
+                 "sk", "sv", "base")
 
     def __init__(self):
         self.c = nv.LayerState()
@@ -36,6 +37,10 @@ class _LayerStore:
         self.k8 = self.v8 = self.ks8 = self.vs8 = None
         self.len8 = 0
         self.archive_at = -1
+        # a branch (PivotKVCache.fork): views of the parent's 16-bit rows [0, base), which precede this layer's own rows
+        # in the sequence (k / v / length then describe the own rows alone; the ids in `pos` cover the whole sequence)
+        self.sk = self.sv = None
+        self.base = 0
 
     def _sync(self):
         k, v, c = self._k, self._v, self.c
@@ -327,7 +332,7 @@ class _CacheView:
             return []
         if st.pending:
             self._o._flush()
-        if st.len8:
+        if st.len8 or st.base:
             return self._o._dense(st, self._w)
         buf = st.k if self._w == "k" else st.v
         return buf[:, :, :st.length]

@@ -170,6 +170,12 @@ _SIGNATURES = {
     "rtk_attention_decode_workspace_bytes_fp8kv": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
     "rtk_attention_decode_fp8kv": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp,
                                          _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "rtk_attention_workspace_bytes_shared": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_forward_shared": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp,
+                                           _vp, _i, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "rtk_attention_decode_workspace_bytes_shared": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_shared": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp,
+                                          _vp, _i, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),
     "rtk_p2p_free": (C.c_int, [_vp]),
     "rtk_p2p_export": (C.c_int, [_vp, _vp, C.POINTER(_sz)]),

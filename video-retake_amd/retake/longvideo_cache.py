@@ -78,6 +78,10 @@ class PivotKVCache(DynamicCache):
     _flushes = 0                  # identity of the most recent compressed flush whose rows the cache holds
     _compressed_in_forward = False
     last_compressed_mark = None   # the mark `after_forward` took after the most recent forward that compressed a chunk
+    # fork (not in the reference)
+    forked_from = None            # a branch: the parent's mark it was forked at (PivotKVCache.fork)
+    _fork_dead = None             # ... and why it is no longer valid, once the parent has given up the shared rows
+    _branches = None              # a parent: weak set of its branches
 
     def __init__(self, config, reserve_tokens: Optional[int] = None, reserve_archive_tokens: Optional[int] = None) -> None:
         """reserve_tokens (not in the reference): tokens per layer this cache is expected to hold at most - compressed
@@ -214,18 +218,27 @@ class PivotKVCache(DynamicCache):
         launch (see chunk_attention).  [1, Lq, Hq, D], or None when the library declines the shape.
         kv_cache_dtype="fp8_e4m3": `layer_idx` names the layer whose archive precedes those views; query_offset counts
         over archive + views; a shape the library declines raises NotImplementedError (no other route reads the archive)."""
-        archive = None
+        archive = shared = None
         if self.kv_cache_dtype is not None:
             if layer_idx is None:
                 raise ValueError("PivotKVCache.attention needs layer_idx when kv_cache_dtype is set")
             archive = self.archive(layer_idx)
+        if self.forked_from is not None:   # a branch: key_states / value_states are its own rows, the parent's precede them
+            self._branch_check()
+            if layer_idx is None:
+                raise ValueError("PivotKVCache.attention needs layer_idx on a branch (PivotKVCache.fork)")
+            shared = self.shared(layer_idx)
         route = []
         out = chunk_attention(query_states, key_states, value_states, scaling=scaling, workspace=self._attn_ws,
                               query_offset=query_offset, archive=archive, packed_gqa=self.decode_attention == "packed",
-                              route=route)
+                              route=route, shared=shared)
         if out is not None:
             self.attention_calls += 1
             self.decode_attention_calls += route == ["packed"]
+        elif self.forked_from is not None:
+            raise NotImplementedError("a branch (PivotKVCache.fork): the native chunk attention refuses this shape "
+                                      f"({nv.lib.rtk_last_error().decode(errors='replace')}) and no other route reads the "
+                                      "parent's rows")
         elif self.kv_cache_dtype is not None:
             raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r}: the native chunk attention refuses this shape "
                                       f"({nv.lib.rtk_last_error().decode(errors='replace')}) and no other route reads the fp8 rows")
@@ -247,6 +260,121 @@ class PivotKVCache(DynamicCache):
         st = self._layers[layer_idx]
         return st.k8[:, :, :n], st.v8[:, :, :n], st.ks8[:, :, :n], st.vs8[:, :, :n]
 
+    # ---- fork: a branch reads the parent's rows where they lie (not in the reference) ---------------
+    def shared_len(self, layer_idx) -> int:
+        """Rows of the parent's 16-bit buffers that precede the layer's own rows: 0 unless this cache is a branch."""
+        if layer_idx is None or layer_idx >= len(self._layers):
+            return 0
+        return self._layers[layer_idx].base
+
+    def shared(self, layer_idx):
+        """(ks, vs) views [1, Hkv, base, D] of the parent's rows the branch shares in this layer, or None."""
+        if not self.shared_len(layer_idx):
+            return None
+        st = self._layers[layer_idx]
+        return st.sk, st.sv
+
+    def _branch_check(self, who="PivotKVCache"):
+        """A branch is valid while its parent has not given up the rows they share: ValueError - what `rewind` raises for
+        such a mark - once the parent was rewound or cropped below the fork point, or had its buffers rewritten wholesale.
+        (A parent that was merely released is fine: the views own the storage.)"""
+        m = self.forked_from
+        if m is None:
+            return
+        parent = m.cache
+        if self._fork_dead is None and parent is not None:
+            if parent._mark_is_dead(m.serial):
+                self._fork_dead = "rows"
+            elif m.epoch != parent._epoch:
+                self._fork_dead = "epoch"
+        if self._fork_dead == "rows":
+            raise ValueError(f"{who}: the mark this branch was forked at has been invalidated - the parent cache was rewound "
+                             "or cropped to an earlier point since, and the rows the branch shares have been given up")
+        if self._fork_dead == "epoch":
+            raise ValueError(f"{who}: buffers of the parent cache were replaced or rewritten wholesale after the branch was "
+                             "forked (key_cache / value_cache / position_cache assigned, or stored rows rotated in place)")
+
+    def _branch_refuse_write(self):
+        if self.forked_from is not None:
+            raise NotImplementedError("a branch (PivotKVCache.fork): key_cache / value_cache / position_cache are dense copies "
+                                      "of [the parent's rows | the branch's own]; assigning through them is not supported")
+
+    def fork(self, mark: Optional[CacheMark] = None, reserve_tokens: Optional[int] = None) -> "PivotKVCache":
+        """A BRANCH of this cache at `mark` (default: `self.mark()`, which flushes first; a given mark is checked as `rewind`
+        checks it): a second live conversation about the same video for the memory of its own rows.  Per layer the branch
+        holds VIEWS of this cache's 16-bit rows [0, mark.length) and archive rows [0, mark.len8) - rows below a restore
+        point are never rewritten - a copy of the position ids [0, mark.pos_len) (P x 8 bytes a row: every id-reading
+        kernel stays as it is) and empty K / V buffers of its own, `reserve_tokens` rows (default 1024) to begin with.
+        `branch.forked_from` is the mark; get_seq_length / get_prev_temporal_idx / num_evicted_tokens / archive_len answer
+        for the whole sequence, as this cache's did at the mark.
+
+        A branch serves text and decode rows (`update` with compression off, `append_pre_rope`) into its own buffers,
+        `attention` over [archive | shared | own] (rtk_attention_forward_shared / rtk_attention_decode_shared - no other
+        route sees the shared rows: a call the native attention declines raises NotImplementedError), `mark` / `rewind` /
+        `crop` within its own rows (the crop floor is the fork point) and `_prefill.followup_position_ids(
+        branch.forked_from, n, device)` when forked at `video_end`.  It refuses, before any launch: a compressing update
+        (NotImplementedError: branches carry questions, not video), assignment through key_cache / value_cache (reading
+        them gives a dense copy in sequence order, a diagnostic), a fork of its own.
+
+        The branch stays valid while this cache keeps the shared rows: rewinding it to `mark` itself, answering its own
+        questions above `mark`, or releasing it altogether are all fine; rewinding or cropping it BELOW `mark` makes every
+        later call on the branch raise the ValueError `rewind` raises for such a mark.  A parent that outgrows a buffer
+        allocates a new one and the old one stays alive until the branches are dropped (`reserve_tokens` avoids that).
+
+        ValueError without attention_kernel="hip"; NotImplementedError with defer_rerotation, on a float32 model, with
+        head_dim != 128, or on a branch (no nested forks)."""
+        if self.attention_kernel != "hip":
+            raise ValueError("PivotKVCache.fork needs attention_kernel='hip': only the native attention reads the rows a "
+                             "branch shares with its parent")
+        if self.defer_rerotation:
+            raise NotImplementedError("PivotKVCache.fork: not served with defer_rerotation (see PivotKVCache.mark)")
+        if self.forked_from is not None:
+            raise NotImplementedError("PivotKVCache.fork: this cache is itself a branch; nested forks are not served "
+                                      "(fork the parent again)")
+        if self.head_dim != 128:
+            raise NotImplementedError(f"PivotKVCache.fork needs head_dim 128, got {self.head_dim}")
+        for st in self._layers:
+            if st._k is not None and st._k.dtype not in (torch.bfloat16, torch.float16):
+                raise NotImplementedError(f"PivotKVCache.fork needs a bfloat16 or float16 model, got {st._k.dtype}")
+        if mark is None:
+            mark = self.mark()
+        else:
+            self._flush()
+            self._shift_latch_check()
+            self._check_mark(mark)
+        br = type(self)(self.config, reserve_tokens=reserve_tokens)
+        br.attention_kernel, br.kv_cache_dtype, br.decode_attention = self.attention_kernel, self.kv_cache_dtype, self.decode_attention
+        br.kvcache_compression = False
+        cap = br.reserve_tokens or 1024
+        for l, m in enumerate(mark.layers):
+            pst, st = self._layers[l], br._store(l)
+            if m.has_kv:
+                k, v = pst._k, pst._v
+                st.sk, st.sv, st.base = k[:, :, :m.length], v[:, :, :m.length], m.length
+                shape = (1, k.shape[1], cap, k.shape[3])
+                st.k = torch.empty(shape, dtype=k.dtype, device=k.device)
+                st.v = torch.empty(shape, dtype=k.dtype, device=k.device)
+                if m.len8:
+                    st.k8, st.v8, st.ks8, st.vs8 = (t[:, :, :m.len8] for t in (pst.k8, pst.v8, pst.ks8, pst.vs8))
+                    st.len8, st.archive_at = m.len8, m.archive_at
+            if m.has_pos:
+                ids = torch.empty((pst._pos.shape[0], m.pos_len + cap), dtype=torch.int64, device=pst._pos.device)
+                ids[:, :m.pos_len].copy_(pst._pos[:, :m.pos_len])
+                st.pos, st.pos_len, st.pos_ndim = ids, m.pos_len, m.pos_ndim
+        br._pos_layers = mark.pos_layers
+        br.num_evicted_tokens = [mark.layers[l].num_evicted for l in range(mark.n_evicted)]
+        if mark.seen_tokens is not None:
+            br._seen_tokens = mark.seen_tokens
+        br._flushes = mark.flushes
+        br._warned = True
+        br.forked_from = mark
+        # the branch's own restore point at the fork: its `video_end` and crop floor
+        br.last_compressed_mark = br._take_mark(True)._with_resume(mark.resume_position_ids)
+        if self._branches is None:
+            self._branches = weakref.WeakSet()
+        self._branches.add(br)
+        return br
+
     def _archive_reserve(self, st: _LayerStore, more: int, Hkv: int, D: int, device):
         need = st.len8 + more
         if st.k8 is not None and st.k8.shape[2] >= need:
@@ -267,10 +395,16 @@ class PivotKVCache(DynamicCache):
         sequence, while position_cache[l] stays in sequence order: the two then no longer line up row for row (attention
         is unaffected: every archived row is visible to every later query)."""
         buf, codes, scales = (st.k, st.k8, st.ks8) if which == "k" else (st.v, st.v8, st.vs8)
-        Hkv, D, n8, at = buf.shape[1], buf.shape[3], st.len8, st.archive_at
-        out = torch.empty((1, Hkv, st.length + n8, D), dtype=buf.dtype, device=buf.device)
+        if st.base:   # a branch: the 16-bit rows are [the parent's rows it shares | its own]
+            self._branch_check()
+            buf = torch.cat([st.sk if which == "k" else st.sv, buf[:, :, :st.length]], dim=2)
+        Hkv, D, n8, n16 = buf.shape[1], buf.shape[3], st.len8, st.base + st.length
+        if not n8:
+            return buf
+        at = st.archive_at
+        out = torch.empty((1, Hkv, n16 + n8, D), dtype=buf.dtype, device=buf.device)
         out[:, :, :at].copy_(buf[:, :, :at])
-        out[:, :, at + n8:].copy_(buf[:, :, at:st.length])
+        out[:, :, at + n8:].copy_(buf[:, :, at:n16])
         fp8_dequantize_rows(codes[:, :, :n8], scales[:, :, :n8], buf.dtype, out[:, :, at:at + n8])
         return out
 
@@ -371,7 +505,9 @@ class PivotKVCache(DynamicCache):
     def mark(self) -> CacheMark:
         """A restore point of the cache as it stands (see CacheMark).  Like reading `position_cache` it first flushes
         deferred work (the flush waits for the worker streams), so a mark taken between an `update` and `after_forward`
-        equals the one taken after it.  O(layers) on the host; launches nothing besides that flush."""
+        equals the one taken after it.  O(layers) on the host; launches nothing besides that flush.  (A branch's marks
+        count its own rows.)"""
+        self._branch_check("PivotKVCache.mark")
         if self.defer_rerotation:
             raise NotImplementedError("PivotKVCache.mark: a cache with defer_rerotation (the sharded prefill's block caches) "
                                       "holds un-rotated keys and provisional ids until `finalize`; it has no restore points")
@@ -399,6 +535,9 @@ class PivotKVCache(DynamicCache):
         """Every mark taken after `serial` so far is invalid from now on (its rows are about to be overwritten)."""
         if serial < self._mark_serial:   # (ranges that start at or above `serial` lie inside the new one)
             self._dead_marks = tuple(r for r in self._dead_marks if r[0] < serial) + ((serial, self._mark_serial),)
+        for br in self._branches or ():   # (noted on the branches: this cache may be released before they look)
+            if br.forked_from.serial > serial:
+                br._fork_dead = "rows"
 
     def _check_mark(self, mark: CacheMark):
         if not isinstance(mark, CacheMark):
@@ -428,6 +567,7 @@ class PivotKVCache(DynamicCache):
         `kvcache_compression`, `keypatches_mask_chunk`, the batch and the scratch are left alone.  Every mark taken after
         `mark` is invalid afterwards.  ValueError, before anything changes: a mark of another cache, an invalidated one,
         one from before the buffers were replaced (the epoch), or a cache that is shorter than the mark says."""
+        self._branch_check("PivotKVCache.rewind")
         self._flush()
         self._shift_latch_check()
         self._check_mark(mark)
@@ -462,7 +602,8 @@ class PivotKVCache(DynamicCache):
         `last_compressed_mark` recorded it - or None when the cache holds compressed rows and no such record of them."""
         m = self.last_compressed_mark
         if m is not None and m.epoch == self._epoch and m.flushes == self._flushes:
-            return [m.layers[l].length + m.layers[l].len8 if l < m.n_layers else 0 for l in range(len(self._layers))]
+            return [m.layers[l].length + m.layers[l].len8 + self._layers[l].base if l < m.n_layers else 0
+                    for l in range(len(self._layers))]
         if self._flushes == 0 and not any(self.num_evicted_tokens):
             return [0] * len(self._layers)
         return None
@@ -474,6 +615,7 @@ class PivotKVCache(DynamicCache):
         only: below it a length alone cannot say what `num_evicted_tokens` or the archive split were - ValueError, and
         the cache stays as it was.  Like `rewind` it moves numbers only.  Every mark taken after `video_end` is invalid
         afterwards (which of them name dropped rows is not tracked)."""
+        self._branch_check("PivotKVCache.crop")
         self._flush()
         self._shift_latch_check()
         cur = self.get_seq_length()
@@ -488,7 +630,7 @@ class PivotKVCache(DynamicCache):
         floor = self._crop_floor()
         drops = []
         for l, st in enumerate(self._layers):
-            total = st.c.length + st.len8 if st._k is not None else 0
+            total = st.c.length + st.len8 + st.base if st._k is not None else 0
             drop = max(0, total - max_length)
             if drop and (floor is None or total - drop < floor[l]):
                 raise ValueError(
@@ -514,6 +656,7 @@ class PivotKVCache(DynamicCache):
 
     @key_cache.setter
     def key_cache(self, value):  # the base class assigns [] in __init__
+        self._branch_refuse_write()
         self._flush()
         self._epoch += 1
         self._layers = []
@@ -526,6 +669,7 @@ class PivotKVCache(DynamicCache):
 
     @value_cache.setter
     def value_cache(self, value):
+        self._branch_refuse_write()
         self._epoch += 1
         for i, v in enumerate(value):
             if i >= len(self._layers):
@@ -534,6 +678,7 @@ class PivotKVCache(DynamicCache):
                 self._adopt(i, "v", v)
 
     def _adopt(self, i: int, which: str, value):
+        self._branch_refuse_write()
         if getattr(self, "kv_cache_dtype", None) is not None:
             raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype!r}: key_cache / value_cache are dequantised copies "
                                       "of [16-bit rows | archive]; assigning through them is not supported")
@@ -555,7 +700,7 @@ class PivotKVCache(DynamicCache):
         if len(self._layers) <= layer_idx or self._layers[layer_idx].k is None:
             return 0
         st = self._layers[layer_idx]
-        return st.length + st.len8 + (st.pending_keep if st.pending else 0)
+        return st.base + st.length + st.len8 + (st.pending_keep if st.pending else 0)
 
     def __len__(self):
         return len(self._layers)
@@ -585,6 +730,7 @@ class PivotKVCache(DynamicCache):
 
     @position_cache.setter
     def position_cache(self, value):
+        self._branch_refuse_write()
         self._flush()
         self._epoch += 1
         self._pos_layers = len(value)
@@ -1274,6 +1420,8 @@ class PivotKVCache(DynamicCache):
         l + 1's temporal offset.  Only a caller that shares one ids tensor between its layers and shifts it in place itself
         (the Qwen2-VL attention patch: `shift_temporal_ids_` then finds the shift done) should set it.
         """
+        if self.forked_from is not None:
+            self._branch_update_check("PivotKVCache.update")
         b = self._batch
         if b is not None and b.shift_latch is not None and b.shift_latch[0]:
             self._shift_failed(b)
@@ -1408,6 +1556,14 @@ class PivotKVCache(DynamicCache):
         n = P0 + L
         return st._k.narrow(2, 0, n), st._v.narrow(2, 0, n)
 
+    def _branch_update_check(self, who: str):
+        """What every row-writing entry point of a branch checks first: the branch is still valid, and the call does not
+        compress (branches carry questions, not video)."""
+        self._branch_check(who)
+        if self.kvcache_compression:
+            raise NotImplementedError(f"{who}: a branch (PivotKVCache.fork) does not compress video chunks - branches carry "
+                                      "questions, not video (set kvcache_compression = False, or feed the video to the parent)")
+
     def _next_layer_prev(self, layer_idx: int, dev_index: int):
         """Address of the last temporal id cached for layer_idx + 1 (None: nothing cached, the rule's prev = -1), or
         False when this launch must not shift for it: there is no such layer, its previous chunk is still pending, or its
@@ -1452,6 +1608,8 @@ class PivotKVCache(DynamicCache):
         chunk-batched score passes can then read `query_states` where it lies (no copy of the queries is made;
         `query_states` must stay unmodified until the chunk's flush, and is kept alive by the cache), else over
         `query_states`; pass `query_states` itself to force the in-place rotation."""
+        if self.forked_from is not None:
+            self._branch_update_check("PivotKVCache.update_pre_rope")
         self._shift_latch_check()
         if not (self.kvcache_compression and self.pos_embed_reforge and self.one_call_update) or self.overlap_streams > 0 \
                 or position_ids is None or not key_states.is_cuda or key_states.shape[0] != 1 \
@@ -1504,6 +1662,8 @@ class PivotKVCache(DynamicCache):
         clone).  Replaces ~25 eager launches per layer and token.  Returns (rotated q, keys, values) like `update`, or
         None - nothing touched - when the op-by-op route has to run (compression on: `update_pre_rope`; no reforging;
         rotary modules that must be called; CPU tensors)."""
+        if self.forked_from is not None:
+            self._branch_update_check("PivotKVCache.append_pre_rope")
         self._shift_latch_check()
         if self.kvcache_compression or not (self.pos_embed_reforge and self.one_call_update) or position_ids is None \
                 or not key_states.is_cuda or key_states.shape[0] != 1 \
@@ -1537,7 +1697,7 @@ class PivotKVCache(DynamicCache):
             self._flush()
         st = self.reserve(layer_idx, n, k)
         self._pos_reserve(st, P, pos.ndim, n, dev)
-        if st.c.pos_len != st.c.length + st.len8:   # a cache whose earlier rows carry no ids (filled without reforging): not ours
+        if st.c.pos_len != st.base + st.c.length + st.len8:   # a cache whose earlier rows carry no ids (filled without reforging): not ours
             return None
         io = self._aio
         _fill_io(io, q, qs, k, ks, v, vs, pos)

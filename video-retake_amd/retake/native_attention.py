@@ -12,7 +12,7 @@ from . import _native as nv
 
 
 def chunk_attention(query_states, key_states, value_states, scaling=None, workspace=None, query_offset=None, archive=None,
-                    packed_gqa=False, route=None):
+                    packed_gqa=False, route=None, shared=None):
     """Attention of a chunk's queries over [compressed prefix | current chunk] in one HIP launch (rtk_attention_forward):
     what the reference's attention patches hand to torch / flash_attn after the cache update (qwen2_vl.py:88-117,
     :188-219, :303-358; llava_onevision.py:118-139).
@@ -35,7 +35,13 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
     packed_gqa: try the GQA-packed few-row kernel first (rtk_attention_decode, or rtk_attention_decode_fp8kv with an
     archive: bf16 / fp16, head_dim 128, (Hq / Hkv) * Lq <= 16).  A shape it declines (RTK_EUNSUPPORTED) takes the call above
     in this same invocation, so it returns the bits the default returns.  Its partials are kept in `workspace` under a key
-    of their own.  route: optional list; the call appends "packed" or "chunk", whichever kernel produced the result."""
+    of their own.  route: optional list; the call appends "packed" or "chunk", whichever kernel produced the result.
+
+    shared: optional (ks, vs) - rows [1, Hkv, Ls, D] of the same dtype that live in ANOTHER buffer (their own head / row
+    strides, contiguous head_dim) and precede key_states / value_states in the sequence, after the archive: the keys are
+    [archive | shared | key_states] (rtk_attention_forward_shared / rtk_attention_decode_shared, bf16 / fp16 with head_dim
+    128 only; a branch of PivotKVCache.fork reads its parent's rows this way).  Every query row sees all of them;
+    query_offset counts over the L8 + Ls + Lk keys.  Combines with archive= and packed_gqa= as above."""
     nv.require_device(query_states, key_states, value_states)
     if query_states.dim() != 4 or key_states.dim() != 4 or value_states.dim() != 4 or query_states.shape[0] != 1:
         raise ValueError("chunk_attention takes [1, H, L, D] tensors (one unpadded sequence)")
@@ -65,7 +71,18 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
         if k8.stride(3) != 1 or k8.stride(2) != D or ks8.stride(2) != 1:
             raise ValueError("archive rows must be dense (D codes per row, one scale per row)")
         L8 = k8.shape[2]
-    q_off = L8 + Lk - Lq if query_offset is None else int(query_offset)
+    Ls = 0
+    if shared is not None:
+        ks, vs = shared
+        nv.require_device(ks, vs)
+        if ks.dim() != 4 or ks.shape[:2] != (1, Hkv) or ks.shape[3] != D or vs.shape != ks.shape or vs.stride() != ks.stride():
+            raise ValueError("shared keys / values must be [1, Hkv, Ls, D], laid out alike")
+        if ks.dtype != key_states.dtype or vs.dtype != key_states.dtype:
+            raise ValueError("shared keys / values must have the dtype of key_states")
+        if ks.stride(3) != 1:
+            return None
+        Ls = ks.shape[2]
+    q_off = L8 + Ls + Lk - Lq if query_offset is None else int(query_offset)
     stream = nv.raw_stream(query_states.device.index)
     out = torch.empty((1, Lq, Hq, D), dtype=query_states.dtype, device=query_states.device)
 
@@ -82,8 +99,14 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
 
     qkv = (nv.ptr(query_states), query_states.stride(1), query_states.stride(2), nv.ptr(key_states), nv.ptr(value_states),
            key_states.stride(1), key_states.stride(2))
-    if archive is not None:   # (an empty archive included: the library then runs the 16-bit call itself)
-        qkv += (nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), L8, k8.stride(1), ks8.stride(1))
+    a8 = (nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), L8, k8.stride(1), ks8.stride(1)) if archive is not None \
+        else (None, None, None, None, 0, 0, 0)
+    if shared is not None:    # (no shared rows included: the library then runs the two-segment call itself)
+        qkv += (nv.ptr(ks), nv.ptr(vs), Ls, ks.stride(1), ks.stride(2)) + a8
+        shape = (Hq, Hkv, Lq, Lk, L8, Ls, D, code)
+        sfx = "_shared"
+    elif archive is not None:   # (an empty archive included: the library then runs the 16-bit call itself)
+        qkv += a8
         shape = (Hq, Hkv, Lq, Lk, L8, D, code)
         sfx = "_fp8kv"
     else:
@@ -94,7 +117,7 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
     for tag, fn, query, ws_tag in routes + (("chunk", "rtk_attention_forward", "rtk_attention_workspace_bytes", "attention_ws"),):
         need = getattr(nv.lib, query + sfx)(*shape)
         ws = scratch(ws_tag, need)
-        rc = getattr(nv.lib, fn + sfx)(*qkv, nv.ptr(out), Hq, Hkv, Lq, Lk, q_off - L8, D, code, scale, nv.ptr(ws), need, stream)
+        rc = getattr(nv.lib, fn + sfx)(*qkv, nv.ptr(out), Hq, Hkv, Lq, Lk, q_off - L8 - Ls, D, code, scale, nv.ptr(ws), need, stream)
         if rc == nv.RTK_EUNSUPPORTED:
             continue
         nv.check(rc, fn + sfx)
@@ -160,12 +183,16 @@ def native_attention(module, cache, query_states, key_states, value_states, atte
     if getattr(cache, "attention_kernel", None) != "hip":
         return None
     fp8 = getattr(cache, "kv_cache_dtype", None) is not None
+    branch = getattr(cache, "forked_from", None) is not None
 
     def decline(why):
         # with fp8 rows the patch's own route would read the 16-bit rows only and silently miss the archive
         if fp8:
             raise NotImplementedError(f"kv_cache_dtype={cache.kv_cache_dtype!r}: the native chunk attention is the only "
                                       f"route that reads the fp8 rows, and it does not serve this call: {why}")
+        if branch:   # likewise the rows a branch shares with its parent
+            raise NotImplementedError("a branch (PivotKVCache.fork): the native chunk attention is the only route that reads "
+                                      f"the parent's rows, and it does not serve this call: {why}")
         return None
 
     if output_attentions:
@@ -180,7 +207,8 @@ def native_attention(module, cache, query_states, key_states, value_states, atte
         return decline("the layer has an active sliding window")
     layer_idx = getattr(module, "layer_idx", None)
     Lq = query_states.shape[2]
-    Lk = key_states.shape[2] + (cache.archive_len(layer_idx) if fp8 else 0)   # keys of the whole sequence
+    Lk = key_states.shape[2] + (cache.archive_len(layer_idx) if fp8 else 0) \
+        + (cache.shared_len(layer_idx) if branch else 0)   # keys of the whole sequence
     if isinstance(attention_mask, str):
         if attention_mask != "causal":
             return decline(f"attention mask {attention_mask!r}")

@@ -47,6 +47,8 @@
  *                                       rtk_attention_decode_fp8kv (+ _workspace_bytes_fp8kv), rtk_fp8kv_dequant: opt-in (kv_cache_dtype="fp8_e4m3" with attention_kernel="hip")
  *   §L  "Shared 16-bit rows"            rtk_attention_forward_shared, rtk_attention_decode_shared (+ _workspace_bytes_shared):
  *                                       the keys are [archive | rows of another buffer | own rows] (PivotKVCache.fork)
+ *   §M  "Group decode"                  rtk_attention_decode_group (+ _workspace_bytes): one token of each of several
+ *                                       branches in one launch that reads the shared rows once (retake/branch_group.py)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -906,6 +908,47 @@ int rtk_attention_decode_shared(const void* q, int64_t q_stride_h, int64_t q_str
                                 const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
                                 int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
                                 int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+
+/* Group decode: ONE new token of each of n_branches sequences that share [archive L8 | shared Ls] and differ in their own
+ * rows - the forks of one PivotKVCache, each a token into its answer - in one launch that fetches every archive and
+ * shared K / V row from HBM once, whatever n_branches is.  Branch b's one query row per head, q_b [Hq, 1, D], attends to
+ * every archive row, every shared row and every one of its own Lk_b rows (the query IS the last own row: no diagonal).
+ * ks .. scale_stride_h as rtk_attention_decode_shared; the archive and the shared segment may each be empty.  out is
+ * [n_branches, Hq, D], contiguous.
+ * The kernel packs row b * G + g (G = Hq / Hkv) of all branches onto the columns of one or two 16x16x32 MFMA operands
+ * that read the same K fragments and the same V image, so n_branches * G <= 32.
+ * Plan, fixed here.  The shared keys are counted in the padded space of rtk_attention_decode_shared without own rows,
+ * Kp = L8p + Lsp (each rounded up to the key tile T = 32), and split by the rule of rtk_attention_decode over Kp keys
+ * (ns_sh splits; none when Kp == 0): a function of (Hkv, L8, Ls) alone.  Branch b's own rows are split every
+ * RTK_DECODE_GROUP_OWN_KEYS = 512 keys: a function of Lk_b alone.  The launch runs ns_sh shared workgroups and
+ * n_own = max_b ceil(Lk_b / 512) own workgroups per branch, per kv head; a branch with no key in an own split leaves an
+ * empty partial.  The partials (layout of rtk_attention_decode with (branch, head) as the head index) are folded in the
+ * order shared splits, then own splits, empty ones skipped; no atomics.  The workspace is
+ *   (ns_sh + n_own) * n_branches * Hq * (D + 2) * sizeof(float) bytes.
+ * Hence branch b's output bits depend neither on which other branches are in the group nor on b's position in it.  They
+ * are not those of rtk_attention_decode_shared: the fp32 sums are grouped differently.
+ * RTK_BF16 / RTK_F16, D == 128, n_branches <= RTK_DECODE_GROUP_MAX and n_branches * G <= 32 only: RTK_EUNSUPPORTED
+ * otherwise, with the reason in rtk_last_error().  Errors, all before any launch: RTK_EINVAL for NULL pointers,
+ * n_branches < 1, Lk_b < 1, L8 / Ls < 0, NULL ks / vs with Ls > 0 or NULL archive pointers with L8 > 0; RTK_EUNSUPPORTED
+ * for pointers or strides that are not multiples of 16 bytes, row strides below D, heads of 2 GiB or more;
+ * RTK_EWORKSPACE for a short workspace.  The workspace query returns 0 for what the call would refuse. */
+typedef struct rtk_decode_branch {
+    const void* q;            /* [Hq, 1, D]: this branch's one query row per head, head stride q_stride_h (elements) */
+    int64_t q_stride_h;
+    const void* k;            /* its OWN rows [Hkv, Lk, D], the new token's included */
+    const void* v;
+    int64_t kv_stride_h, kv_stride_l;
+    int Lk;                   /* >= 1 */
+} rtk_decode_branch;
+#define RTK_DECODE_GROUP_MAX 8          /* the array travels as a kernel argument */
+#define RTK_DECODE_GROUP_OWN_KEYS 512   /* keys per own split */
+size_t rtk_attention_decode_group_workspace_bytes(const int* own_rows, int n_branches, int Hq, int Hkv, int L8, int Ls,
+                                                  int D, int dtype);
+int rtk_attention_decode_group(const rtk_decode_branch* branches, int n_branches, const void* ks, const void* vs, int Ls,
+                               int64_t s_stride_h, int64_t s_stride_l, const void* k8, const void* v8,
+                               const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                               int64_t scale_stride_h, void* out, int Hq, int Hkv, int D, int dtype, float scale,
+                               void* workspace, size_t workspace_bytes, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

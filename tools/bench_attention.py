@@ -33,6 +33,16 @@ Reported per shape: the K/V bytes one call reads once, what fraction of 8 TB/s a
 generated token (x 28 layers).  --fp8kv: all but the last Lq keys as fp8 rows - the packed two-segment call, the packed
 16-bit call on [dequantised archive | tail] (their ratio, and whether the outputs are bit-equal: they must be when
 L8 % 32 == 0), and rtk_attention_forward_fp8kv.
+
+    python tools/bench_attention.py --group [--out profiles/group_decode_bench.json]
+
+B = 1, 2 and 4 branches of one fork point decoding a token each (Hq 28 / Hkv 4, 100 352 shared rows, 64 own rows per
+branch, bf16): ONE rtk_attention_decode_group call against the B successive rtk_attention_decode_shared calls it replaces,
+same tensors, same process, every entry point called directly with resident outputs and workspaces.  Once with the shared
+rows as 16-bit rows and once as an fp8 archive in their place.  A sample is DECODE_INNER steps between one pair of HIP
+events; the samples of the two routes are INTERLEAVED (group, successive, group, ...), the median of `reps` each.
+Reported: microseconds per step, their ratio, the shared bytes a step reads once, and what fraction of 8 TB/s the group
+call reaches on them.
 """
 from __future__ import annotations
 
@@ -270,11 +280,102 @@ def main_decode(args):
               f"{r['sdpa']['us']:.1f} | {r['kv_bytes'] / 1e6:.1f} | {p['fraction_of_8_TBps']:.3f} | {p['fraction_of_copy']:.3f} | "
               f"{p['ms_per_token']:.2f} | {r['forward']['ms_per_token']:.2f} |")
 
+GROUP_SHARED, GROUP_OWN, GROUP_BRANCHES = 100352, 64, (1, 2, 4)
+
+
+def main_group(args):
+    import ctypes as C
+
+    import retake._native as nv
+    import retake.longvideo_cache as lc
+
+    dev = torch.device("cuda:0")
+    dtype, code, scale, stream = torch.bfloat16, nv.RTK_BF16, D ** -0.5, nv.stream()
+    g = torch.Generator(device=dev).manual_seed(0)
+    rnd = lambda *shape: (1.7 * torch.randn(shape, generator=g, device=dev)).to(dtype)   # noqa: E731
+    ks, vs = rnd(1, HKV, GROUP_SHARED, D), rnd(1, HKV, GROUP_SHARED, D)
+    ak, sk = lc.fp8_quantize_rows(ks)
+    av, sv = lc.fp8_quantize_rows(vs)
+    Bmax = max(GROUP_BRANCHES)
+    qs = [rnd(1, 1, HQ * D).view(1, 1, HQ, D).transpose(1, 2) for _ in range(Bmax)]
+    owns = [(rnd(1, HKV, GROUP_OWN + 256, D)[:, :, :GROUP_OWN], rnd(1, HKV, GROUP_OWN + 256, D)[:, :, :GROUP_OWN]) for _ in range(Bmax)]
+    rows = []
+    for kind in ("shared16", "fp8_archive"):
+        if kind == "shared16":
+            s16 = (nv.ptr(ks), nv.ptr(vs), GROUP_SHARED, ks.stride(1), ks.stride(2))
+            a8 = (None, None, None, None, 0, 0, 0)
+            shared_bytes = 2 * HKV * GROUP_SHARED * D * 2
+        else:
+            s16 = (None, None, 0, 0, 0)
+            a8 = (nv.ptr(ak), nv.ptr(av), nv.ptr(sk), nv.ptr(sv), GROUP_SHARED, ak.stride(1), sk.stride(1))
+            shared_bytes = 2 * HKV * GROUP_SHARED * (D + 4)
+        for B in GROUP_BRANCHES:
+            brs, own_rows = (nv.DecodeBranch * B)(), (C.c_int * B)(*([GROUP_OWN] * B))
+            for b in range(B):
+                br, (k, v) = brs[b], owns[b]
+                br.q, br.q_stride_h, br.k, br.v = qs[b].data_ptr(), qs[b].stride(1), k.data_ptr(), v.data_ptr()
+                br.kv_stride_h, br.kv_stride_l, br.Lk = k.stride(1), k.stride(2), GROUP_OWN
+            need_g = nv.lib.rtk_attention_decode_group_workspace_bytes(own_rows, B, HQ, HKV, a8[4], s16[2], D, code)
+            need_s = nv.lib.rtk_attention_decode_workspace_bytes_shared(HQ, HKV, 1, GROUP_OWN, a8[4], s16[2], D, code)
+            ws_g = torch.empty(max(need_g, 16), dtype=torch.uint8, device=dev)
+            ws_s = torch.empty(max(need_s, 16), dtype=torch.uint8, device=dev)
+            out_g = torch.empty((B, 1, HQ, D), dtype=dtype, device=dev)
+            out_s = torch.empty((B, 1, HQ, D), dtype=dtype, device=dev)
+            succ = [(nv.ptr(qs[b]), qs[b].stride(1), qs[b].stride(2), nv.ptr(owns[b][0]), nv.ptr(owns[b][1]), owns[b][0].stride(1),
+                     owns[b][0].stride(2)) + s16 + a8 + (nv.ptr(out_s[b]), HQ, HKV, 1, GROUP_OWN, GROUP_OWN - 1, D, code, scale,
+                                                          nv.ptr(ws_s), need_s, stream) for b in range(B)]
+
+            def group():
+                for _ in range(DECODE_INNER):
+                    nv.check(nv.lib.rtk_attention_decode_group(brs, B, *s16, *a8, nv.ptr(out_g), HQ, HKV, D, code, scale,
+                                                               nv.ptr(ws_g), need_g, stream), "rtk_attention_decode_group")
+
+            def successive():
+                for _ in range(DECODE_INNER):
+                    for a in succ:
+                        nv.check(nv.lib.rtk_attention_decode_shared(*a), "rtk_attention_decode_shared")
+
+            for _ in range(args.warmup):
+                group()
+                successive()
+            torch.cuda.synchronize()
+            times = {"group": [], "successive": []}
+            for _ in range(args.reps):   # interleaved: both routes see the same drift of clocks and cache state
+                for name, fn in (("group", group), ("successive", successive)):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    e1.synchronize()
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / DECODE_INNER)
+            row = {"kind": kind, "B": B, "Hq": HQ, "Hkv": HKV, "D": D, "dtype": "bfloat16", "shared_rows": GROUP_SHARED,
+                   "own_rows": GROUP_OWN, "reps": args.reps, "inner": DECODE_INNER, "shared_bytes": shared_bytes}
+            for name, t in times.items():
+                us = statistics.median(t)
+                row[name] = {"us": us, "min_us": min(t), "max_us": max(t), "ms_per_token": us * LAYERS * 1e-3}
+            row["group"]["fraction_of_8_TBps"] = shared_bytes / (row["group"]["us"] * 1e-6) / HBM_PEAK
+            row["ratio_successive_over_group"] = row["successive"]["us"] / row["group"]["us"]
+            row["max_abs_diff_group_vs_successive"] = (out_g.float() - out_s.float()).abs().max().item()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    doc = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "hbm_peak_bytes_per_s": HBM_PEAK, "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("\n| shared rows as | B | group call us | B successive calls us | successive / group | shared MB | group: of 8 TB/s "
+          "| group ms / token |")
+    print("|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['kind']} | {r['B']} | {r['group']['us']:.1f} | {r['successive']['us']:.1f} | "
+              f"{r['ratio_successive_over_group']:.2f} | {r['shared_bytes'] / 1e6:.1f} | {r['group']['fraction_of_8_TBps']:.3f} | "
+              f"{r['group']['ms_per_token']:.2f} |")
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fp8kv", action="store_true", help="the two-segment fp8 call against the 16-bit kernel on dequantised rows")
     ap.add_argument("--decode", action="store_true", help="the GQA-packed few-row kernel against the call it replaces")
+    ap.add_argument("--group", action="store_true", help="one group-decode call against the B successive per-branch calls it replaces")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -283,9 +384,13 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_attention.py needs the GPU: a CPU run measures nothing")
-    if args.out is None:
+    if args.out is None and not args.group:
         args.out = os.path.join(ROOT, "profiles", ("fp8kv_" if args.fp8kv else "") + ("decode_" if args.decode else "") +
                                 "attention_bench.json")
+    if args.group:
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "group_decode_bench.json")
+        return main_group(args)
     if args.decode:
         return main_decode(args)
     if args.fp8kv:

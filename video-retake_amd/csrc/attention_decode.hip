@@ -26,6 +26,8 @@
 // a 16-bit tile of the dequantised rows would have left, so with L8 % 32 == 0 every fp32 sum is grouped as in the 16-bit
 // call over the concatenation.  (The k-steps of S^T take channels 64 a + 16 g + 8 b + j, step 2 a + b, lane group g: 16
 // consecutive codes of a row dequantise into one lane's operands of two steps.)
+#include <algorithm>
+
 #include "attention_shared.cuh"
 
 namespace rtk {
@@ -153,6 +155,346 @@ int decode_launch_shared(const DecodePlan& pl, const void* q, int64_t q_sh, int6
     return RTK_OK;
 }
 
+// ---- group decode (rtk_attention_decode_group): ONE token of each of B branches that share [archive | shared rows] ----
+// attn_decode_group_d128_kernel, grid (ns_sh + B * max_own) x Hkv:
+//   * x < ns_sh: a SHARED workgroup - one kv head, one range of the padded [archive L8p | shared Lsp] key space.  Its
+//     columns are all R = B * G packed rows, row b * G + g from branch b; with R > 16 (NCG = 2) the K fragments in
+//     registers feed a second S^T = mfma(K, Q) against a second set of Q fragments and the V image in LDS a second
+//     O^T = mfma(V^T, P^T), so a K or V row is fetched from HBM once per call whatever B is;
+//   * x >= ns_sh: an OWN workgroup - branch (x - ns_sh) / max_own, keys [j * GRP_OWN_KEYS, ...) of that branch's own rows,
+//     j = (x - ns_sh) % max_own; its columns are that branch's G rows.  A branch with no keys in split j leaves an empty
+//     partial (m = -inf), which attn_combine_kernel skips.
+// The query is each branch's last own row, so every row sees every key: no diagonal.  The tile loop, the softmax and the
+// fold of the four waves are those of attention_decode_d128_body.inc, once per column group; partials go to
+// [split][branch * Hq + head] - the layout attn_combine_kernel reads with (branch, head) as the head index - shared
+// splits first, then own splits.  A column's arithmetic depends on no other column, so a branch's bits depend neither
+// on its position in the group nor on the other members.  No atomics, no flags; plain vector stores.
+constexpr int GRP_OWN_KEYS = RTK_DECODE_GROUP_OWN_KEYS;   // keys per own split: retake_hip.h states it
+
+struct GroupBranch {
+    const char *q, *k, *v;
+    int64_t q_sh, kv_sh;                // head strides, elements
+    uint32_t kv_row_bytes, kv_bytes;    // row stride; extent of one head: the descriptor's bound
+    int Lk, pad;
+};
+struct GroupArgs {
+    GroupBranch br[RTK_DECODE_GROUP_MAX];
+    int B, G, Hq, ns_sh, kps_sh, max_own;
+};
+
+template <int DT, int NCG>
+__global__ __launch_bounds__(256, 2) void attn_decode_group_d128_kernel(GroupArgs ga, Archive8 a8, Shared16 s16,
+                                                                        float* __restrict__ part_acc,
+                                                                        float* __restrict__ part_ml, float c2) {
+    using Hh = H16<DT>;
+    constexpr int NR = NCG * DEC_R;                                                   // columns of the workgroup
+    constexpr int WAVE_LDS = NR * DEC_OPITCH * 4 > DEC_WAVE_LDS ? NR * DEC_OPITCH * 4 : DEC_WAVE_LDS;
+    __shared__ __attribute__((aligned(16))) char lds[4 * WAVE_LDS];   // [wave]: V tile, then the wave's O
+    __shared__ float ml_s[4][NR][2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = uniform_int(tid >> 6);
+    const int c = lane & 15, g = lane >> 4;   // column within a group and lane group
+    const int hkv = blockIdx.y, G = ga.G;
+    const bool own = (int)blockIdx.x >= ga.ns_sh;
+    const int ox = own ? (int)blockIdx.x - ga.ns_sh : 0, ob = ox / ga.max_own, oj = ox % ga.max_own;
+    GroupBranch me = ga.br[0];   // (selected, not indexed: the array stays in the kernel argument segment)
+#pragma unroll
+    for (int b = 1; b < RTK_DECODE_GROUP_MAX; ++b)
+        if (ob == b) me = ga.br[b];
+    const int nrows = own ? G : ga.B * G;
+    // the key space of this workgroup: [archive tiles [0, archp) | 16-bit rows from archp on]
+    const int L8 = a8.L8, L8p = (L8 + DEC_T - 1) / DEC_T * DEC_T;
+    const int Lsp = (s16.Ls + DEC_T - 1) / DEC_T * DEC_T;
+    const int archp = own ? 0 : L8p;
+    const int keys = own ? me.Lk : L8p + Lsp;
+    const int vis16 = own ? me.Lk - 1 : L8p + s16.Ls - 1;   // last key of the 16-bit segment
+    const int span = own ? GRP_OWN_KEYS : ga.kps_sh;
+    const int k_lo = (own ? oj : (int)blockIdx.x) * span, k_hi = min(keys, k_lo + span);
+    const uint32_t row_bytes = own ? me.kv_row_bytes : s16.row_bytes;
+
+    const __amdgpu_buffer_rsrc_t rk = bounded_rsrc(own ? me.k + (int64_t)hkv * me.kv_sh * 2 : s16.k + (int64_t)hkv * s16.sh * 2,
+                                                   own ? me.kv_bytes : s16.bytes);
+    const __amdgpu_buffer_rsrc_t rv = bounded_rsrc(own ? me.v + (int64_t)hkv * me.kv_sh * 2 : s16.v + (int64_t)hkv * s16.sh * 2,
+                                                   own ? me.kv_bytes : s16.bytes);
+    const __amdgpu_buffer_rsrc_t rk8 = bounded_rsrc(a8.k8 + (int64_t)hkv * a8.sh8, (uint32_t)L8 * 128u);
+    const __amdgpu_buffer_rsrc_t rv8 = bounded_rsrc(a8.v8 + (int64_t)hkv * a8.sh8, (uint32_t)L8 * 128u);
+    const __amdgpu_buffer_rsrc_t rks = bounded_rsrc(a8.ks + (int64_t)hkv * a8.shs, (uint32_t)L8 * 4u);
+    const __amdgpu_buffer_rsrc_t rvs = bounded_rsrc(a8.vs + (int64_t)hkv * a8.shs, (uint32_t)L8 * 4u);
+
+    auto step_off = [&](int s) { return 128 * (s >> 1) + 32 * g + 16 * (s & 1); };
+    // Q fragments (B operand) of column group cg: packed row 16 cg + c, zero past the workgroup's rows
+    u32x4 qf[NCG][4];
+#pragma unroll
+    for (int cg = 0; cg < NCG; ++cg) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qf[cg][s] = u32x4{0u, 0u, 0u, 0u};
+        const int r = 16 * cg + c;
+        if (r < nrows) {
+            const int bi = own ? ob : r / G, gi = own ? r : r % G;
+            const char* qb = ga.br[0].q;
+            int64_t qsh = ga.br[0].q_sh;
+#pragma unroll
+            for (int b = 1; b < RTK_DECODE_GROUP_MAX; ++b)
+                if (bi == b) {
+                    qb = ga.br[b].q;
+                    qsh = ga.br[b].q_sh;
+                }
+            const char* qr = qb + (int64_t)(hkv * G + gi) * qsh * 2;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) qf[cg][s] = *(const u32x4*)(qr + step_off(s));
+        }
+    }
+
+    // one tile's operands, as in attention_decode_d128_body.inc
+    u32x4 kr[8], vr[8];
+    auto load_k = [&](int kb) {
+        if (kb < archp) {   // rows >= L8 of the last archive tile: zero codes, zero scales
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const uint32_t row = (uint32_t)(kb + 16 * b + c);
+#pragma unroll
+                for (int a = 0; a < 2; ++a) kr[2 * b + a] = load16(rk8, row * 128u + 16u * (4 * a + g));
+                kr[4][b] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rks, row * 4u, 0, 0);
+            }
+            return;
+        }
+        kb -= archp;   // rows past the segment's end read as zero
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) kr[4 * b + s] = load16(rk, (uint32_t)(kb + 16 * b + c) * row_bytes + (uint32_t)step_off(s));
+    };
+    auto load_v = [&](int kb) {
+        if (kb < archp) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint32_t row = (uint32_t)(kb + 8 * u + (lane >> 3));
+                vr[u] = load16(rv8, row * 128u + 16u * (lane & 7));
+                vr[4][u] = (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rvs, row * 4u, 0, 0);
+            }
+            return;
+        }
+        kb -= archp;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) vr[u] = load16(rv, (uint32_t)(kb + 4 * u + g) * row_bytes + 16u * c);
+    };
+
+    char* vt = lds + wave * WAVE_LDS;
+    const int v_rd = DEC_VPITCH * (4 * g + (c >> 2)) + 8 * (c & 3);
+
+    f32x4 oacc[NCG][8];
+    float m[NCG], l[NCG];
+#pragma unroll
+    for (int cg = 0; cg < NCG; ++cg) {
+#pragma unroll
+        for (int db = 0; db < 8; ++db) oacc[cg][db] = f32x4{0.f, 0.f, 0.f, 0.f};
+        m[cg] = -INFINITY;
+        l[cg] = 0.f;
+    }
+
+    auto process = [&](int kb, bool next) {
+        const bool arch = kb < archp;
+        u32x4 ka[8];
+        if (arch) {
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int a = 0; a < 2; ++a)
+                    fp8_dequant16<DT>(kr[2 * b + a], __uint_as_float(kr[4][b]), ka[4 * b + 2 * a], ka[4 * b + 2 * a + 1]);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                u32x4 x, y;
+                fp8_dequant16<DT>(vr[u], __uint_as_float(vr[4][u]), x, y);
+                char* w = vt + DEC_VPITCH * (8 * u + (lane >> 3)) + 32 * (lane & 7);
+                *(u32x4*)w = x;
+                *(u32x4*)(w + 16) = y;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) ka[e] = kr[e];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) *(u32x4*)(vt + DEC_VPITCH * (4 * u + g) + 16 * c) = vr[u];
+        }
+        if (next) load_v(kb + DEC_STEP);
+        wave_lds_sync();
+        // logits of column group cg: s0[e] = key 4 g + e, s1[e] = key 16 + 4 g + e of the tile
+        f32x4 s0[NCG], s1[NCG];
+#pragma unroll
+        for (int cg = 0; cg < NCG; ++cg) {
+            s0[cg] = f32x4{0.f, 0.f, 0.f, 0.f};
+            s1[cg] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                s0[cg] = mma32<DT>(ka[s], qf[cg][s], s0[cg]);
+                s1[cg] = mma32<DT>(ka[4 + s], qf[cg][s], s1[cg]);
+            }
+        }
+        if (next) load_k(kb + DEC_STEP);
+        const int lim = (arch ? L8 - 1 : vis16) - kb;   // the last key of the tile that exists; every row sees it
+        u32x4 pf[NCG];
+#pragma unroll
+        for (int cg = 0; cg < NCG; ++cg) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (4 * g + e > lim) s0[cg][e] = -INFINITY;
+                if (16 + 4 * g + e > lim) s1[cg][e] = -INFINITY;
+            }
+            float mx = fmaxf(fmaxf(fmaxf(s0[cg][0], s1[cg][0]), fmaxf(s0[cg][1], s1[cg][1])),
+                             fmaxf(fmaxf(s0[cg][2], s1[cg][2]), fmaxf(s0[cg][3], s1[cg][3])));
+            mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
+            mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
+            const float mnew = fmaxf(m[cg], mx * c2);
+            const float alpha = __builtin_amdgcn_exp2f(m[cg] - safe_max(mnew));
+#pragma unroll
+            for (int db = 0; db < 8; ++db) oacc[cg][db] *= alpha;
+            l[cg] *= alpha;
+            m[cg] = mnew;
+            const float nm = -safe_max(mnew);
+            float ls = 0.f;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                s0[cg][e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[cg][e], c2, nm));
+                s1[cg][e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[cg][e], c2, nm));
+                ls += s0[cg][e] + s1[cg][e];
+            }
+            l[cg] += ls;
+            pf[cg] = u32x4{Hh::pack2(s0[cg][0], s0[cg][1]), Hh::pack2(s0[cg][2], s0[cg][3]), Hh::pack2(s1[cg][0], s1[cg][1]),
+                           Hh::pack2(s1[cg][2], s1[cg][3])};
+        }
+#pragma unroll
+        for (int db = 0; db < 8; ++db) {   // one transposed read of the V image feeds every column group
+            u32x2 h2[2];
+#pragma unroll
+            for (int jh = 0; jh < 2; ++jh) {
+                const i16x4 t4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                    (__attribute__((address_space(3))) i16x4*)(vt + v_rd + DEC_VPITCH * 16 * jh + 32 * db));
+                h2[jh] = __builtin_bit_cast(u32x2, t4);
+            }
+            const u32x4 vf = {h2[0][0], h2[0][1], h2[1][0], h2[1][1]};
+#pragma unroll
+            for (int cg = 0; cg < NCG; ++cg) oacc[cg][db] = mma32<DT>(vf, pf[cg], oacc[cg][db]);
+        }
+        wave_lds_sync();   // the reads above before the next tile's writes
+    };
+
+    // this wave's tiles: u = wave, wave + 4, ... of the range
+    const int kb0 = k_lo + DEC_T * wave;
+    if (kb0 < k_hi) {
+        load_k(kb0);
+        load_v(kb0);
+    }
+    for (int kb = kb0; kb < k_hi; kb += DEC_STEP) process(kb, kb + DEC_STEP < k_hi);
+
+    // fold the four waves in wave order; the workgroup leaves one partial per packed row
+    {
+        float* ow = (float*)vt;
+#pragma unroll
+        for (int cg = 0; cg < NCG; ++cg) {
+            float lc = l[cg];
+            lc += __shfl_xor(lc, 16, WAVE);
+            lc += __shfl_xor(lc, 32, WAVE);
+#pragma unroll
+            for (int db = 0; db < 8; ++db) *(f32x4*)(ow + (16 * cg + c) * DEC_OPITCH + 16 * db + 4 * g) = oacc[cg][db];
+            if (g == 0) {
+                ml_s[wave][16 * cg + c][0] = m[cg];
+                ml_s[wave][16 * cg + c][1] = lc;
+            }
+        }
+    }
+    __syncthreads();
+    const int ch = tid & 15;   // channels 8 ch .. 8 ch + 7
+    const size_t split = own ? (size_t)(ga.ns_sh + oj) : (size_t)blockIdx.x;
+#pragma unroll
+    for (int cg = 0; cg < NCG; ++cg) {
+        const int row = 16 * cg + (tid >> 4);   // packed row
+        if (row >= nrows) continue;
+        float mg = -INFINITY;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) mg = fmaxf(mg, ml_s[w][row][0]);
+        f32x4 n0 = {0.f, 0.f, 0.f, 0.f}, n1 = {0.f, 0.f, 0.f, 0.f};
+        float den = 0.f;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float mw = ml_s[w][row][0];
+            if (mw == -INFINITY) continue;   // the wave had no tile
+            const float wt = __builtin_amdgcn_exp2f(mw - mg);
+            const float* ow = (const float*)(lds + w * WAVE_LDS) + row * DEC_OPITCH + 8 * ch;
+            const f32x4 a = *(const f32x4*)ow, b = *(const f32x4*)(ow + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                n0[e] = __builtin_fmaf(wt, a[e], n0[e]);
+                n1[e] = __builtin_fmaf(wt, b[e], n1[e]);
+            }
+            den = __builtin_fmaf(wt, ml_s[w][row][1], den);
+        }
+        const int bi = own ? ob : row / G, gi = own ? row : row % G;
+        const size_t prow = (split * ga.B + bi) * ga.Hq + (size_t)(hkv * G + gi);
+        float* pa = part_acc + prow * 128 + 8 * ch;
+        *(f32x4*)pa = n0;
+        *(f32x4*)(pa + 4) = n1;
+        if (ch == 0) *(float2*)(part_ml + 2 * prow) = make_float2(mg, den);
+    }
+}
+
+// retake_hip.h states this rule: the shared split from (Hkv, L8, Ls) alone, the own split from a branch's Lk alone
+struct GroupPlan {
+    int ns_sh, kps_sh, max_own;
+    size_t ws_bytes;
+};
+GroupPlan group_plan(const int* own_rows, int B, int Hq, int Hkv, int L8, int Ls) {
+    GroupPlan gp{0, DEC_STEP, 1, 0};
+    const long long keys = shared_keys(0, L8, Ls, DEC_T);
+    if (keys > 0) {
+        const DecodePlan pl = decode_plan(Hq, Hkv, 1, keys);
+        gp.ns_sh = pl.nsplit;
+        gp.kps_sh = pl.keys_per_split;
+    }
+    for (int b = 0; b < B; ++b) gp.max_own = std::max(gp.max_own, (own_rows[b] + GRP_OWN_KEYS - 1) / GRP_OWN_KEYS);
+    gp.ws_bytes = (size_t)(gp.ns_sh + gp.max_own) * B * Hq * (128 + 2) * sizeof(float);
+    return gp;
+}
+
+// what the group kernel takes: dtype, head_dim, the number of branches and of packed rows
+int group_check_envelope(const char* who, int n_branches, int Hq, int Hkv, int D, int dtype) {
+    if (dtype != RTK_BF16 && dtype != RTK_F16) {
+        set_error("%s: unsupported dtype code %d (the group kernel takes RTK_BF16 or RTK_F16)", who, dtype);
+        return RTK_EUNSUPPORTED;
+    }
+    if (D != 128) {
+        set_error("%s: unsupported head_dim %d (the group kernel takes 128)", who, D);
+        return RTK_EUNSUPPORTED;
+    }
+    if (n_branches > RTK_DECODE_GROUP_MAX) {
+        set_error("%s: unsupported group of %d branches (at most %d)", who, n_branches, RTK_DECODE_GROUP_MAX);
+        return RTK_EUNSUPPORTED;
+    }
+    if ((long long)n_branches * (Hq / Hkv) > 2 * DEC_R) {
+        set_error("%s: unsupported shape: n_branches * (Hq / Hkv) = %d * %d packed rows (at most %d)", who, n_branches, Hq / Hkv,
+                  2 * DEC_R);
+        return RTK_EUNSUPPORTED;
+    }
+    return RTK_OK;
+}
+
+template <int DT>
+int group_launch(const GroupPlan& gp, const GroupArgs& ga, const Archive8& a8, const Shared16& s16, void* out, int Hkv, float c2,
+                 void* ws, hipStream_t st) {
+    constexpr int D = 128;
+    const int nsplit = gp.ns_sh + gp.max_own, heads = ga.B * ga.Hq;
+    float* part_acc = (float*)ws;
+    float* part_ml = part_acc + (size_t)nsplit * heads * D;
+    const dim3 grid((unsigned)(gp.ns_sh + ga.B * gp.max_own), (unsigned)Hkv);
+    if (ga.B * ga.G > DEC_R)
+        hipLaunchKernelGGL((attn_decode_group_d128_kernel<DT, 2>), grid, dim3(256), 0, st, ga, a8, s16, part_acc, part_ml, c2);
+    else
+        hipLaunchKernelGGL((attn_decode_group_d128_kernel<DT, 1>), grid, dim3(256), 0, st, ga, a8, s16, part_acc, part_ml, c2);
+    RTK_LAUNCH_CHECK("attn_decode_group_d128_kernel");
+    const size_t total = (size_t)heads * D;
+    hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc, part_ml,
+                       (char*)out, heads, 1, D, nsplit);
+    RTK_LAUNCH_CHECK("attn_combine_kernel");
+    return RTK_OK;
+}
+
 }  // namespace
 }  // namespace rtk
 
@@ -272,4 +614,68 @@ extern "C" int rtk_attention_decode_shared(const void* q, int64_t q_stride_h, in
                                               Lq, Lk, q_offset, c2, workspace, (hipStream_t)stream);
     return decode_launch_shared<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, s16, out, Hq, Hkv, Lq,
                                          Lk, q_offset, c2, workspace, (hipStream_t)stream);
+}
+
+extern "C" size_t rtk_attention_decode_group_workspace_bytes(const int* own_rows, int n_branches, int Hq, int Hkv, int L8,
+                                                             int Ls, int D, int dtype) {
+    const char* who = "rtk_attention_decode_group_workspace_bytes";
+    if (!own_rows || n_branches < 1) {
+        set_error("%s: NULL own_rows or n_branches %d < 1", who, n_branches);
+        return 0;
+    }
+    if (Hq < 1 || Hkv < 1 || Hq % Hkv != 0 || group_check_envelope(who, n_branches, Hq, Hkv, D, dtype) != RTK_OK) return 0;
+    for (int b = 0; b < n_branches; ++b)
+        if (shared_check_shape(who, Hq, Hkv, 1, own_rows[b], L8, Ls, D, dtype, DEC_T) != RTK_OK) return 0;
+    return group_plan(own_rows, n_branches, Hq, Hkv, L8, Ls).ws_bytes;
+}
+
+extern "C" int rtk_attention_decode_group(const rtk_decode_branch* branches, int n_branches, const void* ks, const void* vs,
+                                          int Ls, int64_t s_stride_h, int64_t s_stride_l, const void* k8, const void* v8,
+                                          const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                          int64_t scale_stride_h, void* out, int Hq, int Hkv, int D, int dtype, float scale,
+                                          void* workspace, size_t workspace_bytes, rtk_stream_t stream) {
+    const char* who = "rtk_attention_decode_group";
+    RTK_CHECK_ARG(branches && out, "%s: NULL branches / out pointer", who);
+    RTK_CHECK_ARG(n_branches >= 1, "%s: n_branches %d < 1", who, n_branches);
+    RTK_CHECK_ARG(Hq >= 1 && Hkv >= 1, "%s: Hq and Hkv must be positive", who);
+    RTK_CHECK_ARG(Hq % Hkv == 0, "%s: Hq %d is not a multiple of Hkv %d", who, Hq, Hkv);
+    int rc = group_check_envelope(who, n_branches, Hq, Hkv, D, dtype);
+    if (rc != RTK_OK) return rc;
+    int own_rows[RTK_DECODE_GROUP_MAX];
+    for (int b = 0; b < n_branches; ++b) {
+        const rtk_decode_branch& br = branches[b];
+        RTK_CHECK_ARG(br.q && br.k && br.v, "%s: NULL q / k / v pointer of branch %d", who, b);
+        RTK_CHECK_ARG(br.Lk >= 1, "%s: branch %d has Lk %d (its own rows include the new token's: at least 1)", who, b, br.Lk);
+        rc = shared_check_shape(who, Hq, Hkv, 1, br.Lk, L8, Ls, D, dtype, DEC_T);
+        if (rc != RTK_OK) return rc;
+        own_rows[b] = br.Lk;
+    }
+    Shared16 s16{};
+    if (Ls > 0) {
+        rc = shared_check_operands(who, ks, vs, Ls, s_stride_h, s_stride_l, D, DEC_T);
+        if (rc != RTK_OK) return rc;
+        s16 = Shared16{(const char*)ks, (const char*)vs, s_stride_h, (uint32_t)(s_stride_l * 2),
+                       (uint32_t)(((size_t)(Ls - 1) * s_stride_l + D) * 2), Ls};
+    }
+    Archive8 a8{};
+    if (L8 > 0) {
+        RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
+        a8 = Archive8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
+    }
+    GroupArgs ga{};
+    for (int b = 0; b < n_branches; ++b) {
+        const rtk_decode_branch& br = branches[b];
+        rc = attn_check_operands(who, br.q, br.q_stride_h, D, br.k, br.v, br.kv_stride_h, br.kv_stride_l, a8.k8, a8.v8, a8.ks,
+                                 a8.vs, a8.sh8, a8.shs, out, 1, br.Lk, br.Lk - 1, D, dtype, scale, 0, DEC_T);
+        if (rc != RTK_OK) return rc;
+        ga.br[b] = GroupBranch{(const char*)br.q, (const char*)br.k, (const char*)br.v, br.q_stride_h, br.kv_stride_h,
+                               (uint32_t)(br.kv_stride_l * 2), (uint32_t)(((size_t)(br.Lk - 1) * br.kv_stride_l + D) * 2), br.Lk, 0};
+    }
+    const GroupPlan gp = group_plan(own_rows, n_branches, Hq, Hkv, L8, Ls);
+    rc = attn_check_workspace(who, "rtk_attention_decode_group_workspace_bytes", gp.ws_bytes, workspace, workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    ga.B = n_branches, ga.G = Hq / Hkv, ga.Hq = Hq, ga.ns_sh = gp.ns_sh, ga.kps_sh = gp.kps_sh, ga.max_own = gp.max_own;
+    const float c2 = scale * 1.44269504088896340736f;
+    if (dtype == RTK_BF16) return group_launch<RTK_BF16>(gp, ga, a8, s16, out, Hkv, c2, workspace, (hipStream_t)stream);
+    return group_launch<RTK_F16>(gp, ga, a8, s16, out, Hkv, c2, workspace, (hipStream_t)stream);
 }

@@ -101,6 +101,15 @@ class PivotKVBatch(C.Structure):
                 ("compact_sync_ints", _u64)]
 
 
+class DecodeBranch(C.Structure):
+    """rtk_decode_branch (include/retake_hip.h)."""
+    _fields_ = [("q", _vp), ("q_stride_h", _i64), ("k", _vp), ("v", _vp), ("kv_stride_h", _i64), ("kv_stride_l", _i64),
+                ("Lk", _i32)]
+
+
+DECODE_GROUP_MAX = 8   # RTK_DECODE_GROUP_MAX
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -176,6 +185,9 @@ _SIGNATURES = {
     "rtk_attention_decode_workspace_bytes_shared": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rtk_attention_decode_shared": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp,
                                           _vp, _i, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "rtk_attention_decode_group_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_group": (C.c_int, [C.POINTER(DecodeBranch), _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64,
+                                         _i64, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),
     "rtk_p2p_free": (C.c_int, [_vp]),
     "rtk_p2p_export": (C.c_int, [_vp, _vp, C.POINTER(_sz)]),

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from . import _prefill
+from .branch_group import BranchGroup, group_attention_forward
 from .longvideo_cache import apply_rotary_pos_emb, build_kvcache, native_attention
 from .qwen2_vl import _compress_memory_bank, _visual_compression_settings
 
@@ -51,6 +52,12 @@ def retake_Qwen2Attention_init(self, config, layer_idx: Optional[int] = None):
 def retake_Qwen2Attention_forward(self, hidden_states, position_embeddings, attention_mask, past_key_value=None,
                                   cache_position=None, **kwargs):
     """Qwen2 attention with PivotKV hooks (reference: llava_onevision.py:59-141)."""
+    if isinstance(past_key_value, BranchGroup):
+        # (build) B forks of one cache decoding a token each: the group's one launch in place of prologue + attention
+        # (branch_group.py); the ids the caller handed over stay as they are, as below
+        out = group_attention_forward(self, hidden_states, kwargs.get("position_ids"), past_key_value, None, scaling=self.scaling,
+                                      shift_ids_in_place=False, output_attentions=kwargs.get("output_attentions", False))
+        return out, None
     from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS  # third-party
     from transformers.models.qwen2.modeling_qwen2 import eager_attention_forward  # third-party
 

@@ -59,18 +59,8 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
         return None
     code = nv.dtype_code(query_states)
     scale = float(D) ** -0.5 if scaling is None else float(scaling)
-    L8 = 0
-    if archive is not None:
-        k8, v8, ks8, vs8 = archive
-        nv.require_device(k8, v8, ks8, vs8)
-        if k8.dtype != torch.uint8 or v8.dtype != torch.uint8 or ks8.dtype != torch.float32 or vs8.dtype != torch.float32:
-            raise ValueError("archive = (codes uint8, codes uint8, scales float32, scales float32)")
-        if k8.dim() != 4 or k8.shape[:2] != (1, Hkv) or k8.shape[3] != D or v8.shape != k8.shape or v8.stride() != k8.stride() \
-                or ks8.shape != k8.shape[:3] or vs8.shape != ks8.shape or vs8.stride() != ks8.stride():
-            raise ValueError("archive codes must be [1, Hkv, L8, D] and scales [1, Hkv, L8], K and V laid out alike")
-        if k8.stride(3) != 1 or k8.stride(2) != D or ks8.stride(2) != 1:
-            raise ValueError("archive rows must be dense (D codes per row, one scale per row)")
-        L8 = k8.shape[2]
+    a8 = _check_archive(archive, Hkv, D) if archive is not None else (None, None, None, None, 0, 0, 0)
+    L8 = a8[4]
     Ls = 0
     if shared is not None:
         ks, vs = shared
@@ -99,8 +89,6 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
 
     qkv = (nv.ptr(query_states), query_states.stride(1), query_states.stride(2), nv.ptr(key_states), nv.ptr(value_states),
            key_states.stride(1), key_states.stride(2))
-    a8 = (nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), L8, k8.stride(1), ks8.stride(1)) if archive is not None \
-        else (None, None, None, None, 0, 0, 0)
     if shared is not None:    # (no shared rows included: the library then runs the two-segment call itself)
         qkv += (nv.ptr(ks), nv.ptr(vs), Ls, ks.stride(1), ks.stride(2)) + a8
         shape = (Hq, Hkv, Lq, Lk, L8, Ls, D, code)
@@ -125,6 +113,93 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
             route.append(tag)
         return out
     return None
+
+
+def _check_archive(archive, Hkv, D):
+    k8, v8, ks8, vs8 = archive
+    nv.require_device(k8, v8, ks8, vs8)
+    if k8.dtype != torch.uint8 or v8.dtype != torch.uint8 or ks8.dtype != torch.float32 or vs8.dtype != torch.float32:
+        raise ValueError("archive = (codes uint8, codes uint8, scales float32, scales float32)")
+    if k8.dim() != 4 or k8.shape[:2] != (1, Hkv) or k8.shape[3] != D or v8.shape != k8.shape or v8.stride() != k8.stride() \
+            or ks8.shape != k8.shape[:3] or vs8.shape != ks8.shape or vs8.stride() != ks8.stride():
+        raise ValueError("archive codes must be [1, Hkv, L8, D] and scales [1, Hkv, L8], K and V laid out alike")
+    if k8.stride(3) != 1 or k8.stride(2) != D or ks8.stride(2) != 1:
+        raise ValueError("archive rows must be dense (D codes per row, one scale per row)")
+    return (nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), k8.shape[2], k8.stride(1), ks8.stride(1))
+
+
+def group_decode_attention(queries, owns, shared, archive, scaling=None, workspace=None):
+    """ONE new token of each of B sequences that share [archive | shared] and differ in their own rows, in one HIP launch
+    that reads every archive and shared row once (rtk_attention_decode_group): the decode step of B forks of one
+    PivotKVCache (retake/branch_group.py).
+
+    queries: B tensors [1, Hq, 1, D]; owns: B pairs (k, v) of views [1, Hkv, Lk_b, D] - branch b's OWN rows, the new
+    token's included, any head / row strides, contiguous head_dim; shared: (ks, vs) [1, Hkv, Ls, D] or None; archive:
+    (k8, v8, k_scale, v_scale) as chunk_attention takes it, or None.  Branch b's query sees every archive row, every shared
+    row and every one of its own rows.  Returns [B, 1, Hq, D]; row b's bits depend neither on the other branches nor on
+    b's place among them.  None - nothing was touched - when the library declines the call (RTK_EUNSUPPORTED: more than 8
+    branches or B * Hq / Hkv > 32 packed rows, float32, head_dim other than 128, a layout it does not take).
+
+    workspace: optional dict the partials are kept in between calls."""
+    B = len(queries)
+    if B < 1 or len(owns) != B:
+        raise ValueError("group_decode_attention takes one query and one (k, v) pair per branch, at least one branch")
+    q0, k0 = queries[0], owns[0][0]
+    if q0.dim() != 4 or k0.dim() != 4:
+        raise ValueError("group_decode_attention takes [1, Hq, 1, D] queries and [1, Hkv, Lk, D] keys / values")
+    _, Hq, _, D = q0.shape
+    Hkv = k0.shape[1]
+    for q, (k, v) in zip(queries, owns):
+        nv.require_device(q, k, v)
+        if q.shape != (1, Hq, 1, D) or k.dim() != 4 or k.shape[:2] != (1, Hkv) or k.shape[3] != D:
+            raise ValueError("group_decode_attention takes [1, Hq, 1, D] queries and [1, Hkv, Lk, D] keys / values")
+        if k.shape != v.shape or k.stride() != v.stride():
+            raise ValueError("a branch's keys and values must share shape and strides")
+        if k.shape[2] < 1:
+            raise ValueError("every branch needs own rows: at least the new token's")
+        if not (q.dtype == k.dtype == v.dtype == q0.dtype) or q.device != q0.device:
+            raise ValueError("queries, keys and values must share a dtype and a device")
+    if q0.dtype not in (torch.bfloat16, torch.float16) or any(q.stride(3) != 1 or k.stride(3) != 1 for q, (k, _) in zip(queries, owns)):
+        return None
+    code = nv.dtype_code(q0)
+    scale = float(D) ** -0.5 if scaling is None else float(scaling)
+    a8 = _check_archive(archive, Hkv, D) if archive is not None else (None, None, None, None, 0, 0, 0)
+    s16 = (None, None, 0, 0, 0)
+    if shared is not None:
+        ks, vs = shared
+        nv.require_device(ks, vs)
+        if ks.dim() != 4 or ks.shape[:2] != (1, Hkv) or ks.shape[3] != D or vs.shape != ks.shape or vs.stride() != ks.stride():
+            raise ValueError("shared keys / values must be [1, Hkv, Ls, D], laid out alike")
+        if ks.dtype != q0.dtype or vs.dtype != q0.dtype:
+            raise ValueError("shared keys / values must have the dtype of the queries")
+        if ks.stride(3) != 1:
+            return None
+        s16 = (nv.ptr(ks), nv.ptr(vs), ks.shape[2], ks.stride(1), ks.stride(2))
+    if B > nv.DECODE_GROUP_MAX:   # (the library says so itself, but its array holds no more)
+        return None
+    brs = (nv.DecodeBranch * B)()
+    rows = (nv.C.c_int * B)()
+    for b, (q, (k, v)) in enumerate(zip(queries, owns)):
+        br = brs[b]
+        br.q, br.q_stride_h = q.data_ptr(), q.stride(1)
+        br.k, br.v, br.kv_stride_h, br.kv_stride_l, br.Lk = k.data_ptr(), v.data_ptr(), k.stride(1), k.stride(2), k.shape[2]
+        rows[b] = k.shape[2]
+    need = nv.lib.rtk_attention_decode_group_workspace_bytes(rows, B, Hq, Hkv, a8[4], s16[2], D, code)
+    stream = nv.raw_stream(q0.device.index)
+    ws = None
+    if need:
+        key = ("attention_group_ws", q0.device.index, stream)
+        ws = None if workspace is None else workspace.get(key)
+        if ws is None or ws.numel() < need:
+            ws = torch.empty(need, dtype=torch.uint8, device=q0.device)
+            if workspace is not None:
+                workspace[key] = ws
+    out = torch.empty((B, 1, Hq, D), dtype=q0.dtype, device=q0.device)
+    rc = nv.lib.rtk_attention_decode_group(brs, B, *s16, *a8, nv.ptr(out), Hq, Hkv, D, code, scale, nv.ptr(ws), need, stream)
+    if rc == nv.RTK_EUNSUPPORTED:
+        return None
+    nv.check(rc, "rtk_attention_decode_group")
+    return out
 
 
 def fp8_quantize_rows(x: torch.Tensor):

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _prefill
+from .branch_group import BranchGroup, group_attention_forward
 from .longvideo_cache import apply_multimodal_rotary_pos_emb, build_kvcache, native_attention, repeat_kv
 from .visual_compression import (memory_bank_compress_keyframe, memory_bank_compress_MALLM,
                                  memory_bank_compress_MALLM_hard, memory_bank_compress_MALLM_hard_to)
@@ -84,10 +85,20 @@ def _qkv_and_cache_update(self, hidden_states, position_ids, past_key_value, cac
     return query_states, key_states, value_states
 
 
+def _group_decode(self, hidden_states, position_ids, group, output_attentions=False):
+    """(build) `past_key_value` is a BranchGroup - B forks of one cache decoding a token each: the group's one launch in
+    place of prologue + attention (branch_group.py)."""
+    out = group_attention_forward(self, hidden_states, position_ids, group, self.rope_scaling["mrope_section"],
+                                  output_attentions=output_attentions)
+    return out, None, group
+
+
 def retake_Qwen2VLAttention_forward(self, hidden_states, attention_mask=None, position_ids=None, past_key_value=None,
                                     output_attentions=False, use_cache=False, cache_position=None,
                                     position_embeddings=None):
     """Eager attention (reference: qwen2_vl.py:42-122)."""
+    if isinstance(past_key_value, BranchGroup):
+        return _group_decode(self, hidden_states, position_ids, past_key_value, output_attentions)
     bsz, q_len, _ = hidden_states.size()
     query_states, key_states, value_states = _qkv_and_cache_update(self, hidden_states, position_ids, past_key_value,
                                                                    cache_position)
@@ -121,6 +132,8 @@ def retake_Qwen2VLSdpaAttention_forward(self, hidden_states, attention_mask=None
     if output_attentions:  # SDPA cannot return the weights: same fallback as the reference (:137-150)
         return retake_Qwen2VLAttention_forward(self, hidden_states, attention_mask, position_ids, past_key_value,
                                                output_attentions, use_cache, cache_position, position_embeddings)
+    if isinstance(past_key_value, BranchGroup):
+        return _group_decode(self, hidden_states, position_ids, past_key_value)
     bsz, q_len, _ = hidden_states.size()
     query_states, key_states, value_states = _qkv_and_cache_update(self, hidden_states, position_ids, past_key_value,
                                                                    cache_position)
@@ -147,6 +160,8 @@ def retake_Qwen2VLFlashAttention2_forward(self, hidden_states, attention_mask=No
                                           cache_position=None, position_embeddings=None):
     """FlashAttention-2 variant (reference: qwen2_vl.py:224-363): same prologue, HF's flash-attention
     helper for the kernel (third-party; present when flash-attn for ROCm is installed)."""
+    if isinstance(past_key_value, BranchGroup):
+        return _group_decode(self, hidden_states, position_ids, past_key_value, output_attentions)
     from transformers.modeling_flash_attention_utils import _flash_attention_forward  # third-party
 
     def half_dtype():   # what fp32 states are cast to: autocast's dtype, else the pre-quantization dtype, else the weight dtype

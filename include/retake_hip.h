@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (63 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (64 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -49,6 +49,8 @@
  *                                       the keys are [archive | rows of another buffer | own rows] (PivotKVCache.fork)
  *   §M  "Group decode"                  rtk_attention_decode_group (+ _workspace_bytes): one token of each of several
  *                                       branches in one launch that reads the shared rows once (retake/branch_group.py)
+ *   §N  "Sliding window"                rtk_pivotkv_slide_batched: rows of many buffers moved down in place, one call - the
+ *                                       oldest video rows of every layer dropped (opt-in: video_window_rows)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -949,6 +951,39 @@ int rtk_attention_decode_group(const rtk_decode_branch* branches, int n_branches
                                const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
                                int64_t scale_stride_h, void* out, int Hq, int Hkv, int D, int dtype, float scale,
                                void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Sliding window (opt-in: longvideo_kwargs["video_window_rows"]; NOT in the reference, which processes a finished video).
+ * Every attention route reads a layer's rows as buf[:, :, :length], contiguous from the buffer's base, so dropping the OLDEST
+ * video rows while the text rows in front of them stay is an in-place move: every later row goes down by `drop` rows - K, V
+ * and the position ids of every layer, or the codes, scales and ids of the fp8 archive - in ONE call (one kernel launch per
+ * RTK_SLIDE_MAX_UNITS moving units).
+ *
+ * One unit = `streams` independent byte streams (the kv heads of a K / V / code / scale buffer, the id planes of a position
+ * buffer).  Per unit and stream s it is
+ *     memmove(base + s*stream_stride + first*row_bytes, base + s*stream_stride + (first + drop)*row_bytes, rows*row_bytes):
+ * no byte outside the destination range is written; the rows above it keep their old contents.  Source and destination
+ * usually overlap almost entirely (drop ~ one chunk's keep, rows ~ the whole window).  The kernel needs no order between
+ * workgroups - no flags, no counters, no cooperative launch: the byte at offset x only ever depends on x + drop_bytes,
+ * x + 2 drop_bytes, ..., so a workgroup owns one stream, or one slice of the residues mod drop_bytes of one stream, and walks
+ * it from low addresses to high; every byte is read by the workgroup that overwrites it (pivotkv_slide.hip).
+ * 16-byte accesses where base, stride, drop and length allow, else 4-byte ones; the result is the same.
+ * A unit with drop == 0 or rows == 0 is skipped; n_units == 0 (or nothing but such units) launches nothing.  More than
+ * RTK_SLIDE_MAX_UNITS moving units take more launches.  `units` is a HOST array.
+ * Errors, all before any launch: RTK_EINVAL for NULL pointers, negative first / drop / rows, streams <= 0, a row_bytes that
+ * is not a positive multiple of 4, a base or stream_stride that is not 4-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rtk_slide_unit {
+    void*   base;           /* first byte of stream 0 */
+    int64_t stream_stride;  /* bytes between streams (kv heads, id planes) */
+    int32_t streams;        /* Hkv for K / V / codes / scales, P for position ids */
+    int32_t row_bytes;      /* D*esize, D (e4m3 codes), 4 (scales), 8 (ids); a multiple of 4 */
+    int64_t first;          /* destination row of the first moved row */
+    int64_t drop;           /* source row = destination row + drop */
+    int64_t rows;           /* rows moved */
+} rtk_slide_unit;
+#define RTK_SLIDE_MAX_UNITS 96   /* moving units per launch (the array travels as a kernel argument) */
+int rtk_pivotkv_slide_batched(const rtk_slide_unit* units, int n_units, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

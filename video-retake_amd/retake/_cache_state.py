@@ -24,7 +24,7 @@ class _LayerStore:
     rtk_layer_state block (`c`) the library reads and advances itself (rtk_pivotkv_update / rtk_pivotkv_flush)."""
 
     __slots__ = ("c", "cref", "_k", "_v", "_pos", "pending_event", "pos_ndim", "k8", "v8", "ks8", "vs8", "len8", "archive_at",
-                 "sk", "sv", "base")
+                 "sk", "sv", "base", "pinned")
 
     def __init__(self):
         self.c = nv.LayerState()
@@ -41,6 +41,10 @@ class _LayerStore:
         # in the sequence (k / v / length then describe the own rows alone; the ids in `pos` cover the whole sequence)
         self.sk = self.sv = None
         self.base = 0
+        # video_window_rows: the 16-bit rows the layer held before its first compressed chunk arrived (the system prompt, the
+        # attention sink) - a slide never drops or moves them; -1 until that chunk (with fp8 rows the archive IS the video
+        # region and `archive_at` is this number)
+        self.pinned = -1
 
     def _sync(self):
         k, v, c = self._k, self._v, self.c

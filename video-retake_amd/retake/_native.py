@@ -110,6 +110,15 @@ class DecodeBranch(C.Structure):
 DECODE_GROUP_MAX = 8   # RTK_DECODE_GROUP_MAX
 
 
+SLIDE_MAX_UNITS = 96   # RTK_SLIDE_MAX_UNITS: moving units per kernel launch of rtk_pivotkv_slide_batched
+
+
+class SlideUnit(C.Structure):
+    """rtk_slide_unit (include/retake_hip.h)."""
+    _fields_ = [("base", _vp), ("stream_stride", _i64), ("streams", _i32), ("row_bytes", _i32), ("first", _i64),
+                ("drop", _i64), ("rows", _i64)]
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -188,6 +197,7 @@ _SIGNATURES = {
     "rtk_attention_decode_group_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i, _i]),
     "rtk_attention_decode_group": (C.c_int, [C.POINTER(DecodeBranch), _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64,
                                          _i64, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "rtk_pivotkv_slide_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),
     "rtk_p2p_free": (C.c_int, [_vp]),
     "rtk_p2p_export": (C.c_int, [_vp, _vp, C.POINTER(_sz)]),

@@ -211,6 +211,18 @@ class PivotKVCache(DynamicCache):
         # the GQA-packed few-row kernel first (chunk_attention(packed_gqa=True)); None (default): exactly as without it
         self.decode_attention = None
         self.decode_attention_calls = 0   # ... of which took the packed kernel
+        # MI355X build option, two top-level keys of longvideo_kwargs (build_kvcache reads them; NOT in the reference, which
+        # processes a finished video): video_window_rows = W bounds the compressed video rows a layer holds, for streams that
+        # do not end.  A layer's VIDEO REGION is everything behind its pinned rows - the rows it held before its first
+        # compressed chunk arrived (the system prompt: the attention sink), see _LayerStore.pinned; with fp8 rows it is the
+        # archive.  When `after_forward` finds more than W + video_window_slack rows there it drops the oldest region - W of
+        # them: every later row of K, V and the ids (codes, scales and ids of the archive) moves down in place, all layers in
+        # one rtk_pivotkv_slide_batched call (`_slide_window`).  Slides happen ONLY in `after_forward`: a caller that never
+        # calls it gets no window.  None (default): off, nothing changes.  The slack trades memory for fewer slides: a
+        # slide moves the whole window whatever it drops.
+        self.video_window_rows = None
+        self.video_window_slack = 0
+        self.window_dropped: List[int] = []   # per layer: rows the window has dropped so far (also counted as evicted)
         self._attn_ws: Dict[Any, torch.Tensor] = {}
 
     def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None, layer_idx=None):
@@ -379,7 +391,8 @@ class PivotKVCache(DynamicCache):
         need = st.len8 + more
         if st.k8 is not None and st.k8.shape[2] >= need:
             return
-        cap = max(need, 2 * (st.k8.shape[2] if st.k8 is not None else 0), self.reserve_archive_tokens or 1024)
+        cap = max(need, 2 * (st.k8.shape[2] if st.k8 is not None else 0), self.reserve_archive_tokens or 1024,
+                  self._window_room(st, 0, more))
         new = [torch.empty((1, Hkv, cap, D), dtype=torch.uint8, device=device) for _ in range(2)] + \
               [torch.empty((1, Hkv, cap), dtype=torch.float32, device=device) for _ in range(2)]
         if st.len8:
@@ -573,6 +586,12 @@ class PivotKVCache(DynamicCache):
         self._check_mark(mark)
         for st, m in zip(self._layers, mark.layers):
             st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at = m.length, m.pos_len, m.pos_ndim, m.len8, m.archive_at
+            # `pinned` is not in the mark and need not be: it is set once, to the layer's length at its first compressed
+            # chunk, and a slide - the only thing that moves rows - voids every earlier mark.  So a valid mark either lies at
+            # or below that length (taken before any video row existed: the next compressed chunk pins afresh) or above it
+            # (the pinned rows and the number are still what they were)
+            if st.pinned >= m.length:
+                st.pinned = -1
             if not m.has_kv and st._k is not None:    # a layer that was skipped at the mark owns nothing again
                 st.k = st.v = None
             if not m.has_pos and st._pos is not None:
@@ -686,6 +705,7 @@ class PivotKVCache(DynamicCache):
         if st.pending:
             self._flush()
         self._epoch += 1
+        st.pinned = -1   # (video_window_rows: a layer replaced wholesale pins what it holds at its next compressed chunk)
         if isinstance(value, list) and len(value) == 0:
             st.k = st.v = None
             st.length = 0
@@ -747,7 +767,9 @@ class PivotKVCache(DynamicCache):
         need = st.pos_len + more
         if st.pos is not None and st.pos.shape[1] >= need:
             return
-        cap = max(need, 2 * (st.pos.shape[1] if st.pos is not None else 0), 4096, self.reserve_tokens + self.reserve_archive_tokens)
+        first = st.archive_at if self.kv_cache_dtype is not None else st.pinned
+        cap = max(need, 2 * (st.pos.shape[1] if st.pos is not None else 0), 4096, self.reserve_tokens + self.reserve_archive_tokens,
+                  self._window_room(st, first if first >= 0 else st.pos_len, more))
         buf = torch.empty((P, cap), dtype=torch.int64, device=device)
         if st.pos is not None and st.pos_len:
             buf[:, :st.pos_len].copy_(st.pos[:, :st.pos_len])
@@ -760,10 +782,16 @@ class PivotKVCache(DynamicCache):
             self._prompt_len = int(n) if n is not None and int(n) > 0 else 0
 
     def after_forward(self, **kwargs):
+        """The reference's hook after every forward of a video chunk (:146-150): the deferred eviction of the chunk is
+        flushed, the sliding window (video_window_rows) - which acts here and nowhere else: a caller that never calls
+        after_forward gets no window - drops what exceeds it, and
+        `video_end` is taken."""
         self._flush()
         self._prompt_len = 0
         if self._compressed_in_forward:   # the work is flushed: a few tuples per chunk
             self._compressed_in_forward = False
+            if self.video_window_rows is not None:
+                self._slide_window()
             if not self.defer_rerotation:
                 self.last_compressed_mark = self._take_mark(True)
 
@@ -771,6 +799,76 @@ class PivotKVCache(DynamicCache):
         """Prompt rows of a chunk of L rows arriving now: the recorded prompt_length if 0 < Lp < L, else 0 (an ordinary chunk)."""
         n = self._prompt_len
         return n if 0 < n < L else 0
+
+    # ---- the sliding video window (video_window_rows; not in the reference) ---------------------
+    def _slide_window(self):
+        """Drop the oldest rows of every layer whose video region holds more than W + slack rows, down to W: K, V and the
+        ids of all such layers (the archive's codes, scales and ids with fp8 rows) move down in place in ONE
+        rtk_pivotkv_slide_batched call on the current stream (per device; a call is one kernel launch per 96 moving
+        tensors: 28 layers x (K, V, ids) is one, 28 x 5 archive tensors two).  Layers slide independently - each has its own
+        count, a skipped layer none.  length / len8 and pos_len shrink, num_evicted_tokens and window_dropped grow by it,
+        `_seen_tokens` is left alone; get_prev_temporal_idx still reads the last stored id.  Rows below every earlier mark
+        are rewritten, so the epoch moves: earlier marks raise in `rewind`, live branches are dead; the `video_end` that
+        `after_forward` takes next is valid.  No buffer is allocated or replaced."""
+        W, S = self.video_window_rows, self.video_window_slack
+        fp8 = self.kv_cache_dtype is not None
+        plan, by_device = [], {}
+        for l, st in enumerate(self._layers):
+            first = st.archive_at if fp8 else st.pinned
+            if st._k is None or first < 0:
+                continue
+            region = st.len8 if fp8 else st.c.length - first
+            if region <= W + S:
+                continue
+            d = region - W
+            ids = st._pos is not None and st.c.pos_len > 0
+            if st.c.cap == 0 or (ids and st.c.pos_len != st.c.length + st.len8):
+                raise ValueError(f"video_window_rows: layer {l} cannot slide - its buffers are not the cache's own dense blocks, "
+                                 f"or it keeps ids for {st.c.pos_len} of its {st.c.length + st.len8} rows")
+            units = by_device.setdefault(st._k.get_device(), [])
+            if fp8:    # the archive [0, len8): codes of D bytes a row, one fp32 scale a row
+                Hkv, cap8, D = st.k8.shape[1], st.k8.shape[2], st.k8.shape[3]
+                for t, row in ((st.k8, D), (st.v8, D), (st.ks8, 4), (st.vs8, 4)):
+                    units.append((t.data_ptr(), cap8 * row, Hkv, row, 0, d, W))
+            else:
+                k = st._k
+                row = k.shape[3] * k.element_size()
+                for t in (k, st._v):
+                    units.append((t.data_ptr(), k.shape[2] * row, k.shape[1], row, first, d, W))
+            if ids:    # in sequence order: the region's ids begin at `first`, those of later 16-bit rows follow them
+                units.append((st._pos.data_ptr(), st._pos.shape[1] * 8, st._pos.shape[0], 8, first, d,
+                              st.c.pos_len - first - d))
+            plan.append((l, st, d, ids))
+        if not plan:
+            return
+        for idx, units in by_device.items():
+            arr = (nv.SlideUnit * len(units))(*[nv.SlideUnit(*u) for u in units])
+            nv.check(_on_device(idx, nv.lib.rtk_pivotkv_slide_batched, arr, len(units), nv.raw_stream(idx)),
+                     "rtk_pivotkv_slide_batched")
+        dropped = self.window_dropped
+        dropped.extend([0] * (len(self._layers) - len(dropped)))
+        for l, st, d, ids in plan:
+            if fp8:
+                st.len8 -= d
+            else:
+                st.c.length -= d
+            if ids:
+                st.c.pos_len -= d
+            self.update_num_evicted_tokens(d, l)
+            dropped[l] += d
+        self._epoch += 1
+        for br in self._branches or ():   # (noted on the branches: this cache may be released before they look)
+            if br._fork_dead is None:
+                br._fork_dead = "epoch"
+
+    def _window_room(self, st: _LayerStore, first: int, more: int) -> int:
+        """video_window_rows: the rows at which a buffer stops growing - the pinned rows (`first`; not known yet: what the
+        layer holds), a full window with its slack and `more` (the in-flight chunk).  0 with the window off, and 0 while
+        `kvcache_compression` is off: text, question and decode rows grow a buffer as they always did (by doubling), so the
+        plateau holds only if the caller's `reserve_tokens` covers them on top of pinned + W + slack + one chunk."""
+        if self.video_window_rows is None or not self.kvcache_compression:
+            return 0
+        return max(first, 0) + self.video_window_rows + self.video_window_slack + more
 
     # ---- bookkeeping lists (reference :152-215) ------------------------------------------------
     def update_num_evicted_tokens(self, num_tokens: int, layer_idx: int):
@@ -897,7 +995,9 @@ class PivotKVCache(DynamicCache):
         if st.k is not None and st.k.shape[2] >= need and st.k.is_contiguous() and st.v.is_contiguous() \
                 and st.v.shape[2] == st.k.shape[2]:
             return st
-        cap = max(need, 2 * (st.k.shape[2] if st.k is not None else 0), 1024, self.reserve_tokens)
+        room = 0 if self.kv_cache_dtype is not None else \
+            self._window_room(st, st.pinned if st.pinned >= 0 else st.length, tokens)
+        cap = max(need, 2 * (st.k.shape[2] if st.k is not None else 0), 1024, self.reserve_tokens, room)
         shape = (1, like.shape[1], cap, like.shape[3])
         nk = torch.empty(shape, dtype=like.dtype, device=like.device)
         nvv = torch.empty(shape, dtype=like.dtype, device=like.device)
@@ -1527,6 +1627,8 @@ class PivotKVCache(DynamicCache):
             nv.check(rc, "rtk_pivotkv_update")
         if io.flags & nv.RTK_UPDATE_SHIFT_NEXT:
             self._preshifted = (weakref.ref(pos), _version_of(pos), layer_idx + 1, stream)
+        if st.pinned < 0:    # the layer's first compressed chunk: what it held before it is pinned (video_window_rows)
+            st.pinned = P0
         if not self._warned:
             self._warn_compression()
         if not pre:  # the reference's cache_kwargs protocol (:235, :241-243)
@@ -1838,6 +1940,8 @@ class PivotKVCache(DynamicCache):
         u.q, u.k, u.v, u.ids, u.mask = query_states, key_states, value_states, position_ids, mask
         b.x_like = value_states[:, :, :1]
         u.st = st = self.reserve(layer_idx, key_states.shape[2], key_states)
+        if st.pinned < 0:    # the layer's first compressed chunk: what it holds now is pinned (video_window_rows)
+            st.pinned = st.length
         tail = st.length * D * st.k.element_size()
         u.k_tail, u.v_tail = C.c_void_p(st.k.data_ptr() + tail), C.c_void_p(st.v.data_ptr() + tail)
         u.a_scale = float(getattr(rotary_emb_fn, "attention_scaling", 1.0)) if reforge else 1.0
@@ -2002,6 +2106,20 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
                                  "cannot read the fp8 rows")
             if cache.defer_rerotation:
                 raise ValueError("kv_cache_dtype='fp8_e4m3' does not serve defer_rerotation (the sharded prefill)")
+        W, S = config.longvideo_kwargs.get("video_window_rows", None), config.longvideo_kwargs.get("video_window_slack", 0)
+        keys = "video_window_rows / video_window_slack"
+        if not (W is None or (isinstance(W, int) and not isinstance(W, bool) and W > 0)) \
+                or not (isinstance(S, int) and not isinstance(S, bool) and S >= 0):
+            raise ValueError(f"{keys}: video_window_rows must be an int > 0 (or None: no window) and video_window_slack "
+                             f"an int >= 0, got {W!r} and {S!r}")
+        if W is not None:
+            if cache.defer_rerotation:
+                raise ValueError(f"{keys} do not serve defer_rerotation (the sharded prefill): its block caches hold "
+                                 "un-rotated keys and provisional ids until `finalize`")
+            if cache.prompt_guided_scoring:
+                raise ValueError(f"{keys} do not serve prompt_guided_scoring: a prompt-guided cache belongs to one question, "
+                                 "a window to a stream that does not end")
+            cache.video_window_rows, cache.video_window_slack = W, S
         if cache.prompt_guided_scoring:   # what the mode does not serve: refused here, never a silent fallback
             for key, value, served in (("score_rounding", cache.score_rounding, "fp32"),
                                        ("kv_cache_dtype", cache.kv_cache_dtype, None),

@@ -25,6 +25,11 @@
 // Few query rows — both kernels take a key range per blockIdx "split" and leave un-normalised (m, l, acc) partials in
 // the caller's workspace; attn_combine_kernel folds them split 0, 1, 2 ... in that fixed order (no atomics).  The
 // number of splits is a function of the shape alone.
+// rtk_attention_forward_fp8kv / _shared run the fast path's body (attention_d128_body.inc) over [e4m3 archive | 16-bit
+// rows] and [archive | another buffer's 16-bit rows | 16-bit rows]: attn_fwd_d128_fp8kv_kernel, attn_fwd_d128_shared_kernel.
+// Host side: each entry point keeps its own checks and its fall-through, then attn_forward (operands, plan, workspace,
+// dtype) -> attn_launch -> attn_launch_d128, the one launcher of the three d128 kernels; what the packed decode entry
+// points (attention_decode.hip) use as well - descriptors, combine launch, checks - is in attention_shared.cuh.
 #include "attention_shared.cuh"
 
 namespace rtk {
@@ -206,107 +211,62 @@ AttnPlan attn_plan(int Hq, int Lq, int Lk, int D, int dtype) {
     return p;
 }
 
-template <int DT>
-int attn_launch(const AttnPlan& pl, const void* q, int64_t q_sh, int64_t q_sl, const void* k, const void* v, int64_t kv_sh,
-                int64_t kv_sl, void* out, int Hq, int Hkv, int Lq, int Lk, int off, int D, float c2, void* ws, hipStream_t st) {
-    const int G = Hq / Hkv;
-    float* part_acc = (float*)ws;
-    float* part_ml = part_acc ? part_acc + (size_t)pl.nsplit * Hq * Lq * D : nullptr;
+// One launch of a d128 kernel variant: kern_split / kern_whole are its SPLIT = true / false instantiations, `tail` the
+// a8 / s16 it takes after the common parameters.
+template <class K, class... Tail>
+int attn_launch_d128(K kern_split, K kern_whole, const char* name, const AttnPlan& pl, const AttnArgs& a, const Partials& p,
+                     const Tail&... tail) {
+    const dim3 grid((unsigned)(a.Hq * ((a.Lq + AT_QB - 1) / AT_QB)), (unsigned)pl.nsplit);
+    hipLaunchKernelGGL(pl.nsplit > 1 ? kern_split : kern_whole, grid, dim3(256), 0, a.st, (const char*)a.q, a.q_sh,
+                       (uint32_t)(a.q_sl * 2), rows_extent(a.Lq, a.q_sl, 128, 2), (const char*)a.k, (const char*)a.v, a.kv_sh,
+                       (uint32_t)(a.kv_sl * 2), rows_extent(a.Lk, a.kv_sl, 128, 2), (char*)a.out, p.acc, p.ml, a.Hq, a.Hq / a.Hkv,
+                       a.Lq, a.Lk, a.off, base2_scale(a.scale), pl.keys_per_split, tail...);
+    RTK_LAUNCH_CHECK(name);
+    return RTK_OK;
+}
+
+// the kernel of the segments the call has ([archive | shared | own], a8 / s16 empty without), then the combine
+template <int DT> int attn_launch(const AttnPlan& pl, const AttnArgs& a, const Archive8& a8, const Shared16& s16) {
+    const Partials p = split_partials(pl.ws_bytes ? a.workspace : nullptr, pl.nsplit, a.Hq, a.Lq, a.D);
+    int rc = RTK_OK;
     if constexpr (DT != RTK_F32) {
         if (pl.fast) {
-            const size_t es = 2;
-            const uint32_t q_bytes = (uint32_t)(((size_t)(Lq - 1) * q_sl + D) * es);
-            const uint32_t kv_bytes = (uint32_t)(((size_t)(Lk - 1) * kv_sl + D) * es);
-            const dim3 grid((unsigned)(Hq * ((Lq + AT_QB - 1) / AT_QB)), (unsigned)pl.nsplit);
-            if (pl.nsplit > 1)
-                hipLaunchKernelGGL((attn_fwd_d128_kernel<DT, true>), grid, dim3(256), 0, st, (const char*)q, q_sh,
-                                   (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh,
-                                   (uint32_t)(kv_sl * es), kv_bytes, (char*)out, part_acc, part_ml, Hq, G, Lq, Lk, off, c2,
-                                   pl.keys_per_split);
+            if (s16.Ls > 0)
+                rc = attn_launch_d128(attn_fwd_d128_shared_kernel<DT, true>, attn_fwd_d128_shared_kernel<DT, false>,
+                                      "attn_fwd_d128_shared_kernel", pl, a, p, a8, s16);
+            else if (a8.L8 > 0)
+                rc = attn_launch_d128(attn_fwd_d128_fp8kv_kernel<DT, true>, attn_fwd_d128_fp8kv_kernel<DT, false>,
+                                      "attn_fwd_d128_fp8kv_kernel", pl, a, p, a8);
             else
-                hipLaunchKernelGGL((attn_fwd_d128_kernel<DT, false>), grid, dim3(256), 0, st, (const char*)q, q_sh,
-                                   (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh,
-                                   (uint32_t)(kv_sl * es), kv_bytes, (char*)out, part_acc, part_ml, Hq, G, Lq, Lk, off, c2,
-                                   pl.keys_per_split);
-            RTK_LAUNCH_CHECK("attn_fwd_d128_kernel");
+                rc = attn_launch_d128(attn_fwd_d128_kernel<DT, true>, attn_fwd_d128_kernel<DT, false>, "attn_fwd_d128_kernel", pl, a, p);
         }
     }
     if (!pl.fast) {
-        const dim3 grid((unsigned)((Lq + 3) / 4), (unsigned)Hq, (unsigned)pl.nsplit);
-        hipLaunchKernelGGL((attn_fwd_general_kernel<DT>), grid, dim3(256), 0, st, (const char*)q, q_sh, q_sl, (const char*)k,
-                           (const char*)v, kv_sh, kv_sl, (char*)out, part_acc, part_ml, Hq, G, Lq, Lk, off, D, c2,
-                           pl.keys_per_split, pl.nsplit);
+        const dim3 grid((unsigned)((a.Lq + 3) / 4), (unsigned)a.Hq, (unsigned)pl.nsplit);
+        hipLaunchKernelGGL((attn_fwd_general_kernel<DT>), grid, dim3(256), 0, a.st, (const char*)a.q, a.q_sh, a.q_sl, (const char*)a.k,
+                           (const char*)a.v, a.kv_sh, a.kv_sl, (char*)a.out, p.acc, p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, a.D,
+                           base2_scale(a.scale), pl.keys_per_split, pl.nsplit);
         RTK_LAUNCH_CHECK("attn_fwd_general_kernel");
     }
-    if (pl.nsplit > 1) {
-        const size_t total = (size_t)Lq * Hq * D;
-        hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc,
-                           part_ml, (char*)out, Hq, Lq, D, pl.nsplit);
-        RTK_LAUNCH_CHECK("attn_combine_kernel");
-    }
-    return RTK_OK;
+    if (rc != RTK_OK || pl.nsplit == 1) return rc;
+    return attn_combine<DT>(p, a.out, a.Hq, a.Lq, a.D, pl.nsplit, a.st);
 }
 
-template <int DT>
-int attn_launch_fp8kv(const AttnPlan& pl, const void* q, int64_t q_sh, int64_t q_sl, const void* k, const void* v, int64_t kv_sh,
-                      int64_t kv_sl, const Archive8& a8, void* out, int Hq, int Hkv, int Lq, int Lk, int off, float c2, void* ws,
-                      hipStream_t st) {
-    constexpr int D = 128;
-    constexpr size_t es = 2;
-    float* part_acc = (float*)ws;
-    float* part_ml = part_acc ? part_acc + (size_t)pl.nsplit * Hq * Lq * D : nullptr;
-    const uint32_t q_bytes = (uint32_t)(((size_t)(Lq - 1) * q_sl + D) * es);
-    const uint32_t kv_bytes = (uint32_t)(((size_t)(Lk - 1) * kv_sl + D) * es);
-    const dim3 grid((unsigned)(Hq * ((Lq + AT_QB - 1) / AT_QB)), (unsigned)pl.nsplit);
-    if (pl.nsplit > 1)
-        hipLaunchKernelGGL((attn_fwd_d128_fp8kv_kernel<DT, true>), grid, dim3(256), 0, st, (const char*)q, q_sh,
-                           (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * es),
-                           kv_bytes, (char*)out, part_acc, part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8);
-    else
-        hipLaunchKernelGGL((attn_fwd_d128_fp8kv_kernel<DT, false>), grid, dim3(256), 0, st, (const char*)q, q_sh,
-                           (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * es),
-                           kv_bytes, (char*)out, part_acc, part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8);
-    RTK_LAUNCH_CHECK("attn_fwd_d128_fp8kv_kernel");
-    if (pl.nsplit > 1) {
-        const size_t total = (size_t)Lq * Hq * D;
-        hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc,
-                           part_ml, (char*)out, Hq, Lq, D, pl.nsplit);
-        RTK_LAUNCH_CHECK("attn_combine_kernel");
+// What the three entry points share once their own checks are through: the operands, the plan over the padded key count,
+// the workspace (`query`: the entry point that sizes it) and the dtype switch.
+int attn_forward(const char* who, const char* query, const AttnArgs& a, const Archive8& a8, const Shared16& s16) {
+    int rc = attn_check_operands(who, a.q, a.q_sh, a.q_sl, a.k, a.v, a.kv_sh, a.kv_sl, a8.k8, a8.v8, a8.ks, a8.vs, a8.sh8, a8.shs,
+                                 a.out, a.Lq, a.Lk, a.off, a.D, a.dtype, a.scale, AT_QB, AT_KT);
+    if (rc != RTK_OK) return rc;
+    const AttnPlan pl = attn_plan(a.Hq, a.Lq, (int)shared_keys(a.Lk, a8.L8, s16.Ls, AT_KT), a.D, a.dtype);
+    rc = attn_check_workspace(who, query, pl.ws_bytes, a.workspace, a.workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    switch (a.dtype) {
+        case RTK_F32: return attn_launch<RTK_F32>(pl, a, a8, s16);
+        case RTK_BF16: return attn_launch<RTK_BF16>(pl, a, a8, s16);
+        default: return attn_launch<RTK_F16>(pl, a, a8, s16);
     }
-    return RTK_OK;
 }
-
-template <int DT>
-int attn_launch_shared(const AttnPlan& pl, const void* q, int64_t q_sh, int64_t q_sl, const void* k, const void* v, int64_t kv_sh,
-                       int64_t kv_sl, const Archive8& a8, const Shared16& s16, void* out, int Hq, int Hkv, int Lq, int Lk, int off,
-                       float c2, void* ws, hipStream_t st) {
-    constexpr int D = 128;
-    constexpr size_t es = 2;
-    float* part_acc = (float*)ws;
-    float* part_ml = part_acc ? part_acc + (size_t)pl.nsplit * Hq * Lq * D : nullptr;
-    const uint32_t q_bytes = (uint32_t)(((size_t)(Lq - 1) * q_sl + D) * es);
-    const uint32_t kv_bytes = (uint32_t)(((size_t)(Lk - 1) * kv_sl + D) * es);
-    const dim3 grid((unsigned)(Hq * ((Lq + AT_QB - 1) / AT_QB)), (unsigned)pl.nsplit);
-    if (pl.nsplit > 1)
-        hipLaunchKernelGGL((attn_fwd_d128_shared_kernel<DT, true>), grid, dim3(256), 0, st, (const char*)q, q_sh,
-                           (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * es),
-                           kv_bytes, (char*)out, part_acc, part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8, s16);
-    else
-        hipLaunchKernelGGL((attn_fwd_d128_shared_kernel<DT, false>), grid, dim3(256), 0, st, (const char*)q, q_sh,
-                           (uint32_t)(q_sl * es), q_bytes, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * es),
-                           kv_bytes, (char*)out, part_acc, part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8, s16);
-    RTK_LAUNCH_CHECK("attn_fwd_d128_shared_kernel");
-    if (pl.nsplit > 1) {
-        const size_t total = (size_t)Lq * Hq * D;
-        hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc,
-                           part_ml, (char*)out, Hq, Lq, D, pl.nsplit);
-        RTK_LAUNCH_CHECK("attn_combine_kernel");
-    }
-    return RTK_OK;
-}
-
-// the archive padded to whole key tiles: the key count the split plan of an fp8kv call is made for
-inline long long fp8kv_keys(int Lk, int L8) { return (long long)Lk + ((long long)L8 + AT_KT - 1) / AT_KT * AT_KT; }
 
 }  // namespace
 
@@ -338,7 +298,7 @@ int fp8kv_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, 
         set_error("%s: unsupported dtype code %d / head_dim %d (RTK_BF16 or RTK_F16 with head_dim 128)", who, dtype, D);
         return RTK_EUNSUPPORTED;
     }
-    if (fp8kv_keys(Lk, L8) > 0x3fffffff || (long long)L8 * 128 >= (1ll << 31) - AT_KT * 128) {
+    if (shared_keys(Lk, L8, 0, AT_KT) > 0x3fffffff || (long long)L8 * 128 >= (1ll << 31) - AT_KT * 128) {
         set_error("%s: unsupported extent: %d archive rows + %d keys", who, L8, Lk);
         return RTK_EUNSUPPORTED;
     }
@@ -422,27 +382,17 @@ extern "C" int rtk_attention_forward(const void* q, int64_t q_stride_h, int64_t 
                                      rtk_stream_t stream) {
     const char* who = "rtk_attention_forward";
     RTK_CHECK_ARG(q && k && v && out, "%s: NULL q / k / v / out pointer", who);
-    int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
+    const int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
     if (rc != RTK_OK) return rc;
-    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, nullptr, nullptr, nullptr, nullptr,
-                             0, 0, out, Lq, Lk, q_offset, D, dtype, scale, AT_QB, AT_KT);
-    if (rc != RTK_OK) return rc;
-    const AttnPlan pl = attn_plan(Hq, Lq, Lk, D, dtype);
-    rc = attn_check_workspace(who, "rtk_attention_workspace_bytes", pl.ws_bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    const float c2 = scale * 1.44269504088896340736f;   // the kernels exponentiate in base 2
-    hipStream_t st = (hipStream_t)stream;
-    void* ws = pl.ws_bytes ? workspace : nullptr;
-    switch (dtype) {
-        case RTK_F32: return attn_launch<RTK_F32>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, c2, ws, st);
-        case RTK_BF16: return attn_launch<RTK_BF16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, c2, ws, st);
-        default: return attn_launch<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, c2, ws, st);
-    }
+    return attn_forward(who, "rtk_attention_workspace_bytes",
+                        AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                 scale, workspace, workspace_bytes, (hipStream_t)stream},
+                        Archive8{}, Shared16{});
 }
 
 extern "C" size_t rtk_attention_workspace_bytes_fp8kv(int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype) {
     if (fp8kv_check_shape("rtk_attention_workspace_bytes_fp8kv", Hq, Hkv, Lq, Lk, L8, D, dtype) != RTK_OK) return 0;
-    return attn_plan(Hq, Lq, (int)fp8kv_keys(Lk, L8), D, dtype).ws_bytes;
+    return attn_plan(Hq, Lq, (int)shared_keys(Lk, L8, 0, AT_KT), D, dtype).ws_bytes;
 }
 
 extern "C" int rtk_attention_forward_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -458,22 +408,13 @@ extern "C" int rtk_attention_forward_fp8kv(const void* q, int64_t q_stride_h, in
     if (L8 == 0)   // no archive yet: the 16-bit call itself
         return rtk_attention_forward(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset,
                                      D, dtype, scale, workspace, workspace_bytes, stream);
-    RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
-    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, k8, v8, k_scale, v_scale,
-                             stride8_h, scale_stride_h, out, Lq, Lk, q_offset, D, dtype, scale, AT_QB, AT_KT);
+    Archive8 a8;
+    rc = make_archive8(who, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h, a8);
     if (rc != RTK_OK) return rc;
-    const AttnPlan pl = attn_plan(Hq, Lq, (int)fp8kv_keys(Lk, L8), D, dtype);
-    rc = attn_check_workspace(who, "rtk_attention_workspace_bytes_fp8kv", pl.ws_bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    const float c2 = scale * 1.44269504088896340736f;
-    const Archive8 a8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
-    void* ws = pl.ws_bytes ? workspace : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RTK_BF16)
-        return attn_launch_fp8kv<RTK_BF16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, out, Hq, Hkv, Lq, Lk,
-                                           q_offset, c2, ws, st);
-    return attn_launch_fp8kv<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, out, Hq, Hkv, Lq, Lk,
-                                      q_offset, c2, ws, st);
+    return attn_forward(who, "rtk_attention_workspace_bytes_fp8kv",
+                        AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                 scale, workspace, workspace_bytes, (hipStream_t)stream},
+                        a8, Shared16{});
 }
 
 extern "C" size_t rtk_attention_workspace_bytes_shared(int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype) {
@@ -496,27 +437,14 @@ extern "C" int rtk_attention_forward_shared(const void* q, int64_t q_stride_h, i
         return rtk_attention_forward_fp8kv(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, k8, v8, k_scale, v_scale, L8,
                                            stride8_h, scale_stride_h, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype, scale, workspace,
                                            workspace_bytes, stream);
-    rc = shared_check_operands(who, ks, vs, Ls, s_stride_h, s_stride_l, D, AT_KT);
+    Shared16 s16;
+    rc = make_shared16(who, ks, vs, Ls, s_stride_h, s_stride_l, D, AT_KT, s16);
     if (rc != RTK_OK) return rc;
-    Archive8 a8{};
-    if (L8 > 0) {
-        RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
-        a8 = Archive8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
-    }
-    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8.k8, a8.v8, a8.ks, a8.vs, a8.sh8,
-                             a8.shs, out, Lq, Lk, q_offset, D, dtype, scale, AT_QB, AT_KT);
+    Archive8 a8;
+    rc = make_archive8(who, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h, a8);
     if (rc != RTK_OK) return rc;
-    const AttnPlan pl = attn_plan(Hq, Lq, (int)shared_keys(Lk, L8, Ls, AT_KT), D, dtype);
-    rc = attn_check_workspace(who, "rtk_attention_workspace_bytes_shared", pl.ws_bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    const float c2 = scale * 1.44269504088896340736f;
-    const Shared16 s16{(const char*)ks, (const char*)vs, s_stride_h, (uint32_t)(s_stride_l * 2),
-                       (uint32_t)(((size_t)(Ls - 1) * s_stride_l + D) * 2), Ls};
-    void* ws = pl.ws_bytes ? workspace : nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == RTK_BF16)
-        return attn_launch_shared<RTK_BF16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, s16, out, Hq, Hkv, Lq,
-                                            Lk, q_offset, c2, ws, st);
-    return attn_launch_shared<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, s16, out, Hq, Hkv, Lq, Lk,
-                                       q_offset, c2, ws, st);
+    return attn_forward(who, "rtk_attention_workspace_bytes_shared",
+                        AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                 scale, workspace, workspace_bytes, (hipStream_t)stream},
+                        a8, s16);
 }

@@ -20,7 +20,13 @@
 //   * each wave keeps its own (m, l, acc); the four are folded through LDS in wave order 0, 1, 2, 3 and the workgroup
 //     leaves ONE un-normalised partial per packed row in the layout attn_combine_kernel reads, which then runs unchanged.
 //     No atomics, no flags; plain vector stores.
-// The plan (decode_plan) is a function of the shape alone.
+// The plan (decode_plan) is a function of the shape alone.  attn_decode_d128_shared_kernel is the same body
+// (attention_decode_d128_body.inc) with another buffer's 16-bit rows between the archive and the kernel's own
+// (rtk_attention_decode_shared); attn_decode_group_d128_kernel (rtk_attention_decode_group, below) serves one token of
+// several branches.  The body and the group kernel share dec_step_off, dec_v_frag and dec_softmax_step; their tile loads,
+// dequantise-and-stage step and four-wave fold are written in each (as shared functions they compile the
+// existing kernels differently).  Host side: each entry point keeps its own checks and its fall-through, then
+// decode_forward (operands, plan, workspace, dtype) -> decode_launch -> decode_launch_d128, the one launcher.
 // FP8 = true: the keys are [e4m3 archive | 16-bit rows], counted in a key space where the archive is padded to whole
 // 32-key tiles (a tile is of one kind).  Archive tiles are dequantised (fp8_dequant16) into the registers / the LDS image
 // a 16-bit tile of the dequantised rows would have left, so with L8 % 32 == 0 every fp32 sum is grouped as in the 16-bit
@@ -61,6 +67,49 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// the byte offset, within a 256-byte row, of the 16-byte chunk a lane of group g feeds to k-step s
+__device__ __forceinline__ int dec_step_off(int s, int g) { return 128 * (s >> 1) + 32 * g + 16 * (s & 1); }
+
+// The A operand of O^T = mfma(V^T, P^T) for d-block db, read transposed from a wave's V image: `vrd` = the image + the
+// lane's v_rd
+__device__ __forceinline__ u32x4 dec_v_frag(const char* vrd, int db) {
+    u32x2 h2[2];
+#pragma unroll
+    for (int jh = 0; jh < 2; ++jh) {
+        const i16x4 t4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+            (__attribute__((address_space(3))) i16x4*)(vrd + DEC_VPITCH * 16 * jh + 32 * db));
+        h2[jh] = __builtin_bit_cast(u32x2, t4);
+    }
+    return u32x4{h2[0][0], h2[0][1], h2[1][0], h2[1][1]};
+}
+
+// One tile's step of the online softmax of the lane's packed row: s0 / s1 are its 8 raw logits (masked ones -inf), the
+// other 24 sit in the lanes 16 and 32 apart.  Rescales the running (m, l, oacc) and returns the probabilities packed as
+// the B operand of O^T = mfma(V^T, P^T).
+template <int DT>
+__device__ __forceinline__ u32x4 dec_softmax_step(f32x4 s0, f32x4 s1, float c2, float& m, float& l, f32x4 (&oacc)[8]) {
+    using Hh = H16<DT>;
+    float mx = fmaxf(fmaxf(fmaxf(s0[0], s1[0]), fmaxf(s0[1], s1[1])), fmaxf(fmaxf(s0[2], s1[2]), fmaxf(s0[3], s1[3])));
+    mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
+    const float mnew = fmaxf(m, mx * c2);
+    const float alpha = __builtin_amdgcn_exp2f(m - safe_max(mnew));
+#pragma unroll
+    for (int db = 0; db < 8; ++db) oacc[db] *= alpha;
+    l *= alpha;
+    m = mnew;
+    const float nm = -safe_max(m);
+    float ls = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        s0[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[e], c2, nm));
+        s1[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[e], c2, nm));
+        ls += s0[e] + s1[e];
+    }
+    l += ls;
+    return u32x4{Hh::pack2(s0[0], s0[1]), Hh::pack2(s0[2], s0[3]), Hh::pack2(s1[0], s1[1]), Hh::pack2(s1[2], s1[3])};
+}
+
 template <int DT, bool FP8>
 __global__ __launch_bounds__(256, 2) void attn_decode_d128_kernel(
     const char* __restrict__ q, int64_t q_sh, int64_t q_sl, const char* __restrict__ k, const char* __restrict__ v,
@@ -98,18 +147,10 @@ DecodePlan decode_plan(int Hq, int Hkv, int Lq, long long keys) {
     return DecodePlan{(int)ns, (int)kps, (size_t)ns * Hq * Lq * (128 + 2) * sizeof(float)};
 }
 
-inline long long decode_fp8kv_keys(int Lk, int L8) { return (long long)Lk + ((long long)L8 + DEC_T - 1) / DEC_T * DEC_T; }
-
 // what the packed kernel takes of the shapes attn_check_shape admits
 int decode_check_envelope(const char* who, int Hq, int Hkv, int Lq, int D, int dtype) {
-    if (dtype != RTK_BF16 && dtype != RTK_F16) {
-        set_error("%s: unsupported dtype code %d (the packed kernel takes RTK_BF16 or RTK_F16)", who, dtype);
-        return RTK_EUNSUPPORTED;
-    }
-    if (D != 128) {
-        set_error("%s: unsupported head_dim %d (the packed kernel takes 128)", who, D);
-        return RTK_EUNSUPPORTED;
-    }
+    const int rc = d128_check_envelope(who, "packed", D, dtype);
+    if (rc != RTK_OK) return rc;
     if ((long long)(Hq / Hkv) * Lq > DEC_R) {
         set_error("%s: unsupported shape: (Hq / Hkv) * Lq = %d * %d packed rows (at most %d)", who, Hq / Hkv, Lq, DEC_R);
         return RTK_EUNSUPPORTED;
@@ -117,42 +158,34 @@ int decode_check_envelope(const char* who, int Hq, int Hkv, int Lq, int D, int d
     return RTK_OK;
 }
 
-template <int DT, bool FP8>
-int decode_launch(const DecodePlan& pl, const void* q, int64_t q_sh, int64_t q_sl, const void* k, const void* v, int64_t kv_sh,
-                  int64_t kv_sl, const Archive8& a8, void* out, int Hq, int Hkv, int Lq, int Lk, int off, float c2, void* ws,
-                  hipStream_t st) {
-    constexpr int D = 128;
-    float* part_acc = (float*)ws;
-    float* part_ml = part_acc + (size_t)pl.nsplit * Hq * Lq * D;
-    const uint32_t kv_bytes = (uint32_t)(((size_t)(Lk - 1) * kv_sl + D) * 2);
-    hipLaunchKernelGGL((attn_decode_d128_kernel<DT, FP8>), dim3((unsigned)pl.nsplit, (unsigned)Hkv), dim3(256), 0, st,
-                       (const char*)q, q_sh, q_sl, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * 2), kv_bytes, part_acc,
-                       part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8);
-    RTK_LAUNCH_CHECK("attn_decode_d128_kernel");
-    const size_t total = (size_t)Lq * Hq * D;
-    hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc, part_ml,
-                       (char*)out, Hq, Lq, D, pl.nsplit);
-    RTK_LAUNCH_CHECK("attn_combine_kernel");
-    return RTK_OK;
+// One launch of a packed kernel variant (`tail`: the a8 / s16 it takes after the common parameters), then the combine.
+template <int DT, class K, class... Tail>
+int decode_launch_d128(K kern, const char* name, const DecodePlan& pl, const AttnArgs& a, const Tail&... tail) {
+    const Partials p = split_partials(a.workspace, pl.nsplit, a.Hq, a.Lq, 128);
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nsplit, (unsigned)a.Hkv), dim3(256), 0, a.st, (const char*)a.q, a.q_sh, a.q_sl,
+                       (const char*)a.k, (const char*)a.v, a.kv_sh, (uint32_t)(a.kv_sl * 2), rows_extent(a.Lk, a.kv_sl, 128, 2), p.acc,
+                       p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, base2_scale(a.scale), pl.keys_per_split, tail...);
+    RTK_LAUNCH_CHECK(name);
+    return attn_combine<DT>(p, a.out, a.Hq, a.Lq, 128, pl.nsplit, a.st);
 }
 
-template <int DT>
-int decode_launch_shared(const DecodePlan& pl, const void* q, int64_t q_sh, int64_t q_sl, const void* k, const void* v,
-                         int64_t kv_sh, int64_t kv_sl, const Archive8& a8, const Shared16& s16, void* out, int Hq, int Hkv, int Lq,
-                         int Lk, int off, float c2, void* ws, hipStream_t st) {
-    constexpr int D = 128;
-    float* part_acc = (float*)ws;
-    float* part_ml = part_acc + (size_t)pl.nsplit * Hq * Lq * D;
-    const uint32_t kv_bytes = (uint32_t)(((size_t)(Lk - 1) * kv_sl + D) * 2);
-    hipLaunchKernelGGL((attn_decode_d128_shared_kernel<DT>), dim3((unsigned)pl.nsplit, (unsigned)Hkv), dim3(256), 0, st,
-                       (const char*)q, q_sh, q_sl, (const char*)k, (const char*)v, kv_sh, (uint32_t)(kv_sl * 2), kv_bytes, part_acc,
-                       part_ml, Hq, Hq / Hkv, Lq, Lk, off, c2, pl.keys_per_split, a8, s16);
-    RTK_LAUNCH_CHECK("attn_decode_d128_shared_kernel");
-    const size_t total = (size_t)Lq * Hq * D;
-    hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc, part_ml,
-                       (char*)out, Hq, Lq, D, pl.nsplit);
-    RTK_LAUNCH_CHECK("attn_combine_kernel");
-    return RTK_OK;
+// the kernel of the segments the call has: [archive | shared | own], a8 / s16 empty without
+template <int DT> int decode_launch(const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const Shared16& s16) {
+    if (s16.Ls > 0) return decode_launch_d128<DT>(attn_decode_d128_shared_kernel<DT>, "attn_decode_d128_shared_kernel", pl, a, a8, s16);
+    if (a8.L8 > 0) return decode_launch_d128<DT>(attn_decode_d128_kernel<DT, true>, "attn_decode_d128_kernel", pl, a, a8);
+    return decode_launch_d128<DT>(attn_decode_d128_kernel<DT, false>, "attn_decode_d128_kernel", pl, a, a8);
+}
+
+// What the three entry points share once their own checks are through: the operands, the plan over the padded key count,
+// the workspace (`query`: the entry point that sizes it) and the dtype switch.
+int decode_forward(const char* who, const char* query, const AttnArgs& a, const Archive8& a8, const Shared16& s16) {
+    int rc = attn_check_operands(who, a.q, a.q_sh, a.q_sl, a.k, a.v, a.kv_sh, a.kv_sl, a8.k8, a8.v8, a8.ks, a8.vs, a8.sh8, a8.shs,
+                                 a.out, a.Lq, a.Lk, a.off, a.D, a.dtype, a.scale, 0, DEC_T);
+    if (rc != RTK_OK) return rc;
+    const DecodePlan pl = decode_plan(a.Hq, a.Hkv, a.Lq, shared_keys(a.Lk, a8.L8, s16.Ls, DEC_T));
+    rc = attn_check_workspace(who, query, pl.ws_bytes, a.workspace, a.workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    return a.dtype == RTK_BF16 ? decode_launch<RTK_BF16>(pl, a, a8, s16) : decode_launch<RTK_F16>(pl, a, a8, s16);
 }
 
 // ---- group decode (rtk_attention_decode_group): ONE token of each of B branches that share [archive | shared rows] ----
@@ -186,7 +219,6 @@ template <int DT, int NCG>
 __global__ __launch_bounds__(256, 2) void attn_decode_group_d128_kernel(GroupArgs ga, Archive8 a8, Shared16 s16,
                                                                         float* __restrict__ part_acc,
                                                                         float* __restrict__ part_ml, float c2) {
-    using Hh = H16<DT>;
     constexpr int NR = NCG * DEC_R;                                                   // columns of the workgroup
     constexpr int WAVE_LDS = NR * DEC_OPITCH * 4 > DEC_WAVE_LDS ? NR * DEC_OPITCH * 4 : DEC_WAVE_LDS;
     __shared__ __attribute__((aligned(16))) char lds[4 * WAVE_LDS];   // [wave]: V tile, then the wave's O
@@ -220,7 +252,6 @@ __global__ __launch_bounds__(256, 2) void attn_decode_group_d128_kernel(GroupArg
     const __amdgpu_buffer_rsrc_t rks = bounded_rsrc(a8.ks + (int64_t)hkv * a8.shs, (uint32_t)L8 * 4u);
     const __amdgpu_buffer_rsrc_t rvs = bounded_rsrc(a8.vs + (int64_t)hkv * a8.shs, (uint32_t)L8 * 4u);
 
-    auto step_off = [&](int s) { return 128 * (s >> 1) + 32 * g + 16 * (s & 1); };
     // Q fragments (B operand) of column group cg: packed row 16 cg + c, zero past the workgroup's rows
     u32x4 qf[NCG][4];
 #pragma unroll
@@ -240,11 +271,11 @@ __global__ __launch_bounds__(256, 2) void attn_decode_group_d128_kernel(GroupArg
                 }
             const char* qr = qb + (int64_t)(hkv * G + gi) * qsh * 2;
 #pragma unroll
-            for (int s = 0; s < 4; ++s) qf[cg][s] = *(const u32x4*)(qr + step_off(s));
+            for (int s = 0; s < 4; ++s) qf[cg][s] = *(const u32x4*)(qr + dec_step_off(s, g));
         }
     }
 
-    // one tile's operands, as in attention_decode_d128_body.inc
+    // one tile's operands, laid out as in attention_decode_d128_body.inc
     u32x4 kr[8], vr[8];
     auto load_k = [&](int kb) {
         if (kb < archp) {   // rows >= L8 of the last archive tile: zero codes, zero scales
@@ -261,7 +292,7 @@ __global__ __launch_bounds__(256, 2) void attn_decode_group_d128_kernel(GroupArg
 #pragma unroll
         for (int b = 0; b < 2; ++b)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) kr[4 * b + s] = load16(rk, (uint32_t)(kb + 16 * b + c) * row_bytes + (uint32_t)step_off(s));
+            for (int s = 0; s < 4; ++s) kr[4 * b + s] = load16(rk, (uint32_t)(kb + 16 * b + c) * row_bytes + (uint32_t)dec_step_off(s, g));
     };
     auto load_v = [&](int kb) {
         if (kb < archp) {
@@ -338,38 +369,11 @@ __global__ __launch_bounds__(256, 2) void attn_decode_group_d128_kernel(GroupArg
                 if (4 * g + e > lim) s0[cg][e] = -INFINITY;
                 if (16 + 4 * g + e > lim) s1[cg][e] = -INFINITY;
             }
-            float mx = fmaxf(fmaxf(fmaxf(s0[cg][0], s1[cg][0]), fmaxf(s0[cg][1], s1[cg][1])),
-                             fmaxf(fmaxf(s0[cg][2], s1[cg][2]), fmaxf(s0[cg][3], s1[cg][3])));
-            mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
-            mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
-            const float mnew = fmaxf(m[cg], mx * c2);
-            const float alpha = __builtin_amdgcn_exp2f(m[cg] - safe_max(mnew));
-#pragma unroll
-            for (int db = 0; db < 8; ++db) oacc[cg][db] *= alpha;
-            l[cg] *= alpha;
-            m[cg] = mnew;
-            const float nm = -safe_max(mnew);
-            float ls = 0.f;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                s0[cg][e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[cg][e], c2, nm));
-                s1[cg][e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[cg][e], c2, nm));
-                ls += s0[cg][e] + s1[cg][e];
-            }
-            l[cg] += ls;
-            pf[cg] = u32x4{Hh::pack2(s0[cg][0], s0[cg][1]), Hh::pack2(s0[cg][2], s0[cg][3]), Hh::pack2(s1[cg][0], s1[cg][1]),
-                           Hh::pack2(s1[cg][2], s1[cg][3])};
+            pf[cg] = dec_softmax_step<DT>(s0[cg], s1[cg], c2, m[cg], l[cg], oacc[cg]);
         }
 #pragma unroll
         for (int db = 0; db < 8; ++db) {   // one transposed read of the V image feeds every column group
-            u32x2 h2[2];
-#pragma unroll
-            for (int jh = 0; jh < 2; ++jh) {
-                const i16x4 t4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) i16x4*)(vt + v_rd + DEC_VPITCH * 16 * jh + 32 * db));
-                h2[jh] = __builtin_bit_cast(u32x2, t4);
-            }
-            const u32x4 vf = {h2[0][0], h2[0][1], h2[1][0], h2[1][1]};
+            const u32x4 vf = dec_v_frag(vt + v_rd, db);
 #pragma unroll
             for (int cg = 0; cg < NCG; ++cg) oacc[cg][db] = mma32<DT>(vf, pf[cg], oacc[cg][db]);
         }
@@ -455,14 +459,8 @@ GroupPlan group_plan(const int* own_rows, int B, int Hq, int Hkv, int L8, int Ls
 
 // what the group kernel takes: dtype, head_dim, the number of branches and of packed rows
 int group_check_envelope(const char* who, int n_branches, int Hq, int Hkv, int D, int dtype) {
-    if (dtype != RTK_BF16 && dtype != RTK_F16) {
-        set_error("%s: unsupported dtype code %d (the group kernel takes RTK_BF16 or RTK_F16)", who, dtype);
-        return RTK_EUNSUPPORTED;
-    }
-    if (D != 128) {
-        set_error("%s: unsupported head_dim %d (the group kernel takes 128)", who, D);
-        return RTK_EUNSUPPORTED;
-    }
+    const int rc = d128_check_envelope(who, "group", D, dtype);
+    if (rc != RTK_OK) return rc;
     if (n_branches > RTK_DECODE_GROUP_MAX) {
         set_error("%s: unsupported group of %d branches (at most %d)", who, n_branches, RTK_DECODE_GROUP_MAX);
         return RTK_EUNSUPPORTED;
@@ -478,21 +476,13 @@ int group_check_envelope(const char* who, int n_branches, int Hq, int Hkv, int D
 template <int DT>
 int group_launch(const GroupPlan& gp, const GroupArgs& ga, const Archive8& a8, const Shared16& s16, void* out, int Hkv, float c2,
                  void* ws, hipStream_t st) {
-    constexpr int D = 128;
     const int nsplit = gp.ns_sh + gp.max_own, heads = ga.B * ga.Hq;
-    float* part_acc = (float*)ws;
-    float* part_ml = part_acc + (size_t)nsplit * heads * D;
+    const Partials p = split_partials(ws, nsplit, heads, 1, 128);
     const dim3 grid((unsigned)(gp.ns_sh + ga.B * gp.max_own), (unsigned)Hkv);
-    if (ga.B * ga.G > DEC_R)
-        hipLaunchKernelGGL((attn_decode_group_d128_kernel<DT, 2>), grid, dim3(256), 0, st, ga, a8, s16, part_acc, part_ml, c2);
-    else
-        hipLaunchKernelGGL((attn_decode_group_d128_kernel<DT, 1>), grid, dim3(256), 0, st, ga, a8, s16, part_acc, part_ml, c2);
+    const auto kern = ga.B * ga.G > DEC_R ? attn_decode_group_d128_kernel<DT, 2> : attn_decode_group_d128_kernel<DT, 1>;
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, ga, a8, s16, p.acc, p.ml, c2);
     RTK_LAUNCH_CHECK("attn_decode_group_d128_kernel");
-    const size_t total = (size_t)heads * D;
-    hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, part_acc, part_ml,
-                       (char*)out, heads, 1, D, nsplit);
-    RTK_LAUNCH_CHECK("attn_combine_kernel");
-    return RTK_OK;
+    return attn_combine<DT>(p, out, heads, 1, 128, nsplit, st);
 }
 
 }  // namespace
@@ -517,25 +507,17 @@ extern "C" int rtk_attention_decode(const void* q, int64_t q_stride_h, int64_t q
     if (rc != RTK_OK) return rc;
     rc = decode_check_envelope(who, Hq, Hkv, Lq, D, dtype);
     if (rc != RTK_OK) return rc;
-    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, nullptr, nullptr, nullptr, nullptr,
-                             0, 0, out, Lq, Lk, q_offset, D, dtype, scale, 0, DEC_T);
-    if (rc != RTK_OK) return rc;
-    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, Lk);
-    rc = attn_check_workspace(who, "rtk_attention_decode_workspace_bytes", pl.ws_bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    const float c2 = scale * 1.44269504088896340736f;   // the kernels exponentiate in base 2
-    if (dtype == RTK_BF16)
-        return decode_launch<RTK_BF16, false>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, Archive8{}, out, Hq,
-                                              Hkv, Lq, Lk, q_offset, c2, workspace, (hipStream_t)stream);
-    return decode_launch<RTK_F16, false>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, Archive8{}, out, Hq, Hkv,
-                                         Lq, Lk, q_offset, c2, workspace, (hipStream_t)stream);
+    return decode_forward(who, "rtk_attention_decode_workspace_bytes",
+                          AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                   scale, workspace, workspace_bytes, (hipStream_t)stream},
+                          Archive8{}, Shared16{});
 }
 
 extern "C" size_t rtk_attention_decode_workspace_bytes_fp8kv(int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype) {
     const char* who = "rtk_attention_decode_workspace_bytes_fp8kv";
     if (fp8kv_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype) != RTK_OK) return 0;
     if (decode_check_envelope(who, Hq, Hkv, Lq, D, dtype) != RTK_OK) return 0;
-    return decode_plan(Hq, Hkv, Lq, decode_fp8kv_keys(Lk, L8)).ws_bytes;
+    return decode_plan(Hq, Hkv, Lq, shared_keys(Lk, L8, 0, DEC_T)).ws_bytes;
 }
 
 extern "C" int rtk_attention_decode_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -553,20 +535,13 @@ extern "C" int rtk_attention_decode_fp8kv(const void* q, int64_t q_stride_h, int
     if (L8 == 0)   // no archive yet: the 16-bit packed call itself
         return rtk_attention_decode(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D,
                                     dtype, scale, workspace, workspace_bytes, stream);
-    RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
-    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, k8, v8, k_scale, v_scale, stride8_h,
-                             scale_stride_h, out, Lq, Lk, q_offset, D, dtype, scale, 0, DEC_T);
+    Archive8 a8;
+    rc = make_archive8(who, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h, a8);
     if (rc != RTK_OK) return rc;
-    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, decode_fp8kv_keys(Lk, L8));
-    rc = attn_check_workspace(who, "rtk_attention_decode_workspace_bytes_fp8kv", pl.ws_bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    const float c2 = scale * 1.44269504088896340736f;
-    const Archive8 a8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
-    if (dtype == RTK_BF16)
-        return decode_launch<RTK_BF16, true>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, out, Hq, Hkv, Lq,
-                                             Lk, q_offset, c2, workspace, (hipStream_t)stream);
-    return decode_launch<RTK_F16, true>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, out, Hq, Hkv, Lq, Lk,
-                                        q_offset, c2, workspace, (hipStream_t)stream);
+    return decode_forward(who, "rtk_attention_decode_workspace_bytes_fp8kv",
+                          AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                   scale, workspace, workspace_bytes, (hipStream_t)stream},
+                          a8, Shared16{});
 }
 
 extern "C" size_t rtk_attention_decode_workspace_bytes_shared(int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype) {
@@ -593,27 +568,16 @@ extern "C" int rtk_attention_decode_shared(const void* q, int64_t q_stride_h, in
         return rtk_attention_decode_fp8kv(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, k8, v8, k_scale, v_scale, L8,
                                           stride8_h, scale_stride_h, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype, scale, workspace,
                                           workspace_bytes, stream);
-    rc = shared_check_operands(who, ks, vs, Ls, s_stride_h, s_stride_l, D, DEC_T);
+    Shared16 s16;
+    rc = make_shared16(who, ks, vs, Ls, s_stride_h, s_stride_l, D, DEC_T, s16);
     if (rc != RTK_OK) return rc;
-    Archive8 a8{};
-    if (L8 > 0) {
-        RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
-        a8 = Archive8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
-    }
-    rc = attn_check_operands(who, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8.k8, a8.v8, a8.ks, a8.vs, a8.sh8,
-                             a8.shs, out, Lq, Lk, q_offset, D, dtype, scale, 0, DEC_T);
+    Archive8 a8;
+    rc = make_archive8(who, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h, a8);
     if (rc != RTK_OK) return rc;
-    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, shared_keys(Lk, L8, Ls, DEC_T));
-    rc = attn_check_workspace(who, "rtk_attention_decode_workspace_bytes_shared", pl.ws_bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    const float c2 = scale * 1.44269504088896340736f;
-    const Shared16 s16{(const char*)ks, (const char*)vs, s_stride_h, (uint32_t)(s_stride_l * 2),
-                       (uint32_t)(((size_t)(Ls - 1) * s_stride_l + D) * 2), Ls};
-    if (dtype == RTK_BF16)
-        return decode_launch_shared<RTK_BF16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, s16, out, Hq, Hkv,
-                                              Lq, Lk, q_offset, c2, workspace, (hipStream_t)stream);
-    return decode_launch_shared<RTK_F16>(pl, q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, a8, s16, out, Hq, Hkv, Lq,
-                                         Lk, q_offset, c2, workspace, (hipStream_t)stream);
+    return decode_forward(who, "rtk_attention_decode_workspace_bytes_shared",
+                          AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                   scale, workspace, workspace_bytes, (hipStream_t)stream},
+                          a8, s16);
 }
 
 extern "C" size_t rtk_attention_decode_group_workspace_bytes(const int* own_rows, int n_branches, int Hq, int Hkv, int L8,
@@ -650,18 +614,12 @@ extern "C" int rtk_attention_decode_group(const rtk_decode_branch* branches, int
         if (rc != RTK_OK) return rc;
         own_rows[b] = br.Lk;
     }
-    Shared16 s16{};
-    if (Ls > 0) {
-        rc = shared_check_operands(who, ks, vs, Ls, s_stride_h, s_stride_l, D, DEC_T);
-        if (rc != RTK_OK) return rc;
-        s16 = Shared16{(const char*)ks, (const char*)vs, s_stride_h, (uint32_t)(s_stride_l * 2),
-                       (uint32_t)(((size_t)(Ls - 1) * s_stride_l + D) * 2), Ls};
-    }
-    Archive8 a8{};
-    if (L8 > 0) {
-        RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
-        a8 = Archive8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
-    }
+    Shared16 s16;
+    rc = make_shared16(who, ks, vs, Ls, s_stride_h, s_stride_l, D, DEC_T, s16);
+    if (rc != RTK_OK) return rc;
+    Archive8 a8;
+    rc = make_archive8(who, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h, a8);
+    if (rc != RTK_OK) return rc;
     GroupArgs ga{};
     for (int b = 0; b < n_branches; ++b) {
         const rtk_decode_branch& br = branches[b];
@@ -669,13 +627,13 @@ extern "C" int rtk_attention_decode_group(const rtk_decode_branch* branches, int
                                  a8.vs, a8.sh8, a8.shs, out, 1, br.Lk, br.Lk - 1, D, dtype, scale, 0, DEC_T);
         if (rc != RTK_OK) return rc;
         ga.br[b] = GroupBranch{(const char*)br.q, (const char*)br.k, (const char*)br.v, br.q_stride_h, br.kv_stride_h,
-                               (uint32_t)(br.kv_stride_l * 2), (uint32_t)(((size_t)(br.Lk - 1) * br.kv_stride_l + D) * 2), br.Lk, 0};
+                               (uint32_t)(br.kv_stride_l * 2), rows_extent(br.Lk, br.kv_stride_l, D, 2), br.Lk, 0};
     }
     const GroupPlan gp = group_plan(own_rows, n_branches, Hq, Hkv, L8, Ls);
     rc = attn_check_workspace(who, "rtk_attention_decode_group_workspace_bytes", gp.ws_bytes, workspace, workspace_bytes);
     if (rc != RTK_OK) return rc;
     ga.B = n_branches, ga.G = Hq / Hkv, ga.Hq = Hq, ga.ns_sh = gp.ns_sh, ga.kps_sh = gp.kps_sh, ga.max_own = gp.max_own;
-    const float c2 = scale * 1.44269504088896340736f;
+    const float c2 = base2_scale(scale);
     if (dtype == RTK_BF16) return group_launch<RTK_BF16>(gp, ga, a8, s16, out, Hkv, c2, workspace, (hipStream_t)stream);
     return group_launch<RTK_F16>(gp, ga, a8, s16, out, Hkv, c2, workspace, (hipStream_t)stream);
 }

@@ -1,8 +1,8 @@
 // attention_decode_d128_body.inc - the body of attn_decode_d128_kernel / attn_decode_d128_shared_kernel
 // (attention_decode.hip), which include it with `constexpr bool FP8, SHARED`, `Archive8 a8` and `Shared16 s16` in scope,
 // besides their common parameters.  (The same text compiles the existing instantiations to the same code; a function the
-// kernels shared would not - tools/kernel_diff.py.)
-    using Hh = H16<DT>;
+// kernels shared would not - tools/kernel_diff.py.  dec_step_off, dec_v_frag and dec_softmax_step, which the group
+// kernel uses too, are functions of attention_decode.hip: those leave this body's code as it was.)
     __shared__ __attribute__((aligned(16))) char lds[4 * DEC_WAVE_LDS];   // [wave]: V tile, then the wave's O
     __shared__ float ml_s[4][DEC_R][2];
     // FP8: from here on Lk and off count in the padded key space
@@ -41,8 +41,6 @@
         rsv = bounded_rsrc(s16.v + (int64_t)hkv * s16.sh * 2, s16.bytes);
     }
 
-    // the byte offset, within a 256-byte row, of the 16-byte chunk this lane feeds to k-step s
-    auto step_off = [&](int s) { return 128 * (s >> 1) + 32 * g + 16 * (s & 1); };
     // Q fragments (B operand): packed row c, zero for c >= R
     u32x4 qf[4];
 #pragma unroll
@@ -50,7 +48,7 @@
     if (c < R) {
         const char* qr = q + ((int64_t)(hkv * G + qg) * q_sh + (int64_t)qi * q_sl) * 2;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) qf[s] = *(const u32x4*)(qr + step_off(s));
+        for (int s = 0; s < 4; ++s) qf[s] = *(const u32x4*)(qr + dec_step_off(s, g));
     }
 
     // One tile's operands, in flight from the moment the previous tile's are consumed.  16-bit tile: kr[4 b + s] = the step-s chunk of key row 16 b + c; vr[u] = chunk c of
@@ -77,7 +75,7 @@
                 for (int b = 0; b < 2; ++b)
 #pragma unroll
                     for (int s = 0; s < 4; ++s)
-                        kr[4 * b + s] = load16(rsk, (uint32_t)(kb + 16 * b + c) * s16.row_bytes + (uint32_t)step_off(s));
+                        kr[4 * b + s] = load16(rsk, (uint32_t)(kb + 16 * b + c) * s16.row_bytes + (uint32_t)dec_step_off(s, g));
                 return;
             }
             kb -= Lsp;
@@ -86,7 +84,7 @@
         for (int b = 0; b < 2; ++b)
 #pragma unroll
             for (int s = 0; s < 4; ++s)
-                kr[4 * b + s] = load16(rk, (uint32_t)(kb + 16 * b + c) * kv_row_bytes + (uint32_t)step_off(s));
+                kr[4 * b + s] = load16(rk, (uint32_t)(kb + 16 * b + c) * kv_row_bytes + (uint32_t)dec_step_off(s, g));
     };
     auto load_v = [&](int kb) {
         if constexpr (FP8) {
@@ -172,38 +170,10 @@
             if (4 * g + e > lim) s0[e] = -INFINITY;
             if (16 + 4 * g + e > lim) s1[e] = -INFINITY;
         }
-        float mx = fmaxf(fmaxf(fmaxf(s0[0], s1[0]), fmaxf(s0[1], s1[1])), fmaxf(fmaxf(s0[2], s1[2]), fmaxf(s0[3], s1[3])));
-        mx = fmaxf(mx, __shfl_xor(mx, 16, WAVE));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, WAVE));
-        const float mnew = fmaxf(m, mx * c2);
-        const float alpha = __builtin_amdgcn_exp2f(m - safe_max(mnew));
-#pragma unroll
-        for (int db = 0; db < 8; ++db) oacc[db] *= alpha;
-        l *= alpha;
-        m = mnew;
-        const float nm = -safe_max(m);
-        float ls = 0.f;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            s0[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s0[e], c2, nm));
-            s1[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s1[e], c2, nm));
-            ls += s0[e] + s1[e];
-        }
-        l += ls;
-        const u32x4 pf = {Hh::pack2(s0[0], s0[1]), Hh::pack2(s0[2], s0[3]), Hh::pack2(s1[0], s1[1]), Hh::pack2(s1[2], s1[3])};
-        auto v_frag = [&](int db) {
-            u32x2 h2[2];
-#pragma unroll
-            for (int jh = 0; jh < 2; ++jh) {
-                const i16x4 t4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) i16x4*)(vt + v_rd + DEC_VPITCH * 16 * jh + 32 * db));
-                h2[jh] = __builtin_bit_cast(u32x2, t4);
-            }
-            return u32x4{h2[0][0], h2[0][1], h2[1][0], h2[1][1]};
-        };
+        const u32x4 pf = dec_softmax_step<DT>(s0, s1, c2, m, l, oacc);
         if (arch || kb + DEC_T - 1 <= off) {   // every row sees every key of the tile that exists (keys >= Lk read as zero)
 #pragma unroll
-            for (int db = 0; db < 8; ++db) oacc[db] = mma32<DT>(v_frag(db), pf, oacc[db]);
+            for (int db = 0; db < 8; ++db) oacc[db] = mma32<DT>(dec_v_frag(vt + v_rd, db), pf, oacc[db]);
         } else {
             // one pass per query position: V rows above its diagonal zeroed, the lanes of its packed rows keep the result
             for (int i = 0; i < Lq; ++i) {
@@ -216,7 +186,7 @@
                 }
 #pragma unroll
                 for (int db = 0; db < 8; ++db) {
-                    const f32x4 t = mma32<DT>(v_frag(db) & keep, pf, oacc[db]);
+                    const f32x4 t = mma32<DT>(dec_v_frag(vt + v_rd, db) & keep, pf, oacc[db]);
 #pragma unroll
                     for (int e = 0; e < 4; ++e) oacc[db][e] = qi == i ? t[e] : oacc[db][e];
                 }

@@ -1,7 +1,8 @@
-// attention_shared.cuh - what attention.hip (the chunk kernels) and attention_decode.hip (the GQA-packed few-row kernel)
-// both use: the bounded buffer loads, the archive descriptor, the cross-split combine kernel and the host-side argument
-// checks of the entry points.  The device parts sit in an unnamed namespace: each file instantiates its own copy under
-// the same name, compiled to the same code (tools/kernel_diff.py matches kernels by name over all files).
+// attention_shared.cuh - what attention.hip (the chunk kernels) and attention_decode.hip (the GQA-packed few-row kernel
+// and the group kernel) both use: the bounded buffer loads, the archive / shared-rows descriptors and how an entry point
+// binds them, the cross-split combine kernel and its launch, and the host-side argument checks of the entry points.  The
+// device parts sit in an unnamed namespace: each file instantiates its own copy under the same name, compiled to the
+// same code (tools/kernel_diff.py matches kernels by name over all files).
 #pragma once
 #include <cmath>
 
@@ -40,6 +41,9 @@ struct Shared16 {
     int Ls;
 };
 
+// bytes from a head's first row to the end of its last: the bound of the head's buffer descriptor
+inline uint32_t rows_extent(int L, int64_t stride_l, int D, size_t es) { return (uint32_t)(((size_t)(L - 1) * stride_l + D) * es); }
+
 template <int DT> __device__ __forceinline__ float ld_elem(const void* p, size_t i) {
     if constexpr (DT == RTK_F32) return ((const float*)p)[i];
     else return H16<DT>::ld(p, i);
@@ -73,9 +77,42 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const float* __restri
     st_elem<DT>(out, idx, num / den);
 }
 
+// the workspace of a key-split call: nsplit x heads x Lq un-normalised rows of D floats, then their (m, l) pairs
+struct Partials {
+    float *acc, *ml;
+};
+inline Partials split_partials(void* ws, int nsplit, int heads, int Lq, int D) {
+    float* acc = (float*)ws;
+    return Partials{acc, acc ? acc + (size_t)nsplit * heads * Lq * D : nullptr};
+}
+// the tail of every key-split launch: out[Lq, heads, D] from the partials
+template <int DT> int attn_combine(const Partials& p, void* out, int heads, int Lq, int D, int nsplit, hipStream_t st) {
+    const size_t total = (size_t)Lq * heads * D;
+    hipLaunchKernelGGL((attn_combine_kernel<DT>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p.acc, p.ml, (char*)out,
+                       heads, Lq, D, nsplit);
+    RTK_LAUNCH_CHECK("attn_combine_kernel");
+    return RTK_OK;
+}
+
 }  // namespace
 
-// ---- host-side checks shared by rtk_attention_forward(_fp8kv) and rtk_attention_decode(_fp8kv) (attention.hip) ----
+// what the three entry points of a kernel family take alike (retake_hip.h "Chunk attention"); off: q_offset
+struct AttnArgs {
+    const void* q;
+    int64_t q_sh, q_sl;
+    const void *k, *v;
+    int64_t kv_sh, kv_sl;
+    void* out;
+    int Hq, Hkv, Lq, Lk, off, D, dtype;
+    float scale;
+    void* workspace;
+    size_t workspace_bytes;
+    hipStream_t st;
+};
+// the kernels exponentiate in base 2: a logit is q . k * scale * log2(e)
+inline float base2_scale(float scale) { return scale * 1.44269504088896340736f; }
+
+// ---- host-side checks shared by rtk_attention_forward*, rtk_attention_decode* and the group call (defined in attention.hip) ----
 int attn_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int D, int dtype);
 int fp8kv_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype);
 // scale, q_offset, 16-byte layout and the 2 GiB head extent with q_slack / kv_slack rows the kernels may address past
@@ -93,7 +130,42 @@ int shared_check_operands(const char* who, const void* ks, const void* vs, int L
 inline long long shared_keys(int Lk, int L8, int Ls, int tile) {
     return (long long)Lk + ((long long)L8 + tile - 1) / tile * tile + ((long long)Ls + tile - 1) / tile * tile;
 }
+// what the MFMA kernels of attention_decode.hip take of dtype and head_dim; `kernel`: "packed" or "group"
+inline int d128_check_envelope(const char* who, const char* kernel, int D, int dtype) {
+    if (dtype != RTK_BF16 && dtype != RTK_F16) {
+        set_error("%s: unsupported dtype code %d (the %s kernel takes RTK_BF16 or RTK_F16)", who, dtype, kernel);
+        return RTK_EUNSUPPORTED;
+    }
+    if (D != 128) {
+        set_error("%s: unsupported head_dim %d (the %s kernel takes 128)", who, D, kernel);
+        return RTK_EUNSUPPORTED;
+    }
+    return RTK_OK;
+}
 // RTK_EWORKSPACE unless `workspace` holds `need` bytes (need 0: nothing is checked); `query`: the entry point that sizes it
 int attn_check_workspace(const char* who, const char* query, size_t need, const void* workspace, size_t workspace_bytes);
+
+// ---- how an entry point binds its archive and shared rows (after its shape check): a8 / s16 stay empty without rows ----
+namespace {
+// RTK_EINVAL for a NULL archive pointer with L8 > 0
+inline int make_archive8(const char* who, const void* k8, const void* v8, const float* k_scale, const float* v_scale, int L8,
+                         int64_t stride8_h, int64_t scale_stride_h, Archive8& a8) {
+    a8 = Archive8{};
+    if (L8 == 0) return RTK_OK;
+    RTK_CHECK_ARG(k8 && v8 && k_scale && v_scale, "%s: NULL archive pointer with L8 = %d", who, L8);
+    a8 = Archive8{(const char*)k8, (const char*)v8, k_scale, v_scale, stride8_h, scale_stride_h, L8};
+    return RTK_OK;
+}
+// shared_check_operands with Ls > 0; `tile`: the kernel's key tile, the rows it may address past the last
+inline int make_shared16(const char* who, const void* ks, const void* vs, int Ls, int64_t s_stride_h, int64_t s_stride_l, int D,
+                         int tile, Shared16& s16) {
+    s16 = Shared16{};
+    if (Ls == 0) return RTK_OK;
+    const int rc = shared_check_operands(who, ks, vs, Ls, s_stride_h, s_stride_l, D, tile);
+    if (rc != RTK_OK) return rc;
+    s16 = Shared16{(const char*)ks, (const char*)vs, s_stride_h, (uint32_t)(s_stride_l * 2), rows_extent(Ls, s_stride_l, D, 2), Ls};
+    return RTK_OK;
+}
+}  // namespace
 
 }  // namespace rtk

@@ -61,36 +61,17 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
     scale = float(D) ** -0.5 if scaling is None else float(scaling)
     a8 = _check_archive(archive, Hkv, D) if archive is not None else (None, None, None, None, 0, 0, 0)
     L8 = a8[4]
-    Ls = 0
-    if shared is not None:
-        ks, vs = shared
-        nv.require_device(ks, vs)
-        if ks.dim() != 4 or ks.shape[:2] != (1, Hkv) or ks.shape[3] != D or vs.shape != ks.shape or vs.stride() != ks.stride():
-            raise ValueError("shared keys / values must be [1, Hkv, Ls, D], laid out alike")
-        if ks.dtype != key_states.dtype or vs.dtype != key_states.dtype:
-            raise ValueError("shared keys / values must have the dtype of key_states")
-        if ks.stride(3) != 1:
-            return None
-        Ls = ks.shape[2]
+    s16 = _check_shared(shared, Hkv, D, key_states.dtype, "key_states") if shared is not None else (None, None, 0, 0, 0)
+    if s16 is None:
+        return None
+    Ls = s16[2]
     q_off = L8 + Ls + Lk - Lq if query_offset is None else int(query_offset)
     stream = nv.raw_stream(query_states.device.index)
     out = torch.empty((1, Lq, Hq, D), dtype=query_states.dtype, device=query_states.device)
-
-    def scratch(tag, need):   # per stream: calls on two streams may overlap
-        if not need:
-            return None
-        key = (tag, query_states.device.index, stream)
-        ws = None if workspace is None else workspace.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=query_states.device)
-            if workspace is not None:
-                workspace[key] = ws
-        return ws
-
     qkv = (nv.ptr(query_states), query_states.stride(1), query_states.stride(2), nv.ptr(key_states), nv.ptr(value_states),
            key_states.stride(1), key_states.stride(2))
     if shared is not None:    # (no shared rows included: the library then runs the two-segment call itself)
-        qkv += (nv.ptr(ks), nv.ptr(vs), Ls, ks.stride(1), ks.stride(2)) + a8
+        qkv += s16 + a8
         shape = (Hq, Hkv, Lq, Lk, L8, Ls, D, code)
         sfx = "_shared"
     elif archive is not None:   # (an empty archive included: the library then runs the 16-bit call itself)
@@ -104,7 +85,7 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
         if packed_gqa else ()
     for tag, fn, query, ws_tag in routes + (("chunk", "rtk_attention_forward", "rtk_attention_workspace_bytes", "attention_ws"),):
         need = getattr(nv.lib, query + sfx)(*shape)
-        ws = scratch(ws_tag, need)
+        ws = _scratch(workspace, ws_tag, query_states.device, stream, need)
         rc = getattr(nv.lib, fn + sfx)(*qkv, nv.ptr(out), Hq, Hkv, Lq, Lk, q_off - L8 - Ls, D, code, scale, nv.ptr(ws), need, stream)
         if rc == nv.RTK_EUNSUPPORTED:
             continue
@@ -126,6 +107,34 @@ def _check_archive(archive, Hkv, D):
     if k8.stride(3) != 1 or k8.stride(2) != D or ks8.stride(2) != 1:
         raise ValueError("archive rows must be dense (D codes per row, one scale per row)")
     return (nv.ptr(k8), nv.ptr(v8), nv.ptr(ks8), nv.ptr(vs8), k8.shape[2], k8.stride(1), ks8.stride(1))
+
+
+def _check_shared(shared, Hkv, D, dtype, whose):
+    """(ks, vs) -> the library's (ks, vs, Ls, stride_h, stride_l), or None: rows it does not take (decline the call).
+    whose: what `dtype` is the dtype of, for the message."""
+    ks, vs = shared
+    nv.require_device(ks, vs)
+    if ks.dim() != 4 or ks.shape[:2] != (1, Hkv) or ks.shape[3] != D or vs.shape != ks.shape or vs.stride() != ks.stride():
+        raise ValueError("shared keys / values must be [1, Hkv, Ls, D], laid out alike")
+    if ks.dtype != dtype or vs.dtype != dtype:
+        raise ValueError(f"shared keys / values must have the dtype of {whose}")
+    if ks.stride(3) != 1:
+        return None
+    return (nv.ptr(ks), nv.ptr(vs), ks.shape[2], ks.stride(1), ks.stride(2))
+
+
+def _scratch(workspace, tag, device, stream, need):
+    """`need` bytes of scratch, kept in the dict `workspace` (if any) under (tag, device, stream) - per stream: calls on two
+    streams may overlap.  None for need 0."""
+    if not need:
+        return None
+    key = (tag, device.index, stream)
+    ws = None if workspace is None else workspace.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        if workspace is not None:
+            workspace[key] = ws
+    return ws
 
 
 def group_decode_attention(queries, owns, shared, archive, scaling=None, workspace=None):
@@ -164,17 +173,9 @@ def group_decode_attention(queries, owns, shared, archive, scaling=None, workspa
     code = nv.dtype_code(q0)
     scale = float(D) ** -0.5 if scaling is None else float(scaling)
     a8 = _check_archive(archive, Hkv, D) if archive is not None else (None, None, None, None, 0, 0, 0)
-    s16 = (None, None, 0, 0, 0)
-    if shared is not None:
-        ks, vs = shared
-        nv.require_device(ks, vs)
-        if ks.dim() != 4 or ks.shape[:2] != (1, Hkv) or ks.shape[3] != D or vs.shape != ks.shape or vs.stride() != ks.stride():
-            raise ValueError("shared keys / values must be [1, Hkv, Ls, D], laid out alike")
-        if ks.dtype != q0.dtype or vs.dtype != q0.dtype:
-            raise ValueError("shared keys / values must have the dtype of the queries")
-        if ks.stride(3) != 1:
-            return None
-        s16 = (nv.ptr(ks), nv.ptr(vs), ks.shape[2], ks.stride(1), ks.stride(2))
+    s16 = _check_shared(shared, Hkv, D, q0.dtype, "the queries") if shared is not None else (None, None, 0, 0, 0)
+    if s16 is None:
+        return None
     if B > nv.DECODE_GROUP_MAX:   # (the library says so itself, but its array holds no more)
         return None
     brs = (nv.DecodeBranch * B)()
@@ -186,14 +187,7 @@ def group_decode_attention(queries, owns, shared, archive, scaling=None, workspa
         rows[b] = k.shape[2]
     need = nv.lib.rtk_attention_decode_group_workspace_bytes(rows, B, Hq, Hkv, a8[4], s16[2], D, code)
     stream = nv.raw_stream(q0.device.index)
-    ws = None
-    if need:
-        key = ("attention_group_ws", q0.device.index, stream)
-        ws = None if workspace is None else workspace.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=q0.device)
-            if workspace is not None:
-                workspace[key] = ws
+    ws = _scratch(workspace, "attention_group_ws", q0.device, stream, need)
     out = torch.empty((B, 1, Hq, D), dtype=q0.dtype, device=q0.device)
     rc = nv.lib.rtk_attention_decode_group(brs, B, *s16, *a8, nv.ptr(out), Hq, Hkv, D, code, scale, nv.ptr(ws), need, stream)
     if rc == nv.RTK_EUNSUPPORTED:

@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (64 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (67 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -51,6 +51,9 @@
  *                                       branches in one launch that reads the shared rows once (retake/branch_group.py)
  *   §N  "Sliding window"                rtk_pivotkv_slide_batched: rows of many buffers moved down in place, one call - the
  *                                       oldest video rows of every layer dropped (opt-in: video_window_rows)
+ *   §O  "Video budget"                  rtk_pivotkv_keep_scores_batched, rtk_pivotkv_budget_select_batched,
+ *                                       rtk_pivotkv_squeeze_batched: a bounded cache that keeps its best-scored video rows
+ *                                       (opt-in: video_budget_rows)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -984,6 +987,66 @@ typedef struct rtk_slide_unit {
 } rtk_slide_unit;
 #define RTK_SLIDE_MAX_UNITS 96   /* moving units per launch (the array travels as a kernel argument) */
 int rtk_pivotkv_slide_batched(const rtk_slide_unit* units, int n_units, rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Video budget (opt-in: longvideo_kwargs["video_budget_rows"]; NOT in the reference, which processes a finished video, and a
+ * rule of this project's own: what it does to answer quality has not been evaluated).  The sliding window bounds a layer's
+ * video region by AGE; the budget bounds it by the attention score every flush already computes: the region keeps one fp32
+ * score per row (the value the selection saw, after the key-patch override to 1.0), and when it holds more than
+ * budget + slack rows the newest row and the budget - 1 best-scored others survive, in sequence order, moved down in place.
+ * The score is a column sum of row-stochastic softmaxes averaged over heads: it averages 1 over any chunk, whatever its
+ * length, so scores of rows from different chunks compare directly.
+ *
+ * rtk_pivotkv_keep_scores_batched - per flush, one launch: dst[r] = score[keep_idx[r]], r < keep, for every unit (a NULL
+ *   keep_idx is the identity).  `score` is the chunk's score row as the selection left it, `dst` the rows of the layer's
+ *   score store the flush has just filled.
+ * rtk_pivotkv_budget_select_batched - per eviction, one launch, one workgroup per unit: writes the ascending int32 list
+ *   idx[keep] of the survivors of score[n]: row n - 1 always, and of rows [0, n - 1) the keep - 1 with the highest score,
+ *   ties to the lowest index (the order of a stable descending sort).  Exact: four 8-bit radix passes over the
+ *   order-preserving key of the fp32 value and one ordered compaction (select.cuh); the scores are re-read from memory on
+ *   every pass, n is not bounded by LDS.  keep == n gives the identity.  RTK_EINVAL unless 1 <= keep <= n.
+ * rtk_pivotkv_squeeze_batched - per eviction, the move: one unit = `streams` independent byte streams, as rtk_slide_unit
+ *   describes them.  Per stream, row[first + r] = row[first + idx[r]] for r < rows_out, as if read from a snapshot; idx is a
+ *   DEVICE array, ascending with idx[r] >= r (rows only move down), and names rows below rows_in.  The kernel clamps idx[r]
+ *   into [r, rows_in - 1]: a bad list cannot make it read or write out of bounds, or loop.  No byte outside rows
+ *   [first, first + rows_out) of each stream is written.  No flags, no counters, no waiting between workgroups, no scratch:
+ *   a workgroup owns a stream, or a 128-byte column slice of every row of a stream, and walks the rows upward R rows a step;
+ *   a step's stores land in rows [k R, (k + 1) R) and every later source lies at or above (k + 1) R (pivotkv_budget.hip).
+ *   16-byte accesses where base, first, stride and row bytes allow, else 4-byte ones; the result is the same.  A unit with
+ *   rows_out == 0 is skipped; more than RTK_SQUEEZE_MAX_UNITS moving units take more launches.
+ * `units` are HOST arrays; n_units == 0 launches nothing and returns 0.  Errors, all before any launch: RTK_EINVAL for NULL
+ * pointers, negative counts, keep outside [1, n], rows_out > rows_in, rows_in beyond int32, streams <= 0, a row_bytes that is
+ * not a positive multiple of 4, a base or stream_stride that is not 4-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rtk_keep_scores_unit {
+    const float*   score;     /* the chunk's scores [L] */
+    const int64_t* keep_idx;  /* kept columns [keep], NULL = 0 .. keep - 1 */
+    float*         dst;       /* [keep] */
+    int32_t        keep;
+} rtk_keep_scores_unit;
+#define RTK_KEEP_SCORES_MAX_UNITS 96
+int rtk_pivotkv_keep_scores_batched(const rtk_keep_scores_unit* units, int n_units, rtk_stream_t stream);
+
+typedef struct rtk_budget_select_unit {
+    const float* score;  /* [n], row n - 1 the newest */
+    int32_t*     idx;    /* out: [keep], ascending */
+    int32_t      n, keep;
+} rtk_budget_select_unit;
+#define RTK_BUDGET_SELECT_MAX_UNITS 96
+int rtk_pivotkv_budget_select_batched(const rtk_budget_select_unit* units, int n_units, rtk_stream_t stream);
+
+typedef struct rtk_squeeze_unit {
+    void*   base;           /* first byte of stream 0 */
+    int64_t stream_stride;  /* bytes between streams (kv heads, id planes) */
+    int32_t streams;
+    int32_t row_bytes;      /* a multiple of 4 */
+    int64_t first;          /* row of the region's first row */
+    int64_t rows_out;       /* rows written: [first, first + rows_out) */
+    int64_t rows_in;        /* rows of the region before the move */
+    const int32_t* idx;     /* DEVICE: [rows_out], source row of each destination row, relative to `first` */
+} rtk_squeeze_unit;
+#define RTK_SQUEEZE_MAX_UNITS 80   /* moving units per launch (the array travels as a kernel argument) */
+int rtk_pivotkv_squeeze_batched(const rtk_squeeze_unit* units, int n_units, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ class _LayerStore:
     rtk_layer_state block (`c`) the library reads and advances itself (rtk_pivotkv_update / rtk_pivotkv_flush)."""
 
     __slots__ = ("c", "cref", "_k", "_v", "_pos", "pending_event", "pos_ndim", "k8", "v8", "ks8", "vs8", "len8", "archive_at",
-                 "sk", "sv", "base", "pinned")
+                 "sk", "sv", "base", "pinned", "sc", "sc_len")
 
     def __init__(self):
         self.c = nv.LayerState()
@@ -45,6 +45,11 @@ class _LayerStore:
         # attention sink) - a slide never drops or moves them; -1 until that chunk (with fp8 rows the archive IS the video
         # region and `archive_at` is this number)
         self.pinned = -1
+        # video_budget_rows: one fp32 score per row of the video region, in region order (row i of the region is row
+        # pinned + i of the 16-bit buffers, or row i of the archive) - the value the selection saw for the row - and how
+        # many leading region rows carry one.  None unless a budget is on
+        self.sc = None
+        self.sc_len = 0
 
     def _sync(self):
         k, v, c = self._k, self._v, self.c
@@ -356,7 +361,9 @@ class _CacheView:
 
 
 # one layer's numbers at a mark.  has_kv / has_pos: did the layer own K / V and id buffers (a skipped layer owns none)
-_LayerMark = collections.namedtuple("_LayerMark", "length pos_len pos_ndim len8 archive_at num_evicted has_kv has_pos")
+# sc_len: the scored rows of the video region (video_budget_rows; 0 without a budget)
+_LayerMark = collections.namedtuple("_LayerMark", "length pos_len pos_ndim len8 archive_at num_evicted has_kv has_pos sc_len",
+                                    defaults=(0,))
 
 
 class CacheMark:

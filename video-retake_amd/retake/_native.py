@@ -119,6 +119,26 @@ class SlideUnit(C.Structure):
                 ("drop", _i64), ("rows", _i64)]
 
 
+KEEP_SCORES_MAX_UNITS = BUDGET_SELECT_MAX_UNITS = 96   # RTK_KEEP_SCORES_MAX_UNITS / RTK_BUDGET_SELECT_MAX_UNITS
+SQUEEZE_MAX_UNITS = 80   # RTK_SQUEEZE_MAX_UNITS: moving units per kernel launch of rtk_pivotkv_squeeze_batched
+
+
+class KeepScoresUnit(C.Structure):
+    """rtk_keep_scores_unit (include/retake_hip.h)."""
+    _fields_ = [("score", _vp), ("keep_idx", _vp), ("dst", _vp), ("keep", _i32)]
+
+
+class BudgetSelectUnit(C.Structure):
+    """rtk_budget_select_unit (include/retake_hip.h)."""
+    _fields_ = [("score", _vp), ("idx", _vp), ("n", _i32), ("keep", _i32)]
+
+
+class SqueezeUnit(C.Structure):
+    """rtk_squeeze_unit (include/retake_hip.h)."""
+    _fields_ = [("base", _vp), ("stream_stride", _i64), ("streams", _i32), ("row_bytes", _i32), ("first", _i64),
+                ("rows_out", _i64), ("rows_in", _i64), ("idx", _vp)]
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -198,6 +218,9 @@ _SIGNATURES = {
     "rtk_attention_decode_group": (C.c_int, [C.POINTER(DecodeBranch), _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64,
                                          _i64, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "rtk_pivotkv_slide_batched": (C.c_int, [_vp, _i, _vp]),
+    "rtk_pivotkv_keep_scores_batched": (C.c_int, [_vp, _i, _vp]),
+    "rtk_pivotkv_budget_select_batched": (C.c_int, [_vp, _i, _vp]),
+    "rtk_pivotkv_squeeze_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),
     "rtk_p2p_free": (C.c_int, [_vp]),
     "rtk_p2p_export": (C.c_int, [_vp, _vp, C.POINTER(_sz)]),

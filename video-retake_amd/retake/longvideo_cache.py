@@ -223,6 +223,18 @@ class PivotKVCache(DynamicCache):
         self.video_window_rows = None
         self.video_window_slack = 0
         self.window_dropped: List[int] = []   # per layer: rows the window has dropped so far (also counted as evicted)
+        # MI355X build option, two top-level keys of longvideo_kwargs (build_kvcache reads them; NOT in the reference, and a
+        # rule of this project's own - answer quality is not evaluated): video_budget_rows = B bounds the same video region
+        # by SCORE instead of by age.  Every region row keeps the fp32 score its chunk's selection saw for it (after the
+        # key-patch override to 1.0; _LayerStore.sc, filled by every flush) - a column sum of row-stochastic softmaxes averaged
+        # over heads, which averages 1 over any chunk whatever its length, so rows of different chunks compare directly.  When
+        # `after_forward` finds more than B + video_budget_slack rows in a layer's region it keeps the NEWEST row
+        # (get_prev_temporal_idx reads its id: the ids of every later chunk stay those of an unbounded cache) and the B - 1
+        # best-scored others, ties to the oldest, in sequence order (`_evict_budget`).  A chunk that keeps all of its rows
+        # is scored all the same (score_when_keeping_all).  None (default): off, nothing changes, no score buffer exists.
+        self.video_budget_rows = None
+        self.video_budget_slack = 0
+        self.budget_dropped: List[int] = []   # per layer: rows the budget has dropped so far (also counted as evicted)
         self._attn_ws: Dict[Any, torch.Tensor] = {}
 
     def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None, layer_idx=None):
@@ -392,7 +404,7 @@ class PivotKVCache(DynamicCache):
         if st.k8 is not None and st.k8.shape[2] >= need:
             return
         cap = max(need, 2 * (st.k8.shape[2] if st.k8 is not None else 0), self.reserve_archive_tokens or 1024,
-                  self._window_room(st, 0, more))
+                  self._window_room(st, 0, more), self._budget_room(st, 0, more))
         new = [torch.empty((1, Hkv, cap, D), dtype=torch.uint8, device=device) for _ in range(2)] + \
               [torch.empty((1, Hkv, cap), dtype=torch.float32, device=device) for _ in range(2)]
         if st.len8:
@@ -468,7 +480,8 @@ class PivotKVCache(DynamicCache):
           staging           kept-row staging of the two-launch eviction (in_place_compaction=False / no reforge)
           deferred_queries  pre-RoPE queries kept alive for a flush that scores them where they lie (prologue_operands="pre_rope")
           worker_scratch    per-update scratch of the stage-by-stage route / worker streams
-          attention_workspace  key-split partials of the native chunk attention (attention_kernel="hip"; few-row shapes only)."""
+          attention_workspace  key-split partials of the native chunk attention (attention_kernel="hip"; few-row shapes only)
+          row_scores        the fp32 score buffers of the video regions - the key exists only with video_budget_rows on."""
         def nbytes(t):
             return 0 if t is None else t.numel() * t.element_size()
 
@@ -499,6 +512,8 @@ class PivotKVCache(DynamicCache):
                 if t is not None and t.data_ptr() not in seen:
                     seen.add(t.data_ptr())
                     out["deferred_queries"] += nbytes(t)
+        if self.video_budget_rows is not None:
+            out["row_scores"] = sum(nbytes(st.sc) for st in self._layers)
         out["worker_scratch"] = sum(nbytes(t) for t in self._ws.values()) + sum(nbytes(t) for sd in self._sides for t in sd.ws.values())
         out["attention_workspace"] = sum(nbytes(t) for t in self._attn_ws.values())
         out["total"] = sum(out.values())
@@ -508,7 +523,7 @@ class PivotKVCache(DynamicCache):
     def _take_mark(self, compressed: bool) -> CacheMark:
         nev = self.num_evicted_tokens
         layers = tuple(_LayerMark(st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at,
-                                  nev[l] if l < len(nev) else 0, st._k is not None, st._pos is not None)
+                                  nev[l] if l < len(nev) else 0, st._k is not None, st._pos is not None, st.sc_len)
                        for l, st in enumerate(self._layers))
         self._mark_serial += 1
         return CacheMark(weakref.ref(self), self._mark_serial, self._epoch, layers, len(self._layers), self._pos_layers, len(nev),
@@ -586,6 +601,7 @@ class PivotKVCache(DynamicCache):
         self._check_mark(mark)
         for st, m in zip(self._layers, mark.layers):
             st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at = m.length, m.pos_len, m.pos_ndim, m.len8, m.archive_at
+            st.sc_len = m.sc_len
             # `pinned` is not in the mark and need not be: it is set once, to the layer's length at its first compressed
             # chunk, and a slide - the only thing that moves rows - voids every earlier mark.  So a valid mark either lies at
             # or below that length (taken before any video row existed: the next compressed chunk pins afresh) or above it
@@ -663,6 +679,8 @@ class PivotKVCache(DynamicCache):
             st.c.length -= drop
             if st.c.pos_len:
                 st.c.pos_len -= drop
+            if self.kv_cache_dtype is None and st.pinned >= 0:   # (video_budget_rows: scores of rows that are gone)
+                st.sc_len = min(st.sc_len, max(st.c.length - st.pinned, 0))
         if hasattr(self, "_seen_tokens"):
             self._seen_tokens = max_length
         m = self.last_compressed_mark
@@ -706,6 +724,7 @@ class PivotKVCache(DynamicCache):
             self._flush()
         self._epoch += 1
         st.pinned = -1   # (video_window_rows: a layer replaced wholesale pins what it holds at its next compressed chunk)
+        st.sc_len = 0    # (video_budget_rows: ... and its region starts afresh there)
         if isinstance(value, list) and len(value) == 0:
             st.k = st.v = None
             st.length = 0
@@ -768,8 +787,9 @@ class PivotKVCache(DynamicCache):
         if st.pos is not None and st.pos.shape[1] >= need:
             return
         first = st.archive_at if self.kv_cache_dtype is not None else st.pinned
+        first = first if first >= 0 else st.pos_len
         cap = max(need, 2 * (st.pos.shape[1] if st.pos is not None else 0), 4096, self.reserve_tokens + self.reserve_archive_tokens,
-                  self._window_room(st, first if first >= 0 else st.pos_len, more))
+                  self._window_room(st, first, more), self._budget_room(st, first, more))
         buf = torch.empty((P, cap), dtype=torch.int64, device=device)
         if st.pos is not None and st.pos_len:
             buf[:, :st.pos_len].copy_(st.pos[:, :st.pos_len])
@@ -783,8 +803,8 @@ class PivotKVCache(DynamicCache):
 
     def after_forward(self, **kwargs):
         """The reference's hook after every forward of a video chunk (:146-150): the deferred eviction of the chunk is
-        flushed, the sliding window (video_window_rows) - which acts here and nowhere else: a caller that never calls
-        after_forward gets no window - drops what exceeds it, and
+        flushed, the sliding window (video_window_rows) or the video budget (video_budget_rows) - which act here and
+        nowhere else: a caller that never calls after_forward gets neither - drops what exceeds it, and
         `video_end` is taken."""
         self._flush()
         self._prompt_len = 0
@@ -792,6 +812,8 @@ class PivotKVCache(DynamicCache):
             self._compressed_in_forward = False
             if self.video_window_rows is not None:
                 self._slide_window()
+            elif self.video_budget_rows is not None:
+                self._evict_budget()
             if not self.defer_rerotation:
                 self.last_compressed_mark = self._take_mark(True)
 
@@ -869,6 +891,127 @@ class PivotKVCache(DynamicCache):
         if self.video_window_rows is None or not self.kvcache_compression:
             return 0
         return max(first, 0) + self.video_window_rows + self.video_window_slack + more
+
+    # ---- the video budget (video_budget_rows; not in the reference) ------------------------------
+    def _budget_room(self, st: _LayerStore, first: int, more: int) -> int:
+        """video_budget_rows: `_window_room`'s sibling - the rows at which a buffer stops growing: the pinned rows, a full
+        budget with its slack and `more` (the in-flight chunk).  0 with the budget off or `kvcache_compression` off."""
+        if self.video_budget_rows is None or not self.kvcache_compression:
+            return 0
+        return max(first, 0) + self.video_budget_rows + self.video_budget_slack + more
+
+    def _keep_scores(self, b: _Batch, layers):
+        """video_budget_rows: the scores of the rows a flush has just committed, `score[keep_idx[r]]` as the selection left
+        them (key-patch rows at 1.0), into the layers' score stores at those rows - one rtk_pivotkv_keep_scores_batched
+        launch per flush, whichever route flushed (so also per `flush_every_layers` group)."""
+        if self.video_budget_rows is None:
+            return
+        keep, fp8 = b.keep, self.kv_cache_dtype is not None
+        units = (nv.KeepScoresUnit * len(layers))()
+        for u, l in zip(units, layers):
+            st, sl = self._layers[l], b.slot(l)
+            at = (st.len8 if fp8 else st.c.length - st.pinned) - keep    # region row of the first kept row
+            if st.sc is None or st.sc.numel() < at + keep:
+                cap = max(at + keep, 2 * (st.sc.numel() if st.sc is not None else 0), 1024, self._budget_room(st, 0, b.L))
+                sc = torch.empty(cap, dtype=torch.float32, device=b.device)
+                if st.sc is not None and st.sc_len:
+                    sc[:st.sc_len].copy_(st.sc[:st.sc_len])
+                st.sc = sc
+            u.score, u.keep_idx = b.score[sl].data_ptr(), b.keep_idx[sl].data_ptr()
+            u.dst, u.keep = st.sc.data_ptr() + 4 * at, keep
+            if st.sc_len == at:   # (else: unscored rows lie in between - text that was not rewound; `_evict_budget` raises)
+                st.sc_len = at + keep
+        idx = b.dev_index
+        nv.check(_on_device(idx, nv.lib.rtk_pivotkv_keep_scores_batched, units, len(layers), nv.raw_stream(idx)),
+                 "rtk_pivotkv_keep_scores_batched")
+
+    def row_scores(self, layer_idx: int) -> torch.Tensor:
+        """video_budget_rows: a copy of the scores the layer's video region keeps, fp32, in region order (deferred work is
+        flushed first).  Empty for a layer without video rows; ValueError with the budget off."""
+        if self.video_budget_rows is None:
+            raise ValueError("PivotKVCache.row_scores: no scores are kept without video_budget_rows")
+        self._flush()
+        st = self._layers[layer_idx] if layer_idx < len(self._layers) else None
+        if st is None or st.sc is None:
+            return torch.empty(0, dtype=torch.float32)
+        return st.sc[:st.sc_len].clone()
+
+    def _evict_budget(self):
+        """Evict every layer whose video region holds n > B + slack rows down to B: the newest row and the B - 1 best-scored
+        others survive (ties to the oldest), in sequence order.  Planned like `_slide_window`, per device: ONE
+        rtk_pivotkv_budget_select_batched call writes each layer's ascending survivor list, ONE rtk_pivotkv_squeeze_batched
+        call moves K, V, ids and scores of all such layers down in place (the archive's codes, scales, ids and scores with
+        fp8 rows).  Pinned rows never move, ids are not rescaled again.  length / len8, pos_len and the scored rows shrink, num_evicted_tokens
+        and budget_dropped grow by n - B.  Rows below every earlier mark are rewritten, so the epoch moves exactly as for a
+        slide.  ValueError, before anything is launched or changed: a region row without a score - text or decode rows
+        appended behind the video and not rewound.  (With fp8 rows such rows live in the 16-bit buffers, but their ids lie
+        between the archive's: the survivors' ids are then no contiguous block, and the eviction raises all the same.  So no
+        16-bit row's id ever lies behind the region's at an eviction: there is nothing for rtk_pivotkv_slide_batched to do.)"""
+        B, S = self.video_budget_rows, self.video_budget_slack
+        fp8 = self.kv_cache_dtype is not None
+        plan, by_device = [], {}
+        for l, st in enumerate(self._layers):
+            first = st.archive_at if fp8 else st.pinned
+            if st._k is None or first < 0:
+                continue
+            n = st.len8 if fp8 else st.c.length - first
+            if n <= B + S:
+                continue
+            ids = st._pos is not None and st.c.pos_len > 0
+            if st.c.cap == 0 or (ids and st.c.pos_len != st.c.length + st.len8):
+                raise ValueError(f"video_budget_rows: layer {l} cannot be evicted - its buffers are not the cache's own dense "
+                                 f"blocks, or it keeps ids for {st.c.pos_len} of its {st.c.length + st.len8} rows")
+            if st.sc is None or st.sc_len != n or (ids and st.c.pos_len != first + n):
+                raise ValueError(f"video_budget_rows: layer {l} holds {n} video rows"
+                                 f"{'' if fp8 else ' and other rows'} behind its pinned rows and scores for "
+                                 f"{st.sc_len if st.sc is not None else 0} of them - text or decode rows were appended after the "
+                                 "video and left in place.  Rewind to `video_end` before the stream goes on (a question's "
+                                 "rows carry no score and cannot take part in the eviction)")
+            by_device.setdefault(st._k.get_device(), []).append((l, st, first, n, ids))
+        if not by_device:
+            return
+        for dev, layers in by_device.items():
+            idx = self._buf(f"budget_idx{dev}", (len(layers), B), torch.int32, layers[0][1]._k.device)
+            sel = (nv.BudgetSelectUnit * len(layers))()
+            units = []
+            for i, (l, st, first, n, ids) in enumerate(layers):
+                ip = idx[i].data_ptr()
+                sel[i].score, sel[i].idx, sel[i].n, sel[i].keep = st.sc.data_ptr(), ip, n, B
+                if fp8:    # the archive [0, len8): codes of D bytes a row, one fp32 scale a row
+                    Hkv, cap8, D = st.k8.shape[1], st.k8.shape[2], st.k8.shape[3]
+                    for t, row in ((st.k8, D), (st.v8, D), (st.ks8, 4), (st.vs8, 4)):
+                        units.append((t.data_ptr(), cap8 * row, Hkv, row, 0, B, n, ip))
+                else:
+                    k = st._k
+                    row = k.shape[3] * k.element_size()
+                    for t in (k, st._v):
+                        units.append((t.data_ptr(), k.shape[2] * row, k.shape[1], row, first, B, n, ip))
+                if ids:    # in sequence order: the region's ids are rows [first, first + n) = [first, pos_len)
+                    P, cap = st._pos.shape
+                    units.append((st._pos.data_ptr(), cap * 8, P, 8, first, B, n, ip))
+                units.append((st.sc.data_ptr(), 0, 1, 4, 0, B, n, ip))
+                plan.append((l, st, n - B, ids))
+            stream = nv.raw_stream(dev)
+            nv.check(_on_device(dev, nv.lib.rtk_pivotkv_budget_select_batched, sel, len(layers), stream),
+                     "rtk_pivotkv_budget_select_batched")
+            arr = (nv.SqueezeUnit * len(units))(*[nv.SqueezeUnit(*u) for u in units])
+            nv.check(_on_device(dev, nv.lib.rtk_pivotkv_squeeze_batched, arr, len(units), stream), "rtk_pivotkv_squeeze_batched")
+        dropped = self.budget_dropped
+        dropped.extend([0] * (len(self._layers) - len(dropped)))
+        for l, st, d, ids in plan:
+            if fp8:
+                st.len8 -= d
+            else:
+                st.c.length -= d
+            if ids:
+                st.c.pos_len -= d
+            st.sc_len = B
+            self.update_num_evicted_tokens(d, l)
+            dropped[l] += d
+        self._epoch += 1
+        for br in self._branches or ():   # (noted on the branches: this cache may be released before they look)
+            if br._fork_dead is None:
+                br._fork_dead = "epoch"
 
     # ---- bookkeeping lists (reference :152-215) ------------------------------------------------
     def update_num_evicted_tokens(self, num_tokens: int, layer_idx: int):
@@ -995,8 +1138,9 @@ class PivotKVCache(DynamicCache):
         if st.k is not None and st.k.shape[2] >= need and st.k.is_contiguous() and st.v.is_contiguous() \
                 and st.v.shape[2] == st.k.shape[2]:
             return st
-        room = 0 if self.kv_cache_dtype is not None else \
-            self._window_room(st, st.pinned if st.pinned >= 0 else st.length, tokens)
+        first = st.pinned if st.pinned >= 0 else st.length
+        room = 0 if self.kv_cache_dtype is not None else max(self._window_room(st, first, tokens),
+                                                             self._budget_room(st, first, tokens))
         cap = max(need, 2 * (st.k.shape[2] if st.k is not None else 0), 1024, self.reserve_tokens, room)
         shape = (1, like.shape[1], cap, like.shape[3])
         nk = torch.empty(shape, dtype=like.dtype, device=like.device)
@@ -1149,6 +1293,7 @@ class PivotKVCache(DynamicCache):
         if rc:
             self._reset_compaction(b)
         nv.check(rc, "rtk_pivotkv_flush")
+        self._keep_scores(b, layers)
         self._end_flush(b, layers)
         return True
 
@@ -1180,6 +1325,7 @@ class PivotKVCache(DynamicCache):
                 self._evict_staged(b, layers, rot)
         # rtk_pivotkv_flush does exactly this itself for its units (pivotkv_update.hip:646-654, 730-738)
         self._advance_layers(b, layers, fp8)
+        self._keep_scores(b, layers)
         self._end_flush(b, layers)
 
     def _wait_workers(self, layers):
@@ -2120,6 +2266,24 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
                 raise ValueError(f"{keys} do not serve prompt_guided_scoring: a prompt-guided cache belongs to one question, "
                                  "a window to a stream that does not end")
             cache.video_window_rows, cache.video_window_slack = W, S
+        B, S = config.longvideo_kwargs.get("video_budget_rows", None), config.longvideo_kwargs.get("video_budget_slack", 0)
+        keys = "video_budget_rows / video_budget_slack"
+        if not (B is None or (isinstance(B, int) and not isinstance(B, bool) and B > 0)) \
+                or not (isinstance(S, int) and not isinstance(S, bool) and S >= 0):
+            raise ValueError(f"{keys}: video_budget_rows must be an int > 0 (or None: no budget) and video_budget_slack "
+                             f"an int >= 0, got {B!r} and {S!r}")
+        if B is not None:
+            if W is not None:
+                raise ValueError(f"{keys} do not go together with video_window_rows: a layer's video region is bounded by "
+                                 "score or by age, not both")
+            if cache.defer_rerotation:
+                raise ValueError(f"{keys} do not serve defer_rerotation (the sharded prefill): its block caches hold "
+                                 "un-rotated keys and provisional ids until `finalize`")
+            if cache.prompt_guided_scoring:
+                raise ValueError(f"{keys} do not serve prompt_guided_scoring: its scores answer one question and are not "
+                                 "comparable between chunks, a budget ranks the rows of a stream that does not end")
+            cache.video_budget_rows, cache.video_budget_slack = B, S
+            cache.score_when_keeping_all = True   # no region row without a score
         if cache.prompt_guided_scoring:   # what the mode does not serve: refused here, never a silent fallback
             for key, value, served in (("score_rounding", cache.score_rounding, "fp32"),
                                        ("kv_cache_dtype", cache.kv_cache_dtype, None),

@@ -1,5 +1,5 @@
 """The video budget's rule (video_budget_rows / video_budget_slack), restated on the CPU in torch: the specification the
-HIP selection (rtk_pivotkv_budget_select_batched) and PivotKVCache._evict_budget are tested against.
+HIP selection (rtk_pivotkv_budget_select_batched) and retake._video_bound.evict_budget are tested against.
 
 A layer's video region holds n rows in sequence order, each with one fp32 score.  When n > B + S the region is evicted down
 to B rows: the NEWEST row always survives, and of the other n - 1 rows the B - 1 with the highest score, ties to the lowest

@@ -72,3 +72,27 @@ def test_more_units_than_one_launch_holds():
     units = [(_scores("many_ones", 50 + i, i), 1 + i % 40) for i in range(nv.BUDGET_SELECT_MAX_UNITS + 5)]
     for (s, keep), got in zip(units, _select(units)):
         assert torch.equal(got.long(), br.survivors(s, keep))
+
+
+def test_keep_scores_more_units_than_one_launch_holds_some_of_them_idle():
+    """rtk_pivotkv_keep_scores_batched: 101 units of 1 to 40 kept rows and 10 idle ones (keep == 0, the last unit among them) in
+    one call - two launches, the idle units take no slot of either - against score[keep_idx] in torch (keep_idx NULL:
+    score[0 .. keep - 1]).  Every destination has two rows more than its unit keeps, which stay as they were."""
+    import retake._native as nv
+
+    n = nv.KEEP_SCORES_MAX_UNITS + 15
+    g = torch.Generator(device="cpu")
+    g.manual_seed(7)
+    keeps = [0 if i % 12 == 2 or i == n - 1 else 1 + i % 40 for i in range(n)]
+    assert keeps.count(0) == 10 and n - keeps.count(0) == nv.KEEP_SCORES_MAX_UNITS + 5
+    scores = [torch.rand(64, generator=g) for _ in range(n)]
+    idxs = [None if i % 7 == 3 else torch.randperm(64, generator=g)[:keep].sort().values for i, keep in enumerate(keeps)]
+    dscores, didxs = [s.to(dev()) for s in scores], [None if x is None else x.to(dev()) for x in idxs]
+    outs = [torch.full((keep + 2,), -7.0, device=dev()) for keep in keeps]
+    arr = (nv.KeepScoresUnit * n)(*[nv.KeepScoresUnit(s.data_ptr(), None if x is None else x.data_ptr(), o.data_ptr(), keep)
+                                    for s, x, o, keep in zip(dscores, didxs, outs, keeps)])
+    nv.check(nv.lib.rtk_pivotkv_keep_scores_batched(arr, n, nv.stream()), "rtk_pivotkv_keep_scores_batched")
+    torch.cuda.synchronize()
+    for i, (s, x, o, keep) in enumerate(zip(scores, idxs, outs, keeps)):
+        want = s[:keep] if x is None else s[x]
+        assert torch.equal(o.cpu(), torch.cat([want, torch.full((2,), -7.0)])), i

@@ -393,6 +393,14 @@ void set_error(const char* fmt, ...);
 int hip_fail(hipError_t e, const char* what);
 }  // namespace rtk
 
+#define RTK_CHECK_ARG(cond, ...)                \
+    do {                                        \
+        if (!(cond)) {                          \
+            rtk::set_error(__VA_ARGS__);        \
+            return RTK_EINVAL;                  \
+        }                                       \
+    } while (0)
+
 // ---- M-RoPE channel -> position-row selection (longvideo_cache.py:68-74), shared by rope.hip and the fused prepare kernel
 namespace rtk {
 struct RowSel {
@@ -546,6 +554,47 @@ inline Units pad_units(const Unit* units, int n) {
     return o;
 }
 
+// The same for units that are translated on the way, some of them idle: fill(i, slot) writes unit i of the host array into
+// a slot (false: idle, it takes none), launch(units, n) -> code launches n >= 1 filled slots: at MAX, and once for the rest
+template <typename Units, typename Fill, typename Launch>
+inline int launch_units(int n_units, Fill&& fill, Launch&& launch) {
+    Units o;
+    constexpr int MAX = (int)(sizeof(o.u) / sizeof(o.u[0]));
+    for (int i = 0, n = 0; i < n_units; ++i) {
+        if (fill(i, o.u[n])) ++n;
+        if (n == MAX || (n > 0 && i == n_units - 1)) {
+            for (int j = n; j < MAX; ++j) o.u[j] = o.u[n - 1];   // (never read)
+            const int rc = launch(o, n);
+            if (rc != RTK_OK) return rc;
+            n = 0;
+        }
+    }
+    return RTK_OK;
+}
+
+// the first words of a batched entry point over a host array: > 0 if there are units to walk, else what it returns
+inline int have_units(const void* units, int n_units, const char* who) {
+    RTK_CHECK_ARG(n_units >= 0, "%s: n_units %d", who, n_units);
+    if (n_units == 0) return RTK_OK;
+    RTK_CHECK_ARG(units, "%s: NULL units", who);
+    return 1;
+}
+
+// a unit of byte streams (rtk_slide_unit, rtk_squeeze_unit): the fields both have
+template <typename Unit>
+inline int check_stream_unit(const Unit& u, const char* who, int i) {
+    RTK_CHECK_ARG(u.streams > 0, "%s: unit %d: streams %d", who, i, u.streams);
+    RTK_CHECK_ARG(u.row_bytes > 0 && u.row_bytes % 4 == 0, "%s: unit %d: row_bytes %d is not a positive multiple of 4", who, i,
+                  u.row_bytes);
+    RTK_CHECK_ARG(((uintptr_t)u.base & 3) == 0 && u.stream_stride % 4 == 0, "%s: unit %d: base / stream_stride not 4-byte aligned",
+                  who, i);
+    return RTK_OK;
+}
+
+// ... and whether its kernel may use 16-byte accesses: every address, stride and byte count it steps by is a multiple of 16
+template <typename... T>
+inline bool aligned16(T... v) { return ((... | (uintptr_t)v) & 15) == 0; }
+
 inline int make_rowsel(RowSel& rs, int P, int D, const int* sections, int nsec, const char* who) {
     if (D > 256 || (D & 1)) {
         set_error("%s: head_dim %d unsupported (must be even and <= 256)", who, D);
@@ -591,14 +640,6 @@ void profile_end(int kid, hipStream_t st);
         if (prof__) rtk::profile_begin(kid, st);                                 \
         hipLaunchKernelGGL(kern, grid, block, shmem, st, __VA_ARGS__);           \
         if (prof__) rtk::profile_end(kid, st);                                   \
-    } while (0)
-
-#define RTK_CHECK_ARG(cond, ...)                \
-    do {                                        \
-        if (!(cond)) {                          \
-            rtk::set_error(__VA_ARGS__);        \
-            return RTK_EINVAL;                  \
-        }                                       \
     } while (0)
 
 #define RTK_LAUNCH_CHECK(what)                                  \

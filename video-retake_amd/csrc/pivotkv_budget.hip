@@ -161,42 +161,34 @@ using namespace rtk;
 
 extern "C" int rtk_pivotkv_keep_scores_batched(const rtk_keep_scores_unit* units, int n_units, rtk_stream_t stream) {
     const char* who = "rtk_pivotkv_keep_scores_batched";
-    RTK_CHECK_ARG(n_units >= 0, "%s: n_units %d", who, n_units);
-    if (n_units == 0) return RTK_OK;
-    RTK_CHECK_ARG(units, "%s: NULL units", who);
+    const int rc = have_units(units, n_units, who);
+    if (rc <= 0) return rc;
     for (int i = 0; i < n_units; ++i) {
         const rtk_keep_scores_unit& u = units[i];
         RTK_CHECK_ARG(u.keep >= 0, "%s: unit %d: keep %d", who, i, u.keep);
         RTK_CHECK_ARG(u.keep == 0 || (u.score && u.dst), "%s: unit %d: NULL score / dst", who, i);
     }
     hipStream_t st = (hipStream_t)stream;
-    KeepScoreUnits ku;
-    int n = 0, most = 0;
-    auto launch = [&]() -> int {
-        if (n == 0) return RTK_OK;
-        for (int i = n; i < RTK_KEEP_SCORES_MAX_UNITS; ++i) ku.u[i] = ku.u[n - 1];   // (never read)
-        RTK_LAUNCH(KID_KEEPSC, keep_scores_kernel, dim3((most + KSC_BLOCK - 1) / KSC_BLOCK, n), dim3(KSC_BLOCK), 0, st, ku);
-        RTK_LAUNCH_CHECK("keep_scores_kernel");
-        n = most = 0;
-        return RTK_OK;
-    };
-    for (int i = 0; i < n_units; ++i) {
-        if (units[i].keep == 0) continue;
-        ku.u[n] = units[i];
-        most = std::max(most, units[i].keep);
-        if (++n == RTK_KEEP_SCORES_MAX_UNITS) {
-            const int rc = launch();
-            if (rc != RTK_OK) return rc;
-        }
-    }
-    return launch();
+    int most = 0;   // of the launch being filled: its largest unit's rows
+    return launch_units<KeepScoreUnits>(
+        n_units,
+        [&](int i, rtk_keep_scores_unit& slot) {
+            slot = units[i];
+            most = std::max(most, slot.keep);
+            return slot.keep != 0;
+        },
+        [&](const KeepScoreUnits& ku, int n) -> int {
+            RTK_LAUNCH(KID_KEEPSC, keep_scores_kernel, dim3((most + KSC_BLOCK - 1) / KSC_BLOCK, n), dim3(KSC_BLOCK), 0, st, ku);
+            RTK_LAUNCH_CHECK("keep_scores_kernel");
+            most = 0;
+            return RTK_OK;
+        });
 }
 
 extern "C" int rtk_pivotkv_budget_select_batched(const rtk_budget_select_unit* units, int n_units, rtk_stream_t stream) {
     const char* who = "rtk_pivotkv_budget_select_batched";
-    RTK_CHECK_ARG(n_units >= 0, "%s: n_units %d", who, n_units);
-    if (n_units == 0) return RTK_OK;
-    RTK_CHECK_ARG(units, "%s: NULL units", who);
+    const int rc = have_units(units, n_units, who);
+    if (rc <= 0) return rc;
     for (int i = 0; i < n_units; ++i) {
         const rtk_budget_select_unit& u = units[i];
         RTK_CHECK_ARG(u.score && u.idx, "%s: unit %d: NULL score / idx", who, i);
@@ -204,11 +196,9 @@ extern "C" int rtk_pivotkv_budget_select_batched(const rtk_budget_select_unit* u
         RTK_CHECK_ARG(u.keep >= 1 && u.keep <= u.n, "%s: unit %d: keep %d of n %d", who, i, u.keep, u.n);
     }
     hipStream_t st = (hipStream_t)stream;
-    BudgetSelectUnits bu;
-    for (int i0 = 0; i0 < n_units; i0 += RTK_BUDGET_SELECT_MAX_UNITS) {
-        const int n = std::min(n_units - i0, RTK_BUDGET_SELECT_MAX_UNITS);
-        for (int i = 0; i < RTK_BUDGET_SELECT_MAX_UNITS; ++i) bu.u[i] = units[i0 + std::min(i, n - 1)];
-        RTK_LAUNCH(KID_BSELECT, budget_select_kernel, dim3(n), dim3(BSEL_BLOCK), 0, st, bu);
+    for (int b = 0; b < n_units; b += RTK_BUDGET_SELECT_MAX_UNITS) {
+        const int n = std::min(n_units - b, RTK_BUDGET_SELECT_MAX_UNITS);
+        RTK_LAUNCH(KID_BSELECT, budget_select_kernel, dim3(n), dim3(BSEL_BLOCK), 0, st, pad_units<BudgetSelectUnits>(units + b, n));
         RTK_LAUNCH_CHECK("budget_select_kernel");
     }
     return RTK_OK;
@@ -216,9 +206,8 @@ extern "C" int rtk_pivotkv_budget_select_batched(const rtk_budget_select_unit* u
 
 extern "C" int rtk_pivotkv_squeeze_batched(const rtk_squeeze_unit* units, int n_units, rtk_stream_t stream) {
     const char* who = "rtk_pivotkv_squeeze_batched";
-    RTK_CHECK_ARG(n_units >= 0, "%s: n_units %d", who, n_units);
-    if (n_units == 0) return RTK_OK;
-    RTK_CHECK_ARG(units, "%s: NULL units", who);
+    int rc = have_units(units, n_units, who);
+    if (rc <= 0) return rc;
     for (int i = 0; i < n_units; ++i) {
         const rtk_squeeze_unit& u = units[i];
         RTK_CHECK_ARG(u.base, "%s: unit %d: NULL pointer", who, i);
@@ -228,48 +217,36 @@ extern "C" int rtk_pivotkv_squeeze_batched(const rtk_squeeze_unit* units, int n_
         RTK_CHECK_ARG(u.rows_in <= 0x7fff0000, "%s: unit %d: rows_in %lld does not fit the int32 index list", who, i,
                       (long long)u.rows_in);
         RTK_CHECK_ARG(u.rows_out == 0 || u.idx, "%s: unit %d: NULL idx", who, i);
-        RTK_CHECK_ARG(u.streams > 0, "%s: unit %d: streams %d", who, i, u.streams);
-        RTK_CHECK_ARG(u.row_bytes > 0 && u.row_bytes % 4 == 0, "%s: unit %d: row_bytes %d is not a positive multiple of 4", who,
-                      i, u.row_bytes);
-        RTK_CHECK_ARG(((uintptr_t)u.base & 3) == 0 && u.stream_stride % 4 == 0, "%s: unit %d: base / stream_stride not 4-byte aligned",
-                      who, i);
+        if ((rc = check_stream_unit(u, who, i)) != RTK_OK) return rc;
         RTK_CHECK_ARG(u.first <= (INT64_MAX >> 2) / u.row_bytes, "%s: unit %d: first overflows a byte offset", who, i);
-        RTK_CHECK_ARG((u.row_bytes + SQZ_SLICE - 1) / SQZ_SLICE <= 0x3fffffff / u.streams,
+        // (the slices of a row, written so that a row_bytes near INT32_MAX does not overflow)
+        RTK_CHECK_ARG((u.row_bytes - 1) / SQZ_SLICE + 1 <= 0x3fffffff / u.streams,
                       "%s: unit %d: too many workgroups for one launch", who, i);
     }
     hipStream_t st = (hipStream_t)stream;
-    SqueezeUnits su;
-    int n = 0;
-    unsigned grid_x = 0;
-    auto launch = [&]() -> int {
-        if (n == 0) return RTK_OK;
-        for (int i = n; i < RTK_SQUEEZE_MAX_UNITS; ++i) su.u[i] = su.u[n - 1];   // (never read)
-        RTK_LAUNCH(KID_SQUEEZE, squeeze_units_kernel, dim3(grid_x, n), dim3(SQZ_BLOCK), 0, st, su);
-        RTK_LAUNCH_CHECK("squeeze_units_kernel");
-        n = 0;
-        grid_x = 0;
-        return RTK_OK;
-    };
-    for (int i = 0; i < n_units; ++i) {
-        const rtk_squeeze_unit& u = units[i];
-        if (u.rows_out == 0) continue;
-        SqueezeDev& dv = su.u[n];
-        dv.dst = (char*)u.base + u.first * u.row_bytes;
-        dv.idx = u.idx;
-        dv.stream_stride = u.stream_stride;
-        dv.row_bytes = u.row_bytes;
-        dv.rows_out = (int32_t)u.rows_out;
-        dv.rows_in = (int32_t)u.rows_in;
-        dv.streams = u.streams;
-        dv.pad = 0;
-        const bool wide16 = (((uintptr_t)dv.dst | (uintptr_t)dv.stream_stride | (uintptr_t)dv.row_bytes) & 15) == 0;
-        const int slices = (u.row_bytes + SQZ_SLICE - 1) / SQZ_SLICE;
-        dv.slices = slices | (wide16 ? SQZ_WIDE16 : 0);
-        grid_x = std::max(grid_x, (unsigned)(slices * u.streams));
-        if (++n == RTK_SQUEEZE_MAX_UNITS) {
-            const int rc = launch();
-            if (rc != RTK_OK) return rc;
-        }
-    }
-    return launch();
+    unsigned grid_x = 0;   // of the launch being filled: its largest unit's
+    return launch_units<SqueezeUnits>(
+        n_units,
+        [&](int i, SqueezeDev& dv) {
+            const rtk_squeeze_unit& u = units[i];
+            if (u.rows_out == 0) return false;
+            dv.dst = (char*)u.base + u.first * u.row_bytes;
+            dv.idx = u.idx;
+            dv.stream_stride = u.stream_stride;
+            dv.row_bytes = u.row_bytes;
+            dv.rows_out = (int32_t)u.rows_out;
+            dv.rows_in = (int32_t)u.rows_in;
+            dv.streams = u.streams;
+            dv.pad = 0;
+            const int slices = (u.row_bytes - 1) / SQZ_SLICE + 1;
+            dv.slices = slices | (aligned16(dv.dst, dv.stream_stride, dv.row_bytes) ? SQZ_WIDE16 : 0);
+            grid_x = std::max(grid_x, (unsigned)(slices * u.streams));
+            return true;
+        },
+        [&](const SqueezeUnits& su, int n) -> int {
+            RTK_LAUNCH(KID_SQUEEZE, squeeze_units_kernel, dim3(grid_x, n), dim3(SQZ_BLOCK), 0, st, su);
+            RTK_LAUNCH_CHECK("squeeze_units_kernel");
+            grid_x = 0;
+            return RTK_OK;
+        });
 }

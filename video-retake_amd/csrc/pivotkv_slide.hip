@@ -114,18 +114,13 @@ using namespace rtk;
 
 extern "C" int rtk_pivotkv_slide_batched(const rtk_slide_unit* units, int n_units, rtk_stream_t stream) {
     const char* who = "rtk_pivotkv_slide_batched";
-    RTK_CHECK_ARG(n_units >= 0, "%s: n_units %d", who, n_units);
-    if (n_units == 0) return RTK_OK;
-    RTK_CHECK_ARG(units, "%s: NULL units", who);
+    int rc = have_units(units, n_units, who);
+    if (rc <= 0) return rc;
     for (int i = 0; i < n_units; ++i) {
         const rtk_slide_unit& u = units[i];
         RTK_CHECK_ARG(u.base, "%s: unit %d: NULL pointer", who, i);
         RTK_CHECK_ARG(u.first >= 0 && u.drop >= 0 && u.rows >= 0, "%s: unit %d: negative first / drop / rows", who, i);
-        RTK_CHECK_ARG(u.streams > 0, "%s: unit %d: streams %d", who, i, u.streams);
-        RTK_CHECK_ARG(u.row_bytes > 0 && u.row_bytes % 4 == 0, "%s: unit %d: row_bytes %d is not a positive multiple of 4", who,
-                      i, u.row_bytes);
-        RTK_CHECK_ARG(((uintptr_t)u.base & 3) == 0 && u.stream_stride % 4 == 0, "%s: unit %d: base / stream_stride not 4-byte aligned",
-                      who, i);
+        if ((rc = check_stream_unit(u, who, i)) != RTK_OK) return rc;
         RTK_CHECK_ARG(u.first <= (INT64_MAX >> 2) / u.row_bytes && u.drop <= (INT64_MAX >> 2) / u.row_bytes &&
                           u.rows <= (INT64_MAX >> 2) / u.row_bytes,
                       "%s: unit %d: first / drop / rows overflow a byte offset", who, i);
@@ -135,37 +130,29 @@ extern "C" int rtk_pivotkv_slide_batched(const rtk_slide_unit* units, int n_unit
                       "%s: unit %d: too many workgroups for one launch", who, i);
     }
     hipStream_t st = (hipStream_t)stream;
-    SlideUnits su;
-    int n = 0;
-    unsigned grid_x = 0;
-    auto launch = [&]() -> int {
-        if (n == 0) return RTK_OK;
-        for (int i = n; i < RTK_SLIDE_MAX_UNITS; ++i) su.u[i] = su.u[n - 1];   // (never read)
-        RTK_LAUNCH(KID_SLIDE, slide_units_kernel, dim3(grid_x, n), dim3(SLIDE_BLOCK), 0, st, su);
-        RTK_LAUNCH_CHECK("slide_units_kernel");
-        n = 0;
-        grid_x = 0;
-        return RTK_OK;
-    };
-    for (int i = 0; i < n_units; ++i) {
-        const rtk_slide_unit& u = units[i];
-        if (u.drop == 0 || u.rows == 0) continue;
-        SlideDev& dv = su.u[n];
-        dv.dst = (char*)u.base + u.first * u.row_bytes;
-        dv.stream_stride = u.stream_stride;
-        dv.drop_bytes = u.drop * u.row_bytes;
-        dv.n_bytes = u.rows * u.row_bytes;
-        dv.streams = u.streams;
-        const bool wide16 = (((uintptr_t)dv.dst | (uintptr_t)dv.stream_stride | (uintptr_t)dv.drop_bytes | (uintptr_t)dv.n_bytes) & 15) == 0;
-        const int64_t tile = (int64_t)SLIDE_BLOCK * SLIDE_U * (wide16 ? 16 : 4);
-        // slices of a wide drop; no more of them than there is work for (a drop far beyond the moved rows)
-        const int64_t slices = dv.drop_bytes < tile ? 1 : (std::min(dv.drop_bytes, dv.n_bytes) + tile - 1) / tile;
-        dv.slices = (int32_t)slices | (wide16 ? SLIDE_WIDE16 : 0);
-        grid_x = std::max(grid_x, (unsigned)(slices * u.streams));
-        if (++n == RTK_SLIDE_MAX_UNITS) {
-            const int rc = launch();
-            if (rc != RTK_OK) return rc;
-        }
-    }
-    return launch();
+    unsigned grid_x = 0;   // of the launch being filled: its largest unit's
+    return launch_units<SlideUnits>(
+        n_units,
+        [&](int i, SlideDev& dv) {
+            const rtk_slide_unit& u = units[i];
+            if (u.drop == 0 || u.rows == 0) return false;
+            dv.dst = (char*)u.base + u.first * u.row_bytes;
+            dv.stream_stride = u.stream_stride;
+            dv.drop_bytes = u.drop * u.row_bytes;
+            dv.n_bytes = u.rows * u.row_bytes;
+            dv.streams = u.streams;
+            const bool wide16 = aligned16(dv.dst, dv.stream_stride, dv.drop_bytes, dv.n_bytes);
+            const int64_t tile = (int64_t)SLIDE_BLOCK * SLIDE_U * (wide16 ? 16 : 4);
+            // slices of a wide drop; no more of them than there is work for (a drop far beyond the moved rows)
+            const int64_t slices = dv.drop_bytes < tile ? 1 : (std::min(dv.drop_bytes, dv.n_bytes) + tile - 1) / tile;
+            dv.slices = (int32_t)slices | (wide16 ? SLIDE_WIDE16 : 0);
+            grid_x = std::max(grid_x, (unsigned)(slices * u.streams));
+            return true;
+        },
+        [&](const SlideUnits& su, int n) -> int {
+            RTK_LAUNCH(KID_SLIDE, slide_units_kernel, dim3(grid_x, n), dim3(SLIDE_BLOCK), 0, st, su);
+            RTK_LAUNCH_CHECK("slide_units_kernel");
+            grid_x = 0;
+            return RTK_OK;
+        });
 }

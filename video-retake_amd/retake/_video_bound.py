@@ -1,0 +1,216 @@
+"""The bounded video region of PivotKVCache (not in the reference): ONE mechanism, two policies.  A layer's region is
+everything behind its pinned rows - the rows it held before its first compressed chunk arrived (the system prompt: the
+attention sink); with fp8 rows it is the archive, whose ids begin at `archive_at`.  `video_window_rows` bounds it by age (`slide_window`: the oldest rows go), `video_budget_rows` by score (`evict_budget`: the newest row
+and the best-scored others stay); build_kvcache refuses the two together.  The functions take the cache.
+
+`after_forward` calls the policy that is on.  `_plan` walks the layers, picks those whose region holds more than rows + slack, refuses
+what cannot be moved - before anything is launched or changed - and describes what moves as byte streams `(data_ptr,
+stream_stride, streams, row_bytes, first)`.  The policy appends its own tail to each and launches per device on the current
+stream; `_commit` keeps the books: length / len8 and pos_len shrink, num_evicted_tokens and the policy's `*_dropped` list
+grow, `_seen_tokens` is left alone.  Rows below every earlier mark are rewritten, so the epoch moves: earlier marks raise
+in `rewind`, live branches are dead; the `video_end` that `after_forward` takes next is valid.  No buffer is allocated or
+replaced.
+"""
+import torch
+
+from . import _native as nv
+from ._cache_state import _Batch, _LayerStore, _on_device
+
+
+def bound(cache):
+    """(rows, slack) of the window or the budget, whichever is on; None with both off."""
+    if cache.video_window_rows is not None:
+        return cache.video_window_rows, cache.video_window_slack
+    return None if cache.video_budget_rows is None else (cache.video_budget_rows, cache.video_budget_slack)
+
+
+def configure(cache, config, word: str, prompt_guided: str, clash=None):
+    """build_kvcache: longvideo_kwargs' video_<word>_rows / video_<word>_slack, validated and set on the cache -> the rows
+    (None: off).  `prompt_guided`: the policy's own sentence on why it does not serve prompt_guided_scoring; `clash`: the
+    option the policy does not go together with and why, if that option is on."""
+    rows_key, slack_key = f"video_{word}_rows", f"video_{word}_slack"
+    rows, slack = config.longvideo_kwargs.get(rows_key, None), config.longvideo_kwargs.get(slack_key, 0)
+    keys = f"{rows_key} / {slack_key}"
+
+    def is_int(x, least):
+        return isinstance(x, int) and not isinstance(x, bool) and x >= least
+    if not (rows is None or is_int(rows, 1)) or not is_int(slack, 0):
+        raise ValueError(f"{keys}: {rows_key} must be an int > 0 (or None: no {word}) and {slack_key} "
+                         f"an int >= 0, got {rows!r} and {slack!r}")
+    if rows is not None:
+        if clash is not None:
+            raise ValueError(f"{keys} do not go together with {clash}")
+        if cache.defer_rerotation:
+            raise ValueError(f"{keys} do not serve defer_rerotation (the sharded prefill): its block caches hold "
+                             "un-rotated keys and provisional ids until `finalize`")
+        if cache.prompt_guided_scoring:
+            raise ValueError(f"{keys} do not serve prompt_guided_scoring: {prompt_guided}")
+        setattr(cache, rows_key, rows)
+        setattr(cache, slack_key, slack)
+    return rows
+
+
+def region_room(cache, st: _LayerStore, first: int, more: int) -> int:
+    """The rows at which a buffer stops growing - the pinned rows (`first`; not known yet: what the layer holds), a full
+    window or budget with its slack and `more` (the in-flight chunk).  0 with both off, and 0 while `kvcache_compression` is
+    off: text, question and decode rows grow a buffer as they always did (by doubling), so the plateau holds only if the
+    caller's `reserve_tokens` covers them on top of pinned + rows + slack + one chunk."""
+    b = bound(cache)
+    return 0 if b is None or not cache.kvcache_compression else max(first, 0) + sum(b) + more
+
+
+def _streams(first: int, *ts):
+    """Dense tensors of ONE shape - [1, H, cap, D], [1, H, cap] or [P, cap] - as H (P) byte streams of cap rows each, from
+    row `first` on.  (The shape is read once: this runs per layer on the host, in front of every move.)"""
+    shape = ts[0].shape
+    ax = min(len(shape), 3) - 1
+    row = ts[0].element_size() * (shape[3] if len(shape) == 4 else 1)
+    return [(t.data_ptr(), shape[ax] * row, shape[ax - 1], row, first) for t in ts]
+
+
+def _plan(cache, key: str, cannot: str, check=lambda *layer: None):
+    """{device index: [(layer, store, first, n, ids, streams)]} of the layers whose region [first, first + n) holds more than
+    rows + slack rows - layers are bounded independently: each has its own count, a skipped layer none.  `streams`: the
+    moving tensors, the id buffer last if the layer keeps ids (`ids`).  ValueError for a layer that cannot be moved, then
+    whatever the policy's own `check` of the layer raises."""
+    rows, slack = bound(cache)
+    fp8 = cache.kv_cache_dtype is not None
+    by_device = {}
+    for l, st in enumerate(cache._layers):
+        first = st.archive_at if fp8 else st.pinned
+        if st._k is None or first < 0:
+            continue
+        n = st.len8 if fp8 else st.c.length - first
+        if n <= rows + slack:
+            continue
+        ids = st._pos is not None and st.c.pos_len > 0
+        if st.c.cap == 0 or (ids and st.c.pos_len != st.c.length + st.len8):
+            raise ValueError(f"{key}: layer {l} {cannot} - its buffers are not the cache's own dense blocks, "
+                             f"or it keeps ids for {st.c.pos_len} of its {st.c.length + st.len8} rows")
+        check(l, st, first, n, ids)
+        # K and V from `first` on; with fp8 rows the archive [0, len8): codes of D bytes a row, one fp32 scale a row
+        streams = _streams(0, st.k8, st.v8) + _streams(0, st.ks8, st.vs8) if fp8 else _streams(first, st._k, st._v)
+        if ids:    # in sequence order: the region's ids begin at `first`
+            streams += _streams(first, st._pos)
+        by_device.setdefault(st._k.get_device(), []).append((l, st, first, n, ids, streams))
+    return by_device
+
+
+def _commit(cache, by_device, dropped):
+    """The bookkeeping once every launch is issued: each planned layer is down to the bound's rows."""
+    rows, fp8 = bound(cache)[0], cache.kv_cache_dtype is not None
+    dropped.extend([0] * (len(cache._layers) - len(dropped)))
+    for layers in by_device.values():
+        for l, st, _, n, ids, _ in layers:
+            d = n - rows
+            if fp8:
+                st.len8 -= d
+            else:
+                st.c.length -= d
+            if ids:
+                st.c.pos_len -= d
+            cache.update_num_evicted_tokens(d, l)
+            dropped[l] += d
+    cache._epoch += 1
+    for br in cache._branches or ():   # (noted on the branches: this cache may be released before they look)
+        if br._fork_dead is None:
+            br._fork_dead = "epoch"
+
+
+def _launch(dev: int, name: str, units, n: int):
+    nv.check(_on_device(dev, getattr(nv.lib, name), units, n, nv.raw_stream(dev)), name)
+
+
+def slide_window(cache):
+    """Drop the oldest rows of every layer whose video region holds more than W + slack rows, down to W: K, V and the ids of
+    all such layers (the archive's codes, scales and ids with fp8 rows) move down in place in ONE rtk_pivotkv_slide_batched
+    call (per device; a call is one kernel launch per 96 moving tensors: 28 layers x (K, V, ids) is one, 28 x 5 archive
+    tensors two).  get_prev_temporal_idx still reads the last stored id."""
+    W = cache.video_window_rows
+    by_device = _plan(cache, "video_window_rows", "cannot slide")
+    for dev, layers in by_device.items():
+        units = []
+        for _, st, first, n, ids, streams in layers:
+            d = n - W
+            units += [s + (d, W) for s in streams]
+            if ids:    # the ids of later 16-bit rows follow the region's and move with them
+                units[-1] = streams[-1] + (d, st.c.pos_len - first - d)
+        _launch(dev, "rtk_pivotkv_slide_batched", (nv.SlideUnit * len(units))(*[nv.SlideUnit(*u) for u in units]), len(units))
+    if by_device:
+        _commit(cache, by_device, cache.window_dropped)
+
+
+def evict_budget(cache):
+    """Evict every layer whose video region holds n > B + slack rows down to B: the newest row (get_prev_temporal_idx reads
+    its id: the ids of every later chunk stay those of an unbounded cache) and the B - 1 best-scored others survive (ties to
+    the oldest), in sequence order.  A row's score is the fp32 score its chunk's selection saw for it (`keep_scores`) - a
+    column sum of row-stochastic softmaxes averaged over heads, which averages 1 over any chunk whatever its length, so
+    rows of different chunks compare directly.  Per device ONE rtk_pivotkv_budget_select_batched call writes
+    each layer's ascending survivor list, ONE rtk_pivotkv_squeeze_batched call moves K, V, ids and scores of all such layers
+    down in place (the archive's codes, scales, ids and scores with fp8 rows).  Pinned rows never move, ids are not
+    rescaled again; the scored rows shrink with the region.  ValueError: a region row without a score - text or decode rows
+    appended behind the video and not rewound.  (With fp8 rows such rows live in the 16-bit buffers, but their ids lie
+    between the archive's: the survivors' ids are then no contiguous block, and the eviction raises all the same.  So the
+    id unit covers exactly [first, first + n) = [first, pos_len): no 16-bit row's id lies behind the region's at an
+    eviction, and there is nothing for rtk_pivotkv_slide_batched to do.)"""
+    B, fp8 = cache.video_budget_rows, cache.kv_cache_dtype is not None
+
+    def scored(l, st, first, n, ids):
+        if st.sc is None or st.sc_len != n or (ids and st.c.pos_len != first + n):
+            raise ValueError(f"video_budget_rows: layer {l} holds {n} video rows"
+                             f"{'' if fp8 else ' and other rows'} behind its pinned rows and scores for "
+                             f"{st.sc_len if st.sc is not None else 0} of them - text or decode rows were appended after the "
+                             "video and left in place.  Rewind to `video_end` before the stream goes on (a question's "
+                             "rows carry no score and cannot take part in the eviction)")
+    by_device = _plan(cache, "video_budget_rows", "cannot be evicted", scored)
+    for dev, layers in by_device.items():
+        idx = cache._buf(f"budget_idx{dev}", (len(layers), B), torch.int32, layers[0][1]._k.device)
+        sel = (nv.BudgetSelectUnit * len(layers))()
+        units = []
+        for i, (_, st, _, n, _, streams) in enumerate(layers):
+            ip = idx[i].data_ptr()
+            sel[i].score, sel[i].idx, sel[i].n, sel[i].keep = st.sc.data_ptr(), ip, n, B
+            units += [s + (B, n, ip) for s in streams + [(st.sc.data_ptr(), 0, 1, 4, 0)]]
+        _launch(dev, "rtk_pivotkv_budget_select_batched", sel, len(layers))
+        _launch(dev, "rtk_pivotkv_squeeze_batched", (nv.SqueezeUnit * len(units))(*[nv.SqueezeUnit(*u) for u in units]), len(units))
+    if by_device:
+        _commit(cache, by_device, cache.budget_dropped)
+        for layers in by_device.values():
+            for _, st, *_ in layers:
+                st.sc_len = B
+
+
+def keep_scores(cache, b: _Batch, layers):
+    """video_budget_rows: the scores of the rows a flush has just committed, `score[keep_idx[r]]` as the selection left
+    them (key-patch rows at 1.0), into the layers' score stores at those rows - one rtk_pivotkv_keep_scores_batched
+    launch per flush, whichever route flushed (so also per `flush_every_layers` group)."""
+    if cache.video_budget_rows is None:
+        return
+    keep, fp8 = b.keep, cache.kv_cache_dtype is not None
+    units = (nv.KeepScoresUnit * len(layers))()
+    for u, l in zip(units, layers):
+        st, sl = cache._layers[l], b.slot(l)
+        at = (st.len8 if fp8 else st.c.length - st.pinned) - keep    # region row of the first kept row
+        if st.sc is None or st.sc.numel() < at + keep:
+            cap = max(at + keep, 2 * (st.sc.numel() if st.sc is not None else 0), 1024, region_room(cache, st, 0, b.L))
+            sc = torch.empty(cap, dtype=torch.float32, device=b.device)
+            if st.sc is not None and st.sc_len:
+                sc[:st.sc_len].copy_(st.sc[:st.sc_len])
+            st.sc = sc
+        u.score, u.keep_idx = b.score[sl].data_ptr(), b.keep_idx[sl].data_ptr()
+        u.dst, u.keep = st.sc.data_ptr() + 4 * at, keep
+        if st.sc_len == at:   # (else: unscored rows lie in between - text that was not rewound; `evict_budget` raises)
+            st.sc_len = at + keep
+    _launch(b.dev_index, "rtk_pivotkv_keep_scores_batched", units, len(layers))
+
+
+def row_scores(cache, layer_idx: int) -> torch.Tensor:
+    """video_budget_rows: a copy of the scores the layer's video region keeps, fp32, in region order (deferred work is
+    flushed first).  Empty for a layer without video rows; ValueError with the budget off."""
+    if cache.video_budget_rows is None:
+        raise ValueError("PivotKVCache.row_scores: no scores are kept without video_budget_rows")
+    cache._flush()
+    st = cache._layers[layer_idx] if layer_idx < len(cache._layers) else None
+    if st is None or st.sc is None:
+        return torch.empty(0, dtype=torch.float32)
+    return st.sc[:st.sc_len].clone()

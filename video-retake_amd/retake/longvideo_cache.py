@@ -29,6 +29,7 @@ Where the rest lives (the names are re-exported here, and the other modules of t
     _hf_cache         DynamicCache: which class PivotKVCache subclasses, and why
     _cache_state      what a layer and a slot of the batch own (_LayerStore, _Batch, ...), the list views, CacheMark
     native_attention  chunk_attention, native_attention (causal offset from the HF mask), the fp8 row helpers
+    _video_bound      the bounded video region: the sliding window and the video budget, planned and committed by one mechanism
 """
 from __future__ import annotations
 
@@ -39,7 +40,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from . import _native as nv
+from . import _native as nv, _video_bound
 from ._cache_state import (CacheMark, _Batch, _CacheView, _LayerMark, _LayerStore, _Rotary, _Side, _Update,  # noqa: F401
                            _inv_stamp, _on_device, _version_of)
 from ._hf_cache import DynamicCache, _hf_dynamic_cache_is_legacy, _ListDynamicCache  # noqa: F401
@@ -211,30 +212,19 @@ class PivotKVCache(DynamicCache):
         # the GQA-packed few-row kernel first (chunk_attention(packed_gqa=True)); None (default): exactly as without it
         self.decode_attention = None
         self.decode_attention_calls = 0   # ... of which took the packed kernel
-        # MI355X build option, two top-level keys of longvideo_kwargs (build_kvcache reads them; NOT in the reference, which
-        # processes a finished video): video_window_rows = W bounds the compressed video rows a layer holds, for streams that
-        # do not end.  A layer's VIDEO REGION is everything behind its pinned rows - the rows it held before its first
-        # compressed chunk arrived (the system prompt: the attention sink), see _LayerStore.pinned; with fp8 rows it is the
-        # archive.  When `after_forward` finds more than W + video_window_slack rows there it drops the oldest region - W of
-        # them: every later row of K, V and the ids (codes, scales and ids of the archive) moves down in place, all layers in
-        # one rtk_pivotkv_slide_batched call (`_slide_window`).  Slides happen ONLY in `after_forward`: a caller that never
-        # calls it gets no window.  None (default): off, nothing changes.  The slack trades memory for fewer slides: a
-        # slide moves the whole window whatever it drops.
-        self.video_window_rows = None
-        self.video_window_slack = 0
+        # MI355X build options, top-level keys of longvideo_kwargs (build_kvcache reads them; NOT in the reference, which
+        # processes a finished video), for streams that do not end: a bound on a layer's VIDEO REGION - everything behind its
+        # pinned rows (_LayerStore.pinned); with fp8 rows the archive.  video_window_rows = W bounds it by age: when
+        # `after_forward` finds more than W + video_window_slack rows there it drops the oldest, down to W.  video_budget_rows
+        # = B bounds it by SCORE (a rule of this project's own - answer quality is not evaluated): down to the newest row and
+        # the B - 1 best-scored others; then a chunk that keeps all of its rows is scored all the same
+        # (score_when_keeping_all).  Both act ONLY in `after_forward`: a caller that never calls it gets neither.  The slack
+        # trades memory for fewer moves: a move rewrites the whole region whatever it drops.  None (default): off, nothing
+        # changes, no score buffer exists.  The mechanism, and what each policy does: _video_bound.
+        self.video_window_rows, self.video_window_slack = None, 0
+        self.video_budget_rows, self.video_budget_slack = None, 0
         self.window_dropped: List[int] = []   # per layer: rows the window has dropped so far (also counted as evicted)
-        # MI355X build option, two top-level keys of longvideo_kwargs (build_kvcache reads them; NOT in the reference, and a
-        # rule of this project's own - answer quality is not evaluated): video_budget_rows = B bounds the same video region
-        # by SCORE instead of by age.  Every region row keeps the fp32 score its chunk's selection saw for it (after the
-        # key-patch override to 1.0; _LayerStore.sc, filled by every flush) - a column sum of row-stochastic softmaxes averaged
-        # over heads, which averages 1 over any chunk whatever its length, so rows of different chunks compare directly.  When
-        # `after_forward` finds more than B + video_budget_slack rows in a layer's region it keeps the NEWEST row
-        # (get_prev_temporal_idx reads its id: the ids of every later chunk stay those of an unbounded cache) and the B - 1
-        # best-scored others, ties to the oldest, in sequence order (`_evict_budget`).  A chunk that keeps all of its rows
-        # is scored all the same (score_when_keeping_all).  None (default): off, nothing changes, no score buffer exists.
-        self.video_budget_rows = None
-        self.video_budget_slack = 0
-        self.budget_dropped: List[int] = []   # per layer: rows the budget has dropped so far (also counted as evicted)
+        self.budget_dropped: List[int] = []   # ... and the budget
         self._attn_ws: Dict[Any, torch.Tensor] = {}
 
     def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None, layer_idx=None):
@@ -404,7 +394,7 @@ class PivotKVCache(DynamicCache):
         if st.k8 is not None and st.k8.shape[2] >= need:
             return
         cap = max(need, 2 * (st.k8.shape[2] if st.k8 is not None else 0), self.reserve_archive_tokens or 1024,
-                  self._window_room(st, 0, more), self._budget_room(st, 0, more))
+                  self._region_room(st, 0, more))
         new = [torch.empty((1, Hkv, cap, D), dtype=torch.uint8, device=device) for _ in range(2)] + \
               [torch.empty((1, Hkv, cap), dtype=torch.float32, device=device) for _ in range(2)]
         if st.len8:
@@ -789,7 +779,7 @@ class PivotKVCache(DynamicCache):
         first = st.archive_at if self.kv_cache_dtype is not None else st.pinned
         first = first if first >= 0 else st.pos_len
         cap = max(need, 2 * (st.pos.shape[1] if st.pos is not None else 0), 4096, self.reserve_tokens + self.reserve_archive_tokens,
-                  self._window_room(st, first, more), self._budget_room(st, first, more))
+                  self._region_room(st, first, more))
         buf = torch.empty((P, cap), dtype=torch.int64, device=device)
         if st.pos is not None and st.pos_len:
             buf[:, :st.pos_len].copy_(st.pos[:, :st.pos_len])
@@ -811,9 +801,9 @@ class PivotKVCache(DynamicCache):
         if self._compressed_in_forward:   # the work is flushed: a few tuples per chunk
             self._compressed_in_forward = False
             if self.video_window_rows is not None:
-                self._slide_window()
+                _video_bound.slide_window(self)
             elif self.video_budget_rows is not None:
-                self._evict_budget()
+                _video_bound.evict_budget(self)
             if not self.defer_rerotation:
                 self.last_compressed_mark = self._take_mark(True)
 
@@ -822,196 +812,8 @@ class PivotKVCache(DynamicCache):
         n = self._prompt_len
         return n if 0 < n < L else 0
 
-    # ---- the sliding video window (video_window_rows; not in the reference) ---------------------
-    def _slide_window(self):
-        """Drop the oldest rows of every layer whose video region holds more than W + slack rows, down to W: K, V and the
-        ids of all such layers (the archive's codes, scales and ids with fp8 rows) move down in place in ONE
-        rtk_pivotkv_slide_batched call on the current stream (per device; a call is one kernel launch per 96 moving
-        tensors: 28 layers x (K, V, ids) is one, 28 x 5 archive tensors two).  Layers slide independently - each has its own
-        count, a skipped layer none.  length / len8 and pos_len shrink, num_evicted_tokens and window_dropped grow by it,
-        `_seen_tokens` is left alone; get_prev_temporal_idx still reads the last stored id.  Rows below every earlier mark
-        are rewritten, so the epoch moves: earlier marks raise in `rewind`, live branches are dead; the `video_end` that
-        `after_forward` takes next is valid.  No buffer is allocated or replaced."""
-        W, S = self.video_window_rows, self.video_window_slack
-        fp8 = self.kv_cache_dtype is not None
-        plan, by_device = [], {}
-        for l, st in enumerate(self._layers):
-            first = st.archive_at if fp8 else st.pinned
-            if st._k is None or first < 0:
-                continue
-            region = st.len8 if fp8 else st.c.length - first
-            if region <= W + S:
-                continue
-            d = region - W
-            ids = st._pos is not None and st.c.pos_len > 0
-            if st.c.cap == 0 or (ids and st.c.pos_len != st.c.length + st.len8):
-                raise ValueError(f"video_window_rows: layer {l} cannot slide - its buffers are not the cache's own dense blocks, "
-                                 f"or it keeps ids for {st.c.pos_len} of its {st.c.length + st.len8} rows")
-            units = by_device.setdefault(st._k.get_device(), [])
-            if fp8:    # the archive [0, len8): codes of D bytes a row, one fp32 scale a row
-                Hkv, cap8, D = st.k8.shape[1], st.k8.shape[2], st.k8.shape[3]
-                for t, row in ((st.k8, D), (st.v8, D), (st.ks8, 4), (st.vs8, 4)):
-                    units.append((t.data_ptr(), cap8 * row, Hkv, row, 0, d, W))
-            else:
-                k = st._k
-                row = k.shape[3] * k.element_size()
-                for t in (k, st._v):
-                    units.append((t.data_ptr(), k.shape[2] * row, k.shape[1], row, first, d, W))
-            if ids:    # in sequence order: the region's ids begin at `first`, those of later 16-bit rows follow them
-                units.append((st._pos.data_ptr(), st._pos.shape[1] * 8, st._pos.shape[0], 8, first, d,
-                              st.c.pos_len - first - d))
-            plan.append((l, st, d, ids))
-        if not plan:
-            return
-        for idx, units in by_device.items():
-            arr = (nv.SlideUnit * len(units))(*[nv.SlideUnit(*u) for u in units])
-            nv.check(_on_device(idx, nv.lib.rtk_pivotkv_slide_batched, arr, len(units), nv.raw_stream(idx)),
-                     "rtk_pivotkv_slide_batched")
-        dropped = self.window_dropped
-        dropped.extend([0] * (len(self._layers) - len(dropped)))
-        for l, st, d, ids in plan:
-            if fp8:
-                st.len8 -= d
-            else:
-                st.c.length -= d
-            if ids:
-                st.c.pos_len -= d
-            self.update_num_evicted_tokens(d, l)
-            dropped[l] += d
-        self._epoch += 1
-        for br in self._branches or ():   # (noted on the branches: this cache may be released before they look)
-            if br._fork_dead is None:
-                br._fork_dead = "epoch"
-
-    def _window_room(self, st: _LayerStore, first: int, more: int) -> int:
-        """video_window_rows: the rows at which a buffer stops growing - the pinned rows (`first`; not known yet: what the
-        layer holds), a full window with its slack and `more` (the in-flight chunk).  0 with the window off, and 0 while
-        `kvcache_compression` is off: text, question and decode rows grow a buffer as they always did (by doubling), so the
-        plateau holds only if the caller's `reserve_tokens` covers them on top of pinned + W + slack + one chunk."""
-        if self.video_window_rows is None or not self.kvcache_compression:
-            return 0
-        return max(first, 0) + self.video_window_rows + self.video_window_slack + more
-
-    # ---- the video budget (video_budget_rows; not in the reference) ------------------------------
-    def _budget_room(self, st: _LayerStore, first: int, more: int) -> int:
-        """video_budget_rows: `_window_room`'s sibling - the rows at which a buffer stops growing: the pinned rows, a full
-        budget with its slack and `more` (the in-flight chunk).  0 with the budget off or `kvcache_compression` off."""
-        if self.video_budget_rows is None or not self.kvcache_compression:
-            return 0
-        return max(first, 0) + self.video_budget_rows + self.video_budget_slack + more
-
-    def _keep_scores(self, b: _Batch, layers):
-        """video_budget_rows: the scores of the rows a flush has just committed, `score[keep_idx[r]]` as the selection left
-        them (key-patch rows at 1.0), into the layers' score stores at those rows - one rtk_pivotkv_keep_scores_batched
-        launch per flush, whichever route flushed (so also per `flush_every_layers` group)."""
-        if self.video_budget_rows is None:
-            return
-        keep, fp8 = b.keep, self.kv_cache_dtype is not None
-        units = (nv.KeepScoresUnit * len(layers))()
-        for u, l in zip(units, layers):
-            st, sl = self._layers[l], b.slot(l)
-            at = (st.len8 if fp8 else st.c.length - st.pinned) - keep    # region row of the first kept row
-            if st.sc is None or st.sc.numel() < at + keep:
-                cap = max(at + keep, 2 * (st.sc.numel() if st.sc is not None else 0), 1024, self._budget_room(st, 0, b.L))
-                sc = torch.empty(cap, dtype=torch.float32, device=b.device)
-                if st.sc is not None and st.sc_len:
-                    sc[:st.sc_len].copy_(st.sc[:st.sc_len])
-                st.sc = sc
-            u.score, u.keep_idx = b.score[sl].data_ptr(), b.keep_idx[sl].data_ptr()
-            u.dst, u.keep = st.sc.data_ptr() + 4 * at, keep
-            if st.sc_len == at:   # (else: unscored rows lie in between - text that was not rewound; `_evict_budget` raises)
-                st.sc_len = at + keep
-        idx = b.dev_index
-        nv.check(_on_device(idx, nv.lib.rtk_pivotkv_keep_scores_batched, units, len(layers), nv.raw_stream(idx)),
-                 "rtk_pivotkv_keep_scores_batched")
-
-    def row_scores(self, layer_idx: int) -> torch.Tensor:
-        """video_budget_rows: a copy of the scores the layer's video region keeps, fp32, in region order (deferred work is
-        flushed first).  Empty for a layer without video rows; ValueError with the budget off."""
-        if self.video_budget_rows is None:
-            raise ValueError("PivotKVCache.row_scores: no scores are kept without video_budget_rows")
-        self._flush()
-        st = self._layers[layer_idx] if layer_idx < len(self._layers) else None
-        if st is None or st.sc is None:
-            return torch.empty(0, dtype=torch.float32)
-        return st.sc[:st.sc_len].clone()
-
-    def _evict_budget(self):
-        """Evict every layer whose video region holds n > B + slack rows down to B: the newest row and the B - 1 best-scored
-        others survive (ties to the oldest), in sequence order.  Planned like `_slide_window`, per device: ONE
-        rtk_pivotkv_budget_select_batched call writes each layer's ascending survivor list, ONE rtk_pivotkv_squeeze_batched
-        call moves K, V, ids and scores of all such layers down in place (the archive's codes, scales, ids and scores with
-        fp8 rows).  Pinned rows never move, ids are not rescaled again.  length / len8, pos_len and the scored rows shrink, num_evicted_tokens
-        and budget_dropped grow by n - B.  Rows below every earlier mark are rewritten, so the epoch moves exactly as for a
-        slide.  ValueError, before anything is launched or changed: a region row without a score - text or decode rows
-        appended behind the video and not rewound.  (With fp8 rows such rows live in the 16-bit buffers, but their ids lie
-        between the archive's: the survivors' ids are then no contiguous block, and the eviction raises all the same.  So no
-        16-bit row's id ever lies behind the region's at an eviction: there is nothing for rtk_pivotkv_slide_batched to do.)"""
-        B, S = self.video_budget_rows, self.video_budget_slack
-        fp8 = self.kv_cache_dtype is not None
-        plan, by_device = [], {}
-        for l, st in enumerate(self._layers):
-            first = st.archive_at if fp8 else st.pinned
-            if st._k is None or first < 0:
-                continue
-            n = st.len8 if fp8 else st.c.length - first
-            if n <= B + S:
-                continue
-            ids = st._pos is not None and st.c.pos_len > 0
-            if st.c.cap == 0 or (ids and st.c.pos_len != st.c.length + st.len8):
-                raise ValueError(f"video_budget_rows: layer {l} cannot be evicted - its buffers are not the cache's own dense "
-                                 f"blocks, or it keeps ids for {st.c.pos_len} of its {st.c.length + st.len8} rows")
-            if st.sc is None or st.sc_len != n or (ids and st.c.pos_len != first + n):
-                raise ValueError(f"video_budget_rows: layer {l} holds {n} video rows"
-                                 f"{'' if fp8 else ' and other rows'} behind its pinned rows and scores for "
-                                 f"{st.sc_len if st.sc is not None else 0} of them - text or decode rows were appended after the "
-                                 "video and left in place.  Rewind to `video_end` before the stream goes on (a question's "
-                                 "rows carry no score and cannot take part in the eviction)")
-            by_device.setdefault(st._k.get_device(), []).append((l, st, first, n, ids))
-        if not by_device:
-            return
-        for dev, layers in by_device.items():
-            idx = self._buf(f"budget_idx{dev}", (len(layers), B), torch.int32, layers[0][1]._k.device)
-            sel = (nv.BudgetSelectUnit * len(layers))()
-            units = []
-            for i, (l, st, first, n, ids) in enumerate(layers):
-                ip = idx[i].data_ptr()
-                sel[i].score, sel[i].idx, sel[i].n, sel[i].keep = st.sc.data_ptr(), ip, n, B
-                if fp8:    # the archive [0, len8): codes of D bytes a row, one fp32 scale a row
-                    Hkv, cap8, D = st.k8.shape[1], st.k8.shape[2], st.k8.shape[3]
-                    for t, row in ((st.k8, D), (st.v8, D), (st.ks8, 4), (st.vs8, 4)):
-                        units.append((t.data_ptr(), cap8 * row, Hkv, row, 0, B, n, ip))
-                else:
-                    k = st._k
-                    row = k.shape[3] * k.element_size()
-                    for t in (k, st._v):
-                        units.append((t.data_ptr(), k.shape[2] * row, k.shape[1], row, first, B, n, ip))
-                if ids:    # in sequence order: the region's ids are rows [first, first + n) = [first, pos_len)
-                    P, cap = st._pos.shape
-                    units.append((st._pos.data_ptr(), cap * 8, P, 8, first, B, n, ip))
-                units.append((st.sc.data_ptr(), 0, 1, 4, 0, B, n, ip))
-                plan.append((l, st, n - B, ids))
-            stream = nv.raw_stream(dev)
-            nv.check(_on_device(dev, nv.lib.rtk_pivotkv_budget_select_batched, sel, len(layers), stream),
-                     "rtk_pivotkv_budget_select_batched")
-            arr = (nv.SqueezeUnit * len(units))(*[nv.SqueezeUnit(*u) for u in units])
-            nv.check(_on_device(dev, nv.lib.rtk_pivotkv_squeeze_batched, arr, len(units), stream), "rtk_pivotkv_squeeze_batched")
-        dropped = self.budget_dropped
-        dropped.extend([0] * (len(self._layers) - len(dropped)))
-        for l, st, d, ids in plan:
-            if fp8:
-                st.len8 -= d
-            else:
-                st.c.length -= d
-            if ids:
-                st.c.pos_len -= d
-            st.sc_len = B
-            self.update_num_evicted_tokens(d, l)
-            dropped[l] += d
-        self._epoch += 1
-        for br in self._branches or ():   # (noted on the branches: this cache may be released before they look)
-            if br._fork_dead is None:
-                br._fork_dead = "epoch"
+    # ---- the bounded video region (video_window_rows / video_budget_rows): functions of _video_bound, bound as methods
+    _region_room, _keep_scores, row_scores = _video_bound.region_room, _video_bound.keep_scores, _video_bound.row_scores
 
     # ---- bookkeeping lists (reference :152-215) ------------------------------------------------
     def update_num_evicted_tokens(self, num_tokens: int, layer_idx: int):
@@ -1139,8 +941,7 @@ class PivotKVCache(DynamicCache):
                 and st.v.shape[2] == st.k.shape[2]:
             return st
         first = st.pinned if st.pinned >= 0 else st.length
-        room = 0 if self.kv_cache_dtype is not None else max(self._window_room(st, first, tokens),
-                                                             self._budget_room(st, first, tokens))
+        room = 0 if self.kv_cache_dtype is not None else self._region_room(st, first, tokens)
         cap = max(need, 2 * (st.k.shape[2] if st.k is not None else 0), 1024, self.reserve_tokens, room)
         shape = (1, like.shape[1], cap, like.shape[3])
         nk = torch.empty(shape, dtype=like.dtype, device=like.device)
@@ -2252,37 +2053,13 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
                                  "cannot read the fp8 rows")
             if cache.defer_rerotation:
                 raise ValueError("kv_cache_dtype='fp8_e4m3' does not serve defer_rerotation (the sharded prefill)")
-        W, S = config.longvideo_kwargs.get("video_window_rows", None), config.longvideo_kwargs.get("video_window_slack", 0)
-        keys = "video_window_rows / video_window_slack"
-        if not (W is None or (isinstance(W, int) and not isinstance(W, bool) and W > 0)) \
-                or not (isinstance(S, int) and not isinstance(S, bool) and S >= 0):
-            raise ValueError(f"{keys}: video_window_rows must be an int > 0 (or None: no window) and video_window_slack "
-                             f"an int >= 0, got {W!r} and {S!r}")
-        if W is not None:
-            if cache.defer_rerotation:
-                raise ValueError(f"{keys} do not serve defer_rerotation (the sharded prefill): its block caches hold "
-                                 "un-rotated keys and provisional ids until `finalize`")
-            if cache.prompt_guided_scoring:
-                raise ValueError(f"{keys} do not serve prompt_guided_scoring: a prompt-guided cache belongs to one question, "
-                                 "a window to a stream that does not end")
-            cache.video_window_rows, cache.video_window_slack = W, S
-        B, S = config.longvideo_kwargs.get("video_budget_rows", None), config.longvideo_kwargs.get("video_budget_slack", 0)
-        keys = "video_budget_rows / video_budget_slack"
-        if not (B is None or (isinstance(B, int) and not isinstance(B, bool) and B > 0)) \
-                or not (isinstance(S, int) and not isinstance(S, bool) and S >= 0):
-            raise ValueError(f"{keys}: video_budget_rows must be an int > 0 (or None: no budget) and video_budget_slack "
-                             f"an int >= 0, got {B!r} and {S!r}")
+        W = _video_bound.configure(cache, config, "window", "a prompt-guided cache belongs to one question, a window to a "
+                                   "stream that does not end")
+        B = _video_bound.configure(cache, config, "budget", "its scores answer one question and are not comparable between "
+                                   "chunks, a budget ranks the rows of a stream that does not end",
+                                   clash=None if W is None else "video_window_rows: a layer's video region is bounded by score "
+                                   "or by age, not both")
         if B is not None:
-            if W is not None:
-                raise ValueError(f"{keys} do not go together with video_window_rows: a layer's video region is bounded by "
-                                 "score or by age, not both")
-            if cache.defer_rerotation:
-                raise ValueError(f"{keys} do not serve defer_rerotation (the sharded prefill): its block caches hold "
-                                 "un-rotated keys and provisional ids until `finalize`")
-            if cache.prompt_guided_scoring:
-                raise ValueError(f"{keys} do not serve prompt_guided_scoring: its scores answer one question and are not "
-                                 "comparable between chunks, a budget ranks the rows of a stream that does not end")
-            cache.video_budget_rows, cache.video_budget_slack = B, S
             cache.score_when_keeping_all = True   # no region row without a score
         if cache.prompt_guided_scoring:   # what the mode does not serve: refused here, never a silent fallback
             for key, value, served in (("score_rounding", cache.score_rounding, "fp32"),

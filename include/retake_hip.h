@@ -46,7 +46,9 @@
  *   §K  "FP8 rows of the compressed cache"  rtk_pivotkv_archive_batched, rtk_attention_forward_fp8kv (+ _workspace_bytes_fp8kv),
  *                                       rtk_attention_decode_fp8kv (+ _workspace_bytes_fp8kv), rtk_fp8kv_dequant: opt-in (kv_cache_dtype="fp8_e4m3" with attention_kernel="hip")
  *   §L  "Shared 16-bit rows"            rtk_attention_forward_shared, rtk_attention_decode_shared (+ _workspace_bytes_shared):
- *                                       the keys are [archive | rows of another buffer | own rows] (PivotKVCache.fork)
+ *                                       the keys are [archive | rows of another buffer | own rows] (PivotKVCache.fork);
+ *                                       rtk_attention_decode_wide, _wide_fp8kv, _wide_shared (+ their _workspace_bytes):
+ *                                       the packed calls for up to 64 packed rows, opt-in (multi_token_attention="packed")
  *   §M  "Group decode"                  rtk_attention_decode_group (+ _workspace_bytes): one token of each of several
  *                                       branches in one launch that reads the shared rows once (retake/branch_group.py)
  *   §N  "Sliding window"                rtk_pivotkv_slide_batched: rows of many buffers moved down in place, one call - the
@@ -913,6 +915,43 @@ int rtk_attention_decode_shared(const void* q, int64_t q_stride_h, int64_t q_str
                                 const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
                                 int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
                                 int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+
+/* Wide packed decode: rtk_attention_decode, rtk_attention_decode_fp8kv and rtk_attention_decode_shared for SEVERAL new
+ * rows - the verification step of assisted generation (num_assistant_tokens + 1 rows), a few-token continuation: the same
+ * functions, the same arguments, the envelope R = (Hq / Hkv) * Lq <= 64 packed rows (Lq <= 9 at 7 query heads per kv
+ * head, 8 at 8, 16 at 4, 64 at 1), RTK_BF16 / RTK_F16 with D == 128.  Opt-in (multi_token_attention="packed").
+ *   R <= 16 IS the corresponding rtk_attention_decode* call, bit for bit, workspace size included.
+ *   16 < R <= 64: one workgroup still serves one kv head and one key range, and a tile's K and V rows, fetched from HBM
+ *   once, feed ceil(R / 16) column groups of 16 packed rows, each with its own (max, sum, acc).  Packed row r is position
+ *   r / G of query head hkv * G + r % G (G = Hq / Hkv).  Causal by index per packed row: a key row hidden from a query row
+ *   contributes nothing to it whatever it holds (V rows above a position's diagonal are zeroed, not only their
+ *   probabilities; a tile no row of a column group sees is not read for it).
+ * The plan is that of rtk_attention_decode over the same K (Lk, plus L8 and Ls each rounded up to the key tile T = 32), a
+ * function of (Hkv, K) alone; the partials have its layout, so the workspace queries return nsplit * Hq * Lq * (D + 2) * 4
+ * bytes; the four waves of a workgroup are folded in wave order and the splits in split order: bit-reproducible and
+ * stream-independent.  NOT the bits of rtk_attention_forward*, nor (for R > 16) of Lq single-row rtk_attention_decode*
+ * calls: the fp32 sums are grouped differently.  With L8 % 32 == 0 and Ls % 32 == 0 the segmented calls equal, bit for bit,
+ * rtk_attention_decode_wide over the dequantised, concatenated 16-bit rows with q_offset + L8 + Ls; otherwise the sums
+ * are grouped differently.  Ls == 0 IS the _fp8kv call, and L8 == 0 as well the plain one.
+ * Errors, all before any launch: those of the narrow calls, same codes and messages; RTK_EUNSUPPORTED, naming the
+ * reason, for RTK_F32, D != 128 and (Hq / Hkv) * Lq > 64 - the caller then makes the rtk_attention_forward* call. */
+size_t rtk_attention_decode_wide_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int D, int dtype);
+int rtk_attention_decode_wide(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                              int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                              int D, int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+size_t rtk_attention_decode_wide_workspace_bytes_fp8kv(int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype);
+int rtk_attention_decode_wide_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                    int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                                    const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                    int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
+                                    int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+size_t rtk_attention_decode_wide_workspace_bytes_shared(int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype);
+int rtk_attention_decode_wide_shared(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                     int64_t kv_stride_h, int64_t kv_stride_l, const void* ks, const void* vs, int Ls,
+                                     int64_t s_stride_h, int64_t s_stride_l, const void* k8, const void* v8,
+                                     const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                     int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D,
+                                     int dtype, float scale, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
 
 /* Group decode: ONE new token of each of n_branches sequences that share [archive L8 | shared Ls] and differ in their own
  * rows - the forks of one PivotKVCache, each a token into its answer - in one launch that fetches every archive and

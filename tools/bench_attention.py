@@ -43,6 +43,18 @@ rows as 16-bit rows and once as an fp8 archive in their place.  A sample is DECO
 events; the samples of the two routes are INTERLEAVED (group, successive, group, ...), the median of `reps` each.
 Reported: microseconds per step, their ratio, the shared bytes a step reads once, and what fraction of 8 TB/s the group
 call reaches on them.
+
+    python tools/bench_attention.py --wide [--out profiles/wide_decode_bench.json]
+
+The verification step of assisted generation - Lq 3, 6 and 9 new rows (Hq 28 / Hkv 4: 21, 42 and 63 packed rows, bf16) over
+100 352 keys held as plain rows, as 100 352 shared rows + 64 own rows, and as an fp8 archive in place of the shared rows:
+the wide packed call (rtk_attention_decode_wide / _wide_shared / _wide_fp8kv) against the chunk-kernel call it replaces
+(rtk_attention_forward / _forward_shared / _forward_fp8kv, the route without multi_token_attention) and against the packed
+call at Lq 1 on the same keys, every entry point called directly with resident outputs and workspaces.  A sample is
+DECODE_INNER calls between one pair of HIP events; the samples of the three routes are INTERLEAVED, and each route
+reports its median with the quartiles.  `faster_beyond_iqr`: the replaced call's median exceeds the wide call's by more
+than the sum of the two interquartile ranges - the condition for the Python dispatcher to send the shape to the wide kernel.
+The other geometries the envelope admits (WIDE_OTHER: G = 8, 4, 1 and 16) are timed the same way over the plain rows.
 """
 from __future__ import annotations
 
@@ -371,11 +383,116 @@ def main_group(args):
               f"{r['group']['ms_per_token']:.2f} |")
 
 
+WIDE_ROWS, WIDE_OWN, WIDE_LQS = 100352, 64, (3, 6, 9)
+# the other geometries the envelope admits, over plain rows: (Hq, Hkv, Lq) - G = 8, 4 (NCG 2, 3, 4), 2, 1 (17 and 64 rows), 16
+WIDE_OTHER = [(32, 4, 8), (16, 4, 5), (16, 4, 10), (16, 4, 16), (8, 4, 32), (8, 8, 17), (8, 8, 64), (16, 1, 4)]
+
+
+def main_wide(args):
+    import retake._native as nv
+    import retake.longvideo_cache as lc
+
+    dev = torch.device("cuda:0")
+    dtype, code, scale, stream = torch.bfloat16, nv.RTK_BF16, D ** -0.5, nv.stream()
+    g = torch.Generator(device=dev).manual_seed(0)
+    rnd = lambda *shape: (1.7 * torch.randn(shape, generator=g, device=dev)).to(dtype)   # noqa: E731
+
+    def keys(kind, hkv):
+        """entry-point suffix, own rows, the segment arguments, the segment shape, K/V bytes a call reads once, keep-alive"""
+        kb, vb = rnd(1, hkv, WIDE_ROWS + 256, D), rnd(1, hkv, WIDE_ROWS + 256, D)      # plain rows of a cache buffer
+        ks, vs = kb[:, :, :WIDE_ROWS], vb[:, :, :WIDE_ROWS]                            # ... or another buffer's shared rows
+        if kind == "plain":
+            return "", (ks, vs), (), (), 2 * hkv * WIDE_ROWS * D * 2, ()
+        ko, vo = rnd(1, hkv, WIDE_OWN + 256, D)[:, :, :WIDE_OWN], rnd(1, hkv, WIDE_OWN + 256, D)[:, :, :WIDE_OWN]
+        if kind == "shared16":
+            s16 = (nv.ptr(ks), nv.ptr(vs), WIDE_ROWS, ks.stride(1), ks.stride(2))
+            return ("_shared", (ko, vo), s16 + (None, None, None, None, 0, 0, 0), (0, WIDE_ROWS),
+                    2 * hkv * (WIDE_ROWS + WIDE_OWN) * D * 2, (ks, vs))
+        ak, sk = lc.fp8_quantize_rows(ks.contiguous())
+        av, sv = lc.fp8_quantize_rows(vs.contiguous())
+        a8 = (nv.ptr(ak), nv.ptr(av), nv.ptr(sk), nv.ptr(sv), WIDE_ROWS, ak.stride(1), sk.stride(1))
+        return "_fp8kv", (ko, vo), a8, (WIDE_ROWS,), 2 * hkv * (WIDE_ROWS * (D + 4) + WIDE_OWN * D * 2), (ak, av, sk, sv)
+
+    cases = [(kind, HQ, HKV, WIDE_LQS) for kind in ("plain", "shared16", "fp8_archive")] + \
+            [("plain", hq, hkv, (lq,)) for hq, hkv, lq in WIDE_OTHER]
+    rows = []
+    for kind, hq, hkv, lqs in cases:
+        sfx, (k, v), segs, seg_shape, kv_bytes, _alive = keys(kind, hkv)
+        Lk = k.shape[2]
+        for Lq in lqs:
+            q = rnd(1, Lq, hq * D).view(1, Lq, hq, D).transpose(1, 2)
+
+            def direct(fn, n, query=None):
+                """DECODE_INNER back-to-back calls of one entry point on the first n query rows; resident output, workspace."""
+                qn = q[:, :, :n]
+                need = getattr(nv.lib, (query or fn + "_workspace_bytes") + sfx)(hq, hkv, n, Lk, *seg_shape, D, code)
+                ws = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)   # (0: the chunk kernel needs no split here)
+                out = torch.empty((1, n, hq, D), dtype=dtype, device=dev)
+                call = getattr(nv.lib, fn + sfx)
+                a = (nv.ptr(qn), qn.stride(1), qn.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2)) + tuple(segs) + \
+                    (nv.ptr(out), hq, hkv, n, Lk, Lk - n, D, code, scale, nv.ptr(ws), need, stream)
+
+                def run():
+                    for _ in range(DECODE_INNER):
+                        nv.check(call(*a), fn + sfx)
+                return run, out
+
+            routes = {"wide": direct("rtk_attention_decode_wide", Lq),
+                      "replaced": direct("rtk_attention_forward", Lq, "rtk_attention_workspace_bytes"),
+                      "packed_lq1": direct("rtk_attention_decode", 1)}
+            for _ in range(args.warmup):
+                for run, _o in routes.values():
+                    run()
+            torch.cuda.synchronize()
+            times = {name: [] for name in routes}
+            for _ in range(args.reps):   # interleaved: the routes see the same drift of clocks and cache state
+                for name, (run, _o) in routes.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    run()
+                    e1.record()
+                    e1.synchronize()
+                    times[name].append(e0.elapsed_time(e1) * 1e3 / DECODE_INNER)
+            row = {"kind": kind, "Lq": Lq, "packed_rows": hq // hkv * Lq, "Hq": hq, "Hkv": hkv, "D": D, "dtype": "bfloat16",
+                   "rows": WIDE_ROWS, "own_rows": Lk if kind != "plain" else 0, "reps": args.reps, "inner": DECODE_INNER,
+                   "kv_bytes": kv_bytes}
+            for name, t in times.items():
+                q1, med, q3 = statistics.quantiles(t, n=4)
+                row[name] = {"us": med, "q1_us": q1, "q3_us": q3, "iqr_us": q3 - q1, "min_us": min(t), "max_us": max(t)}
+            w, r = row["wide"], row["replaced"]
+            w["fraction_of_8_TBps"] = kv_bytes / (w["us"] * 1e-6) / HBM_PEAK
+            w["ms_per_step"] = w["us"] * LAYERS * 1e-3
+            r["ms_per_step"] = r["us"] * LAYERS * 1e-3
+            row["ratio_replaced_over_wide"] = r["us"] / w["us"]
+            row["ratio_wide_over_packed_lq1"] = w["us"] / row["packed_lq1"]["us"]
+            row["faster_beyond_iqr"] = bool(r["us"] - w["us"] > r["iqr_us"] + w["iqr_us"])
+            row["max_abs_diff_wide_vs_replaced"] = (routes["wide"][1].float() - routes["replaced"][1].float()).abs().max().item()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            del routes
+        del k, v, segs, _alive
+        torch.cuda.empty_cache()
+    doc = {"device": torch.cuda.get_device_name(0), "torch": torch.__version__, "hbm_peak_bytes_per_s": HBM_PEAK, "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("\n| keys as | Hq / Hkv | Lq | packed rows | wide us (q1 - q3) | replaced chunk call us (q1 - q3) | replaced / wide | packed Lq 1 us "
+          "| wide / packed Lq 1 | K/V MB | wide: of 8 TB/s | faster beyond the IQRs |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        w, c, p = r["wide"], r["replaced"], r["packed_lq1"]
+        print(f"| {r['kind']} | {r['Hq']} / {r['Hkv']} | {r['Lq']} | {r['packed_rows']} | {w['us']:.1f} ({w['q1_us']:.1f} - {w['q3_us']:.1f}) | "
+              f"{c['us']:.1f} ({c['q1_us']:.1f} - {c['q3_us']:.1f}) | {r['ratio_replaced_over_wide']:.2f} | {p['us']:.1f} | "
+              f"{r['ratio_wide_over_packed_lq1']:.2f} | {r['kv_bytes'] / 1e6:.1f} | {w['fraction_of_8_TBps']:.3f} | "
+              f"{r['faster_beyond_iqr']} |")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--fp8kv", action="store_true", help="the two-segment fp8 call against the 16-bit kernel on dequantised rows")
     ap.add_argument("--decode", action="store_true", help="the GQA-packed few-row kernel against the call it replaces")
     ap.add_argument("--group", action="store_true", help="one group-decode call against the B successive per-branch calls it replaces")
+    ap.add_argument("--wide", action="store_true", help="the wide packed kernel against the chunk-kernel call it replaces")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -384,6 +501,10 @@ def main():
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_attention.py needs the GPU: a CPU run measures nothing")
+    if args.wide:
+        if args.out is None:
+            args.out = os.path.join(ROOT, "profiles", "wide_decode_bench.json")
+        return main_wide(args)
     if args.out is None and not args.group:
         args.out = os.path.join(ROOT, "profiles", ("fp8kv_" if args.fp8kv else "") + ("decode_" if args.decode else "") +
                                 "attention_bench.json")

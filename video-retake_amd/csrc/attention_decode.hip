@@ -23,10 +23,12 @@
 // The plan (decode_plan) is a function of the shape alone.  attn_decode_d128_shared_kernel is the same body
 // (attention_decode_d128_body.inc) with another buffer's 16-bit rows between the archive and the kernel's own
 // (rtk_attention_decode_shared); attn_decode_group_d128_kernel (rtk_attention_decode_group, below) serves one token of
-// several branches.  The body and the group kernel share dec_step_off, dec_v_frag and dec_softmax_step; their tile loads,
-// dequantise-and-stage step and four-wave fold are written in each (as shared functions they compile the
-// existing kernels differently).  Host side: each entry point keeps its own checks and its fall-through, then
-// decode_forward (operands, plan, workspace, dtype) -> decode_launch -> decode_launch_d128, the one launcher.
+// several branches; attn_decode_wide_d128_kernel (attention_decode_wide.cuh, rtk_attention_decode_wide*) serves
+// 16 < R <= 64 packed rows as two to four column groups.  The body, the group kernel and the wide kernel share
+// dec_step_off, dec_v_frag and dec_softmax_step; their tile loads, dequantise-and-stage step and four-wave fold are
+// written in each (as shared functions they compile the existing kernels differently).  Host side: the entry
+// points of the narrow and the wide family are decode_call with their family and segments - its checks and fall-throughs,
+// then decode_forward (operands, plan, workspace, dtype) -> decode_launch -> decode_launch_d128, the one launcher.
 // FP8 = true: the keys are [e4m3 archive | 16-bit rows], counted in a key space where the archive is padded to whole
 // 32-key tiles (a tile is of one kind).  Archive tiles are dequantised (fp8_dequant16) into the registers / the LDS image
 // a 16-bit tile of the dequantised rows would have left, so with L8 % 32 == 0 every fp32 sum is grouped as in the 16-bit
@@ -130,6 +132,8 @@ __global__ __launch_bounds__(256, 2) void attn_decode_d128_shared_kernel(
 #include "attention_decode_d128_body.inc"
 }
 
+#include "attention_decode_wide.cuh"
+
 struct DecodePlan {
     int nsplit, keys_per_split;
     size_t ws_bytes;
@@ -147,15 +151,54 @@ DecodePlan decode_plan(int Hq, int Hkv, int Lq, long long keys) {
     return DecodePlan{(int)ns, (int)kps, (size_t)ns * Hq * Lq * (128 + 2) * sizeof(float)};
 }
 
-// what the packed kernel takes of the shapes attn_check_shape admits
-int decode_check_envelope(const char* who, int Hq, int Hkv, int Lq, int D, int dtype) {
-    const int rc = d128_check_envelope(who, "packed", D, dtype);
+// The two families of packed entry points, each [plain, _fp8kv, _shared] (`seg` 0, 1, 2): the narrow one (one column group)
+// and the wide one (attention_decode_wide.cuh), which at R <= DEC_R IS the narrow one.
+struct DecodeFamily {
+    const char *who[3], *query[3], *kernel;
+    int max_rows;
+};
+const DecodeFamily DEC_NARROW{
+    {"rtk_attention_decode", "rtk_attention_decode_fp8kv", "rtk_attention_decode_shared"},
+    {"rtk_attention_decode_workspace_bytes", "rtk_attention_decode_workspace_bytes_fp8kv", "rtk_attention_decode_workspace_bytes_shared"},
+    "packed", DEC_R};
+const DecodeFamily DEC_WIDE{
+    {"rtk_attention_decode_wide", "rtk_attention_decode_wide_fp8kv", "rtk_attention_decode_wide_shared"},
+    {"rtk_attention_decode_wide_workspace_bytes", "rtk_attention_decode_wide_workspace_bytes_fp8kv",
+     "rtk_attention_decode_wide_workspace_bytes_shared"},
+    "wide", WIDE_R};
+// the shared rows and the archive as an entry point receives them: zero where its call has none
+struct DecodeSegs {
+    const void *ks, *vs;
+    int Ls;
+    int64_t s_sh, s_sl;
+    const void *k8, *v8;
+    const float *k_scale, *v_scale;
+    int L8;
+    int64_t sh8, shs;
+};
+
+// what a packed kernel takes of the shapes attn_check_shape admits
+int decode_check_envelope(const char* who, const DecodeFamily& f, int Hq, int Hkv, int Lq, int D, int dtype) {
+    const int rc = d128_check_envelope(who, f.kernel, D, dtype);
     if (rc != RTK_OK) return rc;
-    if ((long long)(Hq / Hkv) * Lq > DEC_R) {
-        set_error("%s: unsupported shape: (Hq / Hkv) * Lq = %d * %d packed rows (at most %d)", who, Hq / Hkv, Lq, DEC_R);
+    if ((long long)(Hq / Hkv) * Lq > f.max_rows) {
+        set_error("%s: unsupported shape: (Hq / Hkv) * Lq = %d * %d packed rows (at most %d)", who, Hq / Hkv, Lq, f.max_rows);
         return RTK_EUNSUPPORTED;
     }
     return RTK_OK;
+}
+// the shape check of the segments the call has, then the family's envelope
+int decode_check_shape(const char* who, const DecodeFamily& f, int seg, int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D,
+                       int dtype) {
+    const int rc = seg == 2   ? shared_check_shape(who, Hq, Hkv, Lq, Lk, L8, Ls, D, dtype, DEC_T)
+                   : seg == 1 ? fp8kv_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype)
+                              : attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
+    return rc != RTK_OK ? rc : decode_check_envelope(who, f, Hq, Hkv, Lq, D, dtype);
+}
+// a workspace query: 0 with the error set for a shape the family does not take
+size_t decode_query(const DecodeFamily& f, int seg, int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype) {
+    if (decode_check_shape(f.query[seg], f, seg, Hq, Hkv, Lq, Lk, L8, Ls, D, dtype) != RTK_OK) return 0;
+    return decode_plan(Hq, Hkv, Lq, shared_keys(Lk, L8, Ls, DEC_T)).ws_bytes;
 }
 
 // One launch of a packed kernel variant (`tail`: the a8 / s16 it takes after the common parameters), then the combine.
@@ -169,23 +212,62 @@ int decode_launch_d128(K kern, const char* name, const DecodePlan& pl, const Att
     return attn_combine<DT>(p, a.out, a.Hq, a.Lq, 128, pl.nsplit, a.st);
 }
 
+// the wide kernel of the call's column groups
+template <int DT, bool FP8, bool SHARED> int wide_launch(const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const Shared16& s16) {
+    const char* name = "attn_decode_wide_d128_kernel";
+    switch (((a.Hq / a.Hkv) * a.Lq + DEC_R - 1) / DEC_R) {
+    case 2: return decode_launch_d128<DT>(attn_decode_wide_d128_kernel<DT, 2, FP8, SHARED>, name, pl, a, a8, s16);
+    case 3: return decode_launch_d128<DT>(attn_decode_wide_d128_kernel<DT, 3, FP8, SHARED>, name, pl, a, a8, s16);
+    default: return decode_launch_d128<DT>(attn_decode_wide_d128_kernel<DT, 4, FP8, SHARED>, name, pl, a, a8, s16);
+    }
+}
+
 // the kernel of the segments the call has: [archive | shared | own], a8 / s16 empty without
-template <int DT> int decode_launch(const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const Shared16& s16) {
+template <int DT> int decode_launch(const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const Shared16& s16, bool wide) {
+    if (wide) {
+        if (s16.Ls > 0) return wide_launch<DT, true, true>(pl, a, a8, s16);
+        if (a8.L8 > 0) return wide_launch<DT, true, false>(pl, a, a8, s16);
+        return wide_launch<DT, false, false>(pl, a, a8, s16);
+    }
     if (s16.Ls > 0) return decode_launch_d128<DT>(attn_decode_d128_shared_kernel<DT>, "attn_decode_d128_shared_kernel", pl, a, a8, s16);
     if (a8.L8 > 0) return decode_launch_d128<DT>(attn_decode_d128_kernel<DT, true>, "attn_decode_d128_kernel", pl, a, a8);
     return decode_launch_d128<DT>(attn_decode_d128_kernel<DT, false>, "attn_decode_d128_kernel", pl, a, a8);
 }
 
-// What the three entry points share once their own checks are through: the operands, the plan over the padded key count,
+// What the entry points share once their own checks are through: the operands, the plan over the padded key count,
 // the workspace (`query`: the entry point that sizes it) and the dtype switch.
-int decode_forward(const char* who, const char* query, const AttnArgs& a, const Archive8& a8, const Shared16& s16) {
+int decode_forward(const char* who, const char* query, bool wide, const AttnArgs& a, const Archive8& a8, const Shared16& s16) {
     int rc = attn_check_operands(who, a.q, a.q_sh, a.q_sl, a.k, a.v, a.kv_sh, a.kv_sl, a8.k8, a8.v8, a8.ks, a8.vs, a8.sh8, a8.shs,
                                  a.out, a.Lq, a.Lk, a.off, a.D, a.dtype, a.scale, 0, DEC_T);
     if (rc != RTK_OK) return rc;
     const DecodePlan pl = decode_plan(a.Hq, a.Hkv, a.Lq, shared_keys(a.Lk, a8.L8, s16.Ls, DEC_T));
     rc = attn_check_workspace(who, query, pl.ws_bytes, a.workspace, a.workspace_bytes);
     if (rc != RTK_OK) return rc;
-    return a.dtype == RTK_BF16 ? decode_launch<RTK_BF16>(pl, a, a8, s16) : decode_launch<RTK_F16>(pl, a, a8, s16);
+    return a.dtype == RTK_BF16 ? decode_launch<RTK_BF16>(pl, a, a8, s16, wide) : decode_launch<RTK_F16>(pl, a, a8, s16, wide);
+}
+
+// An entry point of family f with segments `seg`: its checks, then its fall-throughs - the wide family at R <= DEC_R is
+// the narrow call of the same segments; without shared rows the _shared call is the _fp8kv call, which without an archive
+// is the plain one - then decode_forward.
+int decode_call(const DecodeFamily& f, int seg, const AttnArgs& a, const DecodeSegs& sg) {
+    const char* who = f.who[seg];
+    RTK_CHECK_ARG(a.q && a.k && a.v && a.out, "%s: NULL q / k / v / out pointer", who);
+    int rc = decode_check_shape(who, f, seg, a.Hq, a.Hkv, a.Lq, a.Lk, sg.L8, sg.Ls, a.D, a.dtype);
+    if (rc != RTK_OK) return rc;
+    if (f.max_rows > DEC_R && (a.Hq / a.Hkv) * a.Lq <= DEC_R) return decode_call(DEC_NARROW, seg, a, sg);
+    if (seg == 2 && sg.Ls == 0) return decode_call(f, 1, a, sg);
+    if (seg == 1 && sg.L8 == 0) return decode_call(f, 0, a, sg);
+    Shared16 s16{};
+    Archive8 a8{};
+    if (seg == 2) {
+        rc = make_shared16(who, sg.ks, sg.vs, sg.Ls, sg.s_sh, sg.s_sl, a.D, DEC_T, s16);
+        if (rc != RTK_OK) return rc;
+    }
+    if (seg >= 1) {
+        rc = make_archive8(who, sg.k8, sg.v8, sg.k_scale, sg.v_scale, sg.L8, sg.sh8, sg.shs, a8);
+        if (rc != RTK_OK) return rc;
+    }
+    return decode_forward(who, f.query[seg], f.max_rows > DEC_R, a, a8, s16);
 }
 
 // ---- group decode (rtk_attention_decode_group): ONE token of each of B branches that share [archive | shared rows] ----
@@ -491,33 +573,21 @@ int group_launch(const GroupPlan& gp, const GroupArgs& ga, const Archive8& a8, c
 using namespace rtk;
 
 extern "C" size_t rtk_attention_decode_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int D, int dtype) {
-    const char* who = "rtk_attention_decode_workspace_bytes";
-    if (attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype) != RTK_OK) return 0;
-    if (decode_check_envelope(who, Hq, Hkv, Lq, D, dtype) != RTK_OK) return 0;
-    return decode_plan(Hq, Hkv, Lq, Lk).ws_bytes;
+    return decode_query(DEC_NARROW, 0, Hq, Hkv, Lq, Lk, 0, 0, D, dtype);
 }
 
 extern "C" int rtk_attention_decode(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
                                     int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
                                     int q_offset, int D, int dtype, float scale, void* workspace, size_t workspace_bytes,
                                     rtk_stream_t stream) {
-    const char* who = "rtk_attention_decode";
-    RTK_CHECK_ARG(q && k && v && out, "%s: NULL q / k / v / out pointer", who);
-    int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
-    if (rc != RTK_OK) return rc;
-    rc = decode_check_envelope(who, Hq, Hkv, Lq, D, dtype);
-    if (rc != RTK_OK) return rc;
-    return decode_forward(who, "rtk_attention_decode_workspace_bytes",
-                          AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
-                                   scale, workspace, workspace_bytes, (hipStream_t)stream},
-                          Archive8{}, Shared16{});
+    return decode_call(DEC_NARROW, 0,
+                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                scale, workspace, workspace_bytes, (hipStream_t)stream},
+                       DecodeSegs{});
 }
 
 extern "C" size_t rtk_attention_decode_workspace_bytes_fp8kv(int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype) {
-    const char* who = "rtk_attention_decode_workspace_bytes_fp8kv";
-    if (fp8kv_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype) != RTK_OK) return 0;
-    if (decode_check_envelope(who, Hq, Hkv, Lq, D, dtype) != RTK_OK) return 0;
-    return decode_plan(Hq, Hkv, Lq, shared_keys(Lk, L8, 0, DEC_T)).ws_bytes;
+    return decode_query(DEC_NARROW, 1, Hq, Hkv, Lq, Lk, L8, 0, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -526,29 +596,14 @@ extern "C" int rtk_attention_decode_fp8kv(const void* q, int64_t q_stride_h, int
                                           int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
                                           int D, int dtype, float scale, void* workspace, size_t workspace_bytes,
                                           rtk_stream_t stream) {
-    const char* who = "rtk_attention_decode_fp8kv";
-    RTK_CHECK_ARG(q && k && v && out, "%s: NULL q / k / v / out pointer", who);
-    int rc = fp8kv_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype);
-    if (rc != RTK_OK) return rc;
-    rc = decode_check_envelope(who, Hq, Hkv, Lq, D, dtype);
-    if (rc != RTK_OK) return rc;
-    if (L8 == 0)   // no archive yet: the 16-bit packed call itself
-        return rtk_attention_decode(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D,
-                                    dtype, scale, workspace, workspace_bytes, stream);
-    Archive8 a8;
-    rc = make_archive8(who, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h, a8);
-    if (rc != RTK_OK) return rc;
-    return decode_forward(who, "rtk_attention_decode_workspace_bytes_fp8kv",
-                          AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
-                                   scale, workspace, workspace_bytes, (hipStream_t)stream},
-                          a8, Shared16{});
+    return decode_call(DEC_NARROW, 1,
+                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                scale, workspace, workspace_bytes, (hipStream_t)stream},
+                       DecodeSegs{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h});
 }
 
 extern "C" size_t rtk_attention_decode_workspace_bytes_shared(int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype) {
-    const char* who = "rtk_attention_decode_workspace_bytes_shared";
-    if (shared_check_shape(who, Hq, Hkv, Lq, Lk, L8, Ls, D, dtype, DEC_T) != RTK_OK) return 0;
-    if (decode_check_envelope(who, Hq, Hkv, Lq, D, dtype) != RTK_OK) return 0;
-    return decode_plan(Hq, Hkv, Lq, shared_keys(Lk, L8, Ls, DEC_T)).ws_bytes;
+    return decode_query(DEC_NARROW, 2, Hq, Hkv, Lq, Lk, L8, Ls, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_shared(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -558,26 +613,58 @@ extern "C" int rtk_attention_decode_shared(const void* q, int64_t q_stride_h, in
                                            int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
                                            int D, int dtype, float scale, void* workspace, size_t workspace_bytes,
                                            rtk_stream_t stream) {
-    const char* who = "rtk_attention_decode_shared";
-    RTK_CHECK_ARG(q && k && v && out, "%s: NULL q / k / v / out pointer", who);
-    int rc = shared_check_shape(who, Hq, Hkv, Lq, Lk, L8, Ls, D, dtype, DEC_T);
-    if (rc != RTK_OK) return rc;
-    rc = decode_check_envelope(who, Hq, Hkv, Lq, D, dtype);
-    if (rc != RTK_OK) return rc;
-    if (Ls == 0)   // no shared rows: the two-segment packed call itself
-        return rtk_attention_decode_fp8kv(q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, k8, v8, k_scale, v_scale, L8,
-                                          stride8_h, scale_stride_h, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype, scale, workspace,
-                                          workspace_bytes, stream);
-    Shared16 s16;
-    rc = make_shared16(who, ks, vs, Ls, s_stride_h, s_stride_l, D, DEC_T, s16);
-    if (rc != RTK_OK) return rc;
-    Archive8 a8;
-    rc = make_archive8(who, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h, a8);
-    if (rc != RTK_OK) return rc;
-    return decode_forward(who, "rtk_attention_decode_workspace_bytes_shared",
-                          AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
-                                   scale, workspace, workspace_bytes, (hipStream_t)stream},
-                          a8, s16);
+    return decode_call(DEC_NARROW, 2,
+                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                scale, workspace, workspace_bytes, (hipStream_t)stream},
+                       DecodeSegs{ks, vs, Ls, s_stride_h, s_stride_l, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h});
+}
+
+// ---- the wide family (16 < (Hq / Hkv) * Lq <= 64; at most 16 rows: the call above of the same segments) ----
+extern "C" size_t rtk_attention_decode_wide_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int D, int dtype) {
+    return decode_query(DEC_WIDE, 0, Hq, Hkv, Lq, Lk, 0, 0, D, dtype);
+}
+
+extern "C" int rtk_attention_decode_wide(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                    int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
+                                    int q_offset, int D, int dtype, float scale, void* workspace, size_t workspace_bytes,
+                                    rtk_stream_t stream) {
+    return decode_call(DEC_WIDE, 0,
+                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                scale, workspace, workspace_bytes, (hipStream_t)stream},
+                       DecodeSegs{});
+}
+
+extern "C" size_t rtk_attention_decode_wide_workspace_bytes_fp8kv(int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype) {
+    return decode_query(DEC_WIDE, 1, Hq, Hkv, Lq, Lk, L8, 0, D, dtype);
+}
+
+extern "C" int rtk_attention_decode_wide_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                          int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                                          const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                          int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                                          int D, int dtype, float scale, void* workspace, size_t workspace_bytes,
+                                          rtk_stream_t stream) {
+    return decode_call(DEC_WIDE, 1,
+                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                scale, workspace, workspace_bytes, (hipStream_t)stream},
+                       DecodeSegs{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h});
+}
+
+extern "C" size_t rtk_attention_decode_wide_workspace_bytes_shared(int Hq, int Hkv, int Lq, int Lk, int L8, int Ls, int D, int dtype) {
+    return decode_query(DEC_WIDE, 2, Hq, Hkv, Lq, Lk, L8, Ls, D, dtype);
+}
+
+extern "C" int rtk_attention_decode_wide_shared(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                           int64_t kv_stride_h, int64_t kv_stride_l, const void* ks, const void* vs, int Ls,
+                                           int64_t s_stride_h, int64_t s_stride_l, const void* k8, const void* v8,
+                                           const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                           int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                                           int D, int dtype, float scale, void* workspace, size_t workspace_bytes,
+                                           rtk_stream_t stream) {
+    return decode_call(DEC_WIDE, 2,
+                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                                scale, workspace, workspace_bytes, (hipStream_t)stream},
+                       DecodeSegs{ks, vs, Ls, s_stride_h, s_stride_l, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h});
 }
 
 extern "C" size_t rtk_attention_decode_group_workspace_bytes(const int* own_rows, int n_branches, int Hq, int Hkv, int L8,

@@ -214,6 +214,15 @@ _SIGNATURES = {
     "rtk_attention_decode_workspace_bytes_shared": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rtk_attention_decode_shared": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp,
                                           _vp, _i, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "rtk_attention_decode_wide_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_wide": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz,
+                                        _vp]),
+    "rtk_attention_decode_wide_workspace_bytes_fp8kv": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_wide_fp8kv": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp,
+                                              _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
+    "rtk_attention_decode_wide_workspace_bytes_shared": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_wide_shared": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp,
+                                               _vp, _i, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp]),
     "rtk_attention_decode_group_workspace_bytes": (C.c_size_t, [C.POINTER(C.c_int), _i, _i, _i, _i, _i, _i, _i]),
     "rtk_attention_decode_group": (C.c_int, [C.POINTER(DecodeBranch), _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64,
                                          _i64, _vp, _i, _i, _i, _i, _f, _vp, _sz, _vp]),

@@ -46,7 +46,7 @@ from ._cache_state import (CacheMark, _Batch, _CacheView, _LayerMark, _LayerStor
 from ._hf_cache import DynamicCache, _hf_dynamic_cache_is_legacy, _ListDynamicCache  # noqa: F401
 from ._rope_torch import _rotate, apply_multimodal_rotary_pos_emb, apply_rotary_pos_emb, repeat_kv, rotate_half  # noqa: F401
 from .native_attention import (ATTENTION_KERNELS, KV_CACHE_DTYPES, chunk_attention, fp8_dequantize_rows,  # noqa: F401
-                               fp8_quantize_rows, native_attention)
+                               fp8_quantize_rows, native_attention, wide_dispatch)
 
 _WARNED = set()
 
@@ -212,6 +212,13 @@ class PivotKVCache(DynamicCache):
         # the GQA-packed few-row kernel first (chunk_attention(packed_gqa=True)); None (default): exactly as without it
         self.decode_attention = None
         self.decode_attention_calls = 0   # ... of which took the packed kernel
+        # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it): "packed" makes `attention` try
+        # the wide packed kernel (chunk_attention(packed_wide=True): up to 64 packed rows - the verification step of
+        # assisted generation, a few-token continuation) where the packed one declines, at the geometries where it measured
+        # faster than the chunk kernel (native_attention.wide_dispatch); needs decode_attention="packed".  None (default):
+        # exactly as without it
+        self.multi_token_attention = None
+        self.wide_attention_calls = 0     # ... of which took the wide packed kernel
         # MI355X build options, top-level keys of longvideo_kwargs (build_kvcache reads them; NOT in the reference, which
         # processes a finished video), for streams that do not end: a bound on a layer's VIDEO REGION - everything behind its
         # pinned rows (_LayerStore.pinned); with fp8 rows the archive.  video_window_rows = W bounds it by age: when
@@ -245,10 +252,13 @@ class PivotKVCache(DynamicCache):
         route = []
         out = chunk_attention(query_states, key_states, value_states, scaling=scaling, workspace=self._attn_ws,
                               query_offset=query_offset, archive=archive, packed_gqa=self.decode_attention == "packed",
-                              route=route, shared=shared)
+                              route=route, shared=shared,
+                              packed_wide=self.multi_token_attention == "packed"
+                              and wide_dispatch(query_states.shape[1], key_states.shape[1], query_states.shape[2]))
         if out is not None:
             self.attention_calls += 1
             self.decode_attention_calls += route == ["packed"]
+            self.wide_attention_calls += route == ["wide"]
         elif self.forked_from is not None:
             raise NotImplementedError("a branch (PivotKVCache.fork): the native chunk attention refuses this shape "
                                       f"({nv.lib.rtk_last_error().decode(errors='replace')}) and no other route reads the "
@@ -358,6 +368,7 @@ class PivotKVCache(DynamicCache):
             self._check_mark(mark)
         br = type(self)(self.config, reserve_tokens=reserve_tokens)
         br.attention_kernel, br.kv_cache_dtype, br.decode_attention = self.attention_kernel, self.kv_cache_dtype, self.decode_attention
+        br.multi_token_attention = self.multi_token_attention
         br.kvcache_compression = False
         cap = br.reserve_tokens or 1024
         for l, m in enumerate(mark.layers):
@@ -2047,6 +2058,10 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
         cache.decode_attention = _option_of(config, "decode_attention", (None, "packed"))
         if cache.decode_attention is not None and cache.attention_kernel != "hip":
             raise ValueError("decode_attention='packed' needs attention_kernel='hip': it is a kernel of the native attention")
+        cache.multi_token_attention = _option_of(config, "multi_token_attention", (None, "packed"))
+        if cache.multi_token_attention is not None and cache.decode_attention != "packed":
+            raise ValueError("multi_token_attention='packed' needs decode_attention='packed' (and through it "
+                             "attention_kernel='hip'): it widens that kernel's envelope")
         if cache.kv_cache_dtype is not None:
             if cache.attention_kernel != "hip":
                 raise ValueError("kv_cache_dtype='fp8_e4m3' needs attention_kernel='hip': the third-party attention routes "

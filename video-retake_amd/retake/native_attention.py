@@ -12,7 +12,7 @@ from . import _native as nv
 
 
 def chunk_attention(query_states, key_states, value_states, scaling=None, workspace=None, query_offset=None, archive=None,
-                    packed_gqa=False, route=None, shared=None):
+                    packed_gqa=False, route=None, shared=None, packed_wide=False):
     """Attention of a chunk's queries over [compressed prefix | current chunk] in one HIP launch (rtk_attention_forward):
     what the reference's attention patches hand to torch / flash_attn after the cache update (qwen2_vl.py:88-117,
     :188-219, :303-358; llava_onevision.py:118-139).
@@ -41,7 +41,14 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
     strides, contiguous head_dim) and precede key_states / value_states in the sequence, after the archive: the keys are
     [archive | shared | key_states] (rtk_attention_forward_shared / rtk_attention_decode_shared, bf16 / fp16 with head_dim
     128 only; a branch of PivotKVCache.fork reads its parent's rows this way).  Every query row sees all of them;
-    query_offset counts over the L8 + Ls + Lk keys.  Combines with archive= and packed_gqa= as above."""
+    query_offset counts over the L8 + Ls + Lk keys.  Combines with archive= and packed_gqa= as above.
+
+    packed_wide: after the packed kernel and before the chunk kernel, try the wide packed kernel (rtk_attention_decode_wide,
+    _wide_fp8kv, _wide_shared: bf16 / fp16, head_dim 128, (Hq / Hkv) * Lq <= 64 - the verification step of assisted
+    generation, a few-token continuation).  A shape it declines takes the chunk kernel as above; `route` receives "wide".
+    True asks for the kernel wherever the library serves it; the cache passes wide_dispatch(...), the shapes at which it
+    measured faster than the chunk kernel.
+    Its bits are neither the chunk kernel's nor those of Lq one-row packed calls: the fp32 sums are grouped differently."""
     nv.require_device(query_states, key_states, value_states)
     if query_states.dim() != 4 or key_states.dim() != 4 or value_states.dim() != 4 or query_states.shape[0] != 1:
         raise ValueError("chunk_attention takes [1, H, L, D] tensors (one unpadded sequence)")
@@ -83,6 +90,8 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
         sfx = ""
     routes = (("packed", "rtk_attention_decode", "rtk_attention_decode_workspace_bytes", "attention_decode_ws"),) \
         if packed_gqa else ()
+    if packed_wide:
+        routes += (("wide", "rtk_attention_decode_wide", "rtk_attention_decode_wide_workspace_bytes", "attention_decode_ws"),)
     for tag, fn, query, ws_tag in routes + (("chunk", "rtk_attention_forward", "rtk_attention_workspace_bytes", "attention_ws"),):
         need = getattr(nv.lib, query + sfx)(*shape)
         ws = _scratch(workspace, ws_tag, query_states.device, stream, need)
@@ -94,6 +103,20 @@ def chunk_attention(query_states, key_states, value_states, scaling=None, worksp
             route.append(tag)
         return out
     return None
+
+
+WIDE_DISPATCH_GROUPS = (4, 8)   # Hq / Hkv, inclusive: where the wide packed call measured faster than the chunk-kernel call
+
+
+def wide_dispatch(Hq: int, Hkv: int, Lq: int) -> bool:
+    """Whether multi_token_attention="packed" (PivotKVCache.attention) sends a call of this shape to the wide packed kernel:
+    inside its envelope, 16 < (Hq / Hkv) * Lq <= 64, AND at a geometry where the call measured faster than the chunk-kernel
+    call it replaces (tools/bench_attention.py --wide, profiles/wide_decode_bench.json): 4 <= Hq / Hkv <= 8.  What the chunk
+    kernel pays there is one pass over the keys per query head of a kv head; at Hq / Hkv = 1 and 2 there is little to save
+    and the wide call measured 0.95-0.99x and 0.72x, at Hq 16 / Hkv 1 0.44x.  The C entry points serve those shapes all the
+    same, and so does chunk_attention(packed_wide=True), which asks for them explicitly."""
+    G = Hq // max(Hkv, 1)
+    return WIDE_DISPATCH_GROUPS[0] <= G <= WIDE_DISPATCH_GROUPS[1] and 16 < G * Lq <= 64
 
 
 def _check_archive(archive, Hkv, D):

@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (67 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (69 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -56,6 +56,8 @@
  *   §O  "Video budget"                  rtk_pivotkv_keep_scores_batched, rtk_pivotkv_budget_select_batched,
  *                                       rtk_pivotkv_squeeze_batched: a bounded cache that keeps its best-scored video rows
  *                                       (opt-in: video_budget_rows)
+ *   §P  "DPSelect on a stream"          rtk_dpselect_ingest, rtk_dpselect_select_ring: keyframe selection for a video that
+ *                                       does not end, in a ring of 2 S frames (retake/dpselect_stream.py)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -1086,6 +1088,39 @@ typedef struct rtk_squeeze_unit {
 } rtk_squeeze_unit;
 #define RTK_SQUEEZE_MAX_UNITS 80   /* moving units per launch (the array travels as a kernel argument) */
 int rtk_pivotkv_squeeze_batched(const rtk_squeeze_unit* units, int n_units, rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * DPSelect on a stream (retake/dpselect_stream.py; NOT in the reference, which processes a finished video, and a rule of
+ * this project's own: what it does to answer quality has not been evaluated).  Frames arrive a few at a time and live in a
+ * ring of R = 2 S rows - frames [R,N,C] in the model dtype, dis [R,N] fp32, frame g in row g mod R - until their segment of S
+ * frames has been selected and gathered.  The host cuts a push into pieces (contiguous runs of ring rows) at the ring's wrap
+ * and behind every frame that completes a segment; nothing is read back and every call is ordered by `stream` alone.
+ *
+ * rtk_dpselect_ingest - one pass over a piece: frames_out[i] = x[i] and dis_out[i, n] = 1 - cos(x[i-1, n], x[i, n]), i < t,
+ *   where x[-1] is `prev` [N,C] - the ring row of the frame before the piece.  prev == NULL: the stream begins with x[0] and
+ *   dis_out[0] = 1.0, as at frame 0 of rtk_dpselect_dis.  The arithmetic IS rtk_dpselect_dis's, per dtype, on both of its paths
+ *   (16-byte vector rows of at most 16 vectors per lane, else the scalar path; x, prev and frames_out must all be 16-byte
+ *   aligned for the vector path): a distance has the bits the whole-video call gives the same pair.  x is read once (plus one
+ *   halo row per strip of <= 64 rows).  RTK_EINVAL, before any launch: NULL x / frames_out / dis_out, non-positive sizes, an
+ *   unsupported dtype code, frames_out overlapping x, prev inside the rows being written.
+ *
+ * rtk_dpselect_select_ring - rtk_dpselect_select for one segment: `len` rows from ring row r0 on (rows taken modulo R), with
+ *   `left` (0 .. window/2) valid rows in front and `right` (0 .. window - 1 - window/2) behind that only the peak windows look
+ *   at; fewer than the window reaches only where the stream began or ended, and the window clips there.  Keeps the top `keep`
+ *   keys of the len rows, ties to the lowest index, ascending.
+ *     idx   LOCAL to the segment (0 .. len-1): sync [keep] int64, async [keep,N] int64
+ *     mask  [keep,N] bytes: whether the kept frame is a peak
+ *     keys  workspace AND output: async [N,len] fp32; sync [len] keys followed by the [left+len+right] patch means
+ *   left = right = 0 and r0 = 0 is rtk_dpselect_select on the same rows, bit for bit (one device body serves both).
+ *   RTK_EINVAL: NULL pointers, r0 outside [0,R), len < 1, left / right out of range, len + left + right > R, keep outside
+ *   [1,len]; async with N == 1 returns RTK_EREFCRASH, as rtk_dpselect_select does.
+ *
+ * The kept frames are gathered with rtk_gather_frames(frames_ring + r0 rows, T = len, idx): a segment never wraps.
+ * ------------------------------------------------------------------------------------------- */
+int rtk_dpselect_ingest(const void* x, const void* prev, int t, int N, int C, int dtype, void* frames_out,
+                        float* dis_out, rtk_stream_t stream);
+int rtk_dpselect_select_ring(const float* dis_ring, int R, int N, int r0, int len, int left, int right, int keep,
+                             int window, int sync, int64_t* idx, uint8_t* mask, float* keys, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

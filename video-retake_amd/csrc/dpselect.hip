@@ -23,9 +23,7 @@ __global__ __launch_bounds__(256) void dis_kernel(const typename Elem<DT>::vec_t
                                                   int nvec, int strip, int emit_cos, float* __restrict__ dis) {
     using E = Elem<DT>;
     using vec_t = typename E::vec_t;
-    constexpr int PV = E::PER_VEC;
-    constexpr int NE = VPL * PV;
-    constexpr int KFULL = (VPL <= 6) ? VPL - 1 : VPL - 2;   // vectors below KFULL are full for every lane
+    constexpr int NE = VPL * E::PER_VEC;
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) / WAVE;
     const int nstrips = (T + strip - 1) / strip;
@@ -42,95 +40,14 @@ __global__ __launch_bounds__(256) void dis_kernel(const typename Elem<DT>::vec_t
     float nA[NE], nB[NE];         // normalised rows: odd steps in nA, even steps in nB (no copies between steps)
 
     // rows beyond the strip are clamped to its last row (a harmless re-read of a line that is in flight anyway)
-    auto load_row = [&](vec_t* raw, int t) {
-        const vec_t* p = xrow + (size_t)min(t, t1 - 1) * frame_vecs;
-#pragma unroll
-        for (int k = 0; k < VPL; ++k) {
-            const int v = k * WAVE + lane;
-            raw[k] = p[k < KFULL ? v : min(v, nvec - 1)];
-        }
-    };
-    // normalise the row held in raw[] into cur[] (x / max(||x||, eps)), reference rounding for bf16
-    auto normalise = [&](vec_t* raw, float* cur) {
-#pragma unroll
-        for (int k = KFULL; k < VPL; ++k)
-            if (k * WAVE + lane >= nvec) raw[k] = vec_t{};   // lanes past the end of the row contribute zeros
-#pragma unroll
-        for (int k = 0; k < VPL; ++k) E::unpack(raw[k], cur + k * PV);
-        float ss = 0.f;
-        if constexpr (DT != RTK_F32) {   // sum of squares straight from the packed words, two elements per instruction
-#pragma unroll
-            for (int k = 0; k < VPL; ++k) {
-                ss = H16<DT>::dot2(raw[k].x, raw[k].x, ss);
-                ss = H16<DT>::dot2(raw[k].y, raw[k].y, ss);
-                ss = H16<DT>::dot2(raw[k].z, raw[k].z, ss);
-                ss = H16<DT>::dot2(raw[k].w, raw[k].w, ss);
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < NE; ++e) ss = fmaf(cur[e], cur[e], ss);
-        }
-        ss = wave_sum_uniform(ss);
-        float nrm = sqrtf(ss);
-        if constexpr (DT == RTK_F16) {
-            // fp16 tensors: norm -> fp16, clamp_min(eps) with eps = fp16(1e-8) = 0 (a zero vector divides 0 by 0 like the
-            // reference does), the quotient rounded to fp16.  True IEEE division: the reciprocal-product argument below
-            // is a statement about 8-bit significands.
-            nrm = fmaxf(rhf(nrm), rhf(1e-8f));
-#pragma unroll
-            for (int e = 0; e < NE; ++e) cur[e] = __fdiv_rn(cur[e], nrm);
-#pragma unroll
-            for (int e = 0; e < NE; e += 2) {
-                const uint32_t pk = H16<DT>::pack2(cur[e], cur[e + 1]);
-                cur[e] = H16<DT>::lo(pk);
-                cur[e + 1] = H16<DT>::hi(pk);
-            }
-        } else if constexpr (DT == RTK_BF16) {
-            nrm = rbf(nrm);
-            nrm = fmaxf(nrm, rbf(1e-8f));
-            // bf16(fl32(x / nrm)) without a division per element: x and nrm are bf16 values, and the exact quotient
-            // of two 8-bit significands is never closer than 128 fp32 ulp to a bf16 rounding midpoint (unless it is
-            // exactly representable), while x * fl32(1/nrm) is within 2 fp32 ulp of it - so the reciprocal product
-            // rounds to the same bf16 as the reference's division, always (tools/bf16_quotient_check.py walks every
-            // significand pair, subnormal results included).  Only a norm so large that 1/nrm is subnormal takes
-            // the true division; the branch is wave-uniform.
-            if (__builtin_amdgcn_readfirstlane(__float_as_int(nrm)) > 0x7b800000 /* 2^120 */) {
-#pragma unroll
-                for (int e = 0; e < NE; ++e) cur[e] = __fdiv_rn(cur[e], nrm);
-            } else {
-                const float rn = __frcp_rn(nrm);
-#pragma unroll
-                for (int e = 0; e < NE; ++e) cur[e] *= rn;
-            }
-#pragma unroll
-            for (int e = 0; e < NE; e += 2) {   // hardware pack-convert = round to nearest even, like c10::BFloat16
-                const uint32_t pk = pack2_bf16_dp(cur[e], cur[e + 1]);
-                cur[e] = __uint_as_float(pk << 16);
-                cur[e + 1] = __uint_as_float(pk & 0xffff0000u);
-            }
-        } else {
-            nrm = fmaxf(nrm, 1e-8f);
-#pragma unroll
-            for (int e = 0; e < NE; ++e) cur[e] = cur[e] / nrm;
-        }
-    };
+    auto load_row = [&](vec_t* raw, int t) { dprow_load<DT, VPL>(raw, xrow + (size_t)min(t, t1 - 1) * frame_vecs, nvec, lane); };
+    // normalise the row held in raw[] into cur[] (x / max(||x||, eps)), the reference's rounding per dtype (dprow.cuh)
+    auto normalise = [&](vec_t* raw, float* cur) { dprow_normalise<DT, VPL>(raw, cur, nvec, lane); };
     const int tb = (t0 == 0) ? 1 : t0;   // first row this wave produces a distance for
     float res = 1.0f;                    // lane i: result of row tb + i (or of row 0 for the lane that gets it)
     // cos / distance of row t (in cur[]) against the previous row (prevn[])
     auto emit = [&](int t, const float* prevn, const float* cur) {
-        float dot = 0.f;
-        if constexpr (DT != RTK_F32) {
-#pragma unroll
-            for (int e = 0; e < NE; e += 2) {
-                const uint32_t pk = H16<DT>::pack2(prevn[e] * cur[e], prevn[e + 1] * cur[e + 1]);
-                dot = H16<DT>::dot2(pk, H16<DT>::ONE2, dot);   // + round(product) for both halves
-            }
-        } else {
-#pragma unroll
-            for (int e = 0; e < NE; ++e) dot = fmaf(prevn[e], cur[e], dot);
-        }
-        dot = wave_sum_uniform(dot);
-        if constexpr (DT != RTK_F32) dot = H16<DT>::rnd(dot);
+        const float dot = dprow_dot<DT, VPL>(prevn, cur);
         if (lane == t - tb) res = emit_cos ? dot : 1.0f - dot;
     };
 
@@ -172,31 +89,7 @@ __global__ __launch_bounds__(256) void dis_kernel_generic(const void* __restrict
         if (lane == 0 && !emit_cos) dis[n] = 1.0f;
         return;
     }
-    auto ld = [&](size_t off) -> float {
-        if constexpr (DT != RTK_F32) return H16<DT>::ld(xv, off);
-        else return ((const float*)xv)[off];
-    };
-    const size_t a0 = ((size_t)(t - 1) * N + n) * C, b0 = ((size_t)t * N + n) * C;
-    float sa = 0.f, sb = 0.f;
-    for (int c = lane; c < C; c += WAVE) {
-        const float a = ld(a0 + c), b = ld(b0 + c);
-        sa = fmaf(a, a, sa);
-        sb = fmaf(b, b, sb);
-    }
-    float na = sqrtf(wave_sum(sa)), nb = sqrtf(wave_sum(sb));
-    float dot = 0.f;
-    if constexpr (DT != RTK_F32) {
-        using Hh = H16<DT>;
-        na = fmaxf(Hh::rnd(na), Hh::rnd(1e-8f));
-        nb = fmaxf(Hh::rnd(nb), Hh::rnd(1e-8f));
-        for (int c = lane; c < C; c += WAVE) dot += Hh::rnd(Hh::rnd(ld(a0 + c) / na) * Hh::rnd(ld(b0 + c) / nb));
-        dot = Hh::rnd(wave_sum(dot));
-    } else {
-        na = fmaxf(na, 1e-8f);
-        nb = fmaxf(nb, 1e-8f);
-        for (int c = lane; c < C; c += WAVE) dot = fmaf(ld(a0 + c) / na, ld(b0 + c) / nb, dot);
-        dot = wave_sum(dot);
-    }
+    const float dot = dprow_pair_cos_generic<DT>(xv, ((size_t)(t - 1) * N + n) * C, xv, ((size_t)t * N + n) * C, C, lane);
     if (lane == 0) {
         if (emit_cos) dis[(size_t)(t - 1) * N + n] = dot;
         else dis[(size_t)t * N + n] = 1.0f - dot;
@@ -207,24 +100,8 @@ __global__ __launch_bounds__(256) void dis_kernel_generic(const void* __restrict
 // K3-K7, K9: per-row peak stencil + bonus + exact top-k + ordered emit.  One workgroup per row
 // (sync: the single patch-mean row; async: one row per patch position).
 // ------------------------------------------------------------------------------------------------
-// i is a peak iff arg-max over [i - w/2, i - w/2 + w - 1] ∩ [0,T) is i with first-index-wins ties
-// (max_pool1d_with_indices + `window_maxima[c] == c`, visual_compression.py:121-123,153-156).
-template <typename DFn>
-__device__ __forceinline__ bool is_peak(DFn d, int i, int T, int window) {
-    const float di = d(i);
-    int a = i - window / 2, b = a + window - 1;
-    a = max(a, 0);
-    b = min(b, T - 1);
-    bool pk = true;
-    for (int j = a; j <= b; ++j) {
-        if (j == i) continue;
-        const float dj = d(j);
-        pk = pk && (j < i ? (di > dj) : (di >= dj));
-    }
-    return pk;
-}
-
-constexpr int SEL_BLOCK = 256;
+// The body is select.cuh's dpselect_row, shared with the segment selection of a stream (dpselect_stream.hip): a whole
+// video is a run of T frames with no halo.
 
 __global__ __launch_bounds__(SEL_BLOCK) void dpselect_select_kernel(const float* __restrict__ dis, int T, int N,
                                                                     int tgt, int window, int sync,
@@ -232,41 +109,10 @@ __global__ __launch_bounds__(SEL_BLOCK) void dpselect_select_kernel(const float*
                                                                     uint8_t* __restrict__ mask,
                                                                     float* __restrict__ keys) {
     __shared__ SelectSmem sm;
-    const int tid = threadIdx.x;
     const int row = blockIdx.x;  // patch index in async mode, 0 in sync mode
-    float* krow = keys + (size_t)row * T;
-    float* raw = keys + (size_t)T;  // sync only: patch-mean distance
-    if (sync) {
-        // dis.mean(1)  (:110): one wave per frame row, fixed-order lane partials + shuffle tree
-        const int lane = tid & (WAVE - 1), wid = tid / WAVE;
-        for (int t = wid; t < T; t += SEL_BLOCK / WAVE) {
-            float s = 0.f;
-            for (int n = lane; n < N; n += WAVE) s += dis[(size_t)t * N + n];
-            s = wave_sum(s);
-            if (lane == 0) raw[t] = s / (float)N;
-        }
-        __syncthreads();
-    }
-    auto dfn = [&](int t) -> float { return sync ? raw[t] : dis[(size_t)t * N + row]; };
-    for (int t = tid; t < T; t += SEL_BLOCK) {
-        const float d = dfn(t);
-        krow[t] = is_peak(dfn, t, T, window) ? d + 2.0f : d;  // dis[peaks] += 2  (:133, :160)
-    }
-    __syncthreads();
-    auto key = [&](int t) -> uint32_t { return f2key(krow[t]); };
-    uint32_t thr;
-    int need_eq;
-    block_radix_threshold<SEL_BLOCK>(key, T, tgt, sm, thr, need_eq);
-    block_ordered_compact<SEL_BLOCK>(key, T, thr, need_eq, sm, [&](int r, int t) {
-        const uint8_t pk = is_peak(dfn, t, T, window) ? 1 : 0;
-        if (sync) {
-            idx[r] = t;
-            for (int n = 0; n < N; ++n) mask[(size_t)r * N + n] = pk;  // mask[:,None].repeat(1,N) (:140)
-        } else {
-            idx[(size_t)r * N + row] = t;   // peaks.transpose(0,1)   (:169)
-            mask[(size_t)r * N + row] = pk; // mask.gather(0, peaks)  (:175)
-        }
-    });
+    // keys: async [N, T]; sync [2, T], row 1 the patch-mean distance
+    dpselect_row<SEL_BLOCK>([&](int t) { return dis + (size_t)t * N; }, N, row, T, 0, 0, tgt, window, sync, idx, mask,
+                            keys + (size_t)row * T, keys + (size_t)T, sm);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -443,46 +289,17 @@ static int launch_dis(const void* x, int T, int N, int C, int emit_cos, float* d
         RTK_LAUNCH_CHECK("dis_kernel_generic");
         return RTK_OK;
     }
-    // Strip length: the whole job should be ONE resident set of waves.  Every wave does the same work per row,
-    // so a second, partly filled round of workgroups costs as much as a full one (measured: 12.5k waves on 8k
-    // slots ran at 57 % VALU utilisation); with strips sized so that N * nstrips just fits the resident slots the
-    // halo re-read is 1/strip and no SIMD idles while others finish.  Small jobs fall back to strips of >= 4 rows.
+    // strips sized so that the whole job is one resident set of waves (dprow_strip_rows)
     const vec_t* xv = (const vec_t*)x;
-    size_t slots = 8192;
-#define RTK_DIS_CASE(V)                                                                                  \
-    {                                                                                                    \
-        static int resident = 0; /* waves of this instantiation the chip holds at once */               \
-        if (!resident) {                                                                                 \
-            int dev = 0, cus = 256, nb = 0;                                                              \
-            (void)hipGetDevice(&dev);                                                                    \
-            (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);               \
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, dis_kernel<DT, V>, 256, 0) != hipSuccess || nb < 1) \
-                nb = 1;                                                                                  \
-            resident = nb * cus * 4;                                                                     \
-        }                                                                                                \
-        slots = (size_t)resident;                                                                        \
-        int nstr = (int)std::max<size_t>(1, std::min<size_t>(slots / (size_t)N, (size_t)(T + 3) / 4));      \
-        nstr = std::max(nstr, (T + 63) / 64); /* a strip's results live in one register: <= 64 rows */     \
-        const int strip = (T + nstr - 1) / nstr;                                                         \
-        const size_t waves = (size_t)N * ((T + strip - 1) / strip);                                      \
-        const unsigned grid = (unsigned)((waves * WAVE + 255) / 256);                                    \
-        RTK_LAUNCH(KID_DIS, (dis_kernel<DT, V>), dim3(grid), dim3(256), 0, st, xv, T, N, nvec, strip, emit_cos, dis); \
-    }                                                                                                    \
-    break;
-    switch (vpl) {
-        case 1: RTK_DIS_CASE(1)
-        case 2: RTK_DIS_CASE(2)
-        case 3: RTK_DIS_CASE(3)
-        case 4: RTK_DIS_CASE(4)
-        case 5: RTK_DIS_CASE(5)
-        case 6: RTK_DIS_CASE(6)
-        case 7: case 8: RTK_DIS_CASE(8)
-        case 9: case 10: RTK_DIS_CASE(10)
-        case 11: case 12: RTK_DIS_CASE(12)
-        case 13: case 14: RTK_DIS_CASE(14)
-        default: RTK_DIS_CASE(16)
-    }
-#undef RTK_DIS_CASE
+    dprow_with_vpl(vpl, [&](auto vc) {
+        constexpr int V = decltype(vc)::value;
+        static int resident = 0;   // waves of this instantiation the chip holds at once
+        if (!resident) resident = dprow_resident_waves(dis_kernel<DT, V>);
+        const int strip = dprow_strip_rows(T, N, (size_t)resident);
+        const size_t waves = (size_t)N * ((T + strip - 1) / strip);
+        const unsigned grid = (unsigned)((waves * WAVE + 255) / 256);
+        RTK_LAUNCH(KID_DIS, (dis_kernel<DT, V>), dim3(grid), dim3(256), 0, st, xv, T, N, nvec, strip, emit_cos, dis);
+    });
     RTK_LAUNCH_CHECK("dis_kernel");
     return RTK_OK;
 }

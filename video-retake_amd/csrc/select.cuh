@@ -10,6 +10,24 @@
 
 namespace rtk {
 
+// DPSelect's peak rule: i is a peak iff the arg-max of d over [i - w/2, i - w/2 + w - 1] ∩ [lo, hi] is i, with
+// first-index-wins ties (max_pool1d_with_indices + `window_maxima[c] == c`, visual_compression.py:121-123,153-156).
+// [lo, hi] are the rows that exist: [0, T - 1] for a whole video, the segment plus its halo rows on a stream.
+template <typename DFn>
+__device__ __forceinline__ bool is_peak(DFn d, int i, int lo, int hi, int window) {
+    const float di = d(i);
+    int a = i - window / 2, b = a + window - 1;
+    a = max(a, lo);
+    b = min(b, hi);
+    bool pk = true;
+    for (int j = a; j <= b; ++j) {
+        if (j == i) continue;
+        const float dj = d(j);
+        pk = pk && (j < i ? (di > dj) : (di >= dj));
+    }
+    return pk;
+}
+
 struct SelectSmem {
     uint32_t hist[256];
     uint32_t wave_cnt[2][16];  // per-wave counts of the two compaction scans (<= 16 waves)
@@ -111,6 +129,54 @@ __device__ __forceinline__ void block_ordered_compact(KeyFn key, int n, uint32_t
         out_base += total;
         __syncthreads();  // wave_cnt reused next iteration
     }
+}
+
+// ---- DPSelect: one row (sync: the patch-mean row; async: patch position `row`) of a run of frames -------------------
+// Peak stencil + bonus + exact top-k + ordered emit over frames 0 .. len-1, with `left` / `right` more valid frames in
+// front of and behind them that only the peak windows look at (a whole video: none; a segment of a stream: its halo).
+// rowp(j) -> the N fp32 distances of frame j, -left <= j < len + right.  krow: [len] keys after the bonus (workspace and
+// output), raw: [left + len + right] patch means (sync only).  idx / mask as rtk_dpselect_select documents them, idx local
+// to the run.  All threads of the workgroup (BLOCK threads) must call it.
+constexpr int SEL_BLOCK = 256;
+
+template <int BLOCK, typename RowFn>
+__device__ __forceinline__ void dpselect_row(RowFn rowp, int N, int row, int len, int left, int right, int keep, int window,
+                                             int sync, int64_t* __restrict__ idx, uint8_t* __restrict__ mask,
+                                             float* __restrict__ krow, float* __restrict__ raw, SelectSmem& sm) {
+    const int tid = threadIdx.x;
+    if (sync) {
+        // dis.mean(1)  (:110): one wave per frame row, fixed-order lane partials + shuffle tree
+        const int lane = tid & (WAVE - 1), wid = tid / WAVE;
+        for (int t = wid; t < left + len + right; t += BLOCK / WAVE) {
+            const float* d = rowp(t - left);
+            float s = 0.f;
+            for (int n = lane; n < N; n += WAVE) s += d[n];
+            s = wave_sum(s);
+            if (lane == 0) raw[t] = s / (float)N;
+        }
+        __syncthreads();
+    }
+    auto dfn = [&](int t) -> float { return sync ? raw[t + left] : rowp(t)[row]; };
+    const int lo = -left, hi = len - 1 + right;
+    for (int t = tid; t < len; t += BLOCK) {
+        const float d = dfn(t);
+        krow[t] = is_peak(dfn, t, lo, hi, window) ? d + 2.0f : d;  // dis[peaks] += 2  (:133, :160)
+    }
+    __syncthreads();
+    auto key = [&](int t) -> uint32_t { return f2key(krow[t]); };
+    uint32_t thr;
+    int need_eq;
+    block_radix_threshold<BLOCK>(key, len, keep, sm, thr, need_eq);
+    block_ordered_compact<BLOCK>(key, len, thr, need_eq, sm, [&](int r, int t) {
+        const uint8_t pk = is_peak(dfn, t, lo, hi, window) ? 1 : 0;
+        if (sync) {
+            idx[r] = t;
+            for (int n = 0; n < N; ++n) mask[(size_t)r * N + n] = pk;  // mask[:,None].repeat(1,N) (:140)
+        } else {
+            idx[(size_t)r * N + row] = t;   // peaks.transpose(0,1)   (:169)
+            mask[(size_t)r * N + row] = pk; // mask.gather(0, peaks)  (:175)
+        }
+    });
 }
 
 }  // namespace rtk

@@ -230,6 +230,8 @@ _SIGNATURES = {
     "rtk_pivotkv_keep_scores_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_pivotkv_budget_select_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_pivotkv_squeeze_batched": (C.c_int, [_vp, _i, _vp]),
+    "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),
     "rtk_p2p_free": (C.c_int, [_vp]),
     "rtk_p2p_export": (C.c_int, [_vp, _vp, C.POINTER(_sz)]),

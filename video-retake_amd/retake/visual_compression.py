@@ -13,9 +13,10 @@ from __future__ import annotations
 import torch
 
 from . import _native as nv
+from .dpselect_stream import DPSelectStream  # noqa: F401  (the same selection for a video that does not end)
 
 __all__ = ["memory_bank_compress_keyframe", "memory_bank_compress_MALLM", "memory_bank_compress_MALLM_hard",
-           "memory_bank_compress_MALLM_hard_to", "dpselect_stages"]
+           "memory_bank_compress_MALLM_hard_to", "dpselect_stages", "DPSelectStream"]
 
 
 def dpselect_stages(memory_bank: torch.Tensor, tgt_mem_len: int, window_size: int = 3, sync: bool = True):

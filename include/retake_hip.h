@@ -161,7 +161,9 @@ int rtk_gather_frames(const void* x, int T, int N, int C, int dtype, const int64
 int rtk_adjacent_cosine(const void* x, int T, int N, int C, int dtype, float* cos_out, rtk_stream_t stream);
 
 /* :20-24 / :64-67  idx[n] = first arg-max over t of cos[t,n]; sync != 0: arg-max of the patch-mean row
- * (rounded to bf16 when round_bf16 != 0), written to every n.  cos [T1,N] fp32, idx [N] int64. */
+ * (rounded to bf16 when round_bf16 != 0), written to every n.  cos [T1,N] fp32, idx [N] int64.
+ * The order is torch.max's: NaN (a zero fp16 row: 0 / 0) counts as the maximum, and among equal maxima - several
+ * NaNs included - the lowest t wins.  rtk_mallm_hard_chain takes every step by the same rule. */
 int rtk_mallm_argmax(const float* cos, int T1, int N, int sync, int round_bf16, int64_t* idx, rtk_stream_t stream);
 
 /* :26-46 / :69-82  the merge: x [T,N,C], sizes [T,N] (dtype of x; soft merge only) -> out [T-1,N,C],

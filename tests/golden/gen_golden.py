@@ -983,6 +983,49 @@ def gen_fp16(vc, lc, outdir):
         print(name, "out", tuple(bank.shape))
 
 
+# --------------------------------------------------------------------------------------
+# MA-LLM-hard on lattice banks (tests/mallm_ref.py): exact cosines in every dtype, so ties decide most steps
+# --------------------------------------------------------------------------------------
+def gen_mallm_lattice(vc, outdir):
+    """The reference's loop (qwen2_vl.py:406-408) on one lattice bank (40, 6, 8), m = 4, down to 11 frames: sync and
+    async, fp32 / bf16 / fp16, and the same bank in fp16 with frame 6 all zero - its two pairs are 0 / 0 = NaN there, and
+    the fixture records what torch.max does with them.  Same fields as gen_mallm's files (fp16: as gen_fp16's)."""
+    import torch.nn.functional as F
+
+    import mallm_ref as mr
+
+    seed, T, N, C, m, tgt = mr.FIXTURE_BANK
+    tdt = {"fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}
+    for dtype, zero in [("fp32", False), ("bf16", False), ("fp16", False), ("fp16", True)]:
+        for sync in (False, True):
+            signs, _, x = mr.lattice_bank(seed, T, N, C, m)
+            if zero:
+                signs[6], x[6] = 0, 0.0
+            xt = torch.from_numpy(x)[None].to(tdt[dtype])
+            assert torch.equal(xt.double()[0], torch.from_numpy(x))          # the lattice is exact in the dtype
+            bank, steps_idx = xt.clone(), []
+            while bank.shape[1] > tgt:
+                sim = F.cosine_similarity(bank[:, :-1, :], bank[:, 1:, :], dim=-1)
+                if sync:
+                    sim = sim.mean(-1, keepdim=True).expand(-1, -1, N)
+                steps_idx.append(torch.max(sim, dim=1).indices[0].numpy().copy())
+                bank = vc.memory_bank_compress_MALLM_hard(bank, sync=sync)
+            steps_idx = np.stack(steps_idx).astype(np.int64)
+            ch = mr.hard_chain(signs, m, tgt, sync, dtype)
+            np.testing.assert_array_equal(ch.steps, steps_idx)
+            name = ("fp16" if dtype == "fp16" else "") + f"mallm_lattice_{'sync' if sync else 'async'}_{T}x{N}x{C}_t{tgt}" + \
+                   ("_bf16" if dtype == "bf16" else "") + ("_zero6" if zero else "")
+            bits = (lambda t: t.numpy()) if dtype == "fp32" else (lambda t: t.view(torch.int16).numpy())
+            xb, out = bits(xt), bits(bank)
+            if dtype == "bf16":
+                xb, out = xb.view(np.uint16), out.view(np.uint16)
+            np.savez_compressed(os.path.join(outdir, name + ".npz"), x=xb, dtype=dtype, T=T, N=N, C=C, m=m, seed=seed,
+                                tgt=tgt, sync=sync, hard=True, out=out, steps_idx=steps_idx, zero_frame=6 if zero else -1,
+                                size=np.zeros((0,), np.float32))
+            print(name, "steps", len(steps_idx), "tie share %.2f" % ch.tie_share, "head", ch.head_drops, "tail",
+                  ch.tail_drops, "NaN in out" if np.isnan(bank.float().numpy()).any() else "")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
@@ -1012,6 +1055,8 @@ def main():
         gen_mallm(vc, HERE)
     if args.only in (None, "fp16"):
         gen_fp16(vc, lc, HERE)
+    if args.only in (None, "mallm_lattice"):
+        gen_mallm_lattice(vc, HERE)
 
 
 if __name__ == "__main__":

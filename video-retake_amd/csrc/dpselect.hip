@@ -165,7 +165,16 @@ __global__ __launch_bounds__(256) void gather_rows_bytes_kernel(const uint8_t* _
 // MA-LLM / MA-LLM-hard (visual_compression.py:5-83): one merge step = adjacent cosine (dis_kernel in
 // cosine mode) -> arg-max frame pair per patch position -> merge + shift into a [T-1,N,C] bank.
 // ------------------------------------------------------------------------------------------------
-// idx[n] = first arg-max over t of sim[t,n]; sync: of the patch-mean row, the same for every n (:20-24)
+// The order of torch.max(dim) over similarities (:24 / :67): the maximum wins, NaN counts as the maximum (a zero fp16
+// row gives 0 / 0), and among equals - several NaNs included - the lowest index wins.  Does (v2, i2) come before (v, i)?
+// An empty candidate is (-inf, INT_MAX): every entry comes before it, it comes before none.
+__device__ __forceinline__ bool sim_beats(float v2, int i2, float v, int i) {
+    const bool n2 = v2 != v2, n = v != v;
+    if (n2 != n) return n2;
+    return (n2 || v2 == v) ? i2 < i : v2 > v;
+}
+
+// idx[n] = first arg-max over t of sim[t,n] in that order; sync: of the patch-mean row, the same for every n (:20-24)
 __global__ __launch_bounds__(256) void mallm_argmax_kernel(const float* __restrict__ cosv, int T1, int N, int sync,
                                                            int round_bf16, int64_t* __restrict__ idx) {
     extern __shared__ float mrow[];  // sync: [T1] patch means
@@ -189,7 +198,7 @@ __global__ __launch_bounds__(256) void mallm_argmax_kernel(const float* __restri
     int bidx = 0x7fffffff;
     for (int t = tid; t < T1; t += 256) {
         const float v = sync ? mrow[t] : cosv[(size_t)t * N + n];
-        if (v > best || (v == best && t < bidx) || bidx == 0x7fffffff) {
+        if (sim_beats(v, t, best, bidx)) {
             best = v;
             bidx = t;
         }
@@ -197,7 +206,7 @@ __global__ __launch_bounds__(256) void mallm_argmax_kernel(const float* __restri
     for (int o = 32; o > 0; o >>= 1) {
         const float v2 = __shfl_xor(best, o, WAVE);
         const int i2 = __shfl_xor(bidx, o, WAVE);
-        if (i2 != 0x7fffffff && (bidx == 0x7fffffff || v2 > best || (v2 == best && i2 < bidx))) {
+        if (sim_beats(v2, i2, best, bidx)) {
             best = v2;
             bidx = i2;
         }
@@ -206,7 +215,7 @@ __global__ __launch_bounds__(256) void mallm_argmax_kernel(const float* __restri
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 4; ++w)
-            if (bi[w] != 0x7fffffff && (bi[0] == 0x7fffffff || bv[w] > bv[0] || (bv[w] == bv[0] && bi[w] < bi[0]))) {
+            if (sim_beats(bv[w], bi[w], bv[0], bi[0])) {
                 bv[0] = bv[w];
                 bi[0] = bi[w];
             }

@@ -6,17 +6,26 @@
 // the most similar pair (out[t] = x[t + (t >= idx)], :69-82): the surviving rows are never modified, so of the next
 // call's cosines all but one are the ones just computed - only the pair that closes over the dropped frame is new.
 //   async (per patch position, the shipped patch_sync: False): one wave per patch keeps its T - 1 cosines and the
-//     frame list (next / previous links) in LDS; a step is an arg-max (first index wins, torch.max :66), an unlink and
-//     ONE new pair cosine (two rows of the bank, dprow_pair_cos = dis_kernel's arithmetic bit for bit);
+//     frame list (next / previous links) in LDS; a step is an arg-max (torch.max :66: first index wins, NaN is the
+//     maximum), an unlink and ONE new pair cosine (two rows of the bank, dprow_pair_cos = dis_kernel's arithmetic bit
+//     for bit);
 //   sync (one frame list for all patches): the similarity is the patch mean (:64-65), so a step scores the new pair at
 //     all N patch positions (one workgroup, 16 waves) and takes their mean in rtk_mallm_argmax's summation order.
 // Output: the surviving frame indices ([t, N] / [t]); rtk_gather_frames copies the rows.  Same values as looping
-// memory_bank_compress_MALLM_hard, bit for bit (tests/test_hip_parity.py::test_mallm_hard_chain_*).
+// memory_bank_compress_MALLM_hard, bit for bit (tests/test_update_paths_gpu.py::test_mallm_hard_chain_*; index for index
+// against an integer reference on banks with exact cosines, ties and NaN included: tests/test_mallm_gpu.py).
 #include "dprow.cuh"
 
 namespace rtk {
 
+// "no candidate": what a scan over dead slots only (-inf: no such pair) leaves behind.  While two frames survive some
+// live pair is chosen, so CHAIN_NONE never reaches the frame list.
 constexpr int CHAIN_NONE = 0x7fffffff;
+
+// torch.max takes a NaN similarity (a zero fp16 row: 0 / 0) for the maximum, the first one when there are several.  The
+// frame list holds it as +inf, which no cosine is (normalised entries are about 1 in magnitude at most, or NaN), so that the
+// plain compares of the scans and folds below - greater wins, lower index among equals - order it the same way.
+__device__ __forceinline__ float chain_key(float v) { return v != v ? INFINITY : v; }
 
 // lane-local best over slots lane, lane + 64, ...: ascending scan with a strict '>' keeps the first maximum
 __device__ __forceinline__ void chain_rescan(const float* cs, int n_slots, int lane, float& bv, int& bi) {
@@ -43,7 +52,7 @@ __global__ __launch_bounds__(WAVE) void mallm_hard_chain_kernel(const typename E
     const int lane = threadIdx.x;
     const int n = blockIdx.x;
     for (int i = lane; i < T; i += WAVE) {
-        cs[i] = (i < T - 1) ? cos0[(size_t)i * N + n] : -INFINITY;
+        cs[i] = (i < T - 1) ? chain_key(cos0[(size_t)i * N + n]) : -INFINITY;
         nx[i] = i + 1;
         pv[i] = i - 1;
     }
@@ -66,7 +75,7 @@ __global__ __launch_bounds__(WAVE) void mallm_hard_chain_kernel(const typename E
                 j = j2;
             }
         }
-        if (j == CHAIN_NONE) j = head;   // nothing compares greater than -inf (NaN similarities): the first pair
+        if (j == CHAIN_NONE) j = head;   // not reached while a pair is live; keeps the index inside the frame list
         j = __builtin_amdgcn_readfirstlane(j);
         const int p = __builtin_amdgcn_readfirstlane(pv[j]), q = __builtin_amdgcn_readfirstlane(nx[j]);  // frame j leaves; q exists
         float newc = 0.f;
@@ -77,7 +86,7 @@ __global__ __launch_bounds__(WAVE) void mallm_hard_chain_kernel(const typename E
             pv[q] = p;
             if (p >= 0) {
                 nx[p] = q;
-                cs[p] = newc;
+                cs[p] = chain_key(newc);
             }
         }
         if (p < 0) head = q;
@@ -121,7 +130,7 @@ __global__ __launch_bounds__(SYNC_BLOCK) void mallm_hard_chain_sync_kernel(const
         float s = 0.f;
         for (int j = lane; j < N; j += WAVE) s += cos0[(size_t)t * N + j];
         s = wave_sum(s);
-        if (lane == 0) ms[t] = round_to(s / (float)N, round_mode);
+        if (lane == 0) ms[t] = chain_key(round_to(s / (float)N, round_mode));
     }
     for (int i = tid; i < T; i += SYNC_BLOCK) {
         if (i == T - 1) ms[i] = -INFINITY;
@@ -185,7 +194,7 @@ __global__ __launch_bounds__(SYNC_BLOCK) void mallm_hard_chain_sync_kernel(const
                 float s = 0.f;
                 for (int k = lane; k < N; k += WAVE) s += cn[k];
                 s = wave_sum(s);
-                m = round_to(s / (float)N, round_mode);
+                m = chain_key(round_to(s / (float)N, round_mode));
             }
             if (lane == 0) {
                 ms[j] = -INFINITY;

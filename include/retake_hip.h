@@ -58,6 +58,8 @@
  *                                       (opt-in: video_budget_rows)
  *   §P  "DPSelect on a stream"          rtk_dpselect_ingest, rtk_dpselect_select_ring: keyframe selection for a video that
  *                                       does not end, in a ring of 2 S frames (retake/dpselect_stream.py)
+ *   §Q  "Position re-base"              rtk_pivotkv_rebase_batched: the ids of a bounded video region re-based to follow the
+ *                                       pinned rows and its keys re-rotated in place (opt-in: video_position_limit)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -1123,6 +1125,53 @@ int rtk_dpselect_ingest(const void* x, const void* prev, int t, int N, int C, in
                         float* dis_out, rtk_stream_t stream);
 int rtk_dpselect_select_ring(const float* dis_ring, int R, int N, int r0, int len, int left, int right, int keep,
                              int window, int sync, int64_t* idx, uint8_t* mask, float* keys, rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Position re-base (opt-in: longvideo_kwargs["video_position_limit"]; NOT in the reference, which processes a finished
+ * video, and a rule of this project's own: what it does to answer quality has not been evaluated).  A bounded video region
+ * drops rows but leaves every surviving id where it was, so the ids of a stream that does not end grow without bound while
+ * the rows span a bounded range.  Per unit (a layer), with t = row 0 of its ids and the region's ids t[first, end):
+ *     base  = first > 0 ? t[first - 1] + 1 : 0
+ *     delta = t[first] - base
+ *     if delta > 0 and t[end - 1] >= limit:
+ *         t[first, end) -= delta                                   (id rows 1 and 2 are not touched)
+ *         K[h, first .. first + rows, temporal pairs] <- R(-delta) K   (every head h < H; V is not an argument)
+ *         offsets[slot] += delta
+ * The temporal pairs (d, d + D/2) are all D/2 for P == 1 and the pairs whose channels the M-RoPE sections give to id
+ * row 0 for P == 3; the other channels keep their bits, and a 16-byte chunk pair without a temporal channel is neither
+ * loaded nor stored.  Arithmetic per pair, in fp32: theta = (float)delta * inv_freq[d], (s, c) = correctly rounded
+ * sin / cos of theta, o1 = fma(x1, c, x2 * s), o2 = fma(x2, c, -(x1 * s)), one rounding to the storage dtype.  No
+ * attention_scaling: a stored key already carries it, and a rotation by R(-delta) leaves it in place.
+ *
+ * Everything is decided on the device and nothing is read back.  Two launches per RTK_REBASE_MAX_UNITS units and no order
+ * between workgroups - no flags, no counters, no waiting: a one-wave-per-unit decision launch writes delta[i] (0: unit i
+ * did not trigger) and advances offsets[slot]; the apply launch reads delta[i] alone, so no workgroup reads an id another
+ * one rewrites.  A unit with delta 0 costs one load per workgroup.  The grid is sized to the machine, not to the rows.
+ *   D, dtype        shared by the units: RTK_BF16 / RTK_F16 with D a multiple of 16, RTK_F32 with D a multiple of 8, D <= 256
+ *   inv_freq        DEVICE fp32 [D / 2];  sections_host / nsec: the M-RoPE sections (P == 3)
+ *   offsets         DEVICE int64, indexed by unit.slot: the cumulative delta of a layer.  Slots of one call are distinct
+ *   delta           DEVICE int64 [n_units] scratch, written for every unit
+ * `units` is a HOST array; n_units == 0 launches nothing and returns 0.  Errors, all before any launch: RTK_EINVAL for NULL
+ * pointers, negative sizes / strides / slots / limit, a bad dtype, P other than 1 or 3, first > end, a head stride smaller
+ * than the rows it is asked to walk, ids_stride < end (P == 3), two units with one slot, bad sections; RTK_EUNSUPPORTED for
+ * K pointers or head strides that are not 16-byte aligned, a head_dim outside the envelope, and sections that split a
+ * rotation pair between id rows.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rtk_rebase_unit {
+    void*    k;           /* K buffer of the layer: row r of head h at k + h*k_stride_h + r*D*esize */
+    int64_t  k_stride_h;  /* BYTES between kv heads (cap * D * esize) */
+    int64_t  first;       /* the region's first row (K and ids alike) */
+    int64_t  rows;        /* K rows re-rotated: [first, first + rows) */
+    int64_t* ids;         /* id buffer [P, cap], row 0 the temporal ids */
+    int64_t  ids_stride;  /* elements between id rows */
+    int64_t  end;         /* ids re-based: row 0, [first, end) */
+    int32_t  H;           /* kv heads */
+    int32_t  slot;        /* the layer's slot in `offsets` */
+} rtk_rebase_unit;
+#define RTK_REBASE_MAX_UNITS 64   /* units per pair of launches (the array travels as a kernel argument) */
+int rtk_pivotkv_rebase_batched(const rtk_rebase_unit* units, int n_units, int D, int dtype, int P, const float* inv_freq,
+                               const int* sections_host, int nsec, int64_t limit, int64_t* offsets, int64_t* delta,
+                               rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -139,6 +139,15 @@ class SqueezeUnit(C.Structure):
                 ("rows_out", _i64), ("rows_in", _i64), ("idx", _vp)]
 
 
+REBASE_MAX_UNITS = 64   # RTK_REBASE_MAX_UNITS: units per pair of launches of rtk_pivotkv_rebase_batched
+
+
+class RebaseUnit(C.Structure):
+    """rtk_rebase_unit (include/retake_hip.h)."""
+    _fields_ = [("k", _vp), ("k_stride_h", _i64), ("first", _i64), ("rows", _i64), ("ids", _vp), ("ids_stride", _i64),
+                ("end", _i64), ("H", _i32), ("slot", _i32)]
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -230,6 +239,7 @@ _SIGNATURES = {
     "rtk_pivotkv_keep_scores_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_pivotkv_budget_select_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_pivotkv_squeeze_batched": (C.c_int, [_vp, _i, _vp]),
+    "rtk_pivotkv_rebase_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),

@@ -10,6 +10,10 @@ stream; `_commit` keeps the books: length / len8 and pos_len shrink, num_evicted
 grow, `_seen_tokens` is left alone.  Rows below every earlier mark are rewritten, so the epoch moves: earlier marks raise
 in `rewind`, live branches are dead; the `video_end` that `after_forward` takes next is valid.  No buffer is allocated or
 replaced.
+
+`video_position_limit` (this project's own rule, no reference counterpart) rides on a move: `rebase_positions` shifts the
+ids of the layers just moved down to follow their pinned rows and re-rotates their keys by the same delta, decided on the
+device per layer; `position_offset` is the cumulative delta.
 """
 import torch
 
@@ -48,6 +52,105 @@ def configure(cache, config, word: str, prompt_guided: str, clash=None):
         setattr(cache, rows_key, rows)
         setattr(cache, slack_key, slack)
     return rows
+
+
+def configure_position_limit(cache, config):
+    """build_kvcache: longvideo_kwargs' video_position_limit, validated and set on the cache (None: off).  Every refusal
+    names the key it clashes with; nothing else has happened yet."""
+    kw, key = config.longvideo_kwargs, "video_position_limit"
+    P = kw.get(key, None)
+    if P is None:
+        return None
+    if not isinstance(P, int) or isinstance(P, bool) or P < 0:
+        raise ValueError(f"{key} must be an int >= 0 (or None: the ids are never re-based), got {P!r}")
+    if kw.get("video_window_rows", None) is None and kw.get("video_budget_rows", None) is None:
+        raise ValueError(f"{key} needs video_window_rows or video_budget_rows: the ids are re-based only where a bounded "
+                         "video region has just moved its rows")
+    if not cache.pos_embed_reforge:
+        raise ValueError(f"{key} needs pos_embed_reforge=True: without it the cache keeps no ids to re-base")
+    if cache.kv_cache_dtype is not None:
+        raise ValueError(f"{key} does not serve kv_cache_dtype={cache.kv_cache_dtype!r}: re-quantising e4m3 codes at every "
+                         "re-base compounds a 2^-4 relative error per row, so it is not built")
+    if not cache.native_rope:
+        raise ValueError(f"{key} needs native_rope=True: the rotation by the id delta is computed on the device from the "
+                         "rotary module's inv_freq, a module that has to be called cannot serve it")
+    cache.video_position_limit = P
+    return P
+
+
+def _rebase_rotary(cache):
+    """The native-RoPE snapshot the last chunk was rotated with; ValueError - before anything is launched - for a rotary
+    module that has to be called (no inv_freq, the dynamic / longrope kinds)."""
+    b = cache._batch
+    if b is None or b.rot is None:
+        raise ValueError("video_position_limit: the rotary module of this model has to be called (it has no inv_freq, or is "
+                         "of a dynamic / longrope kind), so the keys cannot be re-rotated by an id delta on the device - "
+                         "build the cache without video_position_limit")
+    return b
+
+
+def _offsets(cache, device):
+    """The device's int64 array of cumulative deltas, one slot per layer (zeros at first; it grows with the layers)."""
+    n = max(int(cache.num_hidden_layers), len(cache._layers))
+    t = cache._position_offsets.get(device)
+    if t is None or t.numel() < n:
+        new = torch.zeros(n, dtype=torch.int64, device=device)
+        if t is not None:
+            new[:t.numel()].copy_(t)
+        cache._position_offsets[device] = t = new
+    return t
+
+
+def rebase_positions(cache, by_device):
+    """video_position_limit (not in the reference; a rule of this project's own): for every layer the policy has just moved,
+    ONE rtk_pivotkv_rebase_batched call per device - decided on the device, nothing is read back.  With t the layer's
+    temporal ids, `first` its first region row and `end` its pos_len:
+
+        base = t[first - 1] + 1 if first > 0 else 0;  delta = t[first] - base
+        if delta > 0 and t[end - 1] >= video_position_limit:
+            t[first:end] -= delta;  K[:, first:length, temporal channels] <- R(-delta) K;  position_offset(layer) += delta
+
+    Called after `_commit`: the lengths are the moved region's.  Rows 1 / 2 of M-RoPE ids, the other channels, V and the
+    pinned rows are not touched; 16-bit rows behind the region move with it, ids and keys alike."""
+    if cache.video_position_limit is None or not by_device:
+        return
+    b = _rebase_rotary(cache)
+    for dev, layers in by_device.items():
+        groups = {}
+        for l, st, *_ in layers:
+            first = st.pinned
+            if st._pos is None or st.c.pos_len <= first or first < 0:
+                continue
+            P, D = st._pos.shape[0], st._k.shape[3]
+            u = nv.RebaseUnit(st._k.data_ptr(), st._k.stride(1) * st._k.element_size(), first, st.c.length - first,
+                              st._pos.data_ptr(), st._pos.stride(0), st.c.pos_len, st._k.shape[1], l)
+            groups.setdefault((D, nv.dtype_code(st._k), P), []).append(u)
+        if not groups:
+            continue
+        device = layers[0][1]._k.device
+        inv = b.rot.inv
+        if inv.device != device:   # (layers spread over devices: a copy of the frequencies on each)
+            inv = cache._buf(f"rebase_inv{dev}", inv.shape, inv.dtype, device)
+            inv.copy_(b.rot.inv)
+        off = _offsets(cache, device)
+        for (D, dt, P), us in groups.items():
+            delta = cache._buf(f"rebase_delta{dev}", (len(us),), torch.int64, device)
+            nsec = b.c.nsec if P == 3 else 0
+            nv.check(_on_device(dev, nv.lib.rtk_pivotkv_rebase_batched, (nv.RebaseUnit * len(us))(*us), len(us), D, dt, P,
+                                inv.data_ptr(), b.sec if nsec else None, nsec, cache.video_position_limit, off.data_ptr(),
+                                delta.data_ptr(), nv.raw_stream(dev)), "rtk_pivotkv_rebase_batched")
+
+
+def position_offset(cache, layer_idx: int) -> torch.Tensor:
+    """video_position_limit: the cumulative delta the layer's region ids have been re-based by, a 0-dim int64 tensor on the
+    layer's device (a view of the array the kernel advances: read without a sync, it is as current as the stream).  A stored id
+    + this = the id an unbounded cache would hold.  A zero with the key off or before any move."""
+    st = cache._layers[layer_idx] if 0 <= layer_idx < len(cache._layers) else None
+    device = st._k.device if st is not None and st._k is not None else None
+    t = cache._position_offsets.get(device) if device is not None else None
+    if t is None or layer_idx >= t.numel():
+        return torch.zeros((), dtype=torch.int64, device=device)
+    return t[layer_idx]
 
 
 def region_room(cache, st: _LayerStore, first: int, more: int) -> int:
@@ -128,6 +231,8 @@ def slide_window(cache):
     tensors two).  get_prev_temporal_idx still reads the last stored id."""
     W = cache.video_window_rows
     by_device = _plan(cache, "video_window_rows", "cannot slide")
+    if by_device and cache.video_position_limit is not None:
+        _rebase_rotary(cache)   # (raises before the move, not between the move and the re-base)
     for dev, layers in by_device.items():
         units = []
         for _, st, first, n, ids, streams in layers:
@@ -138,6 +243,7 @@ def slide_window(cache):
         _launch(dev, "rtk_pivotkv_slide_batched", (nv.SlideUnit * len(units))(*[nv.SlideUnit(*u) for u in units]), len(units))
     if by_device:
         _commit(cache, by_device, cache.window_dropped)
+        rebase_positions(cache, by_device)
 
 
 def evict_budget(cache):
@@ -163,6 +269,8 @@ def evict_budget(cache):
                              "video and left in place.  Rewind to `video_end` before the stream goes on (a question's "
                              "rows carry no score and cannot take part in the eviction)")
     by_device = _plan(cache, "video_budget_rows", "cannot be evicted", scored)
+    if by_device and cache.video_position_limit is not None:
+        _rebase_rotary(cache)   # (raises before the move, not between the move and the re-base)
     for dev, layers in by_device.items():
         idx = cache._buf(f"budget_idx{dev}", (len(layers), B), torch.int32, layers[0][1]._k.device)
         sel = (nv.BudgetSelectUnit * len(layers))()
@@ -178,6 +286,7 @@ def evict_budget(cache):
         for layers in by_device.values():
             for _, st, *_ in layers:
                 st.sc_len = B
+        rebase_positions(cache, by_device)
 
 
 def keep_scores(cache, b: _Batch, layers):

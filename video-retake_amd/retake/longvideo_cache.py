@@ -230,6 +230,17 @@ class PivotKVCache(DynamicCache):
         # changes, no score buffer exists.  The mechanism, and what each policy does: _video_bound.
         self.video_window_rows, self.video_window_slack = None, 0
         self.video_budget_rows, self.video_budget_slack = None, 0
+        # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it; NOT in the reference, a rule of
+        # this project's own - answer quality is not evaluated): video_position_limit = P, an int >= 0, needs a window or a
+        # budget.  A move drops rows but leaves every surviving id where it was, so the ids of a stream that does not end grow
+        # without bound.  With the key on, an `after_forward` that has just moved a layer's rows looks - on the device - at
+        # the layer's temporal ids: if the region's last id has reached P and its first id lies more than one past the
+        # pinned rows' last, the region's ids are shifted down to follow the pinned rows and its keys re-rotated by the same
+        # delta in place (_video_bound.rebase_positions).  P = 0 re-bases at every move: ids then equal "position in cache",
+        # and every row of the region is re-rounded to the storage dtype once per move (half an ulp each time, DESIGN.md
+        # §5) - a higher P trades id range for fewer roundings.  None (default): off, nothing changes, bit for bit.
+        self.video_position_limit = None
+        self._position_offsets: Dict[Any, torch.Tensor] = {}   # per device: int64 [layers], the cumulative deltas
         self.window_dropped: List[int] = []   # per layer: rows the window has dropped so far (also counted as evicted)
         self.budget_dropped: List[int] = []   # ... and the budget
         self._attn_ws: Dict[Any, torch.Tensor] = {}
@@ -825,6 +836,7 @@ class PivotKVCache(DynamicCache):
 
     # ---- the bounded video region (video_window_rows / video_budget_rows): functions of _video_bound, bound as methods
     _region_room, _keep_scores, row_scores = _video_bound.region_room, _video_bound.keep_scores, _video_bound.row_scores
+    position_offset = _video_bound.position_offset
 
     # ---- bookkeeping lists (reference :152-215) ------------------------------------------------
     def update_num_evicted_tokens(self, num_tokens: int, layer_idx: int):
@@ -2068,6 +2080,7 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
                                  "cannot read the fp8 rows")
             if cache.defer_rerotation:
                 raise ValueError("kv_cache_dtype='fp8_e4m3' does not serve defer_rerotation (the sharded prefill)")
+        _video_bound.configure_position_limit(cache, config)
         W = _video_bound.configure(cache, config, "window", "a prompt-guided cache belongs to one question, a window to a "
                                    "stream that does not end")
         B = _video_bound.configure(cache, config, "budget", "its scores answer one question and are not comparable between "

@@ -60,6 +60,8 @@
  *                                       does not end, in a ring of 2 S frames (retake/dpselect_stream.py)
  *   §Q  "Position re-base"              rtk_pivotkv_rebase_batched: the ids of a bounded video region re-based to follow the
  *                                       pinned rows and its keys re-rotated in place (opt-in: video_position_limit)
+ *   §R  "Position renumbering"          rtk_pivotkv_renumber_batched: the id gaps of such a region closed row by row, each
+ *                                       key re-rotated by its own row's delta (opt-in: video_position_gap)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -1172,6 +1174,64 @@ typedef struct rtk_rebase_unit {
 int rtk_pivotkv_rebase_batched(const rtk_rebase_unit* units, int n_units, int D, int dtype, int P, const float* inv_freq,
                                const int* sections_host, int nsec, int64_t limit, int64_t* offsets, int64_t* delta,
                                rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * §R  Position renumbering (opt-in: longvideo_kwargs["video_position_gap"] on top of "video_position_limit"; NOT in the
+ * reference, and a rule of this project's own: what it does to answer quality has not been evaluated).  The re-base above
+ * subtracts ONE delta per layer, the gap between the pinned rows and the first region row.  Under the budget an old,
+ * well-scored survivor keeps t[first] low: that delta stays 0 while evictions open holes everywhere else in the region and
+ * the last id grows as if nothing were bounded.  Renumbering closes the holes row by row; it generalises the re-base's
+ * rule.  Per unit (a layer), with t = row 0 of its ids, the region's ids t[first, end), the K rows [first, first + rows),
+ * rows <= end - first, and prev = t[first - 1] if first > 0, else -1 - all integers, exact:
+ *     e[first] = max(0, t[first] - prev - 1)                   the region follows the pinned rows: the re-base's delta
+ *     e[i]     = max(0, t[i] - t[i - 1] - gap)  (first < i < end)   inner gaps above `gap` close to `gap`
+ *     d[i]     = e[first] + ... + e[i]                         inclusive prefix sum: non-negative, non-decreasing
+ *     total    = d[end - 1]
+ *     if the region is not empty, t[end - 1] >= limit and total > 0:
+ *         t[i] -= d[i]                                             (id rows 1 and 2 are not touched)
+ *         K[h, first + r, temporal pairs] <- R(-d[first + r]) K    (r < rows, every head h < H; V is not an argument)
+ *         offsets[slot] += total
+ * Gaps <= gap stay as they are, 0 (rows of one frame) and negative gaps included: nothing is "repaired".  A row with
+ * d = 0 keeps its bits - it is neither loaded, rotated nor re-rounded.  Ids in [first + rows, end) (16-bit rows behind a
+ * window's region) take their own d, which is the region's total unless gaps above `gap` lie among them.  The temporal
+ * pairs, the other channels and the arithmetic per pair are the re-base's, with d of the row for delta:
+ * theta = (float)d * inv_freq[d], correctly rounded sin / cos, one fma chain, one rounding to the storage dtype.
+ *
+ * With gap at or above every inner gap the call does what rtk_pivotkv_rebase_batched does: ids, K bits and offsets.  For
+ * non-decreasing ids the cap composes - min(min(x, gap) + min(y, gap), gap) = min(x + y, gap) - so a row dropped later
+ * merges two gaps without changing the result: after a triggered move the stored ids are a closed-form function of the
+ * unbounded ids of the surviving rows.  A renumbered region of n rows spans at most 1 + (n - 1) * gap ids behind the
+ * pinned rows; `limit` must exceed pinned + (rows a region may hold) * gap, or every move triggers.
+ *
+ * Everything is decided on the device and nothing is read back.  Two launches per RTK_REBASE_MAX_UNITS units and no order
+ * between workgroups - no flags, no counters, no waiting: the scan launch (one workgroup per unit) only reads ids; it walks
+ * [first, end) in tiles of RTK_RENUMBER_TILE ids (a wave-level inclusive scan, the waves' sums through LDS, a running int64
+ * carry) and writes d into row_delta, delta[i] = total (0: unit i did not trigger) and offsets[slot].  The apply launch
+ * returns at once for delta[i] == 0; otherwise it rewrites the ids from row_delta and rotates the keys in the re-base
+ * apply's layout, a workgroup over a contiguous block of rows, the cos / sin recomputed only where d changes.
+ *   D, dtype, inv_freq, sections_host / nsec, limit, offsets, delta     as for rtk_pivotkv_rebase_batched
+ *   gap             >= 1
+ *   unit.row_delta  DEVICE int64 scratch of at least end - first entries, 8-byte aligned, the unit's own; written if the
+ *                   unit's last id has reached the limit (a unit below it is not scanned), read only if it triggers
+ * Errors, all before any launch: those of rtk_pivotkv_rebase_batched, and RTK_EINVAL for gap < 1, rows > end - first and a
+ * NULL or misaligned row_delta.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rtk_renumber_unit {   /* rtk_rebase_unit's fields, then the scratch */
+    void*    k;
+    int64_t  k_stride_h;
+    int64_t  first;
+    int64_t  rows;
+    int64_t* ids;
+    int64_t  ids_stride;
+    int64_t  end;
+    int32_t  H;
+    int32_t  slot;
+    int64_t* row_delta;   /* DEVICE [end - first] scratch: d of every region id */
+} rtk_renumber_unit;
+#define RTK_RENUMBER_TILE 2048   /* ids the scan kernel's workgroup takes per step (8 per thread) */
+int rtk_pivotkv_renumber_batched(const rtk_renumber_unit* units, int n_units, int D, int dtype, int P, const float* inv_freq,
+                                 const int* sections_host, int nsec, int64_t limit, int64_t gap, int64_t* offsets,
+                                 int64_t* delta, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

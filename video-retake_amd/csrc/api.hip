@@ -32,7 +32,7 @@ static const char* const kKernelNames[KID_COUNT] = {"dpselect_dis", "dpselect_se
                                                     "evict_batched", "commit_batched", "position_shift", "pivotkv_emit",
                                                     "prologue", "compact_units", "archive_units", "slide_units",
                                                     "keep_scores", "budget_select", "squeeze_units", "rebase_decide",
-                                                    "rebase_apply"};
+                                                    "rebase_apply", "renumber_scan", "renumber_apply"};
 struct ProfRec { int kid; hipEvent_t a, b; };
 static std::mutex g_pm;
 static std::atomic<unsigned> g_prof{0};  // bit k set = time kernel id k

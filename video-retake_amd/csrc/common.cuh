@@ -626,7 +626,7 @@ namespace rtk {
 enum KernelId {
     KID_DIS = 0, KID_DPSEL, KID_GATHER, KID_ROPE, KID_UNROT, KID_PASS1, KID_PASS2, KID_FINALIZE, KID_PSEL, KID_APPEND,
     KID_EVICTB, KID_COMMITB, KID_SHIFT, KID_PEMIT, KID_PROLOGUE, KID_COMPACT, KID_ARCHIVE, KID_SLIDE, KID_KEEPSC,
-    KID_BSELECT, KID_SQUEEZE, KID_REBASE_DECIDE, KID_REBASE, KID_COUNT
+    KID_BSELECT, KID_SQUEEZE, KID_REBASE_DECIDE, KID_REBASE, KID_RENUMBER_SCAN, KID_RENUMBER, KID_COUNT
 };
 bool profile_on(int kid);
 void profile_begin(int kid, hipStream_t st);

@@ -148,6 +148,14 @@ class RebaseUnit(C.Structure):
                 ("end", _i64), ("H", _i32), ("slot", _i32)]
 
 
+RENUMBER_TILE = 2048   # RTK_RENUMBER_TILE: ids the scan kernel of rtk_pivotkv_renumber_batched takes per step
+
+
+class RenumberUnit(C.Structure):
+    """rtk_renumber_unit (include/retake_hip.h): rtk_rebase_unit's fields, then the per-row delta scratch."""
+    _fields_ = RebaseUnit._fields_ + [("row_delta", _vp)]
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -240,6 +248,7 @@ _SIGNATURES = {
     "rtk_pivotkv_budget_select_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_pivotkv_squeeze_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_pivotkv_rebase_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "rtk_pivotkv_renumber_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp]),
     "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),

@@ -13,7 +13,9 @@ replaced.
 
 `video_position_limit` (this project's own rule, no reference counterpart) rides on a move: `rebase_positions` shifts the
 ids of the layers just moved down to follow their pinned rows and re-rotates their keys by the same delta, decided on the
-device per layer; `position_offset` is the cumulative delta.
+device per layer; `position_offset` is the cumulative delta.  With `video_position_gap` = G on top (again this project's
+own rule, no reference counterpart, answer quality not evaluated) the delta is per ROW: inner id gaps above G close to G as
+well, each key is re-rotated by its own row's delta, and `position_offset` grows by the last row's.
 """
 import torch
 
@@ -55,11 +57,14 @@ def configure(cache, config, word: str, prompt_guided: str, clash=None):
 
 
 def configure_position_limit(cache, config):
-    """build_kvcache: longvideo_kwargs' video_position_limit, validated and set on the cache (None: off).  Every refusal
-    names the key it clashes with; nothing else has happened yet."""
-    kw, key = config.longvideo_kwargs, "video_position_limit"
-    P = kw.get(key, None)
+    """build_kvcache: longvideo_kwargs' video_position_limit and video_position_gap, validated and set on the cache (None:
+    off).  Every refusal names the key it clashes with; nothing else has happened yet.  The gap needs the limit, and every
+    refusal of the limit holds with the gap set."""
+    kw, key, gap_key = config.longvideo_kwargs, "video_position_limit", "video_position_gap"
+    P, G = kw.get(key, None), kw.get(gap_key, None)
     if P is None:
+        if G is not None:
+            raise ValueError(f"{gap_key} needs {key}: ids are renumbered only where that limit has been reached")
         return None
     if not isinstance(P, int) or isinstance(P, bool) or P < 0:
         raise ValueError(f"{key} must be an int >= 0 (or None: the ids are never re-based), got {P!r}")
@@ -74,7 +79,9 @@ def configure_position_limit(cache, config):
     if not cache.native_rope:
         raise ValueError(f"{key} needs native_rope=True: the rotation by the id delta is computed on the device from the "
                          "rotary module's inv_freq, a module that has to be called cannot serve it")
-    cache.video_position_limit = P
+    if G is not None and (not isinstance(G, int) or isinstance(G, bool) or G < 1):
+        raise ValueError(f"{gap_key} must be an int >= 1 (or None: {key} re-bases a region by one delta), got {G!r}")
+    cache.video_position_limit, cache.video_position_gap = P, G
     return P
 
 
@@ -111,23 +118,42 @@ def rebase_positions(cache, by_device):
             t[first:end] -= delta;  K[:, first:length, temporal channels] <- R(-delta) K;  position_offset(layer) += delta
 
     Called after `_commit`: the lengths are the moved region's.  Rows 1 / 2 of M-RoPE ids, the other channels, V and the
-    pinned rows are not touched; 16-bit rows behind the region move with it, ids and keys alike."""
+    pinned rows are not touched; 16-bit rows behind the region move with it, ids and keys alike.
+
+    With video_position_gap = G (also this project's own rule; the reference has no counterpart and answer quality is not
+    evaluated) the call is rtk_pivotkv_renumber_batched and the delta is per row - under the budget an old survivor keeps
+    t[first] low, the delta above stays 0 and the holes evictions open elsewhere are never closed without it:
+
+        e[first] = max(0, t[first] - prev - 1), prev = t[first - 1] if first > 0 else -1;  e[i] = max(0, t[i] - t[i - 1] - G)
+        d[i] = e[first] + ... + e[i];  total = d[end - 1]
+        if total > 0 and t[end - 1] >= video_position_limit:
+            t[i] -= d[i];  K[:, i, temporal channels] <- R(-d[i]) K;  position_offset(layer) += total
+
+    Gaps <= G stay (0 and negative ones too); a row with d = 0 keeps its bits.  The per-row deltas live in one scratch
+    buffer per device, sized once for a full region, its slack and a chunk: no buffer is replaced after warm-up."""
     if cache.video_position_limit is None or not by_device:
         return
     b = _rebase_rotary(cache)
+    gap = cache.video_position_gap
     for dev, layers in by_device.items():
         groups = {}
+        device = layers[0][1]._k.device
+        if gap is not None:
+            # the per-row deltas: one row of scratch per layer, sized once - a full region with its slack and a chunk in
+            # flight, or whatever lies behind the pinned rows now (16-bit rows behind a window's region) if that is more
+            room = max(max(st.c.pos_len - st.pinned for _, st, *_ in layers), sum(bound(cache)) + b.L)
+            row_delta = cache._buf(f"renumber_rows{dev}", (len(cache._layers), room), torch.int64, device)
         for l, st, *_ in layers:
             first = st.pinned
             if st._pos is None or st.c.pos_len <= first or first < 0:
                 continue
             P, D = st._pos.shape[0], st._k.shape[3]
-            u = nv.RebaseUnit(st._k.data_ptr(), st._k.stride(1) * st._k.element_size(), first, st.c.length - first,
-                              st._pos.data_ptr(), st._pos.stride(0), st.c.pos_len, st._k.shape[1], l)
+            u = (st._k.data_ptr(), st._k.stride(1) * st._k.element_size(), first, st.c.length - first,
+                 st._pos.data_ptr(), st._pos.stride(0), st.c.pos_len, st._k.shape[1], l)
+            u = nv.RebaseUnit(*u) if gap is None else nv.RenumberUnit(*u, row_delta[l].data_ptr())
             groups.setdefault((D, nv.dtype_code(st._k), P), []).append(u)
         if not groups:
             continue
-        device = layers[0][1]._k.device
         inv = b.rot.inv
         if inv.device != device:   # (layers spread over devices: a copy of the frequencies on each)
             inv = cache._buf(f"rebase_inv{dev}", inv.shape, inv.dtype, device)
@@ -136,6 +162,11 @@ def rebase_positions(cache, by_device):
         for (D, dt, P), us in groups.items():
             delta = cache._buf(f"rebase_delta{dev}", (len(us),), torch.int64, device)
             nsec = b.c.nsec if P == 3 else 0
+            if gap is not None:
+                nv.check(_on_device(dev, nv.lib.rtk_pivotkv_renumber_batched, (nv.RenumberUnit * len(us))(*us), len(us), D, dt, P,
+                                    inv.data_ptr(), b.sec if nsec else None, nsec, cache.video_position_limit, gap,
+                                    off.data_ptr(), delta.data_ptr(), nv.raw_stream(dev)), "rtk_pivotkv_renumber_batched")
+                continue
             nv.check(_on_device(dev, nv.lib.rtk_pivotkv_rebase_batched, (nv.RebaseUnit * len(us))(*us), len(us), D, dt, P,
                                 inv.data_ptr(), b.sec if nsec else None, nsec, cache.video_position_limit, off.data_ptr(),
                                 delta.data_ptr(), nv.raw_stream(dev)), "rtk_pivotkv_rebase_batched")
@@ -144,7 +175,11 @@ def rebase_positions(cache, by_device):
 def position_offset(cache, layer_idx: int) -> torch.Tensor:
     """video_position_limit: the cumulative delta the layer's region ids have been re-based by, a 0-dim int64 tensor on the
     layer's device (a view of the array the kernel advances: read without a sync, it is as current as the stream).  A stored id
-    + this = the id an unbounded cache would hold.  A zero with the key off or before any move."""
+    + this = the id an unbounded cache would hold.  A zero with the key off or before any move.
+
+    With video_position_gap it grows by the renumbering's `total`, the delta of the region's LAST id: `stored last id +
+    offset = the unbounded run's last id` still holds for the newest row - later chunks continue from that row - but no
+    longer for every row: an older row has been moved down by less."""
     st = cache._layers[layer_idx] if 0 <= layer_idx < len(cache._layers) else None
     device = st._k.device if st is not None and st._k is not None else None
     t = cache._position_offsets.get(device) if device is not None else None

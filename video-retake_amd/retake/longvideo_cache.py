@@ -240,6 +240,14 @@ class PivotKVCache(DynamicCache):
         # and every row of the region is re-rounded to the storage dtype once per move (half an ulp each time, DESIGN.md
         # §5) - a higher P trades id range for fewer roundings.  None (default): off, nothing changes, bit for bit.
         self.video_position_limit = None
+        # video_position_gap = G, an int >= 1, needs video_position_limit (again NOT in the reference and a rule of this
+        # project's own - answer quality is not evaluated): the delta becomes one per ROW.  Besides the gap behind the pinned
+        # rows, every inner id gap above G closes to G (gaps <= G stay, 0 and negative ones included) and each key is
+        # re-rotated by its own row's delta (_video_bound.rebase_positions).  Under the budget an old survivor keeps the
+        # region's first id low, so without this key the uniform delta stays 0 and the last id grows unbounded.  A
+        # renumbered region of n rows spans at most 1 + (n - 1) G ids: P must exceed pinned + (rows + slack + a chunk's
+        # kept rows) G, or every move triggers and re-rounds nearly every row.  None (default): the uniform re-base.
+        self.video_position_gap = None
         self._position_offsets: Dict[Any, torch.Tensor] = {}   # per device: int64 [layers], the cumulative deltas
         self.window_dropped: List[int] = []   # per layer: rows the window has dropped so far (also counted as evicted)
         self.budget_dropped: List[int] = []   # ... and the budget

@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (69 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (87 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -62,6 +62,9 @@
  *                                       pinned rows and its keys re-rotated in place (opt-in: video_position_limit)
  *   §R  "Position renumbering"          rtk_pivotkv_renumber_batched: the id gaps of such a region closed row by row, each
  *                                       key re-rotated by its own row's delta (opt-in: video_position_gap)
+ *   §S  "Budget re-scoring"             rtk_pivotkv_rescore_batched (+ _workspace_bytes): the stored scores of a budget's old
+ *                                       rows blended with what the newest chunk's last queries see of them (opt-in:
+ *                                       video_budget_rescore)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -1232,6 +1235,46 @@ typedef struct rtk_renumber_unit {   /* rtk_rebase_unit's fields, then the scrat
 int rtk_pivotkv_renumber_batched(const rtk_renumber_unit* units, int n_units, int D, int dtype, int P, const float* inv_freq,
                                  const int* sections_host, int nsec, int64_t limit, int64_t gap, int64_t* offsets,
                                  int64_t* delta, rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * §S  Budget re-scoring (opt-in: longvideo_kwargs["video_budget_rescore"] on top of "video_budget_rows"; NOT in the
+ * reference, which processes a finished video, and a rule of this project's own: what it does to answer quality has not
+ * been evaluated).  The budget ranks a region row by the one score its own chunk's selection saw for it; this call lets
+ * every later chunk look again.  Per unit (a layer), with n old region rows, their stored keys K[g, j] (rotated, as they
+ * lie), the last W rotated query rows Q[h, i] of the chunk that has just gone through the layer and G = Hq / Hkv:
+ *     p_h[i, .] = softmax over j < n of ( Q[h,i] . K[h / G, j] / sqrt(D) )        no mask; rows >= n are never read
+ *     mass[j]   = (1 / Hq) sum_h sum_{i < W} p_h[i, j]                            sum_j mass[j] = W
+ *     obs[j]    = mass[j] n / W                                                   averages 1 over the n rows
+ *     score[j]  = fmaf(alpha, obs[j], (1 - alpha) * score[j])                     j < n; score[n ..] is not touched
+ * in fp32: obs[j] = (sum of the probabilities) * ((float)n / (float)(Hq W)), 1 - alpha rounded once, one product, one fma.
+ * Exact products of the operands, fp32 accumulation, softmax and sums; no atomics.  The keys of a unit are split into ranges
+ * of RTK_RESCORE_KEYS keys - range kr is keys [kr, kr + 1) * RTK_RESCORE_KEYS, a function of n alone - and every sum runs in
+ * an order fixed by (n, W, Hq, Hkv, D, dtype): per range the (max, sum) of every query row, merged in range order; then per
+ * key the probabilities of the query rows in row order, the kv groups in order.  The same values give the same bits
+ * whatever the strides, the addresses, the unit's place in the call and the number of units.
+ *   RTK_BF16 / RTK_F16 with D == 128: the matrix path - the G W query rows of a kv group packed into 32-row blocks
+ *   (r = hh W + i), base-2 softmax.  Anything else: plain FMA, dot / sqrt(D), natural exp - the parity path.
+ *   q_stride_h / q_stride_l   elements between heads / rows of every unit's queries (>= D)
+ *   scratch, scratch_stride   DEVICE, 256-byte aligned; unit i uses [i * scratch_stride, + rtk_pivotkv_rescore_workspace_bytes
+ *                             (.., n of the unit, ..)): the rows' log-sum-exps and the ranges' partials
+ * `units` is a HOST array; n_units == 0 or nothing but n == 0 units launches nothing and returns 0; more than 32 live units
+ * take more launches (three per 32).  rtk_pivotkv_rescore_workspace_bytes returns 0 for a shape the call refuses.
+ * Errors, all before any launch: RTK_EINVAL for NULL pointers, n < 0 or beyond 2^24, alpha outside (0, 1], W < 1, Hq % Hkv,
+ * query strides below D, k_stride_h < n D, a misaligned score, scratch that is misaligned or shorter than the unit needs
+ * and - on the matrix path - q / k pointers or strides that are not 16-byte aligned; RTK_EUNSUPPORTED for another dtype code.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rtk_rescore_unit {
+    const void* q;          /* [Hq, W, D]: element (h, i, d) at q + h*q_stride_h + i*q_stride_l + d (elements) */
+    const void* k;          /* first region key row of kv head 0; row j of head g at k + g*k_stride_h + j*D */
+    int64_t     k_stride_h; /* elements between kv heads (cap * D), >= n * D */
+    float*      score;      /* [n] in / out */
+    int32_t     n;          /* old rows: softmaxed over and blended; 0 = unit skipped */
+} rtk_rescore_unit;
+#define RTK_RESCORE_KEYS 512   /* keys per range: what one workgroup keeps in registers */
+size_t rtk_pivotkv_rescore_workspace_bytes(int Hq, int Hkv, int W, int n_max, int D, int dtype);
+int rtk_pivotkv_rescore_batched(const rtk_rescore_unit* units, int n_units, int Hq, int Hkv, int W, int D, int dtype,
+                                float alpha, int64_t q_stride_h, int64_t q_stride_l, void* scratch, size_t scratch_stride,
+                                rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

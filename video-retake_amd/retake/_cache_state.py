@@ -24,7 +24,7 @@ class _LayerStore:
     rtk_layer_state block (`c`) the library reads and advances itself (rtk_pivotkv_update / rtk_pivotkv_flush)."""
 
     __slots__ = ("c", "cref", "_k", "_v", "_pos", "pending_event", "pos_ndim", "k8", "v8", "ks8", "vs8", "len8", "archive_at",
-                 "sk", "sv", "base", "pinned", "sc", "sc_len")
+                 "sk", "sv", "base", "pinned", "sc", "sc_len", "sc_seen", "oq", "oq_rows", "oq_new")
 
     def __init__(self):
         self.c = nv.LayerState()
@@ -50,6 +50,14 @@ class _LayerStore:
         # many leading region rows carry one.  None unless a budget is on
         self.sc = None
         self.sc_len = 0
+        # video_budget_rescore: how many leading region rows existed at the last re-scoring (the OLD rows of the next one:
+        # it becomes the region's rows after a re-scoring and the budget after an eviction; a rewind caps it at the restored
+        # sc_len), and the last `oq_rows` rotated query rows of the layer's newest chunk [Hq, W, D] in the model dtype
+        # (`oq_new`: captured since the last re-scoring).  No buffer unless the key is on
+        self.sc_seen = 0
+        self.oq = None
+        self.oq_rows = 0
+        self.oq_new = False
 
     def _sync(self):
         k, v, c = self._k, self._v, self.c
@@ -361,9 +369,12 @@ class _CacheView:
 
 
 # one layer's numbers at a mark.  has_kv / has_pos: did the layer own K / V and id buffers (a skipped layer owns none)
-# sc_len: the scored rows of the video region (video_budget_rows; 0 without a budget)
-_LayerMark = collections.namedtuple("_LayerMark", "length pos_len pos_ndim len8 archive_at num_evicted has_kv has_pos sc_len",
-                                    defaults=(0,))
+# sc_len: the scored rows of the video region (video_budget_rows; 0 without a budget); sc_seen: how many of them the last
+# re-scoring had seen (video_budget_rescore) - recorded, but a rewind caps the LIVE count at sc_len instead of restoring this
+# one: a re-scoring above the mark has happened, the blended scores stay, and so does the fact that those rows were observed
+_LayerMark = collections.namedtuple("_LayerMark",
+                                    "length pos_len pos_ndim len8 archive_at num_evicted has_kv has_pos sc_len sc_seen",
+                                    defaults=(0, 0))
 
 
 class CacheMark:

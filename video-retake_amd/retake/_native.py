@@ -156,6 +156,14 @@ class RenumberUnit(C.Structure):
     _fields_ = RebaseUnit._fields_ + [("row_delta", _vp)]
 
 
+RESCORE_KEYS = 512   # RTK_RESCORE_KEYS: keys per range of rtk_pivotkv_rescore_batched (the split of a unit's keys: n alone decides it)
+
+
+class RescoreUnit(C.Structure):
+    """rtk_rescore_unit (include/retake_hip.h)."""
+    _fields_ = [("q", _vp), ("k", _vp), ("k_stride_h", _i64), ("score", _vp), ("n", _i32)]
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -249,6 +257,8 @@ _SIGNATURES = {
     "rtk_pivotkv_squeeze_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_pivotkv_rebase_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "rtk_pivotkv_renumber_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp]),
+    "rtk_pivotkv_rescore_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
+    "rtk_pivotkv_rescore_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _vp, _sz, _vp]),
     "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),

@@ -16,6 +16,10 @@ ids of the layers just moved down to follow their pinned rows and re-rotates the
 device per layer; `position_offset` is the cumulative delta.  With `video_position_gap` = G on top (again this project's
 own rule, no reference counterpart, answer quality not evaluated) the delta is per ROW: inner id gaps above G close to G as
 well, each key is re-rotated by its own row's delta, and `position_offset` grows by the last row's.
+
+`video_budget_rescore` (again this project's own rule, no reference counterpart, answer quality not evaluated) acts in
+front of the budget's eviction: `observe` keeps the last rotated query rows of a layer's newest chunk, `rescore_budget`
+blends the stored scores of the region's old rows with what those queries see of them.
 """
 import torch
 
@@ -83,6 +87,29 @@ def configure_position_limit(cache, config):
         raise ValueError(f"{gap_key} must be an int >= 1 (or None: {key} re-bases a region by one delta), got {G!r}")
     cache.video_position_limit, cache.video_position_gap = P, G
     return P
+
+
+def configure_rescore(cache, config):
+    """build_kvcache: longvideo_kwargs' video_budget_rescore (alpha) and video_budget_observe_rows (W, read only with alpha
+    set), validated and set on the cache (None: off).  Every refusal names its keys; nothing else has happened yet."""
+    kw, key, rows_key = config.longvideo_kwargs, "video_budget_rescore", "video_budget_observe_rows"
+    alpha = kw.get(key, None)
+    if alpha is None:
+        return None
+    W = kw.get(rows_key, 64)
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0 < alpha <= 1:
+        raise ValueError(f"{key} must be a float in (0, 1] (or None: scores stay as they arrived), got {alpha!r}")
+    if not isinstance(W, int) or isinstance(W, bool) or W < 1:
+        raise ValueError(f"{rows_key} must be an int >= 1 (the newest chunk's last query rows that {key} observes with), "
+                         f"got {W!r}")
+    if cache.video_budget_rows is None:
+        raise ValueError(f"{key} needs video_budget_rows: it blends the scores the budget evicts by (video_window_rows bounds "
+                         "a region by age and keeps no scores)")
+    if cache.kv_cache_dtype is not None:
+        raise ValueError(f"{key} does not serve kv_cache_dtype={cache.kv_cache_dtype!r}: the archive's e4m3 key rows are not "
+                         "scored again, it is not built")
+    cache.video_budget_rescore, cache.video_budget_observe_rows = float(alpha), W
+    return cache.video_budget_rescore
 
 
 def _rebase_rotary(cache):
@@ -320,7 +347,7 @@ def evict_budget(cache):
         _commit(cache, by_device, cache.budget_dropped)
         for layers in by_device.values():
             for _, st, *_ in layers:
-                st.sc_len = B
+                st.sc_len = st.sc_seen = B
         rebase_positions(cache, by_device)
 
 
@@ -358,3 +385,81 @@ def row_scores(cache, layer_idx: int) -> torch.Tensor:
     if st is None or st.sc is None:
         return torch.empty(0, dtype=torch.float32)
     return st.sc[:st.sc_len].clone()
+
+
+def observe(cache, st: _LayerStore, q: torch.Tensor):
+    """video_budget_rescore: the last min(W, L) rows of every head of the chunk's ROTATED queries q [1, Hq, L, D] into the
+    layer's buffer [Hq, W, D], on the current stream - every route by which a compressing chunk enters calls this where it
+    returns (a slice copy: the prepare and prologue kernels are not touched)."""
+    W = cache.video_budget_observe_rows
+    _, Hq, L, D = q.shape
+    if st.oq is None or st.oq.shape != (Hq, W, D) or st.oq.dtype != q.dtype or st.oq.device != q.device:
+        st.oq = torch.empty((Hq, W, D), dtype=q.dtype, device=q.device)
+    st.oq_rows = min(W, L)
+    st.oq[:, :st.oq_rows].copy_(q[0, :, L - st.oq_rows:])
+    st.oq_new = True
+
+
+def observed_queries(cache, layer_idx: int) -> torch.Tensor:
+    """video_budget_rescore: a copy [Hq, Wc, D] of the rotated query rows the layer's next re-scoring observes with (its
+    newest chunk's last Wc = min(video_budget_observe_rows, L)); empty before the first chunk; ValueError with the key off."""
+    if cache.video_budget_rescore is None:
+        raise ValueError("PivotKVCache.observed_queries: no queries are kept without video_budget_rescore")
+    st = cache._layers[layer_idx] if 0 <= layer_idx < len(cache._layers) else None
+    if st is None or st.oq is None:
+        return torch.empty(0)
+    return st.oq[:, :st.oq_rows].clone()
+
+
+def rescore_budget(cache):
+    """video_budget_rescore = alpha (not in the reference, which processes a finished video; a rule of this project's own,
+    answer quality not evaluated).  Called by `after_forward` after the flush and in front of `evict_budget` - so before any
+    re-base or renumbering: the keys are read as they lie, rotated, at their current ids.  For every layer whose region
+    holds scored rows only (sc_len == n, what the eviction demands too) and whose newest chunk left its queries, with n_old
+    the region rows that existed at the last re-scoring, Q the layer's observed queries [Hq, Wc, D] and K the region's keys:
+
+        p_h[i, .] = softmax over j < n_old of (Q[h, i] . K[h // G, j] / sqrt(D))      no mask; rows >= n_old are never read
+        obs[j]    = (n_old / (Hq Wc)) sum_h sum_i p_h[i, j]                           averages 1 over the old rows
+        score[j]  = fmaf(alpha, obs[j], (1 - alpha) * score[j])  in fp32, j < n_old;  newer rows keep their arrival score
+
+    ONE rtk_pivotkv_rescore_batched call per device and (Hq, Hkv, Wc, D, dtype) group.  n_old == 0 (the first chunk) does
+    nothing; afterwards n_old is the region's rows (`evict_budget` sets it to the budget).  A layer with question or decode
+    rows left behind its video is skipped - the eviction raises for it as it always did.  The scratch is one buffer per
+    device, sized once for a full region with its slack and a chunk: no buffer is replaced after warm-up."""
+    alpha, W = cache.video_budget_rescore, cache.video_budget_observe_rows
+    groups = {}
+    for l, st in enumerate(cache._layers):
+        first = st.pinned
+        if st._k is None or first < 0 or st.sc is None or st.oq is None or not st.oq_new or st.c.cap == 0:
+            continue
+        n = st.c.length - first
+        if n <= 0 or st.sc_len != n:
+            continue
+        st.oq_new = False
+        n_old, st.sc_seen = min(st.sc_seen, n), n
+        if n_old == 0:
+            continue
+        k, Hq = st._k, st.oq.shape[0]
+        key = (k.get_device(), Hq, k.shape[1], st.oq_rows, k.shape[3], nv.dtype_code(k))
+        unit = nv.RescoreUnit(st.oq.data_ptr(), k.data_ptr() + first * k.shape[3] * k.element_size(), k.stride(1),
+                              st.sc.data_ptr(), n_old)
+        groups.setdefault(key, []).append((l, unit))
+    if not groups:
+        return
+    done = cache.budget_rescored
+    done.extend([0] * (len(cache._layers) - len(done)))
+    L = cache._batch.L if cache._batch is not None else 0
+    for (dev, Hq, Hkv, Wc, D, dt), us in groups.items():
+        device = cache._layers[us[0][0]]._k.device
+        room = max(max(u.n for _, u in us), sum(bound(cache)) + L)
+        stride = nv.lib.rtk_pivotkv_rescore_workspace_bytes(Hq, Hkv, W, room, D, dt)
+        if stride == 0:
+            raise ValueError(f"video_budget_rescore: rtk_pivotkv_rescore_batched does not serve Hq {Hq}, Hkv {Hkv}, "
+                             f"{W} query rows, {room} region rows, head_dim {D}")
+        ws = cache._buf(f"rescore_ws{dev}", (len(cache._layers) * stride + 256,), torch.uint8, device)
+        units = (nv.RescoreUnit * len(us))(*[u for _, u in us])
+        nv.check(_on_device(dev, nv.lib.rtk_pivotkv_rescore_batched, units, len(us), Hq, Hkv, Wc, D, dt, alpha,
+                            W * D, D, (ws.data_ptr() + 255) & ~255, stride, nv.raw_stream(dev)),
+                 "rtk_pivotkv_rescore_batched")
+        for l, _ in us:
+            done[l] += 1

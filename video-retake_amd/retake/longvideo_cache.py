@@ -230,6 +230,13 @@ class PivotKVCache(DynamicCache):
         # changes, no score buffer exists.  The mechanism, and what each policy does: _video_bound.
         self.video_window_rows, self.video_window_slack = None, 0
         self.video_budget_rows, self.video_budget_slack = None, 0
+        # video_budget_rescore = alpha in (0, 1], needs video_budget_rows (again NOT in the reference and a rule of this
+        # project's own - answer quality is not evaluated): in `after_forward`, in front of the eviction, the stored scores of
+        # the region's OLD rows are blended with what the last video_budget_observe_rows (default 64) rotated query rows of
+        # the chunk that has just gone through see of them (_video_bound.rescore_budget).  None (default): off, nothing
+        # changes, bit for bit - no query buffer exists and nothing is launched
+        self.video_budget_rescore, self.video_budget_observe_rows = None, 64
+        self.budget_rescored: List[int] = []  # per layer: re-scorings so far
         # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it; NOT in the reference, a rule of
         # this project's own - answer quality is not evaluated): video_position_limit = P, an int >= 0, needs a window or a
         # budget.  A move drops rows but leaves every surviving id where it was, so the ids of a stream that does not end grow
@@ -501,7 +508,9 @@ class PivotKVCache(DynamicCache):
           deferred_queries  pre-RoPE queries kept alive for a flush that scores them where they lie (prologue_operands="pre_rope")
           worker_scratch    per-update scratch of the stage-by-stage route / worker streams
           attention_workspace  key-split partials of the native chunk attention (attention_kernel="hip"; few-row shapes only)
-          row_scores        the fp32 score buffers of the video regions - the key exists only with video_budget_rows on."""
+          row_scores        the fp32 score buffers of the video regions - the key exists only with video_budget_rows on
+          observe_queries   the layers' last rotated query rows - the key exists only with video_budget_rescore on (the
+                            re-scoring's scratch counts as worker_scratch)."""
         def nbytes(t):
             return 0 if t is None else t.numel() * t.element_size()
 
@@ -534,6 +543,8 @@ class PivotKVCache(DynamicCache):
                     out["deferred_queries"] += nbytes(t)
         if self.video_budget_rows is not None:
             out["row_scores"] = sum(nbytes(st.sc) for st in self._layers)
+        if self.video_budget_rescore is not None:
+            out["observe_queries"] = sum(nbytes(st.oq) for st in self._layers)
         out["worker_scratch"] = sum(nbytes(t) for t in self._ws.values()) + sum(nbytes(t) for sd in self._sides for t in sd.ws.values())
         out["attention_workspace"] = sum(nbytes(t) for t in self._attn_ws.values())
         out["total"] = sum(out.values())
@@ -543,7 +554,8 @@ class PivotKVCache(DynamicCache):
     def _take_mark(self, compressed: bool) -> CacheMark:
         nev = self.num_evicted_tokens
         layers = tuple(_LayerMark(st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at,
-                                  nev[l] if l < len(nev) else 0, st._k is not None, st._pos is not None, st.sc_len)
+                                  nev[l] if l < len(nev) else 0, st._k is not None, st._pos is not None, st.sc_len,
+                                  st.sc_seen)
                        for l, st in enumerate(self._layers))
         self._mark_serial += 1
         return CacheMark(weakref.ref(self), self._mark_serial, self._epoch, layers, len(self._layers), self._pos_layers, len(nev),
@@ -622,6 +634,7 @@ class PivotKVCache(DynamicCache):
         for st, m in zip(self._layers, mark.layers):
             st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at = m.length, m.pos_len, m.pos_ndim, m.len8, m.archive_at
             st.sc_len = m.sc_len
+            st.sc_seen = min(st.sc_seen, m.sc_len)   # (video_budget_rescore: blended scores stay - the observation happened)
             # `pinned` is not in the mark and need not be: it is set once, to the layer's length at its first compressed
             # chunk, and a slide - the only thing that moves rows - voids every earlier mark.  So a valid mark either lies at
             # or below that length (taken before any video row existed: the next compressed chunk pins afresh) or above it
@@ -701,6 +714,7 @@ class PivotKVCache(DynamicCache):
                 st.c.pos_len -= drop
             if self.kv_cache_dtype is None and st.pinned >= 0:   # (video_budget_rows: scores of rows that are gone)
                 st.sc_len = min(st.sc_len, max(st.c.length - st.pinned, 0))
+                st.sc_seen = min(st.sc_seen, st.sc_len)
         if hasattr(self, "_seen_tokens"):
             self._seen_tokens = max_length
         m = self.last_compressed_mark
@@ -744,7 +758,7 @@ class PivotKVCache(DynamicCache):
             self._flush()
         self._epoch += 1
         st.pinned = -1   # (video_window_rows: a layer replaced wholesale pins what it holds at its next compressed chunk)
-        st.sc_len = 0    # (video_budget_rows: ... and its region starts afresh there)
+        st.sc_len = st.sc_seen = 0    # (video_budget_rows: ... and its region starts afresh there)
         if isinstance(value, list) and len(value) == 0:
             st.k = st.v = None
             st.length = 0
@@ -833,6 +847,8 @@ class PivotKVCache(DynamicCache):
             if self.video_window_rows is not None:
                 _video_bound.slide_window(self)
             elif self.video_budget_rows is not None:
+                if self.video_budget_rescore is not None:
+                    _video_bound.rescore_budget(self)
                 _video_bound.evict_budget(self)
             if not self.defer_rerotation:
                 self.last_compressed_mark = self._take_mark(True)
@@ -844,7 +860,7 @@ class PivotKVCache(DynamicCache):
 
     # ---- the bounded video region (video_window_rows / video_budget_rows): functions of _video_bound, bound as methods
     _region_room, _keep_scores, row_scores = _video_bound.region_room, _video_bound.keep_scores, _video_bound.row_scores
-    position_offset = _video_bound.position_offset
+    position_offset, observed_queries = _video_bound.position_offset, _video_bound.observed_queries
 
     # ---- bookkeeping lists (reference :152-215) ------------------------------------------------
     def update_num_evicted_tokens(self, num_tokens: int, layer_idx: int):
@@ -1607,6 +1623,8 @@ class PivotKVCache(DynamicCache):
             self._preshifted = (weakref.ref(pos), _version_of(pos), layer_idx + 1, stream)
         if st.pinned < 0:    # the layer's first compressed chunk: what it held before it is pinned (video_window_rows)
             st.pinned = P0
+        if self.video_budget_rescore is not None:   # the rotated queries lie in q (in place) or in q_out
+            _video_bound.observe(self, st, q if (not pre or q_out is None) else q_out)
         if not self._warned:
             self._warn_compression()
         if not pre:  # the reference's cache_kwargs protocol (:235, :241-243)
@@ -1863,6 +1881,8 @@ class PivotKVCache(DynamicCache):
                 self._append_tail(u)   # on the caller's stream: all this layer's attention needs
                 u.pos_in = self._ids_2d(u, True)
                 self._run_on_worker(u, side)
+        if self.video_budget_rescore is not None:
+            _video_bound.observe(self, st, u.q)
         self.update_num_evicted_tokens(n_new - b.keep, layer_idx)  # reference :310
         st.pending = n_new
         st.pending_keep = b.keep
@@ -2097,6 +2117,7 @@ def build_kvcache(config, reserve_tokens: Optional[int] = None, reserve_archive_
                                    "or by age, not both")
         if B is not None:
             cache.score_when_keeping_all = True   # no region row without a score
+        _video_bound.configure_rescore(cache, config)
         if cache.prompt_guided_scoring:   # what the mode does not serve: refused here, never a silent fallback
             for key, value, served in (("score_rounding", cache.score_rounding, "fp32"),
                                        ("kv_cache_dtype", cache.kv_cache_dtype, None),

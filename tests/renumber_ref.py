@@ -1,4 +1,4 @@
-"""The position renumbering rule (video_position_gap on top of video_position_limit; csrc/pivotkv_renumber.hip) restated on the
+"""The position renumbering rule (video_position_gap on top of video_position_limit; csrc/pivotkv_rebase.hip) restated on the
 host: numpy only, no call into the library.  The rule is this project's own - the reference has no counterpart, and what it
 does to answer quality is not evaluated.  It generalises rebase_ref's one delta per layer to one per row.
 

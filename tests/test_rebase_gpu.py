@@ -2,14 +2,14 @@
 rotation in float64 at the kernel's fp32 angles).  The rule is this project's own; the reference has no counterpart.
 
 One call carries four layers: one triggered with delta 37, one triggered with delta 1000, one whose last id is below the
-limit (delta 11, not applied) and one with delta 0.  Every layer: H = 2 heads of [cap, D] rows, head stride cap * D with
-cap = first + rows + 3 guard rows, ids [P, cap].  first in {0, 5}, rows in {1, 63, 257}: one row, less than one workgroup
-step at D = 128 (32 rows), and several steps with a ragged end.
+limit (delta 11, not applied) and one with delta 0.  Every layer: H = 2 heads (test_head_batches: 4, 5, 9) and a guard head
+of [cap, D] rows, head stride cap * D with cap = first + rows + 3 guard rows, ids [P, cap].  first in {0, 5}, rows in
+{1, 63, 257}: one row, less than one workgroup step at D = 128 (32 rows), and several steps with a ragged end.
 
 Pass criteria: ids (all rows, guard included) and the offset array exact; untriggered layers bit-equal everywhere; in
-triggered layers rows below `first`, guard rows and non-temporal channels bit-equal to the snapshot; every rotated element
-within rebase_ref.bar = half_ulp(dtype, |ref|) + 6 * 2^-24 (|x1| + |x2|) of the float64 rotation of the snapshot (the
-constant is derived in DESIGN.md §5, restated in rebase_ref's docstring; it does not come from a run)."""
+triggered layers rows below `first`, guard rows, the guard head and non-temporal channels bit-equal to the snapshot; every
+rotated element within rebase_ref.bar = half_ulp(dtype, |ref|) + 6 * 2^-24 (|x1| + |x2|) of the float64 rotation of the
+snapshot (the constant is derived in DESIGN.md §5, restated in rebase_ref's docstring; it does not come from a run)."""
 import ctypes as C
 
 import numpy as np
@@ -93,46 +93,71 @@ def _check_layer(name, dtype_name, k_before, k_after, ids_before, ids_after, fir
     return worst
 
 
-@pytest.mark.parametrize("geometry,dtype_name", CASES, ids=[f"{g}-{d}" for g, d in CASES])
-def test_four_layers_in_one_call(geometry, dtype_name):
+def _one_call(geometry, dtype_name, first, rows, H=H):
+    """The four layers at one (first, rows), every pass criterion checked -> worst error / bar.  Every K tensor has a guard
+    head behind the H the call is told of: it keeps its bits."""
     import retake._native as nv
 
     D, P, sections, _ = GEOMETRIES[geometry]
     dtype = getattr(torch, dtype_name)
     inv = synth.inv_freq(D)
     inv_d = torch.from_numpy(inv).to(dev())
+    limit = first + 30
+    cap = first + rows + GUARD
+    rng = np.random.default_rng(1000 * first + rows)
+    guard_rng = np.random.default_rng(77)
+    ks, idss, units = [], [], []
+    want = [DELTAS[0], DELTAS[1], 0, 0]
+    for l in range(4):
+        k = np.concatenate([rng.standard_normal((H, cap, D)), guard_rng.standard_normal((1, cap, D))])
+        k = torch.from_numpy(1.7 * k.astype(np.float32)).to(dtype).to(dev())
+        # (the delta-0 layer reaches the limit too, where it has a second row to do it with)
+        reach = l != 2 and not (l == 3 and rows == 1)
+        ids = torch.from_numpy(_layer_ids(first, rows, DELTAS[l], limit, P, cap, reach)).to(dev())
+        ks.append(k)
+        idss.append(ids)
+        units.append(nv.RebaseUnit(k.data_ptr(), cap * D * k.element_size(), first, rows, ids.data_ptr(), cap,
+                                   first + rows, H, SLOTS[l]))
+    k0 = [k.cpu() for k in ks]
+    ids0 = [i.cpu() for i in idss]
+    offsets = torch.tensor(OFFSETS0, dtype=torch.int64, device=dev())
+    delta = torch.full((4,), -5, dtype=torch.int64, device=dev())
+    _call(units, D, dtype, P, inv_d, sections, limit, offsets, delta)
+    assert delta.tolist() == want, (first, rows)
+    expect = list(OFFSETS0)
+    for l in range(4):
+        expect[SLOTS[l]] += want[l]
+    assert offsets.tolist() == expect, (first, rows)
+    worst = 0.0
+    for l in range(4):
+        ka = ks[l].cpu()
+        assert torch.equal(_bits(ka[H]), _bits(k0[l][H])), (geometry, dtype_name, first, rows, H, l, "the head behind the last")
+        w = _check_layer((geometry, dtype_name, first, rows, H, l), dtype_name, k0[l][:H], ka[:H], ids0[l], idss[l].cpu(),
+                         first, rows, limit, inv, sections, want[l])
+        worst = max(worst, w)
+    return worst
+
+
+@pytest.mark.parametrize("geometry,dtype_name", CASES, ids=[f"{g}-{d}" for g, d in CASES])
+def test_four_layers_in_one_call(geometry, dtype_name):
     worst = 0.0
     for first in (0, 5):
         for rows in (1, 63, 257):
-            limit = first + 30
-            cap = first + rows + GUARD
-            rng = np.random.default_rng(1000 * first + rows)
-            ks, idss, units = [], [], []
-            want = [DELTAS[0], DELTAS[1], 0, 0]
-            for l in range(4):
-                k = torch.from_numpy(1.7 * rng.standard_normal((H, cap, D)).astype(np.float32)).to(dtype).to(dev())
-                # (the delta-0 layer reaches the limit too, where it has a second row to do it with)
-                reach = l != 2 and not (l == 3 and rows == 1)
-                ids = torch.from_numpy(_layer_ids(first, rows, DELTAS[l], limit, P, cap, reach)).to(dev())
-                ks.append(k)
-                idss.append(ids)
-                units.append(nv.RebaseUnit(k.data_ptr(), cap * D * k.element_size(), first, rows, ids.data_ptr(), cap,
-                                           first + rows, H, SLOTS[l]))
-            k0 = [k.cpu() for k in ks]
-            ids0 = [i.cpu() for i in idss]
-            offsets = torch.tensor(OFFSETS0, dtype=torch.int64, device=dev())
-            delta = torch.full((4,), -5, dtype=torch.int64, device=dev())
-            _call(units, D, dtype, P, inv_d, sections, limit, offsets, delta)
-            assert delta.tolist() == want, (first, rows)
-            expect = list(OFFSETS0)
-            for l in range(4):
-                expect[SLOTS[l]] += want[l]
-            assert offsets.tolist() == expect, (first, rows)
-            for l in range(4):
-                w = _check_layer((geometry, dtype_name, first, rows, l), dtype_name, k0[l], ks[l].cpu(), ids0[l], idss[l].cpu(),
-                                 first, rows, limit, inv, sections, want[l])
-                worst = max(worst, w)
+            worst = max(worst, _one_call(geometry, dtype_name, first, rows))
     print(f"rebase[{geometry} {dtype_name}]: worst error / bar {worst:.3f}")
+
+
+HEAD_CASES = [("D128_plain", "bfloat16", 33), ("D32_mrope", "float32", 9)]
+
+
+@pytest.mark.parametrize("heads", [4, 5, 9])
+@pytest.mark.parametrize("geometry,dtype_name,rows", HEAD_CASES, ids=[f"{g}-{d}" for g, d, _ in HEAD_CASES])
+def test_head_batches(geometry, dtype_name, rows, heads):
+    """The rotation walks a row's heads in batches of 4: one full batch, a full batch and a ragged one of 1 (its loads are
+    clamped to the last head, its stores stop there), two full batches and 1.  33 rows at D = 128: one workgroup step of 32
+    and a ragged one.  The pass criteria are the file's, the guard head's bits among them."""
+    worst = _one_call(geometry, dtype_name, 5, rows, heads)
+    print(f"rebase[{geometry} {dtype_name} H={heads}]: worst error / bar {worst:.3f}")
 
 
 def test_more_units_than_one_launch_takes():

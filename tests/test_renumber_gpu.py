@@ -2,9 +2,9 @@
 integers, the rotation rebase_ref's float64 one at the kernel's fp32 angles).  The rule is this project's own; the reference
 has no counterpart and answer quality is not evaluated.
 
-The frame is test_rebase_gpu.py's: H = 2 heads of [cap, D] rows, head stride cap * D with cap = first + rows + 3 guard rows,
-ids [P, cap], first in {0, 5}, several layers in one call with distinct slots and a pre-filled offset array.  The limit is
-first + 2.  The five layers of a call, over a ramp of 16 rows an id:
+The frame is test_rebase_gpu.py's: H = 2 heads (test_head_batches: 4, 5, 9) and a guard head of [cap, D] rows, head stride
+cap * D with cap = first + rows + 3 guard rows, ids [P, cap], first in {0, 5}, several layers in one call with distinct slots
+and a pre-filled offset array.  The limit is first + 2.  The five layers of a call, over a ramp of 16 rows an id:
   0  holes of random size - 1000 and 100 000 among them - in front of random rows;
   1  every gap <= G and the region right behind the pinned rows: total 0, everything stays bit-equal;
   2  only the gap behind the pinned rows open (37): ids, K and offset must equal, BIT FOR BIT, what
@@ -15,9 +15,9 @@ Rows: {1, 63, 257} on every geometry, and {T - 1, T, T + 1, 3 T + 5} for the sca
 bf16 (the scan's carry across tiles and its ragged last tile; the apply's contiguous row blocks).  G in {1, 4}.
 
 Pass criteria: ids (all rows, guard included), `delta` and the offset array exact against the ref; rows with d = 0, rows
-below `first`, guard rows and non-temporal channels bit-equal to the snapshot; every rotated element within rebase_ref.bar =
-half_ulp(dtype, |ref|) + 6 * 2^-24 (|x1| + |x2|) of rebase_ref.rotate(snapshot row, d of the row) - the re-base's bar, derived
-in DESIGN.md §5: the arithmetic per row is the re-base's, so no new constant."""
+below `first`, guard rows, the guard head and non-temporal channels bit-equal to the snapshot; every rotated element within
+rebase_ref.bar = half_ulp(dtype, |ref|) + 6 * 2^-24 (|x1| + |x2|) of rebase_ref.rotate(snapshot row, d of the row) - the
+re-base's bar, derived in DESIGN.md §5: the arithmetic per row is the re-base's, so no new constant."""
 import ctypes as C
 
 import numpy as np
@@ -40,6 +40,7 @@ GEOMETRIES = {   # name: (D, P, sections, dtypes)
     "D128_mrope": (128, 3, [16, 24, 24], ("bfloat16", "float16", "float32")),
     "D64_mrope_mixed_chunk": (64, 3, [4, 14, 14], ("bfloat16", "float16")),   # chunk 0 holds temporal AND h channels
     "D32_plain": (32, 1, None, ("float32",)),
+    "D32_mrope": (32, 3, [4, 6, 6], ()),   # (test_head_batches' alone)
 }
 CASES = [(g, dt) for g, (_, _, _, dts) in GEOMETRIES.items() for dt in dts]
 
@@ -131,7 +132,9 @@ def _check_layer(name, dtype_name, k_before, k_after, ids_before, ids_after, fir
     return total, worst
 
 
-def _one_call(geometry, dtype_name, first, rows, gap):
+def _one_call(geometry, dtype_name, first, rows, gap, H=H):
+    """The five layers at one (first, rows, G), every pass criterion checked -> worst error / bar.  Every K tensor has a guard
+    head behind the H the calls are told of: it keeps its bits."""
     import retake._native as nv
 
     D, P, sections, _ = GEOMETRIES[geometry]
@@ -141,10 +144,12 @@ def _one_call(geometry, dtype_name, first, rows, gap):
     limit = first + 2
     cap = first + rows + GUARD
     rng = np.random.default_rng(100_000 * gap + 1000 * first + rows)
+    guard_rng = np.random.default_rng(77)
     ks, idss, units = [], [], []
     scratch = torch.full((5, rows + 1), -7, dtype=torch.int64, device=dev())     # one guard word behind each row of scratch
     for l in range(5):
-        k = torch.from_numpy(1.7 * rng.standard_normal((H, cap, D)).astype(np.float32)).to(dtype).to(dev())
+        k = np.concatenate([rng.standard_normal((H, cap, D)), guard_rng.standard_normal((1, cap, D))])
+        k = torch.from_numpy(1.7 * k.astype(np.float32)).to(dtype).to(dev())
         ids = torch.from_numpy(_layer_ids(l, rng, first, rows, limit, P, cap)).to(dev())
         ks.append(k)
         idss.append(ids)
@@ -161,11 +166,13 @@ def _one_call(geometry, dtype_name, first, rows, gap):
     offsets = torch.tensor(OFFSETS0, dtype=torch.int64, device=dev())
     delta = torch.full((5,), -5, dtype=torch.int64, device=dev())
     _call(units, D, dtype, P, inv_d, sections, limit, gap, offsets, delta)
-    what = (geometry, dtype_name, first, rows, gap)
+    what = (geometry, dtype_name, first, rows, gap, H)
     assert scratch[:, rows].tolist() == [-7] * 5, (what, "the scan wrote behind its end - first scratch entries")
     expect, worst, totals = list(OFFSETS0), 0.0, []
     for l in range(5):
-        total, w = _check_layer(what + (l,), dtype_name, k0[l], ks[l].cpu(), ids0[l], idss[l].cpu(), first, first + rows, rows, limit,
+        ka = ks[l].cpu()
+        assert torch.equal(_bits(ka[H]), _bits(k0[l][H])), (what, l, "the head behind the last")
+        total, w = _check_layer(what + (l,), dtype_name, k0[l][:H], ka[:H], ids0[l], idss[l].cpu(), first, first + rows, rows, limit,
                                 gap, inv, sections)
         expect[SLOTS[l]] += total
         totals.append(total)
@@ -185,6 +192,20 @@ def test_five_layers_in_one_call(geometry, dtype_name, gap):
         for rows in (1, 63, 257):
             worst = max(worst, _one_call(geometry, dtype_name, first, rows, gap))
     print(f"renumber[{geometry} {dtype_name} G={gap}]: worst error / bar {worst:.3f}")
+
+
+HEAD_CASES = [("D128_plain", "bfloat16", 33), ("D32_mrope", "float32", 9)]
+
+
+@pytest.mark.parametrize("heads", [4, 5, 9])
+@pytest.mark.parametrize("geometry,dtype_name,rows", HEAD_CASES, ids=[f"{g}-{d}" for g, d, _ in HEAD_CASES])
+def test_head_batches(geometry, dtype_name, rows, heads):
+    """The rotation walks a row's heads in batches of 4: one full batch, a full batch and a ragged one of 1 (its loads are
+    clamped to the last head, its stores stop there), two full batches and 1.  33 rows at D = 128: one workgroup step of 32
+    and a ragged one.  The pass criteria are the file's - the guard head's bits and layer 2's bit-for-bit agreement with
+    rtk_pivotkv_rebase_batched among them."""
+    worst = max(_one_call(geometry, dtype_name, 5, rows, gap, heads) for gap in (1, 4))
+    print(f"renumber[{geometry} {dtype_name} H={heads}]: worst error / bar {worst:.3f}")
 
 
 @pytest.mark.parametrize("gap", [1, 4])

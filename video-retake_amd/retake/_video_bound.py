@@ -189,14 +189,11 @@ def rebase_positions(cache, by_device):
         for (D, dt, P), us in groups.items():
             delta = cache._buf(f"rebase_delta{dev}", (len(us),), torch.int64, device)
             nsec = b.c.nsec if P == 3 else 0
-            if gap is not None:
-                nv.check(_on_device(dev, nv.lib.rtk_pivotkv_renumber_batched, (nv.RenumberUnit * len(us))(*us), len(us), D, dt, P,
-                                    inv.data_ptr(), b.sec if nsec else None, nsec, cache.video_position_limit, gap,
-                                    off.data_ptr(), delta.data_ptr(), nv.raw_stream(dev)), "rtk_pivotkv_renumber_batched")
-                continue
-            nv.check(_on_device(dev, nv.lib.rtk_pivotkv_rebase_batched, (nv.RebaseUnit * len(us))(*us), len(us), D, dt, P,
-                                inv.data_ptr(), b.sec if nsec else None, nsec, cache.video_position_limit, off.data_ptr(),
-                                delta.data_ptr(), nv.raw_stream(dev)), "rtk_pivotkv_rebase_batched")
+            name, unit = (("rtk_pivotkv_rebase_batched", nv.RebaseUnit) if gap is None else
+                          ("rtk_pivotkv_renumber_batched", nv.RenumberUnit))
+            nv.check(_on_device(dev, getattr(nv.lib, name), (unit * len(us))(*us), len(us), D, dt, P, inv.data_ptr(),
+                                b.sec if nsec else None, nsec, cache.video_position_limit, *(() if gap is None else (gap,)),
+                                off.data_ptr(), delta.data_ptr(), nv.raw_stream(dev)), name)
 
 
 def position_offset(cache, layer_idx: int) -> torch.Tensor:

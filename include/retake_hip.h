@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (87 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (88 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -65,6 +65,9 @@
  *   §S  "Budget re-scoring"             rtk_pivotkv_rescore_batched (+ _workspace_bytes): the stored scores of a budget's old
  *                                       rows blended with what the newest chunk's last queries see of them (opt-in:
  *                                       video_budget_rescore)
+ *   §T  "Question focus"                rtk_pivotkv_focus_gather_batched: the pinned rows, the video rows a question's queries
+ *                                       choose and the question's rows of every layer gathered out of place into a small
+ *                                       cache of their own (opt-in: PivotKVCache.watch_question / focus)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -1275,6 +1278,50 @@ size_t rtk_pivotkv_rescore_workspace_bytes(int Hq, int Hkv, int W, int n_max, in
 int rtk_pivotkv_rescore_batched(const rtk_rescore_unit* units, int n_units, int Hq, int Hkv, int W, int D, int dtype,
                                 float alpha, int64_t q_stride_h, int64_t q_stride_l, void* scratch, size_t scratch_stride,
                                 rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * §T  Question focus (opt-in: PivotKVCache.watch_question / PivotKVCache.focus; NOT in the reference, and a rule of this
+ * project's own: what it does to answer quality has not been evaluated).  Once a question is known, the video rows it reads
+ * are chosen by its own queries - rtk_pivotkv_rescore_batched with alpha = 1 into a zeroed score row, then
+ * rtk_pivotkv_budget_select_batched, both as they are - and moved, with the pinned rows in front of them and the question's
+ * rows behind them, into a small cache of their own that the answer is decoded over.  The parent cache is only read.
+ *
+ * rtk_pivotkv_focus_gather_batched - the move, OUT OF PLACE: one unit = `streams` independent byte streams (the kv heads of a
+ * K / V buffer, the id planes of a position buffer) with a source and a destination of their own.  Per stream, destination
+ * row r takes
+ *     r <  head                : source row r
+ *     head <= r < head + keep  : source row first + clamp(idx[r - head], 0, n - 1)
+ *     r >= head + keep         : source row tail_src + (r - head - keep),   r < head + keep + tail
+ * idx is a DEVICE int32 array, read once per destination row.  The clamp is in the kernel: a bad list can only name a wrong
+ * row of the region, never a byte outside source rows [first, first + n).  No byte outside destination rows
+ * [0, head + keep + tail) of each stream is written.  Source and destination do not overlap and every destination row has
+ * one writer, so nothing orders workgroups: no flags, no counters, no barrier, no LDS, no scratch.  A workgroup owns 64
+ * contiguous destination rows of one stream, a wave whole rows, 8 rows in flight per thread; the grid depends on the units
+ * alone.  16-byte accesses where both bases, both strides and row_bytes allow, else 4-byte ones; the result is the same.
+ * A unit with head + keep + tail == 0 is skipped; more than RTK_FOCUS_MAX_UNITS moving units take more launches.  The
+ * destinations of different units must not overlap each other (not checked).
+ * `units` is a HOST array; n_units == 0 launches nothing and returns 0.  Errors, all before any launch: RTK_EINVAL for NULL
+ * pointers, negative counts or strides, keep > n, row counts beyond int32, streams <= 0, a row_bytes that is not a positive
+ * multiple of 4, bases or strides that are not 4-byte aligned, a dst_stride below the rows of a destination stream, and a
+ * unit whose source and destination byte spans (first stream's first row to last stream's last row) overlap.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct rtk_focus_unit {
+    const void* src;         /* first byte of source stream 0 (row 0) */
+    void*       dst;         /* first byte of destination stream 0 (row 0) */
+    int64_t src_stride;      /* bytes between source streams */
+    int64_t dst_stride;      /* bytes between destination streams */
+    int32_t streams;         /* Hkv for K / V, P for position ids */
+    int32_t row_bytes;       /* D*esize, 8 (ids); a multiple of 4 */
+    int64_t head;            /* leading rows copied as they lie */
+    int64_t first;           /* source row of the region's first row */
+    int64_t n;               /* region rows */
+    int64_t keep;            /* gathered rows, <= n */
+    int64_t tail_src;        /* source row of the first tail row */
+    int64_t tail;            /* tail rows */
+    const int32_t* idx;      /* DEVICE: [keep], region row of each gathered row */
+} rtk_focus_unit;
+#define RTK_FOCUS_MAX_UNITS 48   /* moving units per launch (the array travels as a kernel argument) */
+int rtk_pivotkv_focus_gather_batched(const rtk_focus_unit* units, int n_units, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

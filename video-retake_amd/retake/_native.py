@@ -164,6 +164,15 @@ class RescoreUnit(C.Structure):
     _fields_ = [("q", _vp), ("k", _vp), ("k_stride_h", _i64), ("score", _vp), ("n", _i32)]
 
 
+FOCUS_MAX_UNITS = 48   # RTK_FOCUS_MAX_UNITS: moving units per kernel launch of rtk_pivotkv_focus_gather_batched
+
+
+class FocusUnit(C.Structure):
+    """rtk_focus_unit (include/retake_hip.h)."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("src_stride", _i64), ("dst_stride", _i64), ("streams", _i32), ("row_bytes", _i32),
+                ("head", _i64), ("first", _i64), ("n", _i64), ("keep", _i64), ("tail_src", _i64), ("tail", _i64), ("idx", _vp)]
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -259,6 +268,7 @@ _SIGNATURES = {
     "rtk_pivotkv_renumber_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp]),
     "rtk_pivotkv_rescore_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "rtk_pivotkv_rescore_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _vp, _sz, _vp]),
+    "rtk_pivotkv_focus_gather_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),

@@ -30,6 +30,7 @@ Where the rest lives (the names are re-exported here, and the other modules of t
     _cache_state      what a layer and a slot of the batch own (_LayerStore, _Batch, ...), the list views, CacheMark
     native_attention  chunk_attention, native_attention (causal offset from the HF mask), the fp8 row helpers
     _video_bound      the bounded video region: the sliding window and the video budget, planned and committed by one mechanism
+    _focus            the question-focused decode cache: watch_question / focus, the rows a question's queries choose
 """
 from __future__ import annotations
 
@@ -40,7 +41,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from . import _native as nv, _video_bound
+from . import _focus, _native as nv, _video_bound
 from ._cache_state import (CacheMark, _Batch, _CacheView, _LayerMark, _LayerStore, _Rotary, _Side, _Update,  # noqa: F401
                            _inv_stamp, _on_device, _version_of)
 from ._hf_cache import DynamicCache, _hf_dynamic_cache_is_legacy, _ListDynamicCache  # noqa: F401
@@ -83,6 +84,9 @@ class PivotKVCache(DynamicCache):
     forked_from = None            # a branch: the parent's mark it was forked at (PivotKVCache.fork)
     _fork_dead = None             # ... and why it is no longer valid, once the parent has given up the shared rows
     _branches = None              # a parent: weak set of its branches
+    # question focus (not in the reference; _focus)
+    _watch = None                 # armed by watch_question: the capture's buffers (None: off, nothing is copied)
+    focused_from = None           # a focused cache (PivotKVCache.focus): the parent's `video_end` it was focused at
 
     def __init__(self, config, reserve_tokens: Optional[int] = None, reserve_archive_tokens: Optional[int] = None) -> None:
         """reserve_tokens (not in the reference): tokens per layer this cache is expected to hold at most - compressed
@@ -373,6 +377,7 @@ class PivotKVCache(DynamicCache):
 
         ValueError without attention_kernel="hip"; NotImplementedError with defer_rerotation, on a float32 model, with
         head_dim != 128, or on a branch (no nested forks)."""
+        _focus._refuse_focused(self, "fork")
         if self.attention_kernel != "hip":
             raise ValueError("PivotKVCache.fork needs attention_kernel='hip': only the native attention reads the rows a "
                              "branch shares with its parent")
@@ -510,7 +515,8 @@ class PivotKVCache(DynamicCache):
           attention_workspace  key-split partials of the native chunk attention (attention_kernel="hip"; few-row shapes only)
           row_scores        the fp32 score buffers of the video regions - the key exists only with video_budget_rows on
           observe_queries   the layers' last rotated query rows - the key exists only with video_budget_rescore on (the
-                            re-scoring's scratch counts as worker_scratch)."""
+                            re-scoring's scratch counts as worker_scratch)
+          focus_queries     the layers' watched query rows - the key exists only while watch_question is armed."""
         def nbytes(t):
             return 0 if t is None else t.numel() * t.element_size()
 
@@ -545,6 +551,8 @@ class PivotKVCache(DynamicCache):
             out["row_scores"] = sum(nbytes(st.sc) for st in self._layers)
         if self.video_budget_rescore is not None:
             out["observe_queries"] = sum(nbytes(st.oq) for st in self._layers)
+        if self._watch is not None:
+            out["focus_queries"] = _focus.watched_bytes(self)
         out["worker_scratch"] = sum(nbytes(t) for t in self._ws.values()) + sum(nbytes(t) for sd in self._sides for t in sd.ws.values())
         out["attention_workspace"] = sum(nbytes(t) for t in self._attn_ws.values())
         out["total"] = sum(out.values())
@@ -861,6 +869,10 @@ class PivotKVCache(DynamicCache):
     # ---- the bounded video region (video_window_rows / video_budget_rows): functions of _video_bound, bound as methods
     _region_room, _keep_scores, row_scores = _video_bound.region_room, _video_bound.keep_scores, _video_bound.row_scores
     position_offset, observed_queries = _video_bound.position_offset, _video_bound.observed_queries
+
+    # ---- the question-focused decode cache: functions of _focus, bound as methods
+    watch_question, unwatch_question, watched_queries = _focus.watch_question, _focus.unwatch_question, _focus.watched_queries
+    focus, focus_scores, focus_kept = _focus.focus, _focus.focus_scores, _focus.focus_kept
 
     # ---- bookkeeping lists (reference :152-215) ------------------------------------------------
     def update_num_evicted_tokens(self, num_tokens: int, layer_idx: int):
@@ -1516,6 +1528,8 @@ class PivotKVCache(DynamicCache):
         """
         if self.forked_from is not None:
             self._branch_update_check("PivotKVCache.update")
+        if self.focused_from is not None:
+            _focus.refuse_compression(self, "PivotKVCache.update")
         b = self._batch
         if b is not None and b.shift_latch is not None and b.shift_latch[0]:
             self._shift_failed(b)
@@ -1708,6 +1722,8 @@ class PivotKVCache(DynamicCache):
         `query_states`; pass `query_states` itself to force the in-place rotation."""
         if self.forked_from is not None:
             self._branch_update_check("PivotKVCache.update_pre_rope")
+        if self.focused_from is not None:
+            _focus.refuse_compression(self, "PivotKVCache.update_pre_rope")
         self._shift_latch_check()
         if not (self.kvcache_compression and self.pos_embed_reforge and self.one_call_update) or self.overlap_streams > 0 \
                 or position_ids is None or not key_states.is_cuda or key_states.shape[0] != 1 \
@@ -1762,6 +1778,8 @@ class PivotKVCache(DynamicCache):
         rotary modules that must be called; CPU tensors)."""
         if self.forked_from is not None:
             self._branch_update_check("PivotKVCache.append_pre_rope")
+        if self.focused_from is not None:
+            _focus.refuse_compression(self, "PivotKVCache.append_pre_rope")
         self._shift_latch_check()
         if self.kvcache_compression or not (self.pos_embed_reforge and self.one_call_update) or position_ids is None \
                 or not key_states.is_cuda or key_states.shape[0] != 1 \
@@ -1809,6 +1827,8 @@ class PivotKVCache(DynamicCache):
             return None
         nv.check(rc, "rtk_pivotkv_append_rope")
         self._pos_layers = max(self._pos_layers, layer_idx + 1)
+        if self._watch is not None:
+            _focus.capture(self, layer_idx, q)
         m = st.c.length
         return q, st._k.narrow(2, 0, m), st._v.narrow(2, 0, m)
 
@@ -1865,6 +1885,8 @@ class PivotKVCache(DynamicCache):
             st.length += n_new
             if self.pos_embed_reforge:
                 self.update_position_ids(position_ids, layer_idx)
+            if self._watch is not None and cache_kwargs.get("query_states") is not None:
+                _focus.capture(self, layer_idx, cache_kwargs["query_states"])
             return st.k[:, :, :st.length], st.v[:, :, :st.length]
 
         u = self._bind_update(key_states, value_states, layer_idx, cache_kwargs, position_ids)

@@ -222,6 +222,28 @@ def test_workspace_bytes():
         assert f(*args) == 0, args
 
 
+def test_the_shared_call_path_refuses_under_its_callers_name_before_anything_is_touched():
+    """`rescore_groups` (the budget's and the focus's one way to the kernel): a shape the kernel does not serve raises with
+    the caller's name, the rows and the room it was sized for - for any group, before the scratch policy is asked for a
+    buffer and before a tensor of any entry is looked at (the entries here hold none)."""
+    import retake._native as nv
+    from retake._video_bound import rescore_groups
+
+    def no_scratch(*_):
+        raise AssertionError("a buffer was asked for")
+
+    served, not_served = (0, 28, 4, 16, 128, nv.RTK_BF16), (0, 30, 4, 16, 128, nv.RTK_BF16)
+    groups = {served: [(None, None, 0, None, 700)], not_served: [(None, None, 0, None, 5), (None, None, 0, None, 900)]}
+    with pytest.raises(ValueError) as e:
+        rescore_groups("PivotKVCache.focus", groups, 1.0, 64, no_scratch)
+    assert str(e.value) == ("PivotKVCache.focus: rtk_pivotkv_rescore_batched does not serve Hq 30, Hkv 4, 16 query rows, "
+                            "900 region rows, head_dim 128")
+    with pytest.raises(ValueError) as e:
+        rescore_groups("video_budget_rescore", groups, 0.5, 64, no_scratch, room=4096, sized_rows=64)
+    assert str(e.value) == ("video_budget_rescore: rtk_pivotkv_rescore_batched does not serve Hq 30, Hkv 4, 64 query rows, "
+                            "4096 region rows, head_dim 128")
+
+
 def test_abi_header_exports_and_library_agree(tmp_path):
     import retake._native as nv
 

@@ -543,6 +543,11 @@ template <class F> inline int with_payload(int dtype, F&& f) {
     if (dtype == RTK_F16) return f(std::integral_constant<int, RTK_F16>{});
     return f(std::integral_constant<int, RTK_BF16>{});
 }
+// f(std::bool_constant<F16>) for the 16-bit matrix instruction of a payload: fp16 for RTK_F16, bf16 for everything else
+template <class F> inline void with_f16(int dtype, F&& f) {
+    if (dtype == RTK_F16) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 // n >= 1 units of a HOST array as the by-value argument of a batched launch (Units = struct { unit u[MAX]; }, grid.y = n);
 // the slots past n repeat the last unit and are never read

@@ -5,10 +5,11 @@
 //   p_h[i, .] = softmax_{j < n}(q[h,i] . k[h / G, j] / sqrt(D))           no mask; keys >= n are never read
 //   obs[j]    = (n / (Hq W)) * sum_h sum_{i < W} p_h[i, j]                averages 1 over the n rows
 //   score[j]  = fmaf(alpha, obs[j], (1 - alpha) * score[j])               (1 - alpha) rounded once, then one product, one fma
-// The contraction is pivotkv_score_prompt.hip's - few query rows against many keys, the G W rows of a kv group packed as
-// r = hh W + i into 32-row blocks - but against ~10^5 keys with a head stride, so the keys are SPLIT: key range kr of a unit
-// is keys [kr * RS_KEYS, (kr + 1) * RS_KEYS), a function of n alone (never of the unit count, the unit's index, the strides
-// or the machine), and every sum below runs in an order fixed by (n, W, Hq, Hkv, D, dtype).  No atomics.  Three launches:
+// The contraction is the thin one of score_thin.cuh (its loads, block step and merges are written there) - few query rows
+// against many keys, the G W rows of a kv group packed as r = hh W + i into 32-row blocks - but against ~10^5 keys with a head
+// stride, so the keys are SPLIT: key range kr of a unit is keys [kr * RS_KEYS, (kr + 1) * RS_KEYS), a function of n alone
+// (never of the unit count, the unit's index, the strides or the machine), and every sum below runs in an order fixed by
+// (n, W, Hq, Hkv, D, dtype).  No atomics.  Three launches:
 //   rescore_lse_kernel    grid (ranges, Hkv, units): a workgroup keeps its range's keys of one group in registers (a wave
 //                         holds RS_NKB blocks of 32), puts the group's query blocks into LDS in fragment order (up to RS_QB
 //                         blocks = 112 KiB a tile; every wave reads them from there, so a query block leaves L2 once per
@@ -22,10 +23,9 @@
 // Arithmetic: exact products of the 16-bit operands, fp32 accumulation, softmax and sums.  fp32 payloads or head_dim != 128:
 // the *_generic kernels (plain FMA, natural exp, dot / sqrt(D)) over the same key ranges and the same merge: the parity path.
 #include <atomic>
-#include <cmath>
 #include <cstring>
 
-#include "score_layout.cuh"
+#include "score_thin.cuh"
 
 namespace rtk {
 namespace {
@@ -55,28 +55,15 @@ struct RescoreUnits {
 
 __device__ __forceinline__ int ranges_of(int n) { return (n + RS_KEYS - 1) / RS_KEYS; }
 
-// this lane's fragment of key j0 + (lane & 31) of a group's rows [n, 128]; keys >= n are not read
-__device__ __forceinline__ void load_region_keys(u32x4* f, const char* kg, int j0, int n, int lane) {
-    const int j = j0 + (lane & 31), hf = lane >> 5;
-    const bool ok = j < n;
-    const u32x4* p = (const u32x4*)(kg + (size_t)(ok ? j : 0) * (HD * 2));
-#pragma unroll
-    for (int x = 0; x < 8; ++x) f[x] = ok ? p[2 * x + hf] : u32x4{0, 0, 0, 0};
-}
-
 // query blocks [rb0, rb0 + nb) of kv group g into LDS, fragment order: chunk x of lane l of block b at lq[(b * 8 + x) * 64 + l]
-// (what the lane reads back is 16 contiguous bytes next to its neighbours': no bank conflicts).  Packed row r = hh W + i is
-// row i of head g G + hh; rows >= G W (the last block's padding) are zeros
+// (what the lane reads back is 16 contiguous bytes next to its neighbours': no bank conflicts).  The rows that pad the last
+// block are zeros
 __device__ __forceinline__ void fill_query_tile(u32x4* lq, const char* qu, int g, int G, int W, int rb0, int nb, int64_t qsh,
                                                 int64_t qpitch, int wid, int lane) {
-    const int nrows = G * W, hf = lane >> 5;
     for (int b = wid; b < nb; b += RS_WAVES) {
-        const int r = (rb0 + b) * 32 + (lane & 31);
-        const bool ok = r < nrows;
-        const int hh = ok ? r / W : 0, i = ok ? r - hh * W : 0;
-        const u32x4* p = (const u32x4*)(qu + (int64_t)(g * G + hh) * qsh + (int64_t)i * qpitch);
-#pragma unroll
-        for (int x = 0; x < 8; ++x) lq[(b * 8 + x) * 64 + lane] = ok ? p[2 * x + hf] : u32x4{0, 0, 0, 0};
+        const u32x4* p;
+        const bool ok = packed_row(p, qu, g, G, W, (rb0 + b) * 32 + (lane & 31), qsh, qpitch);
+        load_frag<64>(lq + b * 8 * 64 + lane, p, ok, lane >> 5);
     }
 }
 __device__ __forceinline__ void read_query_block(u32x4* f, const u32x4* lq, int b, int lane) {
@@ -92,26 +79,7 @@ __device__ __forceinline__ void lse_block(const u32x4 (&kf)[RS_NKB][8], const u3
     const int hf = (threadIdx.x & (WAVE - 1)) >> 5;
     if constexpr (MASKED) asm volatile("" : "+v"(left));
 #pragma unroll
-    for (int kb = 0; kb < RS_NKB; ++kb) {
-        f32x16 acc = f32x16{0};
-#pragma unroll
-        for (int x = 0; x < 8; ++x) mma16<F16>(acc, kf[kb][x], qf[x], acc);   // acc[r] = k[.. + acc_row(r, hf)] . q[row]
-        float t[16];
-        float mn = m;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            t[r] = __fmul_rn(acc[r], c2);
-            if constexpr (MASKED) t[r] = (kb * 32 + acc_row(r, hf) < left) ? t[r] : -INFINITY;
-            mn = fmaxf(mn, t[r]);
-        }
-        if (!MASKED || mn > -INFINITY) {   // (a half-wave whose keys all lie past n has seen nothing yet)
-            float add = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) add += __builtin_amdgcn_exp2f(__fsub_rn(t[r], mn));
-            sum = sum * __builtin_amdgcn_exp2f(__fsub_rn(m, mn)) + add;
-            m = mn;
-        }
-    }
+    for (int kb = 0; kb < RS_NKB; ++kb) lse_step<F16, MASKED>(kf[kb], qf, c2, kb * 32, left, hf, m, sum);
 }
 
 template <bool F16>
@@ -130,7 +98,7 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_lse_kernel(RescoreUnits us
     const char* kg = un.k + (int64_t)g * un.ksh;
     u32x4 kf[RS_NKB][8];
 #pragma unroll
-    for (int kb = 0; kb < RS_NKB; ++kb) load_region_keys(kf[kb], kg, j0 + kb * 32, n, lane);
+    for (int kb = 0; kb < RS_NKB; ++kb) load_key_frag(kf[kb], kg, j0 + kb * 32, n, lane);
     float2* part = un.part + ((size_t)g * ranges_of(n) + kr) * ((size_t)RB * 32);
     for (int rb0 = 0; rb0 < RB; rb0 += RS_QB) {
         const int nb = min(RS_QB, RB - rb0);
@@ -143,26 +111,12 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_lse_kernel(RescoreUnits us
             float m = -INFINITY, sum = 0.f;
             if (full) lse_block<F16, false>(kf, qf, c2, 0, m, sum);
             else lse_block<F16, true>(kf, qf, c2, n - j0, m, sum);
-            // the two halves of the wave saw disjoint keys of the same row
-            const float m2 = __shfl_xor(m, 32, WAVE), s2 = __shfl_xor(sum, 32, WAVE);
-            const float lo_m = hf ? m2 : m, lo_s = hf ? s2 : sum, hi_m = hf ? m : m2, hi_s = hf ? sum : s2;
-            const float mm = fmaxf(lo_m, hi_m);
-            float tot = 0.f;
-            if (lo_m > -INFINITY) tot += lo_s * __builtin_amdgcn_exp2f(lo_m - mm);
-            if (hi_m > -INFINITY) tot += hi_s * __builtin_amdgcn_exp2f(hi_m - mm);
-            if (hf == 0) red[(wid * QBn + b) * 32 + row] = make_float2(mm, tot);
+            const float2 half = merge_halves(m, sum, hf);
+            if (hf == 0) red[(wid * QBn + b) * 32 + row] = half;
         }
         __syncthreads();
-        for (int e = tid; e < nb * 32; e += RS_THREADS) {   // the waves, in wave order (wave 0 always holds a key < n)
-            float mm = -INFINITY;
-            for (int w = 0; w < RS_WAVES; ++w) mm = fmaxf(mm, red[w * QBn * 32 + e].x);
-            float tot = 0.f;
-            for (int w = 0; w < RS_WAVES; ++w) {
-                const float2 v = red[w * QBn * 32 + e];
-                if (v.x > -INFINITY) tot += v.y * __builtin_amdgcn_exp2f(v.x - mm);
-            }
-            part[rb0 * 32 + e] = make_float2(mm, tot);
-        }
+        for (int e = tid; e < nb * 32; e += RS_THREADS)   // the waves, in wave order (wave 0 always holds a key < n)
+            part[rb0 * 32 + e] = merge_in_order<true>(RS_WAVES, [&](int w) { return red[w * QBn * 32 + e]; });
     }
 }
 
@@ -174,14 +128,8 @@ __global__ __launch_bounds__(256) void rescore_merge_kernel(RescoreUnits us, int
     if (e >= Hkv * rows_pad) return;
     const int g = e / rows_pad, r = e - g * rows_pad, KR = ranges_of(un.n);
     const float2* p = un.part + (size_t)g * KR * rows_pad + r;
-    float mm = -INFINITY;
-    for (int kr = 0; kr < KR; ++kr) mm = fmaxf(mm, p[(size_t)kr * rows_pad].x);
-    float tot = 0.f;
-    for (int kr = 0; kr < KR; ++kr) {
-        const float2 v = p[(size_t)kr * rows_pad];
-        if (v.x > -INFINITY) tot += v.y * (BASE2 ? __builtin_amdgcn_exp2f(v.x - mm) : expf(v.x - mm));
-    }
-    un.lse[e] = r < nrows ? mm + (BASE2 ? __builtin_amdgcn_logf(tot) : logf(tot)) : INFINITY;
+    const float2 ms = merge_in_order<BASE2>(KR, [&](int kr) { return p[(size_t)kr * rows_pad]; });
+    un.lse[e] = r < nrows ? lse_of<BASE2>(ms) : INFINITY;
 }
 
 // score[j] <- fmaf(alpha, obs[j], (1 - alpha) score[j]), obs[j] = tot[j] * (n / (Hq W))
@@ -206,7 +154,7 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_col_kernel(RescoreUnits us
     for (int g = 0; g < Hkv; ++g) {
         u32x4 kf[RS_NKB][8];
 #pragma unroll
-        for (int kb = 0; kb < RS_NKB; ++kb) load_region_keys(kf[kb], un.k + (int64_t)g * un.ksh, j0 + kb * 32, n, lane);
+        for (int kb = 0; kb < RS_NKB; ++kb) load_key_frag(kf[kb], un.k + (int64_t)g * un.ksh, j0 + kb * 32, n, lane);
         const float* lg = un.lse + (size_t)g * RB * 32;
         float col[RS_NKB];
 #pragma unroll
@@ -250,53 +198,18 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_col_kernel(RescoreUnits us
     }
 }
 
-// ---- any head_dim, any payload: plain FMA, dot / sqrt(D), natural exp; the same key ranges, the same merge -------------
-template <int DT>
-__device__ __forceinline__ float ldq(const void* p, size_t i) {
-    if constexpr (DT != RTK_F32) return H16<DT>::ld(p, i);
-    else return ((const float*)p)[i];
-}
-
+// ---- any head_dim, any payload: plain FMA, dot / sqrt(D), natural exp (score_thin.cuh); the same key ranges, the same merge
 // (max, sum) of query row i of head h over key range kr: grid (ranges, Hq * W, units)
 template <int DT>
 __global__ __launch_bounds__(256) void rescore_lse_generic(RescoreUnits us, int G, int W, int D, int64_t qsh, int64_t qpitch) {
     extern __shared__ float rs_qs[];  // [D]
-    __shared__ float red_m[4], red_s[4];
     const RescoreDev& un = us.u[blockIdx.z];
-    const int tid = threadIdx.x, kr = blockIdx.x, n = un.n;
+    const int kr = blockIdx.x, n = un.n;
     if (kr * RS_KEYS >= n) return;   // (uniform)
     const int h = blockIdx.y / W, i = blockIdx.y - h * W, g = h / G;
-    const char* qrow = un.q + (int64_t)h * qsh + (int64_t)i * qpitch;
-    const char* kg = un.k + (int64_t)g * un.ksh;
-    for (int d = tid; d < D; d += blockDim.x) rs_qs[d] = ldq<DT>(qrow, d);
-    __syncthreads();
-    const float sqrt_d = sqrtf((float)D);
-    float m = -INFINITY, sum = 0.f;
-    const int jend = min(n, (kr + 1) * RS_KEYS);
-    for (int j = kr * RS_KEYS + tid; j < jend; j += blockDim.x) {
-        float s = 0.f;
-        for (int d = 0; d < D; ++d) s = fmaf(rs_qs[d], ldq<DT>(kg, (size_t)j * D + d), s);
-        s = __fdiv_rn(s, sqrt_d);
-        const float mn = fmaxf(m, s);
-        sum = sum * expf(m - mn) + expf(s - mn);
-        m = mn;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float m2 = __shfl_xor(m, o, WAVE), s2 = __shfl_xor(sum, o, WAVE);
-        const float mm = fmaxf(m, m2);
-        if (mm > -INFINITY) sum = (m > -INFINITY ? sum * expf(m - mm) : 0.f) + (m2 > -INFINITY ? s2 * expf(m2 - mm) : 0.f);
-        m = mm;
-    }
-    if ((tid & 63) == 0) { red_m[tid / 64] = m; red_s[tid / 64] = sum; }
-    __syncthreads();
-    if (tid == 0) {
-        float mm = -INFINITY, ss = 0.f;
-        for (int w = 0; w < 4; ++w) mm = fmaxf(mm, red_m[w]);
-        for (int w = 0; w < 4; ++w)
-            if (red_m[w] > -INFINITY) ss += red_s[w] * expf(red_m[w] - mm);
-        const int rows = G * W;
-        un.part[((size_t)g * ranges_of(n) + kr) * rows + (h - g * G) * W + i] = make_float2(mm, ss);
-    }
+    const float2 ms = range_softmax<DT>(rs_qs, un.q + (int64_t)h * qsh + (int64_t)i * qpitch, un.k + (int64_t)g * un.ksh, 0,
+                                        kr * RS_KEYS, min(n, (kr + 1) * RS_KEYS), D);
+    if (threadIdx.x == 0) un.part[((size_t)g * ranges_of(n) + kr) * (G * W) + (h - g * G) * W + i] = ms;
 }
 
 // the blend of key j: one thread per key, every query row of every head in turn: grid (ceil(n_max / 256), units)
@@ -305,40 +218,20 @@ __global__ __launch_bounds__(256) void rescore_col_generic(RescoreUnits us, int 
                                                            int64_t qpitch, float alpha) {
     extern __shared__ float rs_qs[];  // [D]
     const RescoreDev& un = us.u[blockIdx.y];
-    const int tid = threadIdx.x, n = un.n;
+    const int n = un.n;
     if (blockIdx.x * 256 >= n) return;   // (uniform)
-    const int j = blockIdx.x * 256 + tid;
-    const float sqrt_d = sqrtf((float)D);
+    const int j = blockIdx.x * 256 + threadIdx.x;
     float tot = 0.f;
-    for (int g = 0; g < Hkv; ++g) {
-        const char* kg = un.k + (int64_t)g * un.ksh;
-        float col = 0.f;
-        for (int hh = 0; hh < G; ++hh) {
-            const int h = g * G + hh;
-            float blk = 0.f;   // two-level sum, 64 rows at a time (as prompt_colsum_generic)
-            for (int i = 0; i < W; ++i) {
-                const char* qrow = un.q + (int64_t)h * qsh + (int64_t)i * qpitch;
-                __syncthreads();
-                for (int d = tid; d < D; d += blockDim.x) rs_qs[d] = ldq<DT>(qrow, d);
-                __syncthreads();
-                if (j < n) {
-                    float s = 0.f;
-                    for (int d = 0; d < D; ++d) s = fmaf(rs_qs[d], ldq<DT>(kg, (size_t)j * D + d), s);
-                    blk += expf(__fdiv_rn(s, sqrt_d) - un.lse[(size_t)h * W + i]);
-                }
-                if ((i & 63) == 63 || i + 1 == W) {
-                    col += blk;
-                    blk = 0.f;
-                }
-            }
-        }
-        tot += col;
-    }
+    const char* k = un.k;   // (read once, in front of the loop: the key's address is then stepped by ksh; read per group it
+    const int64_t ksh = un.ksh;   //  is rebuilt from j D each time, which costs two vector registers)
+    for (int g = 0; g < Hkv; ++g)
+        tot += column_sum<DT>(
+            rs_qs, k + (int64_t)g * ksh, (size_t)j * D, j < n, G, W, D,
+            [&](int hh, int i) { return un.q + (int64_t)(g * G + hh) * qsh + (int64_t)i * qpitch; },
+            [&](int hh, int i) { return un.lse[(size_t)(g * G + hh) * W + i]; });
     if (j < n) un.score[j] = blend(un.score[j], tot, __fdiv_rn((float)n, (float)(Hkv * G * W)), alpha);
 }
 
-inline bool payload_dtype(int dtype) { return dtype == RTK_F32 || dtype == RTK_BF16 || dtype == RTK_F16; }
-inline bool rescore_mfma_path(int dtype, int D) { return dtype != RTK_F32 && D == HD; }
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // a unit's scratch: lse [Hkv][rows_pad] fp32, then the ranges' partials [Hkv][ranges(n)][rows_pad] float2
@@ -350,13 +243,13 @@ struct RescorePlan {
 };
 inline bool rescore_plan(RescorePlan& p, int Hq, int Hkv, int W, int D, int dtype) {
     if (Hq < 1 || Hkv < 1 || Hq % Hkv || W < 1 || D < 1 || !payload_dtype(dtype)) return false;
-    p.mfma = rescore_mfma_path(dtype, D);
+    p.mfma = thin_mfma_path(dtype, D);
     p.Hkv = Hkv;
     p.G = Hq / Hkv;
     // (the generic path's grid carries Hq W in its y axis)
     if ((int64_t)p.G * W > (1 << 20) || (!p.mfma && (int64_t)Hq * W > 65535)) return false;
     p.nrows = p.G * W;
-    p.RB = (p.nrows + 31) / 32;
+    p.RB = packed_row_blocks(p.G, W);
     p.rows_pad = p.mfma ? p.RB * 32 : p.nrows;
     p.lse_bytes = al256((size_t)Hkv * p.rows_pad * 4);
     return true;
@@ -428,7 +321,7 @@ extern "C" int rtk_pivotkv_rescore_batched(const rtk_rescore_unit* units, int n_
         }
     }
     const int64_t qsh = q_stride_h * es, qpitch = q_stride_l * es;
-    const float c2 = (float)(1.4426950408889634074 / sqrt((double)D));   // base-2 logits
+    const float c2 = logit_scale2(D);
     int most = 0;   // of the launch being filled: its largest unit's rows
     return launch_units<RescoreUnits>(
         n_units,
@@ -451,16 +344,14 @@ extern "C" int rtk_pivotkv_rescore_batched(const rtk_rescore_unit* units, int n_
             const int KR = (most + RS_KEYS - 1) / RS_KEYS;
             const dim3 gm((Hkv * p.rows_pad + 255) / 256, n);
             if (p.mfma) {
-                auto launch = [&](auto f16) {
-                    constexpr bool F16 = decltype(f16)::value != 0;
+                with_f16(dtype, [&](auto f16) {
+                    constexpr bool F16 = decltype(f16)::value;
                     RTK_LAUNCH(KID_PASS1, rescore_lse_kernel<F16>, dim3(KR, Hkv, n), dim3(RS_THREADS), lds1, st, ru, p.G, W, qsh,
                                qpitch, p.RB, c2);
                     RTK_LAUNCH(KID_PASS1, rescore_merge_kernel<true>, gm, dim3(256), 0, st, ru, Hkv, p.rows_pad, p.nrows);
                     RTK_LAUNCH(KID_PASS2, rescore_col_kernel<F16>, dim3(KR, n), dim3(RS_THREADS), lds2, st, ru, Hkv, p.G, W, qsh,
                                qpitch, p.RB, c2, alpha);
-                };
-                if (dtype == RTK_F16) launch(std::integral_constant<int, 1>{});
-                else launch(std::integral_constant<int, 0>{});
+                });
             } else {
                 with_payload(dtype, [&](auto dt) {
                     constexpr int DT = decltype(dt)::value;

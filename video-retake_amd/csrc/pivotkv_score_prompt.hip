@@ -6,7 +6,8 @@
 // Hq*Lp*Lv*D instead of Hq*L*L*D: a thin problem (few rows, many keys), so the row operand is PACKED - the G*Lp query
 // rows of a KV group (all G heads of the group share its keys) are numbered r = hh*Lp + i and cut into 32-row blocks,
 // the B operand of v_mfma_f32_32x32x16 (S^T = K Q^T as in attention.hip).  Lp = 1 with G = 7 is one block per group, not a
-// 128-row tile per head.  Two launches, no atomics, every sum in an order that depends on the shape alone:
+// 128-row tile per head.  The loads, the block step and the merges are score_thin.cuh's, shared with pivotkv_rescore.hip.
+// Two launches, no atomics, every sum in an order that depends on the shape alone:
 //   prompt_lse_kernel     grid (row blocks, Hkv, units): the block's 4 waves stream the group's video keys (32-key blocks,
 //                         wave w takes blocks w, w+4, ..; straight from L2 into MFMA A fragments, next block in flight), each
 //                         lane keeps the online (max, sum) of ONE packed row, base-2; halves, then waves are merged in
@@ -15,10 +16,9 @@
 //                         group's row blocks as A, col += exp2(s*c - lse2[r]); groups in order, /G, /Hkv, /Lp -> score[j]
 // Arithmetic of score_rounding="fp32": exact products of the 16-bit operands, fp32 accumulation, softmax and sums.
 // fp32 payloads or head_dim != 128: the *_generic kernels (plain FMA, natural exp, dot / sqrt(D)): the parity path.
-#include <cmath>
 #include <cstring>
 
-#include "score_layout.cuh"
+#include "score_thin.cuh"
 
 namespace rtk {
 
@@ -27,84 +27,43 @@ struct PromptUnits {
     const char* q[PS_MAX_UNITS];   // the units' query tensors (packed q~ inside the workspace, or the caller's)
 };
 
-// this lane's fragment of packed row r = rb*32 + (lane & 31) of KV group g: head g*G + r / Lp, chunk row Lv + r % Lp
-__device__ __forceinline__ void load_prompt_rows(u32x4* f, const char* qu, int g, int G, int rb, int nrows, int Lv, int Lp,
-                                                 int64_t qsh, int64_t qpitch, int lane) {
-    const int r = rb * 32 + (lane & 31), hf = lane >> 5;
-    const bool ok = r < nrows;
-    const int hh = ok ? r / Lp : 0, i = ok ? r - hh * Lp : 0;
-    const u32x4* p = (const u32x4*)(qu + (int64_t)(g * G + hh) * qsh + (int64_t)(Lv + i) * qpitch);
-#pragma unroll
-    for (int x = 0; x < 8; ++x) f[x] = ok ? p[2 * x + hf] : u32x4{0, 0, 0, 0};
-}
-// ... of key j0 + (lane & 31) of the group's k~ [L, 128]; keys >= Lv are not read
-__device__ __forceinline__ void load_video_keys(u32x4* f, const char* kg, int j0, int Lv, int lane) {
-    const int j = j0 + (lane & 31), hf = lane >> 5;
-    const bool ok = j < Lv;
-    const u32x4* p = (const u32x4*)(kg + (size_t)(ok ? j : 0) * (HD * 2));
-#pragma unroll
-    for (int x = 0; x < 8; ++x) f[x] = ok ? p[2 * x + hf] : u32x4{0, 0, 0, 0};
+// this lane's fragment of packed row r = rb*32 + (lane & 31) of KV group g: head g*G + r / Lp, prompt row r % Lp (qp: the
+// unit's queries from chunk row Lv on)
+__device__ __forceinline__ void load_prompt_rows(u32x4* f, const char* qp, int g, int G, int rb, int Lp, int64_t qsh,
+                                                 int64_t qpitch, int lane) {
+    const u32x4* p;
+    const bool ok = packed_row(p, qp, g, G, Lp, rb * 32 + (lane & 31), qsh, qpitch);
+    load_frag(f, p, ok, lane >> 5);
 }
 
 template <bool F16>
 __global__ __launch_bounds__(SC_BLOCK) void prompt_lse_kernel(PromptUnits pu, const char* __restrict__ k0, size_t k_unit_bytes,
                                                               float* __restrict__ lse0, size_t lse_unit_floats, int G, int L,
                                                               int Lv, int Lp, int64_t qsh, int64_t qpitch, int RB, float c2) {
-    __shared__ float red_m[4][32], red_s[4][32];
+    __shared__ float2 red[4][32];
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE, hf = lane >> 5, row = lane & 31;
     const int rb = blockIdx.x, g = blockIdx.y, u = blockIdx.z;
-    const int nrows = G * Lp;
     u32x4 qf[8];
-    load_prompt_rows(qf, pu.q[u], g, G, rb, nrows, Lv, Lp, qsh, qpitch, lane);
+    load_prompt_rows(qf, pu.q[u] + (int64_t)Lv * qpitch, g, G, rb, Lp, qsh, qpitch, lane);
     const char* kg = k0 + (size_t)u * k_unit_bytes + (size_t)g * L * (HD * 2);
     const int nkb = (Lv + 31) / 32;
     float m = -INFINITY, sum = 0.f;
     u32x4 a[8], an[8];
-    load_video_keys(a, kg, wid * 32, Lv, lane);
+    load_key_frag(a, kg, wid * 32, Lv, lane);
     for (int kb = wid; kb < nkb; kb += 4) {
-        load_video_keys(an, kg, (kb + 4) * 32, Lv, lane);   // (past the end: nothing is read)
-        f32x16 acc = f32x16{0};
-#pragma unroll
-        for (int x = 0; x < 8; ++x) mma16<F16>(acc, a[x], qf[x], acc);   // acc[r] = k[kb*32 + acc_row(r, hf)] . q[row]
-        float t[16];
-        float mn = m;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            t[r] = (kb * 32 + acc_row(r, hf) < Lv) ? __fmul_rn(acc[r], c2) : -INFINITY;
-            mn = fmaxf(mn, t[r]);
-        }
-        if (mn > -INFINITY) {   // (a half-wave whose keys of a ragged last block are all past Lv has seen nothing yet)
-            float add = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) add += __builtin_amdgcn_exp2f(__fsub_rn(t[r], mn));
-            sum = sum * __builtin_amdgcn_exp2f(__fsub_rn(m, mn)) + add;
-            m = mn;
-        }
+        load_key_frag(an, kg, (kb + 4) * 32, Lv, lane);   // (past the end: nothing is read)
+        lse_step<F16, true>(a, qf, c2, kb * 32, Lv, hf, m, sum);   // (every block is masked: only the last needs it)
 #pragma unroll
         for (int x = 0; x < 8; ++x) a[x] = an[x];
     }
-    // the two halves of the wave saw disjoint keys of the same row; then the four waves, in wave order
-    {
-        const float m2 = __shfl_xor(m, 32, WAVE), s2 = __shfl_xor(sum, 32, WAVE);
-        const float lo_m = hf ? m2 : m, lo_s = hf ? s2 : sum, hi_m = hf ? m : m2, hi_s = hf ? sum : s2;
-        const float mm = fmaxf(lo_m, hi_m);
-        float tot = 0.f;
-        if (lo_m > -INFINITY) tot += lo_s * __builtin_amdgcn_exp2f(lo_m - mm);
-        if (hi_m > -INFINITY) tot += hi_s * __builtin_amdgcn_exp2f(hi_m - mm);
-        if (hf == 0) {
-            red_m[wid][row] = mm;
-            red_s[wid][row] = tot;
-        }
-    }
+    // the two halves of the wave, then the four waves, in wave order
+    const float2 half = merge_halves(m, sum, hf);
+    if (hf == 0) red[wid][row] = half;
     __syncthreads();
     if (tid < 32) {
-        float mm = -INFINITY;
-        for (int w = 0; w < 4; ++w) mm = fmaxf(mm, red_m[w][tid]);
-        float tot = 0.f;
-        for (int w = 0; w < 4; ++w)
-            if (red_m[w][tid] > -INFINITY) tot += red_s[w][tid] * __builtin_amdgcn_exp2f(red_m[w][tid] - mm);
         const int r = rb * 32 + tid;
-        lse0[(size_t)u * lse_unit_floats + (size_t)g * RB * 32 + r] = r < nrows ? mm + __builtin_amdgcn_logf(tot) : INFINITY;
+        const float2 ms = merge_in_order<true>(4, [&](int w) { return red[w][tid]; });
+        lse0[(size_t)u * lse_unit_floats + (size_t)g * RB * 32 + r] = r < G * Lp ? lse_of<true>(ms) : INFINITY;
     }
 }
 
@@ -119,19 +78,18 @@ __global__ __launch_bounds__(SC_BLOCK) void prompt_colsum_kernel(PromptUnits pu,
     const int j0 = blockIdx.x * REG_ROWS + wid * 32;
     if (j0 >= Lv) return;   // wave-uniform; the kernel has no barrier
     const int j = j0 + (lane & 31);
-    const int nrows = G * Lp;
-    const char* qu = pu.q[u];
+    const char* qp = pu.q[u] + (int64_t)Lv * qpitch;
     const float* lse = lse0 + (size_t)u * lse_unit_floats;
     float tot = 0.f;
     for (int g = 0; g < Hkv; ++g) {
         u32x4 kf[8];
-        load_video_keys(kf, k0 + (size_t)u * k_unit_bytes + (size_t)g * L * (HD * 2), j0, Lv, lane);
+        load_key_frag(kf, k0 + (size_t)u * k_unit_bytes + (size_t)g * L * (HD * 2), j0, Lv, lane);
         const float* lg = lse + (size_t)g * RB * 32;
         float col = 0.f;
         u32x4 a[8], an[8];
-        load_prompt_rows(a, qu, g, G, 0, nrows, Lv, Lp, qsh, qpitch, lane);
+        load_prompt_rows(a, qp, g, G, 0, Lp, qsh, qpitch, lane);
         for (int rb = 0; rb < RB; ++rb) {
-            load_prompt_rows(an, qu, g, G, rb + 1, nrows, Lv, Lp, qsh, qpitch, lane);   // (past the end: nothing is read)
+            load_prompt_rows(an, qp, g, G, rb + 1, Lp, qsh, qpitch, lane);   // (past the end: nothing is read)
             float ls[16];
             load_ls(ls, lg, rb, hf);
             f32x16 acc = f32x16{0};
@@ -148,51 +106,17 @@ __global__ __launch_bounds__(SC_BLOCK) void prompt_colsum_kernel(PromptUnits pu,
     if (hf == 0 && j < Lv) score0[(size_t)u * score_unit_floats + j] = __fdiv_rn(__fdiv_rn(tot, (float)Hkv), (float)Lp);
 }
 
-// ---- any head_dim, any payload: plain FMA, the reference's operation order (dot / sqrt(D), natural exp) ----------------
-template <int DT>
-__device__ __forceinline__ float ldp(const void* p, size_t i) {
-    if constexpr (DT != RTK_F32) return H16<DT>::ld(p, i);
-    else return ((const float*)p)[i];
-}
-
+// ---- any head_dim, any payload: plain FMA, the reference's operation order (score_thin.cuh) --------------------------------
 // lse[h*Lp + i] of prompt row i of head h over the video keys: grid (Hq*Lp, units)
 template <int DT>
 __global__ __launch_bounds__(256) void prompt_lse_generic(PromptUnits pu, const char* __restrict__ k0, size_t k_unit_bytes,
                                                           float* __restrict__ lse0, size_t lse_unit_floats, int G, int L, int Lv,
                                                           int Lp, int D, int64_t qsh, int64_t qpitch) {
     extern __shared__ float qs[];  // [D]
-    __shared__ float red_m[4], red_s[4];
-    const int tid = threadIdx.x, u = blockIdx.y;
-    const int h = blockIdx.x / Lp, i = blockIdx.x - h * Lp, g = h / G;
+    const int u = blockIdx.y, h = blockIdx.x / Lp, i = blockIdx.x - h * Lp, g = h / G;
     const char* qrow = pu.q[u] + (int64_t)h * qsh + (int64_t)(Lv + i) * qpitch;
-    const char* kg = k0 + (size_t)u * k_unit_bytes;
-    for (int d = tid; d < D; d += blockDim.x) qs[d] = ldp<DT>(qrow, d);
-    __syncthreads();
-    const float sqrt_d = sqrtf((float)D);
-    float m = -INFINITY, sum = 0.f;
-    for (int j = tid; j < Lv; j += blockDim.x) {
-        float s = 0.f;
-        for (int d = 0; d < D; ++d) s = fmaf(qs[d], ldp<DT>(kg, ((size_t)g * L + j) * D + d), s);
-        s = __fdiv_rn(s, sqrt_d);
-        const float mn = fmaxf(m, s);
-        sum = sum * expf(m - mn) + expf(s - mn);
-        m = mn;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float m2 = __shfl_xor(m, o, WAVE), s2 = __shfl_xor(sum, o, WAVE);
-        const float mm = fmaxf(m, m2);
-        if (mm > -INFINITY) sum = (m > -INFINITY ? sum * expf(m - mm) : 0.f) + (m2 > -INFINITY ? s2 * expf(m2 - mm) : 0.f);
-        m = mm;
-    }
-    if ((tid & 63) == 0) { red_m[tid / 64] = m; red_s[tid / 64] = sum; }
-    __syncthreads();
-    if (tid == 0) {
-        float mm = -INFINITY, ss = 0.f;
-        for (int w = 0; w < 4; ++w) mm = fmaxf(mm, red_m[w]);
-        for (int w = 0; w < 4; ++w)
-            if (red_m[w] > -INFINITY) ss += red_s[w] * expf(red_m[w] - mm);
-        lse0[(size_t)u * lse_unit_floats + blockIdx.x] = mm + logf(ss);
-    }
+    const float2 ms = range_softmax<DT>(qs, qrow, k0 + (size_t)u * k_unit_bytes, (size_t)g * L, 0, Lv, D);
+    if (threadIdx.x == 0) lse0[(size_t)u * lse_unit_floats + blockIdx.x] = lse_of<false>(ms);
 }
 
 // score[j]: one thread per video key, every prompt row of every head in turn: grid (ceil(Lv/256), units)
@@ -202,40 +126,19 @@ __global__ __launch_bounds__(256) void prompt_colsum_generic(PromptUnits pu, con
                                                              float* __restrict__ score0, size_t score_unit_floats, int Hkv, int G,
                                                              int L, int Lv, int Lp, int D, int64_t qsh, int64_t qpitch) {
     extern __shared__ float qs[];  // [D]
-    const int tid = threadIdx.x, u = blockIdx.y;
-    const int j = blockIdx.x * blockDim.x + tid;
-    const char* kg = k0 + (size_t)u * k_unit_bytes;
+    const int u = blockIdx.y;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const float* lse = lse0 + (size_t)u * lse_unit_floats;
-    const float sqrt_d = sqrtf((float)D);
     float tot = 0.f;
     for (int g = 0; g < Hkv; ++g) {
-        float col = 0.f;
-        for (int hh = 0; hh < G; ++hh) {
-            const int h = g * G + hh;
-            float blk = 0.f;   // two-level sum, 64 rows at a time (as score_pass2_generic)
-            for (int i = 0; i < Lp; ++i) {
-                const char* qrow = pu.q[u] + (int64_t)h * qsh + (int64_t)(Lv + i) * qpitch;
-                __syncthreads();
-                for (int d = tid; d < D; d += blockDim.x) qs[d] = ldp<DT>(qrow, d);
-                __syncthreads();
-                if (j < Lv) {
-                    float s = 0.f;
-                    for (int d = 0; d < D; ++d) s = fmaf(qs[d], ldp<DT>(kg, ((size_t)g * L + j) * D + d), s);
-                    blk += expf(__fdiv_rn(s, sqrt_d) - lse[(size_t)h * Lp + i]);
-                }
-                if ((i & 63) == 63 || i + 1 == Lp) {
-                    col += blk;
-                    blk = 0.f;
-                }
-            }
-        }
-        tot += __fdiv_rn(col, (float)G);
+        const float col = column_sum<DT>(
+            qs, k0 + (size_t)u * k_unit_bytes, ((size_t)g * L + j) * D, j < Lv, G, Lp, D,
+            [&](int hh, int i) { return pu.q[u] + (int64_t)(g * G + hh) * qsh + (int64_t)(Lv + i) * qpitch; },
+            [&](int hh, int i) { return lse[(size_t)(g * G + hh) * Lp + i]; });
+        tot += __fdiv_rn(col, (float)G);   // per group /G, then /Hkv, then /Lp: three roundings, in this order
     }
     if (j < Lv) score0[(size_t)u * score_unit_floats + j] = __fdiv_rn(__fdiv_rn(tot, (float)Hkv), (float)Lp);
 }
-
-static inline bool prompt_mfma_path(int base, int D) { return base != RTK_F32 && D == HD; }
-static inline int prompt_row_blocks(int Hq, int Hkv, int Lp) { return ((Hq / Hkv) * Lp + 31) / 32; }
 
 }  // namespace rtk
 
@@ -244,7 +147,7 @@ using namespace rtk;
 extern "C" size_t rtk_pivotkv_score_prompt_workspace_bytes(int Hq, int Hkv, int L, int Lp, int D, int dtype) {
     const int base = dtype & ~RTK_SCORE_MANY_UNITS;
     if (Hq < 1 || Hkv < 1 || Hq % Hkv || D < 1 || Lp < 1 || Lp >= L) return 0;
-    const size_t floats = prompt_mfma_path(base, D) ? (size_t)Hkv * prompt_row_blocks(Hq, Hkv, Lp) * 32 : (size_t)Hq * Lp;
+    const size_t floats = thin_mfma_path(base, D) ? (size_t)Hkv * packed_row_blocks(Hq / Hkv, Lp) * 32 : (size_t)Hq * Lp;
     return (floats * sizeof(float) + 255) & ~(size_t)255;
 }
 
@@ -259,7 +162,7 @@ extern "C" int rtk_pivotkv_score_prompt_batched(void* workspace0, size_t workspa
                   n_units, PS_MAX_UNITS);
     RTK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0 && D >= 1, "rtk_pivotkv_score_prompt_batched: bad shape");
     RTK_CHECK_ARG(Lp >= 1 && Lp < L, "rtk_pivotkv_score_prompt_batched: prompt rows %d must lie in 1 .. L - 1 = %d", Lp, L - 1);
-    if (base != RTK_F32 && base != RTK_BF16 && base != RTK_F16) {
+    if (!payload_dtype(base)) {
         set_error("rtk_pivotkv_score_prompt_batched: the fp32 score arithmetic only (RTK_F32 / RTK_BF16 / RTK_F16), got %d", base);
         return RTK_EUNSUPPORTED;
     }
@@ -275,7 +178,7 @@ extern "C" int rtk_pivotkv_score_prompt_batched(void* workspace0, size_t workspa
     const ScoreWs w = score_ws(Hq, Hkv, L, D, dtype);
     RTK_CHECK_ARG(!workspace0 || n_units == 1 || workspace_stride >= w.total,
                   "rtk_pivotkv_score_prompt_batched: workspace stride too small");
-    const bool mfma = prompt_mfma_path(base, D);
+    const bool mfma = thin_mfma_path(base, D);
     PromptUnits pu;
     memset(&pu, 0, sizeof(pu));
     int64_t qsh, qpitch;   // bytes
@@ -303,18 +206,16 @@ extern "C" int rtk_pivotkv_score_prompt_batched(void* workspace0, size_t workspa
     const size_t lse_unit = scratch_stride / sizeof(float);
     hipStream_t st = (hipStream_t)stream;
     if (mfma) {
-        const int RB = prompt_row_blocks(Hq, Hkv, Lp);
-        const float c2 = (float)(1.4426950408889634074 / sqrt((double)D));   // base-2 logits
+        const int RB = packed_row_blocks(G, Lp);
+        const float c2 = logit_scale2(D);
         const dim3 g1(RB, Hkv, n_units), g2((Lv + REG_ROWS - 1) / REG_ROWS, n_units);
-        auto launch = [&](auto f16) {
-            constexpr bool F16 = decltype(f16)::value != 0;
+        with_f16(base, [&](auto f16) {
+            constexpr bool F16 = decltype(f16)::value;
             RTK_LAUNCH(KID_PASS1, prompt_lse_kernel<F16>, g1, dim3(SC_BLOCK), 0, st, pu, k0, k_unit, lse, lse_unit, G, L, Lv, Lp,
                        qsh, qpitch, RB, c2);
             RTK_LAUNCH(KID_PASS2, prompt_colsum_kernel<F16>, g2, dim3(SC_BLOCK), 0, st, pu, k0, k_unit, (const float*)lse, lse_unit,
                        score0, score_stride_floats, Hkv, G, L, Lv, Lp, qsh, qpitch, RB, c2);
-        };
-        if (base == RTK_F16) launch(std::integral_constant<int, 1>{});
-        else launch(std::integral_constant<int, 0>{});
+        });
     } else {
         RTK_CHECK_ARG((size_t)Hq * Lp < (1u << 31), "rtk_pivotkv_score_prompt_batched: too many prompt rows");
         const dim3 g1(Hq * Lp, n_units), g2((Lv + 255) / 256, n_units);

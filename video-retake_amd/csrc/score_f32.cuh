@@ -13,7 +13,7 @@
 // the tails lose their third, never-taken copy of the step or the loop bounds are written jt + 2.
 // score_pass1_kernel and score_pass2_kernel are plain (non-template) kernels: one translation unit includes this file.
 #pragma once
-#include "score_mfma.cuh"
+#include "score_thin.cuh"
 
 namespace rtk {
 
@@ -345,24 +345,18 @@ _Pragma("unroll") \
 // generic fallback (any head_dim; small problems): plain fp32 VALU, same two passes.
 // ------------------------------------------------------------------------------------------------
 template <int DT>
-__device__ __forceinline__ float ldx(const void* p, size_t i) {
-    if constexpr (DT != RTK_F32) return H16<DT>::ld(p, i);
-    else return ((const float*)p)[i];
-}
-
-template <int DT>
 __global__ __launch_bounds__(256) void score_pass1_generic(const void* __restrict__ q, const void* __restrict__ k,
                                                            int Hq, int Hkv, int L, int D, float* __restrict__ lse) {
     extern __shared__ float qs[];  // [D]
     __shared__ float red_m[4], red_s[4];
     const int i = blockIdx.x, h = blockIdx.y, g = h / (Hq / Hkv), tid = threadIdx.x;
-    for (int d = tid; d < D; d += blockDim.x) qs[d] = ldx<DT>(q, ((size_t)h * L + i) * D + d);
+    for (int d = tid; d < D; d += blockDim.x) qs[d] = ld_any<DT>(q, ((size_t)h * L + i) * D + d);
     __syncthreads();
     const float sqrt_d = sqrtf((float)D);
     float m = -INFINITY, sum = 0.f;
     for (int j = tid; j < L; j += blockDim.x) {
         float s = 0.f;
-        for (int d = 0; d < D; ++d) s = fmaf(qs[d], ldx<DT>(k, ((size_t)g * L + j) * D + d), s);
+        for (int d = 0; d < D; ++d) s = fmaf(qs[d], ld_any<DT>(k, ((size_t)g * L + j) * D + d), s);
         s = __fdiv_rn(s, sqrt_d);
         const float mn = fmaxf(m, s);
         sum = sum * expf(m - mn) + expf(s - mn);
@@ -403,11 +397,11 @@ __global__ __launch_bounds__(256) void score_pass2_generic(const void* __restric
         float blk = 0.f;   // two-level sum: 64-row blocks, then blocks (a plain running sum over G * L terms drifts by ~1e-5)
         for (int i = 0; i < L; ++i) {
             __syncthreads();
-            for (int d = tid; d < D; d += blockDim.x) qs[d] = ldx<DT>(q, ((size_t)h * L + i) * D + d);
+            for (int d = tid; d < D; d += blockDim.x) qs[d] = ld_any<DT>(q, ((size_t)h * L + i) * D + d);
             __syncthreads();
             if (j < L) {
                 float s = 0.f;
-                for (int d = 0; d < D; ++d) s = fmaf(qs[d], ldx<DT>(k, ((size_t)g * L + j) * D + d), s);
+                for (int d = 0; d < D; ++d) s = fmaf(qs[d], ld_any<DT>(k, ((size_t)g * L + j) * D + d), s);
                 blk += expf(__fdiv_rn(s, sqrt_d) - lse[(size_t)h * L + i]);
             }
             if ((i & 63) == 63 || i + 1 == L) {

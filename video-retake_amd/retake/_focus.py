@@ -28,6 +28,7 @@ import torch
 
 from . import _native as nv
 from ._cache_state import _on_device
+from ._video_bound import rescore_groups
 
 
 class _Watch:
@@ -187,14 +188,6 @@ def focus(cache, keep_rows: int, reserve_tokens=None):
         key = (k.get_device(), Q.shape[0], k.shape[1], Wc, k.shape[3], nv.dtype_code(k))
         groups.setdefault(key, []).append(p)
         by_device.setdefault(k.get_device(), []).append(p)
-    strides = {}
-    for key, ps in groups.items():
-        _, Hq, Hkv, Wc, D, dt = key
-        room = max(p[4] for p in ps)
-        strides[key] = nv.lib.rtk_pivotkv_rescore_workspace_bytes(Hq, Hkv, Wc, room, D, dt)
-        if strides[key] == 0:
-            raise ValueError(f"{who}: rtk_pivotkv_rescore_batched does not serve Hq {Hq}, Hkv {Hkv}, {Wc} query rows, "
-                             f"{room} region rows, head_dim {D}")
 
     # ---- what the question's queries see of the region, and the rows that stay: per device, on the current stream ----
     score, kept = {}, {}
@@ -204,19 +197,9 @@ def focus(cache, keep_rows: int, reserve_tokens=None):
         ix = torch.empty((len(ps), max(p[5] for p in ps)), dtype=torch.int32, device=device)
         for i, p in enumerate(ps):
             score[p[0]], kept[p[0]] = sc[i, :p[4]], ix[i, :p[5]]
-    for key, ps in groups.items():
-        dev, Hq, Hkv, Wc, D, dt = key
-        device = ps[0][1]._k.device
-        stride = strides[key]
-        ws = torch.empty(len(ps) * stride + 256, dtype=torch.uint8, device=device)
-        units = (nv.RescoreUnit * len(ps))()
-        for u, (l, st, first, ve, n, keep, tail, ids, Q, _) in zip(units, ps):
-            k = st._k
-            u.q, u.k = Q.data_ptr(), k.data_ptr() + first * k.shape[3] * k.element_size()
-            u.k_stride_h, u.score, u.n = k.stride(1), score[l].data_ptr(), n
-        nv.check(_on_device(dev, nv.lib.rtk_pivotkv_rescore_batched, units, len(ps), Hq, Hkv, Wc, D, dt, 1.0,
-                            w.rows * D, D, (ws.data_ptr() + 255) & ~255, stride, nv.raw_stream(dev)),
-                 "rtk_pivotkv_rescore_batched")
+    rescore_groups(who, {key: [(Q, st._k, first, score[l], n) for l, st, first, _, n, _, _, _, Q, _ in ps]
+                         for key, ps in groups.items()}, 1.0, w.rows,
+                   lambda dev, device, stride, units: torch.empty(units * stride + 256, dtype=torch.uint8, device=device))
     for dev, ps in by_device.items():
         sel = (nv.BudgetSelectUnit * len(ps))()
         for u, p in zip(sel, ps):

@@ -408,6 +408,31 @@ def observed_queries(cache, layer_idx: int) -> torch.Tensor:
     return st.oq[:, :st.oq_rows].clone()
 
 
+def rescore_groups(who, groups, alpha, q_rows, scratch, room=0, sized_rows=None):
+    """rtk_pivotkv_rescore_batched for `groups`: {(device index, Hq, Hkv, Wc, D, dtype code): [(q, k, first, score, n), ..]},
+    one call per group on the device's current stream - q the unit's query buffer [Hq, q_rows, D] (the first Wc rows of
+    each head count), k the layer's key buffer [1, Hkv, cap, D] whose rows [first, first + n) are scored, score its fp32 row.
+    A unit's scratch is sized for max(room, the group's largest n) region rows and `sized_rows` query rows (None: Wc);
+    `scratch(dev, device, stride, units)` answers with a uint8 buffer of at least units * stride + 256 bytes.  ValueError
+    under `who`'s name for a shape the kernel does not serve, raised for every group before the first launch."""
+    strides = {}
+    for key, es in groups.items():
+        _, Hq, Hkv, Wc, D, dt = key
+        rows, most = sized_rows or Wc, max(room, max(e[4] for e in es))
+        strides[key] = nv.lib.rtk_pivotkv_rescore_workspace_bytes(Hq, Hkv, rows, most, D, dt)
+        if strides[key] == 0:
+            raise ValueError(f"{who}: rtk_pivotkv_rescore_batched does not serve Hq {Hq}, Hkv {Hkv}, {rows} query rows, "
+                             f"{most} region rows, head_dim {D}")
+    for (dev, Hq, Hkv, Wc, D, dt), es in groups.items():
+        stride = strides[dev, Hq, Hkv, Wc, D, dt]
+        ws = scratch(dev, es[0][1].device, stride, len(es))
+        units = (nv.RescoreUnit * len(es))(*[
+            nv.RescoreUnit(q.data_ptr(), k.data_ptr() + first * k.shape[3] * k.element_size(), k.stride(1), score.data_ptr(), n)
+            for q, k, first, score, n in es])
+        nv.check(_on_device(dev, nv.lib.rtk_pivotkv_rescore_batched, units, len(es), Hq, Hkv, Wc, D, dt, alpha, q_rows * D, D,
+                            (ws.data_ptr() + 255) & ~255, stride, nv.raw_stream(dev)), "rtk_pivotkv_rescore_batched")
+
+
 def rescore_budget(cache):
     """video_budget_rescore = alpha (not in the reference, which processes a finished video; a rule of this project's own,
     answer quality not evaluated).  Called by `after_forward` after the flush and in front of `evict_budget` - so before any
@@ -424,7 +449,7 @@ def rescore_budget(cache):
     rows left behind its video is skipped - the eviction raises for it as it always did.  The scratch is one buffer per
     device, sized once for a full region with its slack and a chunk: no buffer is replaced after warm-up."""
     alpha, W = cache.video_budget_rescore, cache.video_budget_observe_rows
-    groups = {}
+    groups, layers = {}, []
     for l, st in enumerate(cache._layers):
         first = st.pinned
         if st._k is None or first < 0 or st.sc is None or st.oq is None or not st.oq_new or st.c.cap == 0:
@@ -438,25 +463,16 @@ def rescore_budget(cache):
             continue
         k, Hq = st._k, st.oq.shape[0]
         key = (k.get_device(), Hq, k.shape[1], st.oq_rows, k.shape[3], nv.dtype_code(k))
-        unit = nv.RescoreUnit(st.oq.data_ptr(), k.data_ptr() + first * k.shape[3] * k.element_size(), k.stride(1),
-                              st.sc.data_ptr(), n_old)
-        groups.setdefault(key, []).append((l, unit))
+        groups.setdefault(key, []).append((st.oq, k, first, st.sc, n_old))
+        layers.append(l)
     if not groups:
         return
+    L = cache._batch.L if cache._batch is not None else 0
+    rescore_groups("video_budget_rescore", groups, alpha, W,
+                   lambda dev, device, stride, _: cache._buf(f"rescore_ws{dev}", (len(cache._layers) * stride + 256,),
+                                                             torch.uint8, device),
+                   room=sum(bound(cache)) + L, sized_rows=W)
     done = cache.budget_rescored
     done.extend([0] * (len(cache._layers) - len(done)))
-    L = cache._batch.L if cache._batch is not None else 0
-    for (dev, Hq, Hkv, Wc, D, dt), us in groups.items():
-        device = cache._layers[us[0][0]]._k.device
-        room = max(max(u.n for _, u in us), sum(bound(cache)) + L)
-        stride = nv.lib.rtk_pivotkv_rescore_workspace_bytes(Hq, Hkv, W, room, D, dt)
-        if stride == 0:
-            raise ValueError(f"video_budget_rescore: rtk_pivotkv_rescore_batched does not serve Hq {Hq}, Hkv {Hkv}, "
-                             f"{W} query rows, {room} region rows, head_dim {D}")
-        ws = cache._buf(f"rescore_ws{dev}", (len(cache._layers) * stride + 256,), torch.uint8, device)
-        units = (nv.RescoreUnit * len(us))(*[u for _, u in us])
-        nv.check(_on_device(dev, nv.lib.rtk_pivotkv_rescore_batched, units, len(us), Hq, Hkv, Wc, D, dt, alpha,
-                            W * D, D, (ws.data_ptr() + 255) & ~255, stride, nv.raw_stream(dev)),
-                 "rtk_pivotkv_rescore_batched")
-        for l, _ in us:
-            done[l] += 1
+    for l in layers:
+        done[l] += 1

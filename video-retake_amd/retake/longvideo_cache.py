@@ -31,6 +31,9 @@ Where the rest lives (the names are re-exported here, and the other modules of t
     native_attention  chunk_attention, native_attention (causal offset from the HF mask), the fp8 row helpers
     _video_bound      the bounded video region: the sliding window and the video budget, planned and committed by one mechanism
     _focus            the question-focused decode cache: watch_question / focus, the rows a question's queries choose
+    _flush            the deferred eviction of a chunk: _flush, its one-call and stage-by-stage routes, what they call
+    _update_stages    `update` stage by stage (_update_general): every shape the one-call hot path here does not serve
+    _marks            restore points and branches: mark / rewind / crop / fork, never run during a prefill
 """
 from __future__ import annotations
 
@@ -41,7 +44,7 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from . import _focus, _native as nv, _video_bound
+from . import _flush as _fl, _focus, _marks, _native as nv, _update_stages as _us, _video_bound   # (`_flush` is the method)
 from ._cache_state import (CacheMark, _Batch, _CacheView, _LayerMark, _LayerStore, _Rotary, _Side, _Update,  # noqa: F401
                            _inv_stamp, _on_device, _version_of)
 from ._hf_cache import DynamicCache, _hf_dynamic_cache_is_legacy, _ListDynamicCache  # noqa: F401
@@ -314,123 +317,6 @@ class PivotKVCache(DynamicCache):
         st = self._layers[layer_idx]
         return st.k8[:, :, :n], st.v8[:, :, :n], st.ks8[:, :, :n], st.vs8[:, :, :n]
 
-    # ---- fork: a branch reads the parent's rows where they lie (not in the reference) ---------------
-    def shared_len(self, layer_idx) -> int:
-        """Rows of the parent's 16-bit buffers that precede the layer's own rows: 0 unless this cache is a branch."""
-        if layer_idx is None or layer_idx >= len(self._layers):
-            return 0
-        return self._layers[layer_idx].base
-
-    def shared(self, layer_idx):
-        """(ks, vs) views [1, Hkv, base, D] of the parent's rows the branch shares in this layer, or None."""
-        if not self.shared_len(layer_idx):
-            return None
-        st = self._layers[layer_idx]
-        return st.sk, st.sv
-
-    def _branch_check(self, who="PivotKVCache"):
-        """A branch is valid while its parent has not given up the rows they share: ValueError - what `rewind` raises for
-        such a mark - once the parent was rewound or cropped below the fork point, or had its buffers rewritten wholesale.
-        (A parent that was merely released is fine: the views own the storage.)"""
-        m = self.forked_from
-        if m is None:
-            return
-        parent = m.cache
-        if self._fork_dead is None and parent is not None:
-            if parent._mark_is_dead(m.serial):
-                self._fork_dead = "rows"
-            elif m.epoch != parent._epoch:
-                self._fork_dead = "epoch"
-        if self._fork_dead == "rows":
-            raise ValueError(f"{who}: the mark this branch was forked at has been invalidated - the parent cache was rewound "
-                             "or cropped to an earlier point since, and the rows the branch shares have been given up")
-        if self._fork_dead == "epoch":
-            raise ValueError(f"{who}: buffers of the parent cache were replaced or rewritten wholesale after the branch was "
-                             "forked (key_cache / value_cache / position_cache assigned, or stored rows rotated in place)")
-
-    def _branch_refuse_write(self):
-        if self.forked_from is not None:
-            raise NotImplementedError("a branch (PivotKVCache.fork): key_cache / value_cache / position_cache are dense copies "
-                                      "of [the parent's rows | the branch's own]; assigning through them is not supported")
-
-    def fork(self, mark: Optional[CacheMark] = None, reserve_tokens: Optional[int] = None) -> "PivotKVCache":
-        """A BRANCH of this cache at `mark` (default: `self.mark()`, which flushes first; a given mark is checked as `rewind`
-        checks it): a second live conversation about the same video for the memory of its own rows.  Per layer the branch
-        holds VIEWS of this cache's 16-bit rows [0, mark.length) and archive rows [0, mark.len8) - rows below a restore
-        point are never rewritten - a copy of the position ids [0, mark.pos_len) (P x 8 bytes a row: every id-reading
-        kernel stays as it is) and empty K / V buffers of its own, `reserve_tokens` rows (default 1024) to begin with.
-        `branch.forked_from` is the mark; get_seq_length / get_prev_temporal_idx / num_evicted_tokens / archive_len answer
-        for the whole sequence, as this cache's did at the mark.
-
-        A branch serves text and decode rows (`update` with compression off, `append_pre_rope`) into its own buffers,
-        `attention` over [archive | shared | own] (rtk_attention_forward_shared / rtk_attention_decode_shared - no other
-        route sees the shared rows: a call the native attention declines raises NotImplementedError), `mark` / `rewind` /
-        `crop` within its own rows (the crop floor is the fork point) and `_prefill.followup_position_ids(
-        branch.forked_from, n, device)` when forked at `video_end`.  It refuses, before any launch: a compressing update
-        (NotImplementedError: branches carry questions, not video), assignment through key_cache / value_cache (reading
-        them gives a dense copy in sequence order, a diagnostic), a fork of its own.
-
-        The branch stays valid while this cache keeps the shared rows: rewinding it to `mark` itself, answering its own
-        questions above `mark`, or releasing it altogether are all fine; rewinding or cropping it BELOW `mark` makes every
-        later call on the branch raise the ValueError `rewind` raises for such a mark.  A parent that outgrows a buffer
-        allocates a new one and the old one stays alive until the branches are dropped (`reserve_tokens` avoids that).
-
-        ValueError without attention_kernel="hip"; NotImplementedError with defer_rerotation, on a float32 model, with
-        head_dim != 128, or on a branch (no nested forks)."""
-        _focus._refuse_focused(self, "fork")
-        if self.attention_kernel != "hip":
-            raise ValueError("PivotKVCache.fork needs attention_kernel='hip': only the native attention reads the rows a "
-                             "branch shares with its parent")
-        if self.defer_rerotation:
-            raise NotImplementedError("PivotKVCache.fork: not served with defer_rerotation (see PivotKVCache.mark)")
-        if self.forked_from is not None:
-            raise NotImplementedError("PivotKVCache.fork: this cache is itself a branch; nested forks are not served "
-                                      "(fork the parent again)")
-        if self.head_dim != 128:
-            raise NotImplementedError(f"PivotKVCache.fork needs head_dim 128, got {self.head_dim}")
-        for st in self._layers:
-            if st._k is not None and st._k.dtype not in (torch.bfloat16, torch.float16):
-                raise NotImplementedError(f"PivotKVCache.fork needs a bfloat16 or float16 model, got {st._k.dtype}")
-        if mark is None:
-            mark = self.mark()
-        else:
-            self._flush()
-            self._shift_latch_check()
-            self._check_mark(mark)
-        br = type(self)(self.config, reserve_tokens=reserve_tokens)
-        br.attention_kernel, br.kv_cache_dtype, br.decode_attention = self.attention_kernel, self.kv_cache_dtype, self.decode_attention
-        br.multi_token_attention = self.multi_token_attention
-        br.kvcache_compression = False
-        cap = br.reserve_tokens or 1024
-        for l, m in enumerate(mark.layers):
-            pst, st = self._layers[l], br._store(l)
-            if m.has_kv:
-                k, v = pst._k, pst._v
-                st.sk, st.sv, st.base = k[:, :, :m.length], v[:, :, :m.length], m.length
-                shape = (1, k.shape[1], cap, k.shape[3])
-                st.k = torch.empty(shape, dtype=k.dtype, device=k.device)
-                st.v = torch.empty(shape, dtype=k.dtype, device=k.device)
-                if m.len8:
-                    st.k8, st.v8, st.ks8, st.vs8 = (t[:, :, :m.len8] for t in (pst.k8, pst.v8, pst.ks8, pst.vs8))
-                    st.len8, st.archive_at = m.len8, m.archive_at
-            if m.has_pos:
-                ids = torch.empty((pst._pos.shape[0], m.pos_len + cap), dtype=torch.int64, device=pst._pos.device)
-                ids[:, :m.pos_len].copy_(pst._pos[:, :m.pos_len])
-                st.pos, st.pos_len, st.pos_ndim = ids, m.pos_len, m.pos_ndim
-        br._pos_layers = mark.pos_layers
-        br.num_evicted_tokens = [mark.layers[l].num_evicted for l in range(mark.n_evicted)]
-        if mark.seen_tokens is not None:
-            br._seen_tokens = mark.seen_tokens
-        br._flushes = mark.flushes
-        br._warned = True
-        br.forked_from = mark
-        # the branch's own restore point at the fork: its `video_end` and crop floor
-        br.last_compressed_mark = br._take_mark(True)._with_resume(mark.resume_position_ids)
-        if self._branches is None:
-            self._branches = weakref.WeakSet()
-        self._branches.add(br)
-        return br
-
     def _archive_reserve(self, st: _LayerStore, more: int, Hkv: int, D: int, device):
         need = st.len8 + more
         if st.k8 is not None and st.k8.shape[2] >= need:
@@ -558,175 +444,13 @@ class PivotKVCache(DynamicCache):
         out["total"] = sum(out.values())
         return out
 
-    # ---- mark / rewind / crop (not in the reference) ------------------------------------------------
-    def _take_mark(self, compressed: bool) -> CacheMark:
-        nev = self.num_evicted_tokens
-        layers = tuple(_LayerMark(st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at,
-                                  nev[l] if l < len(nev) else 0, st._k is not None, st._pos is not None, st.sc_len,
-                                  st.sc_seen)
-                       for l, st in enumerate(self._layers))
-        self._mark_serial += 1
-        return CacheMark(weakref.ref(self), self._mark_serial, self._epoch, layers, len(self._layers), self._pos_layers, len(nev),
-                         getattr(self, "_seen_tokens", None), self._flushes, compressed,
-                         None if compressed else self.last_compressed_mark)
-
-    def mark(self) -> CacheMark:
-        """A restore point of the cache as it stands (see CacheMark).  Like reading `position_cache` it first flushes
-        deferred work (the flush waits for the worker streams), so a mark taken between an `update` and `after_forward`
-        equals the one taken after it.  O(layers) on the host; launches nothing besides that flush.  (A branch's marks
-        count its own rows.)"""
-        self._branch_check("PivotKVCache.mark")
-        if self.defer_rerotation:
-            raise NotImplementedError("PivotKVCache.mark: a cache with defer_rerotation (the sharded prefill's block caches) "
-                                      "holds un-rotated keys and provisional ids until `finalize`; it has no restore points")
-        self._flush()
-        return self._take_mark(False)
-
-    @property
-    def video_end(self) -> Optional[CacheMark]:
-        """`last_compressed_mark`: the restore point after the most recent forward that compressed a chunk - after a chunked
-        prefill, the end of the video (None: nothing has been compressed).  The prefill glue attaches the ids of the first
-        text row that followed (CacheMark.resume_position_ids)."""
-        return self.last_compressed_mark
-
-    def set_resume_position_ids(self, position_ids: torch.Tensor):
-        """The prefill glue's note on `video_end`: the ids ([3, 1] / [1], any device) the forward computed for the first text
-        row after the video, before the attention patch shifted them."""
-        m = self.last_compressed_mark
-        if m is not None:
-            self.last_compressed_mark = m._with_resume(position_ids.detach().reshape(-1).to("cpu", torch.int64).clone())
-
-    def _mark_is_dead(self, serial: int) -> bool:
-        return any(lo < serial <= hi for lo, hi in self._dead_marks)
-
-    def _kill_marks_after(self, serial: int):
-        """Every mark taken after `serial` so far is invalid from now on (its rows are about to be overwritten)."""
-        if serial < self._mark_serial:   # (ranges that start at or above `serial` lie inside the new one)
-            self._dead_marks = tuple(r for r in self._dead_marks if r[0] < serial) + ((serial, self._mark_serial),)
-        for br in self._branches or ():   # (noted on the branches: this cache may be released before they look)
-            if br.forked_from.serial > serial:
-                br._fork_dead = "rows"
-
-    def _check_mark(self, mark: CacheMark):
-        if not isinstance(mark, CacheMark):
-            raise ValueError(f"PivotKVCache.rewind takes a CacheMark (PivotKVCache.mark), got {type(mark).__name__}")
-        if mark.cache is not self:
-            raise ValueError("PivotKVCache.rewind: the mark belongs to another cache")
-        if self._mark_is_dead(mark.serial):
-            raise ValueError("PivotKVCache.rewind: the mark has been invalidated - the cache was rewound or cropped to an "
-                             "earlier point since, and the rows the mark names have been given up")
-        if mark.epoch != self._epoch:
-            raise ValueError("PivotKVCache.rewind: buffers of the cache were replaced or rewritten wholesale after the mark was "
-                             "taken (key_cache / value_cache / position_cache assigned, or stored rows rotated in place)")
-        nev = self.num_evicted_tokens
-        if len(self._layers) < mark.n_layers or self._pos_layers < mark.pos_layers or len(nev) < mark.n_evicted:
-            raise ValueError("PivotKVCache.rewind: the cache holds fewer layers than the mark records")
-        for l, m in enumerate(mark.layers):
-            st = self._layers[l]
-            if st.c.length < m.length or st.c.pos_len < m.pos_len or st.len8 < m.len8 or (m.has_kv and st._k is None) \
-                    or (m.has_pos and st._pos is None) or (m.archive_at >= 0 and st.archive_at != m.archive_at):
-                raise ValueError(f"PivotKVCache.rewind: layer {l} is shorter than the mark says")
-
-    def rewind(self, mark: CacheMark) -> None:
-        """Back to the state `mark` recorded: the follow-up question's way of not prefilling the video again (rewind to
-        `video_end`, append the next question).  O(layers) on the host: the numbers are restored, layers / id lists /
-        eviction counts that did not exist at the mark are dropped, `_prompt_len` / the pre-shift memo are cleared.  Nothing
-        is launched, copied, freed or reallocated - every buffer that existed at the mark keeps its address -, and
-        `kvcache_compression`, `keypatches_mask_chunk`, the batch and the scratch are left alone.  Every mark taken after
-        `mark` is invalid afterwards.  ValueError, before anything changes: a mark of another cache, an invalidated one,
-        one from before the buffers were replaced (the epoch), or a cache that is shorter than the mark says."""
-        self._branch_check("PivotKVCache.rewind")
-        self._flush()
-        self._shift_latch_check()
-        self._check_mark(mark)
-        for st, m in zip(self._layers, mark.layers):
-            st.c.length, st.c.pos_len, st.pos_ndim, st.len8, st.archive_at = m.length, m.pos_len, m.pos_ndim, m.len8, m.archive_at
-            st.sc_len = m.sc_len
-            st.sc_seen = min(st.sc_seen, m.sc_len)   # (video_budget_rescore: blended scores stay - the observation happened)
-            # `pinned` is not in the mark and need not be: it is set once, to the layer's length at its first compressed
-            # chunk, and a slide - the only thing that moves rows - voids every earlier mark.  So a valid mark either lies at
-            # or below that length (taken before any video row existed: the next compressed chunk pins afresh) or above it
-            # (the pinned rows and the number are still what they were)
-            if st.pinned >= m.length:
-                st.pinned = -1
-            if not m.has_kv and st._k is not None:    # a layer that was skipped at the mark owns nothing again
-                st.k = st.v = None
-            if not m.has_pos and st._pos is not None:
-                st.pos = None
-        del self._layers[mark.n_layers:]
-        self._pos_layers = mark.pos_layers
-        nev = self.num_evicted_tokens
-        del nev[mark.n_evicted:]
-        for l in range(mark.n_evicted):
-            nev[l] = mark.layers[l].num_evicted
-        if mark.seen_tokens is not None:
-            self._seen_tokens = mark.seen_tokens
-        self._after_rewind(mark.serial)
-        self._flushes = mark.flushes
-        self._compressed_in_forward = False
-        lcm = self.last_compressed_mark
-        if lcm is not None and lcm.serial > mark.serial:   # video_end as it was at the mark
-            self.last_compressed_mark = mark if mark.compressed else mark.video_end
-
-    def _after_rewind(self, serial: int):
-        self._prompt_len = 0
-        self._preshifted = None
-        self._kill_marks_after(serial)
-
-    def _crop_floor(self):
-        """Rows per layer a crop may not go below: the boundary after the most recent compressed flush, as
-        `last_compressed_mark` recorded it - or None when the cache holds compressed rows and no such record of them."""
-        m = self.last_compressed_mark
-        if m is not None and m.epoch == self._epoch and m.flushes == self._flushes:
-            return [m.layers[l].length + m.layers[l].len8 + self._layers[l].base if l < m.n_layers else 0
-                    for l in range(len(self._layers))]
-        if self._flushes == 0 and not any(self.num_evicted_tokens):
-            return [0] * len(self._layers)
-        return None
-
-    def crop(self, max_length: int):
-        """transformers' DynamicCache.crop on this cache: keep the first `max_length` rows of every layer (negative: drop
-        that many trailing rows; at or above the current length: nothing happens).  Assisted and prompt-lookup generation
-        call it to give up rejected candidate tokens.  Served down to the boundary after the most recent compressed flush
-        only: below it a length alone cannot say what `num_evicted_tokens` or the archive split were - ValueError, and
-        the cache stays as it was.  Like `rewind` it moves numbers only.  Every mark taken after `video_end` is invalid
-        afterwards (which of them name dropped rows is not tracked)."""
-        self._branch_check("PivotKVCache.crop")
-        self._flush()
-        self._shift_latch_check()
-        cur = self.get_seq_length()
-        if max_length < 0:
-            max_length = cur - abs(max_length)
-        if cur <= max_length:
-            return
-        if max_length < 0:
-            raise ValueError(f"PivotKVCache.crop: cannot drop more rows than the cache holds ({cur})")
-        if self.defer_rerotation:
-            raise NotImplementedError("PivotKVCache.crop: not served with defer_rerotation (see PivotKVCache.mark)")
-        floor = self._crop_floor()
-        drops = []
-        for l, st in enumerate(self._layers):
-            total = st.c.length + st.len8 + st.base if st._k is not None else 0
-            drop = max(0, total - max_length)
-            if drop and (floor is None or total - drop < floor[l]):
-                raise ValueError(
-                    f"PivotKVCache.crop({max_length}): layer {l} would be cut inside its compressed video rows "
-                    f"({'no boundary is recorded' if floor is None else f'they end at row {floor[l]}'}): a length alone cannot "
-                    "restore num_evicted_tokens or the archive split there - rewind to a mark instead")
-            if drop and st.c.pos_len not in (0, total):
-                raise ValueError(f"PivotKVCache.crop: layer {l} keeps ids for {st.c.pos_len} of its {total} rows")
-            drops.append(drop)
-        for st, drop in zip(self._layers, drops):
-            st.c.length -= drop
-            if st.c.pos_len:
-                st.c.pos_len -= drop
-            if self.kv_cache_dtype is None and st.pinned >= 0:   # (video_budget_rows: scores of rows that are gone)
-                st.sc_len = min(st.sc_len, max(st.c.length - st.pinned, 0))
-                st.sc_seen = min(st.sc_seen, st.sc_len)
-        if hasattr(self, "_seen_tokens"):
-            self._seen_tokens = max_length
-        m = self.last_compressed_mark
-        self._after_rewind(m.serial if m is not None else 0)
+    # ---- mark / rewind / crop, and fork: a branch reads the parent's rows where they lie: functions of _marks, bound as methods
+    video_end = property(_marks.video_end)
+    _take_mark, mark, set_resume_position_ids = _marks._take_mark, _marks.mark, _marks.set_resume_position_ids
+    _mark_is_dead, _kill_marks_after, _check_mark = _marks._mark_is_dead, _marks._kill_marks_after, _marks._check_mark
+    rewind, _after_rewind, _crop_floor, crop = _marks.rewind, _marks._after_rewind, _marks._crop_floor, _marks.crop
+    shared_len, shared, fork, _branch_check = _marks.shared_len, _marks.shared, _marks.fork, _marks._branch_check
+    _branch_refuse_write, _branch_update_check = _marks._branch_refuse_write, _marks._branch_update_check
 
     # ---- list views --------------------------------------------------------------------------
     @property
@@ -977,13 +701,8 @@ class PivotKVCache(DynamicCache):
             if layer_idx < self._pos_layers and c.pos and c.pos_len:
                 prev_ptr = c.pos + 8 * (c.pos_len - 1)
         # the temporal row ([0, 0, :] of [3, 1, n] ids, [0, :] of [1, n] ids) starts at the tensor's first element
-        if nv.current_device() == idx:
-            rc = nv.lib.rtk_position_shift(position_ids.data_ptr(), position_ids.shape[-1], prev_ptr, nv.raw_stream(idx))
-        else:
-            with torch.cuda.device(idx):
-                rc = nv.lib.rtk_position_shift(position_ids.data_ptr(), position_ids.shape[-1], prev_ptr,
-                                               nv.raw_stream(idx))
-        nv.check(rc, "rtk_position_shift")
+        nv.check(_on_device(idx, nv.lib.rtk_position_shift, position_ids.data_ptr(), position_ids.shape[-1], prev_ptr,
+                            nv.raw_stream(idx)), "rtk_position_shift")
         return position_ids
 
     # ---- storage -------------------------------------------------------------------------------
@@ -1010,15 +729,6 @@ class PivotKVCache(DynamicCache):
             nvv[:, :, :st.length].copy_(st.v[:, :, :st.length])
         st.k, st.v = nk, nvv
         return st
-
-    def _next_side(self, device) -> Optional[_Side]:
-        if self.overlap_streams <= 0:
-            return None
-        while len(self._sides) < self.overlap_streams:
-            self._sides.append(_Side(device))
-        side = self._sides[self._side_rr % len(self._sides)]
-        self._side_rr += 1
-        return side
 
     def _buf(self, name: str, shape, dtype, device, ws: Optional[dict] = None) -> torch.Tensor:
         ws = self._ws if ws is None else ws
@@ -1117,388 +827,23 @@ class PivotKVCache(DynamicCache):
             self._flush()
         return sl
 
-    def _flush(self):
-        """Evict every pending (layer, chunk) unit (reference :260-318 for all layers of the chunk): the score passes,
-        the selection, one batched gather / re-rotate launch and one batched placement launch."""
-        b = self._batch
-        if b is not None and b.shift_latch is not None and b.shift_latch[0]:
-            self._shift_failed(b)
-        if b is None or not b.pending:
-            return
-        if self.kv_cache_dtype is None and b.c_pending == len(b.pending) and not b.prompt and self._flush_c(b):
-            return
-        self._flush_general(b)
-
-    def _flush_c(self, b: _Batch) -> bool:
-        """rtk_pivotkv_flush: the whole chain in one call (units appended by rtk_pivotkv_update only)."""
-        layers = b.pending
-        if any(layers[i] >= layers[i + 1] for i in range(len(layers) - 1)):
-            layers = sorted(set(layers))
-        L_ = self._layers
-        n = len(layers)
-        if b.reforge and b.P:
-            for l in layers:
-                st = L_[l]
-                if st.c.pos_len + b.keep > st.c.pos_cap:
-                    self._pos_reserve(st, b.P, b.pos_ndim, b.keep, b.device)
-                elif st.pos_ndim == 0:
-                    st.pos_ndim = b.pos_ndim
-        states = (C.c_void_p * n)(*[L_[l].cref for l in layers])
-        slots = (C.c_int32 * n)(*[b.slot(l) for l in layers])
-        idx = b.dev_index
-        self._order_compaction(b)
-        rc = _on_device(idx, nv.lib.rtk_pivotkv_flush, b.cref, states, slots, n, nv.raw_stream(idx))
-        if rc == nv.RTK_EUNSUPPORTED:
-            return False
-        if rc:
-            self._reset_compaction(b)
-        nv.check(rc, "rtk_pivotkv_flush")
-        self._keep_scores(b, layers)
-        self._end_flush(b, layers)
-        return True
-
-    def _flush_general(self, b: _Batch):
-        """The same chain launched stage by stage (reference :260-318, top to bottom): worker streams, small chunks
-        (selection inside update), rotary modules that have to be called for the new ids' tables, the fp8 archive."""
-        # taken off the batch first: the id shift below finds the last layer's chunk pending and re-enters _flush
-        layers, b.pending = b.pending, []
-        # slot of a layer: the layer itself, or (flush_every_layers) layer mod slots - within one flush slots ascend with the
-        # layers, so the offset is one number (the score runs and the range of the new-id tables rely on it)
-        assert all(b.slot(l) - l == b.slot(layers[0]) - layers[0] for l in layers)
-        fp8 = self.kv_cache_dtype is not None
-        with torch.cuda.device(b.device):
-            self._wait_workers(layers)
-            self._shift_pending_ids(b, layers[-1])
-            self._score_unscored(b, layers)
-            self._select_unselected(b, layers)
-            # reforge: K is re-rotated at the NEW ids (reference :297-306).  With the native RoPE the scan's kernel
-            # computes their cos/sin itself; a third-party rotary module is called once for every pending slot and its
-            # section-merged fp32 tables are handed over.
-            rot = self._rotary(b.rotary_emb_fn, b.device) if (b.reforge and b.P and not b.defer) else None
-            if b.reforge and rot is None and not b.defer and not fp8:
-                self._new_id_tables(b, layers)
-            if fp8:   # the kept rows go to the archive (keep-all chunks included), the 16-bit tail is left to the next chunk
-                self._archive(b, layers, rot)
-            elif b.compact_sync is not None and not b.keep_all and (rot is not None or b.defer or not b.reforge):
-                self._compact(b, layers, rot)
-            else:
-                self._evict_staged(b, layers, rot)
-        # rtk_pivotkv_flush does exactly this itself for its units (pivotkv_update.hip:646-654, 730-738)
-        self._advance_layers(b, layers, fp8)
-        self._keep_scores(b, layers)
-        self._end_flush(b, layers)
-
-    def _wait_workers(self, layers):
-        """The current stream waits for the layers whose chunk was scored on a worker stream (overlap_streams > 0)."""
-        main = torch.cuda.current_stream()
-        for l in layers:
-            st = self._layers[l]
-            if st.pending_event is not None:
-                main.wait_event(st.pending_event)
-                st.pending_event = None
-
-    def _shift_pending_ids(self, b: _Batch, last_layer: int):
-        """Pre-RoPE units: the caller's ids tensor takes the last layer's continuity shift now (qwen2_vl.py:73; what the
-        reference's layer loop leaves behind) - before the flush appends that layer's new ids."""
-        if b.shift_ids is not None:
-            ids, b.shift_ids = b.shift_ids, None
-            b.c.shift_row = None
-            self._shift_row(ids, last_layer)
-
-    def _score_unscored(self, b: _Batch, layers):
-        """The two matrix passes (reference :260-268) of the units `update` left unscored: every run of consecutive
-        slots whose queries live alike in one launch per kernel.  (Keep-all units are never scored: `update` marks them.)"""
-        unscored = sorted(l for l in layers if l not in b.scored)
-        if not unscored:
-            return
-        off = b.slot(layers[0]) - layers[0]   # (one number: see _flush_general)
-
-        def qkey(l):   # queries scored where they lie (prologue route) carry their strides; packed ones None
-            t = b.q_keep[l + off]
-            return None if t is None else t.stride()
-
-        D, Hkv = b.D, b.Hkv
-        i = 0
-        while i < len(unscored):
-            j = i
-            while j + 1 < len(unscored) and unscored[j + 1] == unscored[j] + 1 and qkey(unscored[j + 1]) == qkey(unscored[i]):
-                j += 1
-            l0, n = unscored[i], j - i + 1
-            mptr = [b.masks.get(l) for l in range(l0, l0 + n)]
-            l0 += off     # from here on: the run's first SLOT
-            km = (C.c_void_p * n)(*[m.data_ptr() if m is not None else None for m in mptr]) \
-                if self.skip_masked_columns and any(m is not None for m in mptr) else None
-            qk = [b.q_keep[l] for l in range(l0, l0 + n)]
-            qu, qsh, qsl = None, 0, 0
-            if qk[0] is not None:   # units of the prologue route whose queries are scored in place
-                qu = (C.c_void_p * n)(*[t.data_ptr() for t in qk])
-                qsh, qsl = qk[0].stride(1), qk[0].stride(2)
-            if b.prompt:   # prompt-guided units: the prompt's rows score the video keys, final scores, no partials
-                self._score_prompt_run(b, l0, n, qk, qsh, qsl)
-                i = j + 1
-                continue
-            nv.check(nv.lib.rtk_pivotkv_score_passes_batched_q(
-                C.c_void_p(b.score_ws_base + l0 * b.ws_stride), b.ws_stride,
-                nv.ptr(b.k_unrot[l0]) if b.reforge else None, b.L * D * Hkv * b.esize,
-                nv.ptr(b.partials[l0]), b.part_floats, n, b.Hq, Hkv, b.L, D, b.score_dt,
-                km, nv.ptr(b.key_index[l0]) if km is not None else None, qu, qsh, qsl, nv.stream()),
-                "rtk_pivotkv_score_passes_batched")
-            i = j + 1
-
-    def _score_prompt_run(self, b: _Batch, l0: int, n: int, qk, qsh: int, qsl: int):
-        """rtk_pivotkv_score_prompt_batched for the n consecutive slots from l0 (up to 28 units per call): rows [Lv, L) of
-        the slots' q~ (packed, or qk's tensors where they lie) against rows [0, Lv) of their k~ -> b.score[slot, :Lv]."""
-        D, Hkv = b.D, b.Hkv
-        for u0 in range(0, n, nv.PROMPT_SCORE_MAX_UNITS):
-            m, s0 = min(nv.PROMPT_SCORE_MAX_UNITS, n - u0), l0 + u0
-            qu = (C.c_void_p * m)(*[t.data_ptr() for t in qk[u0:u0 + m]]) if qk[0] is not None else None
-            nv.check(nv.lib.rtk_pivotkv_score_prompt_batched(
-                C.c_void_p(b.score_ws_base + s0 * b.ws_stride), b.ws_stride,
-                nv.ptr(b.k_unrot[s0]) if b.reforge else None, b.L * D * Hkv * b.esize,
-                nv.ptr(b.score[s0]), b.L, C.c_void_p(b.prompt_ws_base + s0 * b.prompt_bytes), b.prompt_bytes, m,
-                b.Hq, Hkv, b.L, b.prompt, D, b.score_dt, qu, qsh, qsl, nv.stream()), "rtk_pivotkv_score_prompt_batched")
-
-    def _select_units(self, b: _Batch, todo, partials, ids):
-        """rtk_select_unit blocks of the layers `todo`; `partials` (None: the scores are final) and `ids` are indexed by slot."""
-        su = (nv.SelectUnit * len(todo))()
-        for u, l in zip(su, todo):
-            sl = b.slot(l)
-            u.partial = partials[sl].data_ptr() if partials is not None else None
-            u.score = b.score[sl].data_ptr()
-            m = b.masks.get(l)
-            u.mask = m.data_ptr() if m is not None else None
-            u.pos = ids[sl].data_ptr() if b.P else None
-            u.keep_idx = b.keep_idx[sl].data_ptr()
-            u.rank = None
-            u.pos_out = (b.pos_new.data_ptr() + sl * b.keep * 8) if b.P else None
-            u.workspace = b.sel_ws[sl].data_ptr()
-        return su
-
-    def _select_prompt_units(self, b: _Batch, todo):
-        """The selection of prompt-guided units: mask override + top-k + id gather / rescale over the Lv VIDEO columns
-        (the existing kernels called with L = Lv: keep of Lv, temporal ids rescaled by keep / Lv).  Their ids are handed
-        over as dense [P, Lv] blocks; a key-patch mask is read up to Lv."""
-        P, keep, Lv = b.P, b.keep, b.Lv
-        slots = [b.slot(l) for l in todo]
-        if P:
-            lo, hi = min(slots), max(slots) + 1
-            b.pos_video[lo:hi].copy_(b.pos_old[lo:hi, :, :Lv])
-        su = self._select_units(b, todo, None, b.pos_video)   # (no partials: the scores are final)
-        rc = nv.lib.rtk_pivotkv_select_batched(su, len(todo), 0, 0, 0, Lv, keep, P, int(b.reforge), b.slots * keep, b.score_dt,
-                                               nv.stream())
-        if rc != nv.RTK_EUNSUPPORTED:
-            nv.check(rc, "rtk_pivotkv_select_batched")
-            return
-        # few video rows (a video's tail chunk): outside the chip-wide kernels, one workgroup per unit
-        rank = self._buf("rank", (Lv,), torch.int32, b.device)
-        for u in su:
-            nv.check(nv.lib.rtk_pivotkv_select(u.score, u.mask, Lv, keep, u.pos, P, int(b.reforge), u.keep_idx, nv.ptr(rank),
-                                               u.pos_out, b.slots * keep, u.workspace, b.sel_bytes, nv.stream()),
-                     "rtk_pivotkv_select")
-
-    def _select_unselected(self, b: _Batch, layers):
-        """Mask override + top-k + id gather / rescale (reference :269-295) of the units not selected inside `update`,
-        in one launch.  Keep-all batches: the selection is the identity (keep_idx is set once per batch) and the units
-        of the one-call path carry their ids in pos_old only: ids x 1.0 = the ids (:288-292)."""
-        todo = [l for l in layers if l not in b.selected]
-        if not todo:
-            return
-        P, keep = b.P, b.keep
-        if b.keep_all:
-            if P:
-                for l in todo:
-                    b.pos_new[:, b.slot(l)].copy_(b.pos_old[b.slot(l)])
-            return
-        if b.prompt:
-            return self._select_prompt_units(b, todo)
-        su = self._select_units(b, todo, b.partials, b.pos_old)
-        nv.check(nv.lib.rtk_pivotkv_select_batched(su, len(todo), b.Hkv, b.rs_n.value, b.Hq // b.Hkv, b.L, keep, P,
-                                                   int(b.reforge), b.slots * keep, b.score_dt, nv.stream()),
-                 "rtk_pivotkv_select_batched")
-
-    def _new_id_tables(self, b: _Batch, layers):
-        """Section-merged fp32 cos / sin tables of the NEW ids of every pending slot, from a rotary module that has
-        to be called (reference :298), for the staged scan."""
-        b.ensure_tables()
-        keep, P = b.keep, b.P
-        lo, hi = b.slot(min(layers)), b.slot(max(layers))
-        n = (hi - lo + 1) * keep
-        pos2d = b.pos_new[:, lo:hi + 1].reshape(P, n)   # a copy when the slot range is partial
-        self._rope_tables(b.cos_new[lo * keep:], b.sin_new[lo * keep:], b.rotary_emb_fn, b.x_like, pos2d, n, b.pos_ndim,
-                          b.sec, n, b.D)
-
-    def _scan_unit(self, b: _Batch, l: int, u):
-        """What the three scans share of layer l's unit.  Fills the fields every unit type names alike - the K source
-        (the slot's un-rotated rows with reforge, else the tail), keep_idx, and the position-id bookkeeping (reference
-        :308-309; the layer's id buffer is grown first) - and returns (layer store, slot, K tail, V tail, their head
-        stride in elements); the tail is where the append put the chunk: rows [length, length + L) of the buffers."""
-        st, sl = self._layers[l], b.slot(l)
-        keep, D = b.keep, b.D
-        tail, stride_h = st.length * D * b.esize, st.k.shape[2] * D
-        k_tail, v_tail = st.k.data_ptr() + tail, st.v.data_ptr() + tail
-        if b.reforge:
-            u.k_src, u.k_src_stride_h = b.k_unrot[sl].data_ptr(), b.L * D
-        else:
-            u.k_src, u.k_src_stride_h = k_tail, stride_h
-        u.keep_idx = b.keep_idx[sl].data_ptr()
-        if b.reforge and b.P:
-            self._pos_reserve(st, b.P, b.pos_ndim, keep, b.device)
-            u.pos_src, u.pos_src_stride = b.pos_new.data_ptr() + sl * keep * 8, b.slots * keep
-            u.pos_dst, u.pos_dst_stride = st.pos.data_ptr() + st.pos_len * 8, st.pos.shape[1]
-        else:
-            u.pos_src = u.pos_dst = None
-        return st, sl, k_tail, v_tail, stride_h
-
-    def _evict_staged(self, b: _Batch, layers, rot):
-        """The eviction scan of the pending layers as two launches (reference :278-318): the evict launch
-        (rtk_pivotkv_evict_batched[_rope]) gathers the kept rows - K re-rotated at the new ids straight into the cache with reforge, else K and V into
-        the staging rows - and rtk_pivotkv_place_batched puts the staged rows at the head of the tail."""
-        keep, D, Hkv, es, dt = b.keep, b.D, b.Hkv, b.esize, b.c.dtype
-        tables = b.reforge and rot is None and not b.defer   # of a called rotary module (_new_id_tables)
-        if not b.keep_all:
-            b.ensure_staging()
-        units = (nv.EvictUnit * len(layers))()
-        places = (nv.PlaceUnit * (0 if b.keep_all else len(layers) * (1 if b.reforge else 2)))()
-        nc = 0
-        for u, l in zip(units, layers):
-            st, sl, k_tail, v_tail, stride_h = self._scan_unit(b, l, u)
-            staged = []   # (staging rows, tail) of this unit: K unless it goes straight into the cache, V
-            if b.reforge:
-                if tables:
-                    u.cos_new = b.cos_new.data_ptr() + sl * keep * D * 4
-                    u.sin_new = b.sin_new.data_ptr() + sl * keep * D * 4
-                u.k_dst, u.k_dst_stride_h = k_tail, stride_h  # straight into the cache
-            elif not b.keep_all:
-                u.k_dst, u.k_dst_stride_h = b.k_stage[sl].data_ptr(), keep * D
-                staged.append((u.k_dst, k_tail))
-            u.v_src, u.v_src_stride_h = v_tail, stride_h
-            if not b.keep_all:   # (keep-all: every row already sits where the append put it)
-                u.v_dst, u.v_dst_stride_h = b.v_stage[sl].data_ptr(), keep * D
-                staged.append((u.v_dst, v_tail))
-            for stage, tail in staged:
-                p = places[nc]
-                p.stage, p.stage_stride_h_bytes = stage, keep * D * es
-                p.tail, p.tail_stride_h_bytes = tail, stride_h * es
-                p.keep_idx = u.keep_idx
-                nc += 1
-        s = nv.stream()
-        if rot is not None:
-            nv.check(nv.lib.rtk_pivotkv_evict_batched_rope(units, len(layers), Hkv, D, keep, b.P, dt, nv.ptr(rot.inv),
-                                                           rot.scaling, b.sec, b.c.nsec, b.round_mode, 1, s),
-                     "rtk_pivotkv_evict_batched_rope")
-        elif b.reforge or not b.keep_all:   # (deferred re-rotation: every kept un-rotated K row is copied, bit 1)
-            nv.check(nv.lib.rtk_pivotkv_evict_batched(units, len(layers), Hkv, D, keep, b.P if b.reforge else 0, dt,
-                                                      3 if b.defer else 1, s), "rtk_pivotkv_evict_batched")
-        # kept rows -> head of the tail: in place, except the ~ratio of them whose source lies inside the destination
-        # range (parked in the staging rows by the launch above) - reference :313-318 without a full second copy
-        if nc:
-            nv.check(nv.lib.rtk_pivotkv_place_batched(places, nc, Hkv, keep, D, dt, s), "rtk_pivotkv_place_batched")
-
-    def _advance_layers(self, b: _Batch, layers, fp8: bool):
-        """The layers' numbers after a stage-by-stage flush: the kept rows are committed (to the archive with fp8 rows),
-        nothing is pending."""
-        keep, ids = b.keep, b.reforge and b.P
-        for l in layers:
-            st = self._layers[l]
-            b.q_units[b.slot(l)] = None
-            if fp8:
-                st.len8 += keep
-            else:
-                st.length += keep
-            st.pending = 0
-            st.pending_keep = 0
-            st.c.mask = None
-            if ids:
-                st.pos_len += keep
-
-    def _end_flush(self, b: _Batch, layers):
-        """The batch's own bookkeeping of a completed flush, whichever route ran it: nothing is pending, what `update`
-        noted per unit (masks, scored / selected marks, the ids tensor to shift, queries kept alive) is dropped, and
-        the position cache covers the flushed layers (reference :308-309)."""
-        b.pending = []
-        b.c_pending = 0
-        self._flushes += 1
-        b.masks.clear()
-        b.scored.clear()
-        b.selected.clear()
-        b.shift_ids = None
-        for l in layers:
-            b.q_keep[b.slot(l)] = None
-        if b.reforge and b.P:
-            self._pos_layers = max(self._pos_layers, max(layers) + 1)
-
-    def _order_compaction(self, b: _Batch):
-        """The in-place compaction's tickets and flags (batch.compact_sync) serve ONE launch at a time: flushes of a batch
-        are ordered on one stream.  A flush that arrives on another stream than the batch's previous one first waits for
-        the device (rare: the caller changed its current stream between two chunks)."""
-        if b.compact_sync is None:
-            return
-        cur = nv.raw_stream(b.dev_index)
-        if b.sync_stream is not None and b.sync_stream != cur:
-            torch.cuda.synchronize(b.device)
-        b.sync_stream = cur
-
-    def _reset_compaction(self, b: _Batch):
-        """After a failed flush: tickets / flags back to zero (a launch that completes leaves them zeroed itself)."""
-        if b.compact_sync is not None:
-            try:
-                b.compact_sync.zero_()
-            except Exception:  # noqa: BLE001  (a device-side abort leaves the context unusable; the first error is what is raised)
-                pass
-
-    def _archive(self, b: _Batch, layers, rot):
-        """The eviction scan of the pending layers into their fp8 archives, one launch (rtk_pivotkv_archive_batched;
-        reference :278-310): kept K re-rotated at the new ids and rounded to the model dtype as the compaction does (taken
-        from the tail as it is without reforge), kept V from the tail, both quantised per (kv head, row) into rows
-        [len8, len8 + keep) of the archive; ids to the position cache.  The 16-bit length does not advance."""
-        keep, D, Hkv = b.keep, b.D, b.Hkv
-        if b.reforge and (rot is None or not b.P or b.defer):
-            raise NotImplementedError("kv_cache_dtype='fp8_e4m3' with pos_embed_reforge needs position ids and the native RoPE, "
-                                      "and no deferred re-rotation")
-        units = (nv.ArchiveUnit * len(layers))()
-        for u, l in zip(units, layers):
-            st = self._layers[l]
-            self._archive_reserve(st, keep, Hkv, D, b.device)
-            if st.archive_at < 0:
-                st.archive_at = st.length
-            _, _, _, v_tail, stride_h = self._scan_unit(b, l, u)
-            u.v_src, u.v_src_stride_h = v_tail, stride_h
-            if b.keep_all:
-                u.keep_idx = None
-            cap8 = st.k8.shape[2]
-            u.k8, u.v8, u.dst_stride_h = st.k8.data_ptr() + st.len8 * D, st.v8.data_ptr() + st.len8 * D, cap8 * D
-            u.k_scale, u.v_scale, u.scale_stride_h = st.ks8.data_ptr() + st.len8 * 4, st.vs8.data_ptr() + st.len8 * 4, cap8
-        mode = nv.COMPACT_K_ROTATE if b.reforge else nv.COMPACT_K_COPY
-        sec = b.sec if b.reforge else None
-        nv.check(nv.lib.rtk_pivotkv_archive_batched(
-            units, len(layers), Hkv, D, keep, b.P if b.reforge else 0, b.c.dtype, mode,
-            nv.ptr(rot.inv) if b.reforge else None, rot.scaling if b.reforge else 1.0,
-            sec, len(sec) if sec is not None else 0, b.round_mode, nv.stream()),
-            "rtk_pivotkv_archive_batched")
-
-    def _compact(self, b: _Batch, layers, rot):
-        """The eviction scan of the pending layers as one in-place launch (rtk_pivotkv_compact_batched; reference
-        :278-318): kept K re-rotated at the new ids (or copied un-rotated when the rotation is deferred; compacted in
-        place without reforge), V compacted inside the tail, ids to the position cache."""
-        units = (nv.CompactUnit * len(layers))()
-        for u, l in zip(units, layers):
-            _, _, k_tail, v_tail, stride_h = self._scan_unit(b, l, u)
-            u.k_tail, u.k_tail_stride_h = k_tail, stride_h
-            u.v_tail, u.v_tail_stride_h = v_tail, stride_h
-            if not b.reforge:   # K is compacted inside its tail like V: no separate source
-                u.k_src, u.k_src_stride_h = None, 0
-        mode = nv.COMPACT_K_INPLACE if not b.reforge else (nv.COMPACT_K_COPY if b.defer else nv.COMPACT_K_ROTATE)
-        rotate = mode == nv.COMPACT_K_ROTATE
-        sec = b.sec if rotate else None
-        self._order_compaction(b)
-        nv.check(nv.lib.rtk_pivotkv_compact_batched(
-            units, len(layers), b.Hkv, b.D, b.keep, b.P if b.reforge else 0, b.c.dtype, mode,
-            nv.ptr(rot.inv) if rotate else None, rot.scaling if rotate else 1.0,
-            sec, len(sec) if sec is not None else 0, b.round_mode, b.c.compact_sync, b.c.compact_sync_ints,
-            nv.stream()),
-            "rtk_pivotkv_compact_batched")
+    # the flush of a chunk's pending units, once per chunk: functions of _flush, bound as methods
+    _flush, _flush_c, _flush_general, _wait_workers = _fl._flush, _fl._flush_c, _fl._flush_general, _fl._wait_workers
+    _shift_pending_ids, _score_unscored, _score_prompt_run = _fl._shift_pending_ids, _fl._score_unscored, _fl._score_prompt_run
+    _select_units, _select_prompt_units, _select_unselected = _fl._select_units, _fl._select_prompt_units, _fl._select_unselected
+    _new_id_tables, _scan_unit, _evict_staged = _fl._new_id_tables, _fl._scan_unit, _fl._evict_staged
+    _archive, _compact, _advance_layers, _end_flush = _fl._archive, _fl._compact, _fl._advance_layers, _fl._end_flush
+    _order_compaction, _reset_compaction = _fl._order_compaction, _fl._reset_compaction
 
     # ---- the hot path ---------------------------------------------------------------------------
+    def _entry_guard(self, who: str):
+        """What `update`, `update_pre_rope` and `append_pre_rope` (`who`) check first, in this order."""
+        if self.forked_from is not None:
+            self._branch_update_check(who)
+        if self.focused_from is not None:
+            _focus.refuse_compression(self, who)
+        self._shift_latch_check()
+
     def update(
         self,
         key_states: torch.Tensor,
@@ -1526,13 +871,8 @@ class PivotKVCache(DynamicCache):
         l + 1's temporal offset.  Only a caller that shares one ids tensor between its layers and shifts it in place itself
         (the Qwen2-VL attention patch: `shift_temporal_ids_` then finds the shift done) should set it.
         """
-        if self.forked_from is not None:
-            self._branch_update_check("PivotKVCache.update")
-        if self.focused_from is not None:
-            _focus.refuse_compression(self, "PivotKVCache.update")
+        self._entry_guard("PivotKVCache.update")
         b = self._batch
-        if b is not None and b.shift_latch is not None and b.shift_latch[0]:
-            self._shift_failed(b)
         if b is not None and b.c_capable and cache_kwargs is not None and self.kvcache_compression \
                 and self.overlap_streams <= 0 and self.one_call_update and b.prompt == self._prompt_rows(b.L):
             out = self._update_c(b, key_states, value_states, layer_idx, cache_kwargs, None)
@@ -1548,10 +888,7 @@ class PivotKVCache(DynamicCache):
         pos = ck.get("position_ids")
         if q is None or pos is None or (layer_idx >= b.slots and not b.wrap) or layer_idx >= len(self._layers):
             return None
-        rot_fn = ck.get("rotary_emb")
-        hit = self._rotaries.get(id(rot_fn))
-        if hit is None or hit[0] is not rot_fn or hit[1] is None or hit[1] is not b.rot \
-                or ck.get("mrope_section") != b.mrope_section or hit[2] != _inv_stamp(rot_fn):
+        if not self._bound_rotary(b, ck.get("rotary_emb")) or ck.get("mrope_section") != b.mrope_section:
             return None
         dt = b.dtype
         if q.shape != b.qshape or key_states.shape != b.kshape or value_states.shape != b.kshape \
@@ -1668,14 +1005,6 @@ class PivotKVCache(DynamicCache):
         n = P0 + L
         return st._k.narrow(2, 0, n), st._v.narrow(2, 0, n)
 
-    def _branch_update_check(self, who: str):
-        """What every row-writing entry point of a branch checks first: the branch is still valid, and the call does not
-        compress (branches carry questions, not video)."""
-        self._branch_check(who)
-        if self.kvcache_compression:
-            raise NotImplementedError(f"{who}: a branch (PivotKVCache.fork) does not compress video chunks - branches carry "
-                                      "questions, not video (set kvcache_compression = False, or feed the video to the parent)")
-
     def _next_layer_prev(self, layer_idx: int, dev_index: int):
         """Address of the last temporal id cached for layer_idx + 1 (None: nothing cached, the rule's prev = -1), or
         False when this launch must not shift for it: there is no such layer, its previous chunk is still pending, or its
@@ -1720,11 +1049,7 @@ class PivotKVCache(DynamicCache):
         chunk-batched score passes can then read `query_states` where it lies (no copy of the queries is made;
         `query_states` must stay unmodified until the chunk's flush, and is kept alive by the cache), else over
         `query_states`; pass `query_states` itself to force the in-place rotation."""
-        if self.forked_from is not None:
-            self._branch_update_check("PivotKVCache.update_pre_rope")
-        if self.focused_from is not None:
-            _focus.refuse_compression(self, "PivotKVCache.update_pre_rope")
-        self._shift_latch_check()
+        self._entry_guard("PivotKVCache.update_pre_rope")
         if not (self.kvcache_compression and self.pos_embed_reforge and self.one_call_update) or self.overlap_streams > 0 \
                 or position_ids is None or not key_states.is_cuda or key_states.shape[0] != 1 \
                 or (torch.is_grad_enabled() and query_states.requires_grad):
@@ -1776,11 +1101,7 @@ class PivotKVCache(DynamicCache):
         clone).  Replaces ~25 eager launches per layer and token.  Returns (rotated q, keys, values) like `update`, or
         None - nothing touched - when the op-by-op route has to run (compression on: `update_pre_rope`; no reforging;
         rotary modules that must be called; CPU tensors)."""
-        if self.forked_from is not None:
-            self._branch_update_check("PivotKVCache.append_pre_rope")
-        if self.focused_from is not None:
-            _focus.refuse_compression(self, "PivotKVCache.append_pre_rope")
-        self._shift_latch_check()
+        self._entry_guard("PivotKVCache.append_pre_rope")
         if self.kvcache_compression or not (self.pos_embed_reforge and self.one_call_update) or position_ids is None \
                 or not key_states.is_cuda or key_states.shape[0] != 1 \
                 or (torch.is_grad_enabled() and query_states.requires_grad):
@@ -1862,241 +1183,11 @@ class PivotKVCache(DynamicCache):
             c.inv_freq = rot.inv.data_ptr() if rot is not None else None
             c.attention_scaling = rot.scaling if rot is not None else 1.0
 
-    def _update_general(self, key_states, value_states, layer_idx, cache_kwargs=None):
-        """`update` stage by stage (inputs and outputs: see its docstring)."""
-        if not self._warned:
-            self._warn_compression()
-        cache_kwargs = cache_kwargs if cache_kwargs is not None else {}
-        position_ids = cache_kwargs.pop("position_ids", None)
-        cache_kwargs.pop("shift_next_position_ids", None)   # (the build's own key: only the one-call route acts on it)
-        nv.require_device(key_states, value_states)
-        assert key_states.shape[0] == 1, "PivotKVCache supports bsz == 1 only"
-
-        # 1) append: the next layer's hidden states see the uncompressed chunk (reference :238)
-        n_new = key_states.shape[2]
-        if len(self._layers) > layer_idx and self._layers[layer_idx].pending:
-            self._flush()
-
-        if not self.kvcache_compression:  # text prefill / decode (reference :319-321)
-            st = self.reserve(layer_idx, n_new, key_states)
-            P0 = st.length
-            st.k[:, :, P0:P0 + n_new].copy_(key_states)
-            st.v[:, :, P0:P0 + n_new].copy_(value_states)
-            st.length += n_new
-            if self.pos_embed_reforge:
-                self.update_position_ids(position_ids, layer_idx)
-            if self._watch is not None and cache_kwargs.get("query_states") is not None:
-                _focus.capture(self, layer_idx, cache_kwargs["query_states"])
-            return st.k[:, :, :st.length], st.v[:, :, :st.length]
-
-        u = self._bind_update(key_states, value_states, layer_idx, cache_kwargs, position_ids)
-        b, st, dev = u.b, u.st, key_states.device
-        with torch.cuda.device(dev):
-            side = self._next_side(dev)
-            if side is None:
-                u.pos_in = self._ids_2d(u, False)
-                prepared = self._fused_prepare(u, self._ws)
-                if not prepared:
-                    self._append_tail(u)
-                self._run_stages(u, self._ws, prepared)
-            else:
-                self._append_tail(u)   # on the caller's stream: all this layer's attention needs
-                u.pos_in = self._ids_2d(u, True)
-                self._run_on_worker(u, side)
-        if self.video_budget_rescore is not None:
-            _video_bound.observe(self, st, u.q)
-        self.update_num_evicted_tokens(n_new - b.keep, layer_idx)  # reference :310
-        st.pending = n_new
-        st.pending_keep = b.keep
-        b.pending.append(layer_idx)
-        self._compressed_in_forward = True
-        self._last_slot = (b, u.slot)
-        return st.k[:, :, :st.length + n_new], st.v[:, :, :st.length + n_new]
-
-    def _bind_update(self, key_states, value_states, layer_idx, cache_kwargs, position_ids) -> _Update:
-        """The argument handling of a compressed `_update_general` call: pops the rest of the cache_kwargs protocol
-        (reference :235, :241-243), checks the operands, finds / builds the batch of the chunk's geometry, binds the
-        rotary, claims the layer's slot and makes room for the chunk."""
-        query_states = cache_kwargs.pop("query_states")
-        rotary_emb_fn = cache_kwargs.pop("rotary_emb")
-        mrope_section = cache_kwargs.pop("mrope_section", None)  # M-RoPE only
-        bsz, Hq, L, D = query_states.shape
-        Hkv = key_states.shape[1]
-        assert bsz == 1
-        nv.require_device(query_states)
-        dev = key_states.device
-        nv.dtype_code(key_states)   # (raises for a dtype the kernels do not serve)
-        for t in (query_states, key_states, value_states):
-            if t.stride(-1) != 1:
-                raise ValueError("q/k/v must be contiguous along head_dim")
-        lp = self._prompt_rows(L)   # prompt-guided unit: the last lp rows are the appended prompt, keep counts video rows
-        keep_len = max(1, int(self.compression_ratio * (L - lp)))  # evict new tokens only (reference :263)
-        if keep_len > L - lp:   # compression_ratio > 1: the reference's topk refuses it (:276)
-            raise RuntimeError(f"PivotKVCache.update: selected index k out of range (keep {keep_len} of {L} tokens)")
-        reforge = bool(self.pos_embed_reforge)
-        rot = self._rotary(rotary_emb_fn, dev) if reforge else None
-        if lp and reforge and rot is None:
-            raise ValueError("prompt_guided_scoring with pos_embed_reforge needs a rotary module of the static inv_freq * "
-                             "position kind and native_rope=True: a rotary module that has to be called is not served")
-        self._fp8_refuse(key_states.dtype, D, reforge, rot, position_ids is not None)
-
-        mask = self.keypatches_mask_chunk
-        if mask is not None:
-            nv.require_device(mask)
-            if mask.dtype != torch.bool or not mask.is_contiguous():
-                mask = mask.to(torch.bool).contiguous()
-            assert mask.numel() in (L, L - lp), "keypatches_mask_chunk must have one entry per chunk token"
-        Pn = 0
-        if position_ids is not None:
-            nv.require_device(position_ids)
-            Pn = 3 if position_ids.ndim == 3 else 1
-        b = self._get_batch(layer_idx, Hq, Hkv, L, D, keep_len, Pn, key_states.dtype, dev, lp)
-        self._bind_rotary(b, rotary_emb_fn, mrope_section, rot)
-        if b.pending and b.c.pre_rope:   # units of the prologue route are flushed among themselves
-            self._flush()
-        b.c.pre_rope = 0
-        u = _Update()
-        u.b, u.layer, u.slot = b, layer_idx, self._claim_slot(b, layer_idx)
-        u.q, u.k, u.v, u.ids, u.mask = query_states, key_states, value_states, position_ids, mask
-        b.x_like = value_states[:, :, :1]
-        u.st = st = self.reserve(layer_idx, key_states.shape[2], key_states)
-        if st.pinned < 0:    # the layer's first compressed chunk: what it holds now is pinned (video_window_rows)
-            st.pinned = st.length
-        tail = st.length * D * st.k.element_size()
-        u.k_tail, u.v_tail = C.c_void_p(st.k.data_ptr() + tail), C.c_void_p(st.v.data_ptr() + tail)
-        u.a_scale = float(getattr(rotary_emb_fn, "attention_scaling", 1.0)) if reforge else 1.0
-        u.pos_in = u.cos = u.sin = None
-        return u
-
-    def _ids_2d(self, u: _Update, snapshot: bool):
-        if u.ids is None:
-            return None
-        p2 = u.ids.reshape(u.b.P, u.b.L)
-        # worker streams read the ids later than the caller's stream runs on: the attention patch shifts the
-        # SAME ids tensor in place for the next layer (qwen2_vl.py:73), so they get a private copy
-        return p2.clone() if snapshot else (p2 if p2.is_contiguous() else p2.contiguous())
-
-    def _run_stages(self, u: _Update, ws, prepared: bool):
-        """The launch stages of one update on the CURRENT stream: un-rotate / pack (unless the fused prepare launch has
-        done it), the chunk's ids into the slot, the matrix passes, the selection."""
-        if not prepared:
-            self._stage_pre(u, ws)
-            if u.b.defer_select and u.pos_in is not None:
-                u.b.pos_old[u.slot].copy_(u.pos_in)
-        self._stage_passes(u, ws)
-        self._stage_post(u, ws)
-
-    def _run_on_worker(self, u: _Update, side: _Side):
-        """`_run_stages` on a worker stream (overlap_streams > 0): it starts after what the caller's stream has queued
-        so far, and the layer's flush waits for its completion event."""
-        main = torch.cuda.current_stream()
-        ready = torch.cuda.Event()
-        ready.record(main)
-        for t in (u.q, u.k, u.v, u.pos_in, u.mask):
-            if t is not None:
-                t.record_stream(side.stream)
-        with torch.cuda.stream(side.stream):
-            side.stream.wait_event(ready)
-            self._run_stages(u, side.ws, False)
-            done = torch.cuda.Event()
-            done.record(side.stream)
-        u.st.pending_event = done
-
-    def _score_ws_pointer(self, u: _Update, ws):
-        b = u.b
-        if b.batched_passes:   # the slot's own workspace: q~ must survive until the batched passes of the flush
-            return b.score_ws_base + u.slot * b.ws_stride
-        wsb = self._buf("score_ws", (b.ws_bytes + 256,), torch.uint8, b.device, ws)
-        return (wsb.data_ptr() + 255) & ~255
-
-    def _score_stage(self, u: _Update, ws, stages):
-        b, q, k = u.b, u.q, u.k
-        score = b.score[u.slot]
-        k_unrot = b.k_unrot[u.slot] if b.reforge else None
-        # the matrix passes of a per-update launch know the chunk's key-patch mask: pass 2 skips the columns the
-        # selection overwrites with 1.0 anyway (reference :272-274)
-        live = u.mask if (stages & nv.SCORE_PASSES) and self.skip_masked_columns else None
-        kidx = self._buf("key_index", (b.L + 1,), torch.int32, b.device, ws) if live is not None else None
-        nv.check(nv.lib.rtk_pivotkv_score_stages_masked(
-            nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), k.stride(1), k.stride(2),
-            b.Hq, b.Hkv, b.L, b.D, b.score_dt, nv.ptr(u.cos), nv.ptr(u.sin), u.a_scale,
-            nv.ptr(score), nv.ptr(k_unrot), C.c_void_p(self._score_ws_pointer(u, ws)), b.ws_bytes, stages,
-            nv.ptr(b.partials[u.slot]), nv.ptr(live), nv.ptr(kidx), nv.stream()), "rtk_pivotkv_score")
-        return score
-
-    def _stage_pre(self, u: _Update, ws):
-        """RoPE tables of the chunk's ids + un-rotate / pack (reference :248-259), on the CURRENT stream."""
-        b = u.b
-        b.ensure_scoring()
-        if b.reforge:
-            L, D = b.L, b.D
-            u.cos = self._buf("old_cos", (L, D), torch.float32, b.device, ws)
-            u.sin = self._buf("old_sin", (L, D), torch.float32, b.device, ws)
-            self._rope_tables(u.cos, u.sin, b.rotary_emb_fn, u.v, u.pos_in, L, u.ids.ndim, b.sec, L, D)
-        self._score_stage(u, ws, nv.SCORE_PREPARE)
-
-    def _stage_passes(self, u: _Update, ws):
-        """the two matrix passes (reference :260-268): deferred to the flush (all layers of the chunk in one
-        launch per kernel) whenever the batched form supports the shape"""
-        b = u.b
-        if b.keep_all:         # nothing to choose: no scores
-            b.scored.add(u.layer)
-            return
-        if b.batched_passes:
-            return
-        self._score_stage(u, ws, nv.SCORE_PASSES)
-        b.scored.add(u.layer)
-
-    def _stage_post(self, u: _Update, ws):
-        """small chunks only: column-mass reduction, mask override + top-k + position ids (reference :269-295)
-        right away; larger chunks leave this to the batched selection of the flush"""
-        b, slot, pos_in = u.b, u.slot, u.pos_in
-        if b.keep_all:         # keep_idx is the identity (set once per batch); ids x 1.0 = the ids (:288-292)
-            if pos_in is not None:
-                b.pos_new[:, slot].copy_(pos_in)
-            b.selected.add(u.layer)
-            return
-        if b.defer_select:
-            b.masks[u.layer] = u.mask
-            return
-        score = self._score_stage(u, ws, nv.SCORE_FINALIZE)
-        L, dev = b.L, b.device
-        rank = self._buf("rank", (L,), torch.int32, dev, ws)
-        pos_out = b.pos_new[:, slot] if pos_in is not None else None
-        sel_ws = self._buf("select_ws", (b.sel_bytes,), torch.uint8, dev, ws)
-        nv.check(nv.lib.rtk_pivotkv_select(nv.ptr(score), nv.ptr(u.mask), L, b.keep, nv.ptr(pos_in), b.P,
-                                           int(b.reforge), nv.ptr(b.keep_idx[slot]), nv.ptr(rank), nv.ptr(pos_out),
-                                           b.slots * b.keep, nv.ptr(sel_ws), b.sel_bytes, nv.stream()),
-                 "rtk_pivotkv_select")
-        b.selected.add(u.layer)
-
-    def _append_tail(self, u: _Update):
-        """reference :238 - the uncompressed view this layer's attention reads"""
-        b, k, v = u.b, u.k, u.v
-        nv.check(nv.lib.rtk_pivotkv_append(
-            nv.ptr(k), k.stride(1), k.stride(2), nv.ptr(v), v.stride(1), v.stride(2), b.Hkv, b.L, b.D, b.c.dtype,
-            u.k_tail, u.v_tail, u.st.k.shape[2] * b.D, nv.stream()), "rtk_pivotkv_append")
-
-    def _fused_prepare(self, u: _Update, ws) -> bool:
-        """append + native RoPE tables + un-rotate in ONE launch (k read once); False if the shape needs the
-        separate kernels."""
-        b, q, k, v, pos_in = u.b, u.q, u.k, u.v, u.pos_in
-        if not (b.reforge and b.rot is not None and pos_in is not None):
-            return False
-        # keep-all chunks are not scored: no q~, no score workspace (any aligned address will do)
-        k_only = b.keep_all and b.partials is None
-        ws_ptr = b.c.score_ws if k_only else self._score_ws_pointer(u, ws)
-        rc = nv.lib.rtk_pivotkv_prepare(
-            nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), k.stride(1), k.stride(2),
-            nv.ptr(v), v.stride(1), v.stride(2),
-            b.Hq, b.Hkv, b.L, b.D, b.prep_dt | (nv.RTK_PREPARE_K_ONLY if k_only else 0), nv.ptr(pos_in), b.L, b.P,
-            nv.ptr(b.rot.inv), u.a_scale, b.sec, b.c.nsec, b.round_mode,
-            nv.ptr(b.k_unrot[u.slot]), C.c_void_p(ws_ptr), b.ws_bytes, u.k_tail, u.v_tail, u.st.k.shape[2] * b.D,
-            nv.ptr(b.pos_old[u.slot]) if b.defer_select else None, nv.stream())
-        if rc == nv.RTK_EUNSUPPORTED:
-            return False
-        nv.check(rc, "rtk_pivotkv_prepare")
-        return True
+    # ---- `update` stage by stage, what the one-call route does not serve: functions of _update_stages, bound as methods
+    _update_general, _bind_update, _ids_2d, _run_stages = _us._update_general, _us._bind_update, _us._ids_2d, _us._run_stages
+    _run_on_worker, _next_side, _score_ws_pointer = _us._run_on_worker, _us._next_side, _us._score_ws_pointer
+    _score_stage, _append_tail, _fused_prepare = _us._score_stage, _us._append_tail, _us._fused_prepare
+    _stage_pre, _stage_passes, _stage_post = _us._stage_pre, _us._stage_passes, _us._stage_post
 
 
 def _option_of(config, key: str, allowed):

@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (88 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (89 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -64,7 +64,8 @@
  *                                       key re-rotated by its own row's delta (opt-in: video_position_gap)
  *   §S  "Budget re-scoring"             rtk_pivotkv_rescore_batched (+ _workspace_bytes): the stored scores of a budget's old
  *                                       rows blended with what the newest chunk's last queries see of them (opt-in:
- *                                       video_budget_rescore)
+ *                                       video_budget_rescore); rtk_pivotkv_rescore_fp8k_batched: the same over the e4m3
+ *                                       key rows of an fp8 archive (opt-in: archive_rescore)
  *   §T  "Question focus"                rtk_pivotkv_focus_gather_batched: the pinned rows, the video rows a question's queries
  *                                       choose and the question's rows of every layer gathered out of place into a small
  *                                       cache of their own (opt-in: PivotKVCache.watch_question / focus)
@@ -1279,10 +1280,35 @@ int rtk_pivotkv_rescore_batched(const rtk_rescore_unit* units, int n_units, int 
                                 float alpha, int64_t q_stride_h, int64_t q_stride_l, void* scratch, size_t scratch_stride,
                                 rtk_stream_t stream);
 
+/* rtk_pivotkv_rescore_fp8k_batched - the same rule over the e4m3 key rows of an fp8 archive (§K; opt-in:
+ * longvideo_kwargs["archive_rescore"] with "kv_cache_dtype"): K[g, j] = dtype(float(code) * scale), rule 5 of §K, where dtype
+ * is the queries' - RTK_BF16 or RTK_F16, with D == 128 only (no archive exists for anything else: RTK_EUNSUPPORTED before any
+ * launch).  The same three launches, key ranges and order of every sum as the matrix path above; the codes are dequantised
+ * where a key fragment is loaded, so the result equals, bit for bit, rtk_pivotkv_rescore_batched over rtk_fp8kv_dequant of
+ * the same codes and scales.  Rows at and behind n are not read, neither codes nor scales.  The scratch is that of
+ * rtk_pivotkv_rescore_workspace_bytes: it does not depend on the key format.  Scores taken on e4m3 keys are a different
+ * rule from scores taken on 16-bit keys; what that does to answer quality has not been evaluated.
+ * Errors, all before any launch: those of rtk_pivotkv_rescore_batched that apply, and RTK_EINVAL for a NULL k8 / k_scale of
+ * a live unit, k8_stride_h < n D, scale_stride_h < n, a k8 pointer or k8_stride_h that is not 16-byte aligned and a k_scale
+ * that is not 4-byte aligned. */
+typedef struct rtk_rescore_fp8k_unit {
+    const void*  q;              /* as rtk_rescore_unit */
+    const void*  k8;             /* codes of the first region row of kv head 0; row j of head g at k8 + g*k8_stride_h + j*D BYTES */
+    int64_t      k8_stride_h;    /* bytes between kv heads, >= n*D */
+    const float* k_scale;        /* scale of row j of head g at k_scale + g*scale_stride_h + j */
+    int64_t      scale_stride_h; /* floats, >= n */
+    float*       score;          /* [n] in / out */
+    int32_t      n;
+} rtk_rescore_fp8k_unit;
+int rtk_pivotkv_rescore_fp8k_batched(const rtk_rescore_fp8k_unit* units, int n_units, int Hq, int Hkv, int W, int D,
+                                     int dtype, float alpha, int64_t q_stride_h, int64_t q_stride_l, void* scratch,
+                                     size_t scratch_stride, rtk_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * §T  Question focus (opt-in: PivotKVCache.watch_question / PivotKVCache.focus; NOT in the reference, and a rule of this
  * project's own: what it does to answer quality has not been evaluated).  Once a question is known, the video rows it reads
- * are chosen by its own queries - rtk_pivotkv_rescore_batched with alpha = 1 into a zeroed score row, then
+ * are chosen by its own queries - rtk_pivotkv_rescore_batched (rtk_pivotkv_rescore_fp8k_batched over the archive of an fp8
+ * parent with archive_rescore) with alpha = 1 into a zeroed score row, then
  * rtk_pivotkv_budget_select_batched, both as they are - and moved, with the pinned rows in front of them and the question's
  * rows behind them, into a small cache of their own that the answer is decoded over.  The parent cache is only read.
  *

@@ -15,7 +15,16 @@ them; keep_rows 4 096 / 8 192 / 16 384, watch rows 16 / 64:
   index_select_K           the route the gather replaces: per layer and tensor torch.cat([head, index_select, tail]);
   decode_full / decode_K   ONE packed decode-attention call (rtk_attention_decode, one query row per head) over the full
                            pinned + n + question rows of a layer and over its focused rows: what the feature is for.
-One JSON document; a summary on stdout.  Needs the GPU: there is no other way to get a time."""
+One JSON document; a summary on stdout.  Needs the GPU: there is no other way to get a time.
+
+    python tools/bench_focus.py --fp8 [--out profiles/focus_fp8_bench.json] [--reps 15] [--warmup 3]
+
+An fp8 parent (kv_cache_dtype="fp8_e4m3" with archive_rescore=True) at the same geometry - the n region rows are the
+archive's, the pinned rows and the question lie in the 16-bit buffers:
+  focus_K_W                the whole `cache.focus(K)`: rtk_pivotkv_rescore_fp8k_batched, the selection and the gather of codes,
+                           scales, ids and 16-bit rows into an fp8 cache of its own;
+  decode_full / decode_K   ONE packed decode-attention call (rtk_attention_decode_fp8kv) over a layer's full archive and over
+                           the focused one, each in front of the layer's 16-bit rows."""
 from __future__ import annotations
 
 import argparse
@@ -66,6 +75,103 @@ def parent(dev, g):
     return cache
 
 
+def parent_fp8(dev, g):
+    """The same parent with fp8 rows: the N region rows in the archive (random rows quantised by the library's rule), the
+    pinned rows and the question in the 16-bit buffers."""
+    from retake.native_attention import fp8_quantize_rows
+
+    kw = {"compression_ratio": 0.25, "compression_method": "pivotkv", "pos_embed_reforge": True}
+    cfg = types.SimpleNamespace(hidden_size=Hq * D, num_hidden_layers=LAYERS, num_attention_heads=Hq, num_key_value_heads=Hkv,
+                                longvideo_kwargs={"kvcache_compression": True, "attention_kernel": "hip", "kv_cache_dtype": "fp8_e4m3",
+                                                  "archive_rescore": True, "decode_attention": "packed",
+                                                  "kvcache_compression_kwargs": kw})
+    cache = lc.build_kvcache(cfg)
+    cap = PINNED + QUESTION + 64
+    rows = torch.empty((1, Hkv, N, D), dtype=torch.bfloat16, device=dev)
+    for l in range(LAYERS):
+        st = cache._store(l)
+        st.k = torch.empty((1, Hkv, cap, D), dtype=torch.bfloat16, device=dev).normal_(0.0, 1.7, generator=g)
+        st.v = torch.empty((1, Hkv, cap, D), dtype=torch.bfloat16, device=dev).normal_(0.0, 1.0, generator=g)
+        st.k8, st.ks8 = fp8_quantize_rows(rows.normal_(0.0, 1.7, generator=g))
+        st.v8, st.vs8 = fp8_quantize_rows(rows.normal_(0.0, 1.0, generator=g))
+        st.pos = torch.arange(cap + N, device=dev).repeat(3, 1).contiguous()
+        st.pos_ndim, st.pinned, st.archive_at, st.len8 = 3, PINNED, PINNED, N
+        st.length, st.pos_len = PINNED, PINNED + N
+    cache._pos_layers = LAYERS
+    cache.num_evicted_tokens = [0] * LAYERS
+    cache.kvcache_compression = False
+    cache.last_compressed_mark = cache._take_mark(True)
+    for st in cache._layers:
+        st.length, st.pos_len = PINNED + QUESTION, PINNED + N + QUESTION
+    return cache
+
+
+def stat(xs):
+    q = statistics.quantiles(xs, n=4) if len(xs) > 1 else [xs[0]] * 3
+    return {"median_us": round(statistics.median(xs), 1), "q1_us": round(q[0], 1), "q3_us": round(q[2], 1), "samples": len(xs)}
+
+
+def main_fp8(args):
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(7)
+    cache = parent_fp8(dev, g)
+    queries = [(1.7 * torch.randn((Hq, max(WS), D), generator=g, device=dev)).bfloat16() for _ in range(LAYERS)]
+    q1 = (1.7 * torch.randn((1, Hq, 1, D), generator=g, device=dev)).bfloat16()
+    ws, route = {}, []
+    arm(cache, max(WS), queries)
+    small = {K: cache.focus(K) for K in KEEPS}         # the caches the focused decode calls read
+
+    def run_decode(K):
+        c = cache if K == 0 else small[K]
+        st = c._layers[0]
+        out = chunk_attention(q1, st.k[:, :, :st.length], st.v[:, :, :st.length], workspace=ws, archive=c.archive(0), packed_gqa=True,
+                              route=route)
+        assert out is not None
+
+    run_decode(0)
+    assert route == ["packed"], route
+    names = [("decode_full", 0)] + [(f"decode_{K}", K) for K in KEEPS]
+    focus_names = [(f"focus_{K}_W{W}", (K, W)) for W in WS for K in KEEPS]
+    samples = {name: [] for name, _ in names + focus_names}
+
+    def timed(name, fn, arg, keep):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn(arg)
+        e1.record()
+        e1.synchronize()
+        if keep:
+            samples[name].append(e0.elapsed_time(e1) * 1e3)
+        del out
+
+    for rep in range(args.warmup + args.reps):
+        for name, K in names:                        # interleaved
+            timed(name, run_decode, K, rep >= args.warmup)
+        for W in WS:
+            arm(cache, W, queries)
+            for name, (K, w) in focus_names:
+                if w == W:
+                    timed(name, lambda a: cache.focus(a[0]), (K, W), rep >= args.warmup)
+    report = {"device": torch.cuda.get_device_name(0),
+              "geometry": {"layers": LAYERS, "Hq": Hq, "Hkv": Hkv, "D": D, "dtype": "bf16", "kv_cache_dtype": "fp8_e4m3", "n": N,
+                           "pinned": PINNED, "question": QUESTION, "keep_rows": list(KEEPS), "watch_rows": list(WS)},
+              "method": f"one process, HIP events, interleaved, median and quartiles of {args.reps} after {args.warmup} warm-up "
+                        "rounds; focus_* includes the host work and the allocations of the new cache"}
+    for name in samples:
+        report[name] = stat(samples[name])
+    for K in KEEPS:
+        report[f"decode_{K}"]["full_over_focused"] = round(report["decode_full"]["median_us"] / report[f"decode_{K}"]["median_us"], 2)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(report, f, indent=1)
+        f.write("\n")
+    for name in samples:
+        print(f"{name}: {report[name]['median_us']:.0f} us (quartiles {report[name]['q1_us']:.0f} .. {report[name]['q3_us']:.0f})")
+    for K in KEEPS:
+        print(f"decode over the full archive {report[f'decode_{K}']['full_over_focused']:.1f} x the call over {K} focused rows")
+    print("wrote", args.out)
+
+
 def arm(cache, W, queries):
     cache.watch_question(W)
     for l in range(LAYERS):
@@ -77,9 +183,14 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "focus_bench.json"))
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--fp8", action="store_true", help="an fp8 parent (archive_rescore): the whole focus and the decode calls")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_focus.py measures on the GPU; none is visible (Time: not measured)")
+    if args.fp8:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "focus_fp8_bench.json")
+        return main_fp8(args)
     dev = torch.device("cuda:0")
     stream = nv.stream()
     g = torch.Generator(device=dev).manual_seed(7)
@@ -190,10 +301,6 @@ def main():
             for name, (K, w) in focus_names:
                 if w == W:
                     timed(name, run_focus, (K, W), rep >= args.warmup)
-
-    def stat(xs):
-        q = statistics.quantiles(xs, n=4) if len(xs) > 1 else [xs[0]] * 3
-        return {"median_us": round(statistics.median(xs), 1), "q1_us": round(q[0], 1), "q3_us": round(q[2], 1), "samples": len(xs)}
 
     report = {"device": torch.cuda.get_device_name(0),
               "geometry": {"layers": LAYERS, "Hq": Hq, "Hkv": Hkv, "D": D, "dtype": "bf16", "n": N, "pinned": PINNED,

@@ -22,8 +22,13 @@
 //                         groups in order, the blend written straight into score[j]
 // Arithmetic: exact products of the 16-bit operands, fp32 accumulation, softmax and sums.  fp32 payloads or head_dim != 128:
 // the *_generic kernels (plain FMA, natural exp, dot / sqrt(D)) over the same key ranges and the same merge: the parity path.
+// rtk_pivotkv_rescore_fp8k_batched (longvideo_kwargs["archive_rescore"]): the same three launches over the e4m3 archive's
+// key rows - the two MFMA kernels take their key source as a template argument (Keys16 / KeysFp8), and the only device code
+// that differs is the fragment load, which dequantises the codes (rule 5 of the fp8 rows) into the registers the 16-bit load
+// fills from the dequantised row.  Hence: the bits of the 16-bit call on the dequantised rows.
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 
 #include "score_thin.cuh"
 
@@ -51,6 +56,38 @@ struct RescoreDev {
 };
 struct RescoreUnits {
     RescoreDev u[RS_MAX_UNITS];
+};
+// the same unit over e4m3 archive rows (rtk_pivotkv_rescore_fp8k_batched): a struct of its own, so that the 16-bit kernels'
+// argument - and with it their code - stays what it was
+struct RescoreFp8kDev {
+    const char* q;
+    const char* k8;    // codes of row 0 of kv head 0
+    int64_t ksh;       // BYTES between kv heads
+    const float* ks;   // scale of row 0 of kv head 0
+    int64_t ssh;       // FLOATS between kv heads
+    float* score;
+    float* lse;
+    float2* part;
+    int32_t n, pad;
+};
+struct RescoreFp8kUnits {
+    RescoreFp8kDev u[RS_MAX_UNITS];
+};
+
+// Where the MFMA kernels' keys come from: the launch's argument and this lane's fragment of key j0 + (lane & 31) of kv group g
+struct Keys16 {
+    using Units = RescoreUnits;
+    template <bool F16>
+    static __device__ __forceinline__ void load(u32x4* f, const RescoreDev& un, int g, int j0, int n, int lane) {
+        load_key_frag(f, un.k + (int64_t)g * un.ksh, j0, n, lane);
+    }
+};
+struct KeysFp8 {   // dequantised to the queries' dtype (rule 5 of the fp8 rows): the registers Keys16 loads from the dequantised rows
+    using Units = RescoreFp8kUnits;
+    template <bool F16>
+    static __device__ __forceinline__ void load(u32x4* f, const RescoreFp8kDev& un, int g, int j0, int n, int lane) {
+        load_key_frag_fp8<F16 ? RTK_F16 : RTK_BF16>(f, un.k8 + (int64_t)g * un.ksh, un.ks + (int64_t)g * un.ssh, j0, n, lane);
+    }
 };
 
 __device__ __forceinline__ int ranges_of(int n) { return (n + RS_KEYS - 1) / RS_KEYS; }
@@ -82,12 +119,12 @@ __device__ __forceinline__ void lse_block(const u32x4 (&kf)[RS_NKB][8], const u3
     for (int kb = 0; kb < RS_NKB; ++kb) lse_step<F16, MASKED>(kf[kb], qf, c2, kb * 32, left, hf, m, sum);
 }
 
-template <bool F16>
-__global__ __launch_bounds__(RS_THREADS) void rescore_lse_kernel(RescoreUnits us, int G, int W, int64_t qsh, int64_t qpitch,
+template <bool F16, class KS = Keys16>
+__global__ __launch_bounds__(RS_THREADS) void rescore_lse_kernel(typename KS::Units us, int G, int W, int64_t qsh, int64_t qpitch,
                                                                int RB, float c2) {
     extern __shared__ __attribute__((aligned(16))) char rs_smem[];
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE, hf = lane >> 5, row = lane & 31;
-    const RescoreDev& un = us.u[blockIdx.z];
+    const auto& un = us.u[blockIdx.z];
     const int kr = blockIdx.x, g = blockIdx.y, n = un.n;
     if (kr * RS_KEYS >= n) return;   // (uniform: the grid is sized for the launch's largest unit)
     const int QBn = min(RB, RS_QB);
@@ -95,10 +132,9 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_lse_kernel(RescoreUnits us
     float2* red = (float2*)(rs_smem + (size_t)QBn * RS_BLOCK_BYTES);   // [RS_WAVES][QBn][32]
     const int j0 = kr * RS_KEYS + wid * (RS_NKB * 32);
     const bool full = j0 + RS_NKB * 32 <= n;   // (wave-uniform)
-    const char* kg = un.k + (int64_t)g * un.ksh;
     u32x4 kf[RS_NKB][8];
 #pragma unroll
-    for (int kb = 0; kb < RS_NKB; ++kb) load_key_frag(kf[kb], kg, j0 + kb * 32, n, lane);
+    for (int kb = 0; kb < RS_NKB; ++kb) KS::template load<F16>(kf[kb], un, g, j0 + kb * 32, n, lane);
     float2* part = un.part + ((size_t)g * ranges_of(n) + kr) * ((size_t)RB * 32);
     for (int rb0 = 0; rb0 < RB; rb0 += RS_QB) {
         const int nb = min(RS_QB, RB - rb0);
@@ -121,9 +157,9 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_lse_kernel(RescoreUnits us
 }
 
 // lse[g][r] of every packed row: the key ranges' (max, sum) in range order.  BASE2: the MFMA path's log2 domain
-template <bool BASE2>
-__global__ __launch_bounds__(256) void rescore_merge_kernel(RescoreUnits us, int Hkv, int rows_pad, int nrows) {
-    const RescoreDev& un = us.u[blockIdx.y];
+template <bool BASE2, class Units = RescoreUnits>
+__global__ __launch_bounds__(256) void rescore_merge_kernel(Units us, int Hkv, int rows_pad, int nrows) {
+    const auto& un = us.u[blockIdx.y];
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= Hkv * rows_pad) return;
     const int g = e / rows_pad, r = e - g * rows_pad, KR = ranges_of(un.n);
@@ -137,12 +173,12 @@ __device__ __forceinline__ float blend(float old, float tot, float fac, float al
     return fmaf(alpha, __fmul_rn(tot, fac), __fmul_rn(__fsub_rn(1.f, alpha), old));
 }
 
-template <bool F16>
-__global__ __launch_bounds__(RS_THREADS) void rescore_col_kernel(RescoreUnits us, int Hkv, int G, int W, int64_t qsh,
+template <bool F16, class KS = Keys16>
+__global__ __launch_bounds__(RS_THREADS) void rescore_col_kernel(typename KS::Units us, int Hkv, int G, int W, int64_t qsh,
                                                                int64_t qpitch, int RB, float c2, float alpha) {
     extern __shared__ __attribute__((aligned(16))) char rs_smem[];
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid / WAVE, hf = lane >> 5;
-    const RescoreDev& un = us.u[blockIdx.y];
+    const auto& un = us.u[blockIdx.y];
     const int kr = blockIdx.x, n = un.n;
     if (kr * RS_KEYS >= n) return;   // (uniform)
     u32x4* lq = (u32x4*)rs_smem;
@@ -154,7 +190,7 @@ __global__ __launch_bounds__(RS_THREADS) void rescore_col_kernel(RescoreUnits us
     for (int g = 0; g < Hkv; ++g) {
         u32x4 kf[RS_NKB][8];
 #pragma unroll
-        for (int kb = 0; kb < RS_NKB; ++kb) load_key_frag(kf[kb], un.k + (int64_t)g * un.ksh, j0 + kb * 32, n, lane);
+        for (int kb = 0; kb < RS_NKB; ++kb) KS::template load<F16>(kf[kb], un, g, j0 + kb * 32, n, lane);
         const float* lg = un.lse + (size_t)g * RB * 32;
         float col[RS_NKB];
 #pragma unroll
@@ -255,6 +291,111 @@ inline bool rescore_plan(RescorePlan& p, int Hq, int Hkv, int W, int D, int dtyp
     return true;
 }
 
+// What both entries do around their units' keys: the checks in front of every launch (check_keys(u, i, plan, es): the unit's
+// own pointers and strides), the scratch, the LDS opt-in and the launches.  KS: where the MFMA kernels' keys come from;
+// fill_keys(u, slot) writes a unit's key pointers into its slot.  The generic pair reads 16-bit or fp32 rows only
+template <class KS, class Unit, class CheckKeys, class FillKeys>
+int rescore_run(const char* who, const Unit* units, int n_units, int Hq, int Hkv, int W, int D, int dtype, float alpha,
+                int64_t q_stride_h, int64_t q_stride_l, void* scratch, size_t scratch_stride, hipStream_t st, CheckKeys&& check_keys,
+                FillKeys&& fill_keys) {
+    using Units = typename KS::Units;
+    constexpr bool GENERIC = std::is_same<KS, Keys16>::value;   // (the parity path exists for 16-bit / fp32 rows)
+    RTK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0 && D >= 1, "%s: bad shape (Hq %d, Hkv %d, D %d)", who, Hq, Hkv, D);
+    RTK_CHECK_ARG(W >= 1, "%s: W %d", who, W);
+    RTK_CHECK_ARG(alpha > 0.f && alpha <= 1.f, "%s: alpha %g is not in (0, 1]", who, (double)alpha);   // (a NaN fails too)
+    if (!payload_dtype(dtype)) {
+        set_error("%s: payloads are RTK_F32 / RTK_BF16 / RTK_F16, got %d", who, dtype);
+        return RTK_EUNSUPPORTED;
+    }
+    if (!GENERIC && !thin_mfma_path(dtype, D)) {
+        set_error("%s: e4m3 keys are dequantised to RTK_BF16 / RTK_F16 rows of head_dim %d, got dtype %d, D %d", who, HD, dtype, D);
+        return RTK_EUNSUPPORTED;
+    }
+    RescorePlan p;
+    RTK_CHECK_ARG(rescore_plan(p, Hq, Hkv, W, D, dtype), "%s: %d query rows per kv group are beyond the plan", who, (Hq / Hkv) * W);
+    const int64_t es = dtype == RTK_F32 ? 4 : 2;
+    RTK_CHECK_ARG(q_stride_h >= D && q_stride_l >= D, "%s: query strides (%lld, %lld) below D", who, (long long)q_stride_h,
+                  (long long)q_stride_l);
+    RTK_CHECK_ARG(!p.mfma || ((q_stride_h * es) % 16 == 0 && (q_stride_l * es) % 16 == 0),
+                  "%s: query rows must be 16-byte aligned", who);
+    RTK_CHECK_ARG(scratch && ((uintptr_t)scratch & 255) == 0 && scratch_stride % 256 == 0,
+                  "%s: scratch must be 256-byte aligned, units a multiple of 256 bytes apart", who);
+    int n_max = 0;
+    for (int i = 0; i < n_units; ++i) {
+        const Unit& u = units[i];
+        RTK_CHECK_ARG(u.n >= 0 && u.n <= RS_MAX_N, "%s: unit %d: n %d (0 .. %d)", who, i, u.n, RS_MAX_N);
+        if (u.n == 0) continue;
+        const int rc = check_keys(u, i, p, es);
+        if (rc != RTK_OK) return rc;
+        RTK_CHECK_ARG(scratch_stride >= p.bytes(u.n), "%s: unit %d: scratch stride %zu < %zu bytes for n %d", who, i,
+                      scratch_stride, p.bytes(u.n), u.n);
+        n_max = std::max(n_max, u.n);
+    }
+    if (n_max == 0) return RTK_OK;
+    const int QBn = std::min(p.RB, RS_QB);
+    const size_t lds1 = (size_t)QBn * RS_BLOCK_BYTES + (size_t)RS_WAVES * QBn * 32 * sizeof(float2), lds2 = (size_t)QBn * RS_BLOCK_BYTES;
+    if (p.mfma && lds1 > 48 * 1024) {   // opt in to the large dynamic LDS window, once per device (and per key source)
+        static std::atomic<uint64_t> opted{0};
+        int dev_id = 0;
+        (void)hipGetDevice(&dev_id);
+        const uint64_t bit = 1ull << (dev_id & 63);
+        if (!(opted.load(std::memory_order_relaxed) & bit)) {
+            constexpr int MOST = RS_QB * RS_BLOCK_BYTES + RS_WAVES * RS_QB * 32 * (int)sizeof(float2);
+            (void)hipFuncSetAttribute((const void*)rescore_lse_kernel<false, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, MOST);
+            (void)hipFuncSetAttribute((const void*)rescore_lse_kernel<true, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, MOST);
+            (void)hipFuncSetAttribute((const void*)rescore_col_kernel<false, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, MOST);
+            (void)hipFuncSetAttribute((const void*)rescore_col_kernel<true, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, MOST);
+            opted.fetch_or(bit, std::memory_order_relaxed);
+        }
+    }
+    const int64_t qsh = q_stride_h * es, qpitch = q_stride_l * es;
+    const float c2 = logit_scale2(D);
+    int most = 0;   // of the launch being filled: its largest unit's rows
+    return launch_units<Units>(
+        n_units,
+        [&](int i, auto& dv) {
+            const Unit& u = units[i];
+            if (u.n == 0) return false;
+            char* ws = (char*)scratch + (size_t)i * scratch_stride;
+            dv.q = (const char*)u.q;
+            fill_keys(u, dv, es);
+            dv.score = u.score;
+            dv.lse = (float*)ws;
+            dv.part = (float2*)(ws + p.lse_bytes);
+            dv.n = u.n;
+            dv.pad = 0;
+            most = std::max(most, u.n);
+            return true;
+        },
+        [&](const Units& ru, int n) -> int {
+            const int KR = (most + RS_KEYS - 1) / RS_KEYS;
+            const dim3 gm((Hkv * p.rows_pad + 255) / 256, n);
+            if (p.mfma) {
+                with_f16(dtype, [&](auto f16) {
+                    constexpr bool F16 = decltype(f16)::value;
+                    RTK_LAUNCH(KID_PASS1, (rescore_lse_kernel<F16, KS>), dim3(KR, Hkv, n), dim3(RS_THREADS), lds1, st, ru, p.G, W,
+                               qsh, qpitch, p.RB, c2);
+                    RTK_LAUNCH(KID_PASS1, (rescore_merge_kernel<true, Units>), gm, dim3(256), 0, st, ru, Hkv, p.rows_pad, p.nrows);
+                    RTK_LAUNCH(KID_PASS2, (rescore_col_kernel<F16, KS>), dim3(KR, n), dim3(RS_THREADS), lds2, st, ru, Hkv, p.G, W,
+                               qsh, qpitch, p.RB, c2, alpha);
+                });
+            } else if constexpr (GENERIC) {
+                with_payload(dtype, [&](auto dt) {
+                    constexpr int DT = decltype(dt)::value;
+                    RTK_LAUNCH(KID_PASS1, rescore_lse_generic<DT>, dim3(KR, Hq * W, n), dim3(256), D * sizeof(float), st, ru, p.G,
+                               W, D, qsh, qpitch);
+                    RTK_LAUNCH(KID_PASS1, rescore_merge_kernel<false>, gm, dim3(256), 0, st, ru, Hkv, p.rows_pad, p.nrows);
+                    RTK_LAUNCH(KID_PASS2, rescore_col_generic<DT>, dim3((most + 255) / 256, n), dim3(256), D * sizeof(float), st,
+                               ru, Hkv, p.G, W, D, qsh, qpitch, alpha);
+                    return 0;
+                });
+            }
+            RTK_LAUNCH_CHECK(who);
+            most = 0;
+            return RTK_OK;
+        });
+}
+
 }  // namespace
 }  // namespace rtk
 
@@ -272,99 +413,45 @@ extern "C" int rtk_pivotkv_rescore_batched(const rtk_rescore_unit* units, int n_
     const char* who = "rtk_pivotkv_rescore_batched";
     const int rc = have_units(units, n_units, who);
     if (rc <= 0) return rc;
-    RTK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && Hq % Hkv == 0 && D >= 1, "%s: bad shape (Hq %d, Hkv %d, D %d)", who, Hq, Hkv, D);
-    RTK_CHECK_ARG(W >= 1, "%s: W %d", who, W);
-    RTK_CHECK_ARG(alpha > 0.f && alpha <= 1.f, "%s: alpha %g is not in (0, 1]", who, (double)alpha);   // (a NaN fails too)
-    if (!payload_dtype(dtype)) {
-        set_error("%s: payloads are RTK_F32 / RTK_BF16 / RTK_F16, got %d", who, dtype);
-        return RTK_EUNSUPPORTED;
-    }
-    RescorePlan p;
-    RTK_CHECK_ARG(rescore_plan(p, Hq, Hkv, W, D, dtype), "%s: %d query rows per kv group are beyond the plan", who, (Hq / Hkv) * W);
-    const int64_t es = dtype == RTK_F32 ? 4 : 2;
-    RTK_CHECK_ARG(q_stride_h >= D && q_stride_l >= D, "%s: query strides (%lld, %lld) below D", who, (long long)q_stride_h,
-                  (long long)q_stride_l);
-    RTK_CHECK_ARG(!p.mfma || ((q_stride_h * es) % 16 == 0 && (q_stride_l * es) % 16 == 0),
-                  "%s: query rows must be 16-byte aligned", who);
-    RTK_CHECK_ARG(scratch && ((uintptr_t)scratch & 255) == 0 && scratch_stride % 256 == 0,
-                  "%s: scratch must be 256-byte aligned, units a multiple of 256 bytes apart", who);
-    int n_max = 0;
-    for (int i = 0; i < n_units; ++i) {
-        const rtk_rescore_unit& u = units[i];
-        RTK_CHECK_ARG(u.n >= 0 && u.n <= RS_MAX_N, "%s: unit %d: n %d (0 .. %d)", who, i, u.n, RS_MAX_N);
-        if (u.n == 0) continue;
-        RTK_CHECK_ARG(u.q && u.k && u.score, "%s: unit %d: NULL q / k / score", who, i);
-        RTK_CHECK_ARG(((uintptr_t)u.score & 3) == 0, "%s: unit %d: score is not 4-byte aligned", who, i);
-        RTK_CHECK_ARG(u.k_stride_h >= (int64_t)u.n * D, "%s: unit %d: k_stride_h %lld < n D", who, i, (long long)u.k_stride_h);
-        RTK_CHECK_ARG(!p.mfma || (((uintptr_t)u.q & 15) == 0 && ((uintptr_t)u.k & 15) == 0 && (u.k_stride_h * es) % 16 == 0),
-                      "%s: unit %d: q / k / k_stride_h must be 16-byte aligned", who, i);
-        RTK_CHECK_ARG(scratch_stride >= p.bytes(u.n), "%s: unit %d: scratch stride %zu < %zu bytes for n %d", who, i,
-                      scratch_stride, p.bytes(u.n), u.n);
-        n_max = std::max(n_max, u.n);
-    }
-    if (n_max == 0) return RTK_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int QBn = std::min(p.RB, RS_QB);
-    const size_t lds1 = (size_t)QBn * RS_BLOCK_BYTES + (size_t)RS_WAVES * QBn * 32 * sizeof(float2), lds2 = (size_t)QBn * RS_BLOCK_BYTES;
-    if (p.mfma && lds1 > 48 * 1024) {   // opt in to the large dynamic LDS window, once per device
-        static std::atomic<uint64_t> opted{0};
-        int dev_id = 0;
-        (void)hipGetDevice(&dev_id);
-        const uint64_t bit = 1ull << (dev_id & 63);
-        if (!(opted.load(std::memory_order_relaxed) & bit)) {
-            constexpr int MOST = RS_QB * RS_BLOCK_BYTES + RS_WAVES * RS_QB * 32 * (int)sizeof(float2);
-            (void)hipFuncSetAttribute((const void*)rescore_lse_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MOST);
-            (void)hipFuncSetAttribute((const void*)rescore_lse_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MOST);
-            (void)hipFuncSetAttribute((const void*)rescore_col_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, MOST);
-            (void)hipFuncSetAttribute((const void*)rescore_col_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, MOST);
-            opted.fetch_or(bit, std::memory_order_relaxed);
-        }
-    }
-    const int64_t qsh = q_stride_h * es, qpitch = q_stride_l * es;
-    const float c2 = logit_scale2(D);
-    int most = 0;   // of the launch being filled: its largest unit's rows
-    return launch_units<RescoreUnits>(
-        n_units,
-        [&](int i, RescoreDev& dv) {
-            const rtk_rescore_unit& u = units[i];
-            if (u.n == 0) return false;
-            char* ws = (char*)scratch + (size_t)i * scratch_stride;
-            dv.q = (const char*)u.q;
+    return rescore_run<Keys16>(
+        who, units, n_units, Hq, Hkv, W, D, dtype, alpha, q_stride_h, q_stride_l, scratch, scratch_stride, (hipStream_t)stream,
+        [&](const rtk_rescore_unit& u, int i, const RescorePlan& p, int64_t es) -> int {
+            RTK_CHECK_ARG(u.q && u.k && u.score, "%s: unit %d: NULL q / k / score", who, i);
+            RTK_CHECK_ARG(((uintptr_t)u.score & 3) == 0, "%s: unit %d: score is not 4-byte aligned", who, i);
+            RTK_CHECK_ARG(u.k_stride_h >= (int64_t)u.n * D, "%s: unit %d: k_stride_h %lld < n D", who, i, (long long)u.k_stride_h);
+            RTK_CHECK_ARG(!p.mfma || (((uintptr_t)u.q & 15) == 0 && ((uintptr_t)u.k & 15) == 0 && (u.k_stride_h * es) % 16 == 0),
+                          "%s: unit %d: q / k / k_stride_h must be 16-byte aligned", who, i);
+            return RTK_OK;
+        },
+        [](const rtk_rescore_unit& u, RescoreDev& dv, int64_t es) {
             dv.k = (const char*)u.k;
             dv.ksh = u.k_stride_h * es;
-            dv.score = u.score;
-            dv.lse = (float*)ws;
-            dv.part = (float2*)(ws + p.lse_bytes);
-            dv.n = u.n;
-            dv.pad = 0;
-            most = std::max(most, u.n);
-            return true;
-        },
-        [&](const RescoreUnits& ru, int n) -> int {
-            const int KR = (most + RS_KEYS - 1) / RS_KEYS;
-            const dim3 gm((Hkv * p.rows_pad + 255) / 256, n);
-            if (p.mfma) {
-                with_f16(dtype, [&](auto f16) {
-                    constexpr bool F16 = decltype(f16)::value;
-                    RTK_LAUNCH(KID_PASS1, rescore_lse_kernel<F16>, dim3(KR, Hkv, n), dim3(RS_THREADS), lds1, st, ru, p.G, W, qsh,
-                               qpitch, p.RB, c2);
-                    RTK_LAUNCH(KID_PASS1, rescore_merge_kernel<true>, gm, dim3(256), 0, st, ru, Hkv, p.rows_pad, p.nrows);
-                    RTK_LAUNCH(KID_PASS2, rescore_col_kernel<F16>, dim3(KR, n), dim3(RS_THREADS), lds2, st, ru, Hkv, p.G, W, qsh,
-                               qpitch, p.RB, c2, alpha);
-                });
-            } else {
-                with_payload(dtype, [&](auto dt) {
-                    constexpr int DT = decltype(dt)::value;
-                    RTK_LAUNCH(KID_PASS1, rescore_lse_generic<DT>, dim3(KR, Hq * W, n), dim3(256), D * sizeof(float), st, ru, p.G,
-                               W, D, qsh, qpitch);
-                    RTK_LAUNCH(KID_PASS1, rescore_merge_kernel<false>, gm, dim3(256), 0, st, ru, Hkv, p.rows_pad, p.nrows);
-                    RTK_LAUNCH(KID_PASS2, rescore_col_generic<DT>, dim3((most + 255) / 256, n), dim3(256), D * sizeof(float), st,
-                               ru, Hkv, p.G, W, D, qsh, qpitch, alpha);
-                    return 0;
-                });
-            }
-            RTK_LAUNCH_CHECK(who);
-            most = 0;
+        });
+}
+
+extern "C" int rtk_pivotkv_rescore_fp8k_batched(const rtk_rescore_fp8k_unit* units, int n_units, int Hq, int Hkv, int W, int D,
+                                                int dtype, float alpha, int64_t q_stride_h, int64_t q_stride_l, void* scratch,
+                                                size_t scratch_stride, rtk_stream_t stream) {
+    const char* who = "rtk_pivotkv_rescore_fp8k_batched";
+    const int rc = have_units(units, n_units, who);
+    if (rc <= 0) return rc;
+    return rescore_run<KeysFp8>(
+        who, units, n_units, Hq, Hkv, W, D, dtype, alpha, q_stride_h, q_stride_l, scratch, scratch_stride, (hipStream_t)stream,
+        [&](const rtk_rescore_fp8k_unit& u, int i, const RescorePlan&, int64_t) -> int {
+            RTK_CHECK_ARG(u.q && u.k8 && u.k_scale && u.score, "%s: unit %d: NULL q / k8 / k_scale / score", who, i);
+            RTK_CHECK_ARG(((uintptr_t)u.score & 3) == 0, "%s: unit %d: score is not 4-byte aligned", who, i);
+            RTK_CHECK_ARG(u.k8_stride_h >= (int64_t)u.n * D, "%s: unit %d: k8_stride_h %lld < n D", who, i, (long long)u.k8_stride_h);
+            RTK_CHECK_ARG(u.scale_stride_h >= (int64_t)u.n, "%s: unit %d: scale_stride_h %lld < n", who, i,
+                          (long long)u.scale_stride_h);
+            RTK_CHECK_ARG(((uintptr_t)u.q & 15) == 0 && ((uintptr_t)u.k8 & 15) == 0 && u.k8_stride_h % 16 == 0,
+                          "%s: unit %d: q / k8 / k8_stride_h must be 16-byte aligned", who, i);
+            RTK_CHECK_ARG(((uintptr_t)u.k_scale & 3) == 0, "%s: unit %d: k_scale is not 4-byte aligned", who, i);
             return RTK_OK;
+        },
+        [](const rtk_rescore_fp8k_unit& u, RescoreFp8kDev& dv, int64_t) {
+            dv.k8 = (const char*)u.k8;
+            dv.ksh = u.k8_stride_h;
+            dv.ks = u.k_scale;
+            dv.ssh = u.scale_stride_h;
         });
 }

@@ -2,14 +2,15 @@
 // mask, which is what prompt-guided scoring (pivotkv_score_prompt.hip) and the budget's re-scoring (pivotkv_rescore.hip, and
 // through it the question-focused cache) compute.  The kernels differ - prompt streams keys past resident query rows, the
 // re-scoring keeps keys in registers and splits them into ranges - and stay in their files; what they share is written here
-// once: the fragment loads, the packed-row numbering, the base-2 online (max, sum) of a 32-key block, the in-order merges
-// with their -inf guards, the generic (parity) path's dot, range softmax and column loop, and the host's path predicates.
+// once: the fragment loads (of 16-bit rows, and of e4m3 archive rows dequantised on the way), the packed-row numbering, the
+// base-2 online (max, sum) of a 32-key block, the in-order merges with their -inf guards, the generic (parity) path's dot, range softmax and column loop, and the host's path predicates.
 // Device and host helpers only, no kernels.  Every sum, product and rounding below is in an order the results are pinned to,
 // bit for bit: exp2(fsub(fmul(acc, c2), .)) stays an fmul and an fsub (colsum_block of score_mfma.cuh contracts them to an
 // fma; these kernels do not), merges run in index order.
 #pragma once
 #include <cmath>
 
+#include "fp8kv.cuh"
 #include "score_layout.cuh"
 
 namespace rtk {
@@ -33,6 +34,24 @@ __device__ __forceinline__ void load_key_frag(u32x4* f, const char* kg, int j0, 
     const int j = j0 + (lane & 31);
     const bool ok = j < n;
     load_frag(f, (const u32x4*)(kg + (size_t)(ok ? j : 0) * (HD * 2)), ok, lane >> 5);
+}
+// The same fragment of a group's e4m3 rows (fp8kv.cuh): codes [n, 128] BYTES at kg, one scale per row at sg.  Chunk c of the
+// 16-bit row is the 8 codes at byte 8 c, dequantised by rule 5 to DT - the registers load_key_frag fills from the dequantised
+// row.  Keys >= n are not read, neither codes nor scales
+template <int DT>
+__device__ __forceinline__ void load_key_frag_fp8(u32x4* f, const char* kg, const float* sg, int j0, int n, int lane) {
+    const int j = j0 + (lane & 31), hf = lane >> 5;
+    const bool ok = j < n;
+    const uint2* p = (const uint2*)(kg + (size_t)(ok ? j : 0) * HD);
+    const float s = ok ? sg[j] : 1.f;
+#pragma unroll
+    for (int x = 0; x < 8; ++x) {
+        const uint2 c = ok ? p[2 * x + hf] : uint2{0, 0};   // (code 0 is +0 at any scale: the zeros of load_frag)
+        uint32_t w0, w1, w2, w3;
+        fp8_dequant4<DT>(c.x, s, w0, w1);
+        fp8_dequant4<DT>(c.y, s, w2, w3);
+        f[x] = u32x4{w0, w1, w2, w3};
+    }
 }
 // Packed row r = hh * rows + i of kv group g is row i of head g G + hh of q (byte strides qsh, qpitch); the G * rows rows of a
 // group are cut into 32-row blocks.  false: r pads the last block (p is then a row that exists, and is not to be read)

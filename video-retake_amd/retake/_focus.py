@@ -23,7 +23,16 @@ rtk_pivotkv_budget_select_batched - both as they are: one re-scoring call per de
 per device.  Then ONE rtk_pivotkv_focus_gather_batched call per device moves, out of place, K, V and ids of every layer:
 rows [0, first), rows first + idx[.], rows [ve, length) - the question and whatever was decoded - into the new cache's
 buffers.  K bits, V bits and ids are unchanged: keys stay rotated at their ids, and holes in the ids are what the budget
-already leaves.  The parent is only read: lengths, counters, marks, branches, scores and `video_end` stay valid."""
+already leaves.  The parent is only read: lengths, counters, marks, branches, scores and `video_end` stay valid.
+
+An fp8 parent (kv_cache_dtype="fp8_e4m3") is served with longvideo_kwargs["archive_rescore"] = True; the focused cache is
+then an fp8 cache itself.  A layer's region is its archive: first = archive_at, n = len8 as recorded at `video_end`, and
+K[g, j] = dtype(float(code) * scale) of the archive's key rows (rtk_pivotkv_rescore_fp8k_batched: the codes are dequantised
+where the kernel loads a key - scores taken on e4m3 keys are another rule than scores taken on 16-bit keys, and what that
+does to answer quality has not been evaluated).  The same gather call moves more streams per layer: the codes of K and V
+(row bytes D) and their scales (row bytes 4) as archive rows idx[.] into an archive reserved for exactly `keep` rows, the ids
+as rows [0, archive_at), archive_at + idx[.], [archive_at + len8, pos_len), and ALL the layer's 16-bit rows - the pinned
+rows and whatever lies behind `video_end` - as they lie (head rows of a unit that gathers nothing)."""
 import torch
 
 from . import _native as nv
@@ -110,8 +119,9 @@ def watched_bytes(cache) -> int:
 
 def _plan(cache, w, keep_rows):
     """[(layer, store, first, ve, n, keep, tail, ids, Q, Wc)] of the layers that own rows - ValueError for what cannot be
-    focused, before anything is launched."""
-    who = "PivotKVCache.focus"
+    focused, before anything is launched.  With fp8 rows the region is the archive: first = archive_at, n = len8, and `tail`
+    counts the 16-bit rows behind `video_end`."""
+    who, fp8 = "PivotKVCache.focus", cache.kv_cache_dtype is not None
     ve = cache.video_end
     if ve is None or ve.serial != w.mark.serial or cache._mark_is_dead(ve.serial) or ve.epoch != cache._epoch \
             or cache._flushes != ve.flushes or cache._compressed_in_forward or len(cache._layers) != ve.n_layers:
@@ -122,16 +132,16 @@ def _plan(cache, w, keep_rows):
     for l, (st, m) in enumerate(zip(cache._layers, ve.layers)):
         if st._k is None:
             continue
-        first, length = st.pinned, st.c.length
-        n, tail = m.length - first, length - m.length
-        if first < 0 or n < 1 or not m.has_kv:
+        first, length = (st.archive_at if fp8 else st.pinned), st.c.length
+        n, tail = (m.len8 if fp8 else m.length - first), length - m.length
+        if first < 0 or n < 1 or not m.has_kv or (fp8 and (st.k8 is None or st.len8 != n or first > m.length)):
             raise ValueError(f"{who}: layer {l} holds no video rows behind its pinned rows")
         if tail < 1:
             raise ValueError(f"{who}: nothing lies behind `video_end` in layer {l} - feed the question first")
         ids = st._pos is not None and st.c.pos_len > 0
-        if st.c.cap == 0 or (ids and st.c.pos_len != length):
+        if st.c.cap == 0 or (ids and st.c.pos_len != length + st.len8):
             raise ValueError(f"{who}: layer {l} cannot be focused - its buffers are not the cache's own dense blocks, or it "
-                             f"keeps ids for {st.c.pos_len} of its {length} rows")
+                             f"keeps ids for {st.c.pos_len} of its {length + st.len8} rows")
         Q, k = w.q.get(l), st._k
         if Q is None:
             raise ValueError(f"{who}: layer {l} has rows behind `video_end` but no watched queries - the question did not "
@@ -156,8 +166,9 @@ def focus(cache, keep_rows: int, reserve_tokens=None):
     window, no budget and no position limit; `position_offset` answers with copies of this cache's values.
     `focus_scores(l)` / `focus_kept(l)` / `focus_dropped`: obs [n], idx [keep] and the per-layer n - keep.
 
-    This cache is not written to.  ValueError, before any launch: keep_rows not an int >= 1; kv_cache_dtype set (the
-    re-scoring kernel does not read e4m3 keys); not armed, or a layer with rows behind `video_end` and no watched queries;
+    This cache is not written to.  ValueError, before any launch: keep_rows not an int >= 1; kv_cache_dtype set without
+    archive_rescore (with it the archive's key rows are scored as they lie and the focused cache is an fp8 cache, its
+    archive reserved for exactly `keep` rows - see the module docstring); not armed, or a layer with rows behind `video_end` and no watched queries;
     `video_end` no longer the mark recorded at arming; nothing behind `video_end`; a shape the re-scoring does not serve.
     NotImplementedError: defer_rerotation, a branch, a focused cache."""
     who = "PivotKVCache.focus"
@@ -172,9 +183,10 @@ def focus(cache, keep_rows: int, reserve_tokens=None):
     if cache.defer_rerotation:
         raise NotImplementedError(f"{who}: a cache with defer_rerotation (the sharded prefill's block caches) holds un-rotated "
                                   "keys and provisional ids until `finalize`; it has no restore points")
-    if cache.kv_cache_dtype is not None:
+    fp8 = cache.kv_cache_dtype is not None
+    if fp8 and not cache.archive_rescore:
         raise ValueError(f"{who} does not serve kv_cache_dtype={cache.kv_cache_dtype!r}: the archive's e4m3 key rows are not "
-                         "scored again, it is not built")
+                         "scored again, it is not built - unless asked for: set archive_rescore=True")
     w = cache._watch
     if w is None:
         raise ValueError(f"{who}: the cache is not armed - call watch_question before the question is fed")
@@ -185,7 +197,7 @@ def focus(cache, keep_rows: int, reserve_tokens=None):
     for p in plan:
         l, st, first, ve, n, keep, tail, ids, Q, Wc = p
         k = st._k
-        key = (k.get_device(), Q.shape[0], k.shape[1], Wc, k.shape[3], nv.dtype_code(k))
+        key = (k.get_device(), Q.shape[0], k.shape[1], Wc, k.shape[3], nv.dtype_code(k)) + (("fp8",) if fp8 else ())
         groups.setdefault(key, []).append(p)
         by_device.setdefault(k.get_device(), []).append(p)
 
@@ -197,8 +209,8 @@ def focus(cache, keep_rows: int, reserve_tokens=None):
         ix = torch.empty((len(ps), max(p[5] for p in ps)), dtype=torch.int32, device=device)
         for i, p in enumerate(ps):
             score[p[0]], kept[p[0]] = sc[i, :p[4]], ix[i, :p[5]]
-    rescore_groups(who, {key: [(Q, st._k, first, score[l], n) for l, st, first, _, n, _, _, _, Q, _ in ps]
-                         for key, ps in groups.items()}, 1.0, w.rows,
+    rescore_groups(who, {key: [(Q, (st.k8, st.ks8), 0, score[l], n) if fp8 else (Q, st._k, first, score[l], n)
+                               for l, st, first, _, n, _, _, _, Q, _ in ps] for key, ps in groups.items()}, 1.0, w.rows,
                    lambda dev, device, stride, units: torch.empty(units * stride + 256, dtype=torch.uint8, device=device))
     for dev, ps in by_device.items():
         sel = (nv.BudgetSelectUnit * len(ps))()
@@ -208,10 +220,11 @@ def focus(cache, keep_rows: int, reserve_tokens=None):
                  "rtk_pivotkv_budget_select_batched")
 
     # ---- the focused cache: buffers of its own, filled by one gather call per device ---------------------------------
-    rows = max(p[2] + p[5] + p[6] for p in plan)
+    rows = max((p[1].c.length if fp8 else p[2]) + p[5] + (0 if fp8 else p[6]) for p in plan)
     fc = type(cache)(cache.config, reserve_tokens=reserve_tokens if reserve_tokens is not None else rows + 1024)
     fc.attention_kernel, fc.decode_attention = cache.attention_kernel, cache.decode_attention
     fc.multi_token_attention = cache.multi_token_attention
+    fc.kv_cache_dtype = cache.kv_cache_dtype
     fc.kvcache_compression = False
     fc._warned = True
     fc._store(len(cache._layers) - 1)
@@ -222,23 +235,35 @@ def focus(cache, keep_rows: int, reserve_tokens=None):
         units = []
         for l, pst, first, ve, n, keep, tail, ids, _, _ in ps:
             st, k = fc._layers[l], pst._k
-            total = first + keep + tail
-            cap = max(fc.reserve_tokens, total)
-            shape = (1, k.shape[1], cap, k.shape[3])
-            st.k = torch.empty(shape, dtype=k.dtype, device=k.device)
-            st.v = torch.empty(shape, dtype=k.dtype, device=k.device)
-            st.length, st.pinned = total, first
-            row = k.shape[3] * k.element_size()
-            # (source, destination, rows of a source stream, streams, row bytes)
-            moves = [(pst._k, st._k, k.shape[2], k.shape[1], row), (pst._v, st._v, k.shape[2], k.shape[1], row)]
+            H, D = k.shape[1], k.shape[3]
+            length = pst.c.length if fp8 else first + keep + tail      # the focused layer's 16-bit rows
+            total = length + (keep if fp8 else 0)                      # ... and its rows in sequence order: its ids
+            cap = max(fc.reserve_tokens, length)
+            st.k = torch.empty((1, H, cap, D), dtype=k.dtype, device=k.device)
+            st.v = torch.empty((1, H, cap, D), dtype=k.dtype, device=k.device)
+            st.length, st.pinned = length, pst.pinned
+            row, ix = D * k.element_size(), kept[l].data_ptr()
+            region = (first, first, n, keep, ve, tail, ix)   # rows [0, first), first + idx[.], [ve, ve + tail)
+            # (source, destination, streams, row bytes, then head, first, n, keep, tail_src, tail, idx)
+            if fp8:
+                st.k8, st.v8 = (torch.empty((1, H, keep, D), dtype=torch.uint8, device=k.device) for _ in range(2))
+                st.ks8, st.vs8 = (torch.empty((1, H, keep), dtype=torch.float32, device=k.device) for _ in range(2))
+                st.len8, st.archive_at = keep, first
+                archive, as_they_lie = (0, 0, n, keep, 0, 0, ix), (length, 0, 0, 0, 0, 0, None)
+                moves = [(pst.k8, st.k8, H, D) + archive, (pst.v8, st.v8, H, D) + archive,
+                         (pst.ks8, st.ks8, H, 4) + archive, (pst.vs8, st.vs8, H, 4) + archive,
+                         (pst._k, st._k, H, row) + as_they_lie, (pst._v, st._v, H, row) + as_they_lie]
+                region = (first, first, n, keep, first + n, pst.c.pos_len - first - n, ix)
+            else:
+                moves = [(pst._k, st._k, H, row) + region, (pst._v, st._v, H, row) + region]
             if ids:
                 P = pst._pos.shape[0]
-                st.pos = torch.empty((P, cap), dtype=torch.int64, device=pst._pos.device)
+                st.pos = torch.empty((P, cap + (keep if fp8 else 0)), dtype=torch.int64, device=pst._pos.device)
                 st.pos_len, st.pos_ndim = total, pst.pos_ndim
-                moves.append((pst._pos, st._pos, pst._pos.shape[1], P, 8))
-            for src, dst, src_cap, streams, rb in moves:
-                units.append(nv.FocusUnit(src.data_ptr(), dst.data_ptr(), src_cap * rb, cap * rb, streams, rb, first, first,
-                                          n, keep, ve, tail, kept[l].data_ptr()))
+                moves.append((pst._pos, st._pos, P, 8) + region)
+            for src, dst, streams, rb, *rest in moves:   # (stream strides: rows of a stream x row bytes)
+                units.append(nv.FocusUnit(src.data_ptr(), dst.data_ptr(), src.shape[-2 if src.dim() == 4 else -1] * rb,
+                                          dst.shape[-2 if dst.dim() == 4 else -1] * rb, streams, rb, *rest))
             fc.update_num_evicted_tokens(n - keep, l)
             fc.focus_dropped[l] = n - keep
         nv.check(_on_device(dev, nv.lib.rtk_pivotkv_focus_gather_batched, (nv.FocusUnit * len(units))(*units), len(units),

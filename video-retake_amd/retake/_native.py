@@ -164,6 +164,12 @@ class RescoreUnit(C.Structure):
     _fields_ = [("q", _vp), ("k", _vp), ("k_stride_h", _i64), ("score", _vp), ("n", _i32)]
 
 
+class RescoreFp8kUnit(C.Structure):
+    """rtk_rescore_fp8k_unit (include/retake_hip.h): the unit over the e4m3 key rows of an fp8 archive."""
+    _fields_ = [("q", _vp), ("k8", _vp), ("k8_stride_h", _i64), ("k_scale", _vp), ("scale_stride_h", _i64), ("score", _vp),
+                ("n", _i32)]
+
+
 FOCUS_MAX_UNITS = 48   # RTK_FOCUS_MAX_UNITS: moving units per kernel launch of rtk_pivotkv_focus_gather_batched
 
 
@@ -268,6 +274,7 @@ _SIGNATURES = {
     "rtk_pivotkv_renumber_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp]),
     "rtk_pivotkv_rescore_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i]),
     "rtk_pivotkv_rescore_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _vp, _sz, _vp]),
+    "rtk_pivotkv_rescore_fp8k_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _vp, _sz, _vp]),
     "rtk_pivotkv_focus_gather_batched": (C.c_int, [_vp, _i, _vp]),
     "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

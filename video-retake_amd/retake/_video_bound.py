@@ -93,6 +93,7 @@ def configure_rescore(cache, config):
     """build_kvcache: longvideo_kwargs' video_budget_rescore (alpha) and video_budget_observe_rows (W, read only with alpha
     set), validated and set on the cache (None: off).  Every refusal names its keys; nothing else has happened yet."""
     kw, key, rows_key = config.longvideo_kwargs, "video_budget_rescore", "video_budget_observe_rows"
+    configure_archive_rescore(cache, config)
     alpha = kw.get(key, None)
     if alpha is None:
         return None
@@ -105,11 +106,27 @@ def configure_rescore(cache, config):
     if cache.video_budget_rows is None:
         raise ValueError(f"{key} needs video_budget_rows: it blends the scores the budget evicts by (video_window_rows bounds "
                          "a region by age and keeps no scores)")
-    if cache.kv_cache_dtype is not None:
+    if cache.kv_cache_dtype is not None and not cache.archive_rescore:
         raise ValueError(f"{key} does not serve kv_cache_dtype={cache.kv_cache_dtype!r}: the archive's e4m3 key rows are not "
-                         "scored again, it is not built")
+                         "scored again, it is not built - unless asked for: set archive_rescore=True")
     cache.video_budget_rescore, cache.video_budget_observe_rows = float(alpha), W
     return cache.video_budget_rescore
+
+
+def configure_archive_rescore(cache, config):
+    """build_kvcache: longvideo_kwargs' archive_rescore, validated and set on the cache (False: off).  True lets
+    video_budget_rescore and PivotKVCache.focus score the e4m3 key rows of an fp8 archive as they lie
+    (rtk_pivotkv_rescore_fp8k_batched) - scores taken on lossy keys are another rule than scores taken on 16-bit keys, hence
+    a key of its own.  What kv_cache_dtype refuses (video_position_limit, prompt_guided_scoring, defer_rerotation) stays
+    refused by those keys' own checks."""
+    key = "archive_rescore"
+    on = config.longvideo_kwargs.get(key, None)
+    if on is not None and not isinstance(on, bool):
+        raise ValueError(f"{key} must be True or False (or None: off), got {on!r}")
+    if on and cache.kv_cache_dtype is None:
+        raise ValueError(f"{key}=True needs kv_cache_dtype: it scores the e4m3 key rows of the fp8 archive, a 16-bit cache "
+                         "has none (video_budget_rescore and focus serve it as it is)")
+    cache.archive_rescore = bool(on)
 
 
 def _rebase_rotary(cache):
@@ -412,25 +429,35 @@ def rescore_groups(who, groups, alpha, q_rows, scratch, room=0, sized_rows=None)
     """rtk_pivotkv_rescore_batched for `groups`: {(device index, Hq, Hkv, Wc, D, dtype code): [(q, k, first, score, n), ..]},
     one call per group on the device's current stream - q the unit's query buffer [Hq, q_rows, D] (the first Wc rows of
     each head count), k the layer's key buffer [1, Hkv, cap, D] whose rows [first, first + n) are scored, score its fp32 row.
+    A key with a seventh element "fp8" is a group over e4m3 archive rows (archive_rescore): k is then (codes uint8
+    [1, Hkv, cap8, D], scales fp32 [1, Hkv, cap8]) and the call is rtk_pivotkv_rescore_fp8k_batched; the dtype code is the
+    queries'.
     A unit's scratch is sized for max(room, the group's largest n) region rows and `sized_rows` query rows (None: Wc);
     `scratch(dev, device, stride, units)` answers with a uint8 buffer of at least units * stride + 256 bytes.  ValueError
     under `who`'s name for a shape the kernel does not serve, raised for every group before the first launch."""
     strides = {}
     for key, es in groups.items():
-        _, Hq, Hkv, Wc, D, dt = key
+        _, Hq, Hkv, Wc, D, dt = key[:6]
         rows, most = sized_rows or Wc, max(room, max(e[4] for e in es))
         strides[key] = nv.lib.rtk_pivotkv_rescore_workspace_bytes(Hq, Hkv, rows, most, D, dt)
         if strides[key] == 0:
             raise ValueError(f"{who}: rtk_pivotkv_rescore_batched does not serve Hq {Hq}, Hkv {Hkv}, {rows} query rows, "
                              f"{most} region rows, head_dim {D}")
-    for (dev, Hq, Hkv, Wc, D, dt), es in groups.items():
-        stride = strides[dev, Hq, Hkv, Wc, D, dt]
-        ws = scratch(dev, es[0][1].device, stride, len(es))
-        units = (nv.RescoreUnit * len(es))(*[
-            nv.RescoreUnit(q.data_ptr(), k.data_ptr() + first * k.shape[3] * k.element_size(), k.stride(1), score.data_ptr(), n)
-            for q, k, first, score, n in es])
-        nv.check(_on_device(dev, nv.lib.rtk_pivotkv_rescore_batched, units, len(es), Hq, Hkv, Wc, D, dt, alpha, q_rows * D, D,
-                            (ws.data_ptr() + 255) & ~255, stride, nv.raw_stream(dev)), "rtk_pivotkv_rescore_batched")
+    for key, es in groups.items():
+        (dev, Hq, Hkv, Wc, D, dt), fp8, stride = key[:6], key[6:] == ("fp8",), strides[key]
+        ws = scratch(dev, es[0][0].device, stride, len(es))
+        if fp8:
+            name = "rtk_pivotkv_rescore_fp8k_batched"
+            units = (nv.RescoreFp8kUnit * len(es))(*[
+                nv.RescoreFp8kUnit(q.data_ptr(), k8.data_ptr() + first * D, k8.stride(1), ks.data_ptr() + first * 4, ks.stride(1),
+                                   score.data_ptr(), n) for q, (k8, ks), first, score, n in es])
+        else:
+            name = "rtk_pivotkv_rescore_batched"
+            units = (nv.RescoreUnit * len(es))(*[
+                nv.RescoreUnit(q.data_ptr(), k.data_ptr() + first * k.shape[3] * k.element_size(), k.stride(1), score.data_ptr(), n)
+                for q, k, first, score, n in es])
+        nv.check(_on_device(dev, getattr(nv.lib, name), units, len(es), Hq, Hkv, Wc, D, dt, alpha, q_rows * D, D,
+                            (ws.data_ptr() + 255) & ~255, stride, nv.raw_stream(dev)), name)
 
 
 def rescore_budget(cache):
@@ -444,17 +471,20 @@ def rescore_budget(cache):
         obs[j]    = (n_old / (Hq Wc)) sum_h sum_i p_h[i, j]                           averages 1 over the old rows
         score[j]  = fmaf(alpha, obs[j], (1 - alpha) * score[j])  in fp32, j < n_old;  newer rows keep their arrival score
 
-    ONE rtk_pivotkv_rescore_batched call per device and (Hq, Hkv, Wc, D, dtype) group.  n_old == 0 (the first chunk) does
+    ONE rtk_pivotkv_rescore_batched call per device and (Hq, Hkv, Wc, D, dtype) group.  With fp8 rows (archive_rescore) a
+    layer's region is its archive - first = archive_at, n = len8 - K[g, j] = dtype(float(code) * scale) of the archive's
+    key rows, and the call is rtk_pivotkv_rescore_fp8k_batched; everything else is the same.  n_old == 0 (the first chunk) does
     nothing; afterwards n_old is the region's rows (`evict_budget` sets it to the budget).  A layer with question or decode
     rows left behind its video is skipped - the eviction raises for it as it always did.  The scratch is one buffer per
     device, sized once for a full region with its slack and a chunk: no buffer is replaced after warm-up."""
     alpha, W = cache.video_budget_rescore, cache.video_budget_observe_rows
+    fp8 = cache.kv_cache_dtype is not None
     groups, layers = {}, []
     for l, st in enumerate(cache._layers):
-        first = st.pinned
+        first = st.archive_at if fp8 else st.pinned
         if st._k is None or first < 0 or st.sc is None or st.oq is None or not st.oq_new or st.c.cap == 0:
             continue
-        n = st.c.length - first
+        n = st.len8 if fp8 else st.c.length - first
         if n <= 0 or st.sc_len != n:
             continue
         st.oq_new = False
@@ -463,7 +493,10 @@ def rescore_budget(cache):
             continue
         k, Hq = st._k, st.oq.shape[0]
         key = (k.get_device(), Hq, k.shape[1], st.oq_rows, k.shape[3], nv.dtype_code(k))
-        groups.setdefault(key, []).append((st.oq, k, first, st.sc, n_old))
+        if fp8:   # the archive from its row 0: codes and scales
+            groups.setdefault(key + ("fp8",), []).append((st.oq, (st.k8, st.ks8), 0, st.sc, n_old))
+        else:
+            groups.setdefault(key, []).append((st.oq, k, first, st.sc, n_old))
         layers.append(l)
     if not groups:
         return

@@ -244,6 +244,11 @@ class PivotKVCache(DynamicCache):
         # changes, bit for bit - no query buffer exists and nothing is launched
         self.video_budget_rescore, self.video_budget_observe_rows = None, 64
         self.budget_rescored: List[int] = []  # per layer: re-scorings so far
+        # archive_rescore = True, needs kv_cache_dtype (NOT in the reference; scores taken on e4m3 keys are another rule than
+        # scores taken on 16-bit keys, and what that does to answer quality is not evaluated): video_budget_rescore and
+        # `focus` score the archive's key rows as they lie - K = dtype(float(code) * scale), dequantised where the kernel
+        # loads a key (rtk_pivotkv_rescore_fp8k_batched).  False (default): both refuse a cache with kv_cache_dtype, as ever
+        self.archive_rescore = False
         # MI355X build option, a top-level key of longvideo_kwargs (build_kvcache reads it; NOT in the reference, a rule of
         # this project's own - answer quality is not evaluated): video_position_limit = P, an int >= 0, needs a window or a
         # budget.  A move drops rows but leaves every surviving id where it was, so the ids of a stream that does not end grow

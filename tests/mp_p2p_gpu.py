@@ -1,5 +1,5 @@
 """Multi-process check of the direct p2p all-gather (retake/p2p.py, rtk_p2p_*), launched by
-tests/test_hip_parity.py::test_p2p_allgather_processes as
+tests/test_sharded_gpu.py::test_p2p_allgather_processes as
 
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 tests/mp_p2p_gpu.py
 

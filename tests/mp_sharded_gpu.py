@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Multi-rank GPU check of the chunk-sharded path, launched by tests/test_hip_parity.py::test_sharded_multi_rank_rccl as
+"""Multi-rank GPU check of the chunk-sharded path, launched by tests/test_sharded_gpu.py::test_sharded_multi_rank_rccl as
     python -m torch.distributed.run --nproc-per-node W --master-addr 127.0.0.1 --master-port P tests/mp_sharded_gpu.py
 Every rank compresses its block of one small synthetic video (bench.py's deterministic tensors as the pre-RoPE
-projections, through the attention prologue at the block's provisional ids) with retake.sharded.sharded_video_step - RCCL
+projections, through the attention prologue at the block's provisional ids) with retake.sharded_bench.sharded_video_step - RCCL
 all-gathers of the distance rows, the temporal offsets and the compressed cache - and compares the assembled cache with
 the cache the same rank builds sequentially on its own: ids, V and K bit patterns equal, in fp32 and in bf16.  Two shapes
 per dtype: chunks divisible by the world size (per-chunk overlapped gathers) and one chunk more (ragged blocks, padded
@@ -187,6 +187,7 @@ def plain_rope_blocks(rank, world, dev):
 def main():
     import bench as B
     from retake import sharded
+    from retake.sharded_bench import verify_sharded_equals_sequential
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
@@ -224,8 +225,8 @@ def main():
     if os.environ.get("RETAKE_TEST_ONLY_MORE_CASES") == "1":
         counts = ()
     state = {}
-    res = sharded.verify_sharded_equals_sequential(rank, world, dev, B.Rotary(dev), layers=2, chunk_counts=counts,
-                                                   state=state, log=lambda m: print(m, flush=True))
+    res = verify_sharded_equals_sequential(rank, world, dev, B.Rotary(dev), layers=2, chunk_counts=counts,
+                                           state=state, log=lambda m: print(m, flush=True))
     assert res["equal"] and len(res["cases"]) == 2 * len(counts) and (not counts or {c["dtype"] for c in res["cases"]} == {"fp32", "bf16"})
     # RETAKE_TEST_MORE_CASES="bf16:64,65": further chunk counts per dtype (world size 8: BASELINE's 64-chunk video in blocks
     # of 8 chunks, and the ragged 65-chunk split)
@@ -233,8 +234,8 @@ def main():
         dname, cc = spec.split(":")
         cc = tuple(int(x) for x in cc.split(","))
         for one in cc:
-            res = sharded.verify_sharded_equals_sequential(rank, world, dev, B.Rotary(dev), layers=2, chunk_counts=(one,), state=state,
-                                                           log=lambda m: print(m, flush=True), dtypes=(dname,))
+            res = verify_sharded_equals_sequential(rank, world, dev, B.Rotary(dev), layers=2, chunk_counts=(one,), state=state,
+                                                   log=lambda m: print(m, flush=True), dtypes=(dname,))
             assert res["equal"] and len(res["cases"]) == 1
     if os.environ.get("RETAKE_TEST_DPSELECT") == "1":
         dpselect_blocks(rank, world, dev)

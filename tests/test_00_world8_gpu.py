@@ -9,11 +9,12 @@ skip with that explanation instead.
 """
 import json
 import os
-import subprocess
 import sys
 
 import pytest
 import torch
+
+import proc_util
 
 pytestmark = pytest.mark.gpu
 
@@ -26,32 +27,13 @@ def _fresh_parent():
                     "(8 concurrent processes) - run tests/test_00_world8_gpu.py first / on its own")
 
 
-def _run(cmd, env=None, timeout=300):
-    """Run `cmd` (launcher + ranks); normal run times here are 4-15 s.  If it is not done after `timeout` seconds the launcher
-    and every rank are killed (tests/proc_util.py: torchrun's ranks live in their own sessions) and the test FAILS with the
-    ranks' last output: this file is the dress rehearsal of the first 8-GPU run, and a deadlock of the eight-rank path must
-    be red, not a skip `pytest -x` sails past.  (The one benign cause of slowness - a ninth GPU process oversubscribing the
-    hardware scheduler - is this pytest process itself, and `_fresh_parent` has skipped before we get here if it holds a
-    HIP context.)"""
-    import proc_util
-
-    try:
-        return proc_util.run_job(cmd, env, timeout, cwd=ROOT)
-    except proc_util.JobTimeout as e:
-        pytest.fail(f"eight ranks on one GPU did not finish in {timeout} s (normally < 20 s) - a hang of the eight-rank path "
-                    f"(or a foreign GPU process oversubscribing the hardware scheduler); killed pids {e.killed}.  "
-                    f"stdout tail: {e.stdout[-1500:]!r}  stderr tail: {e.stderr[-3000:]!r}")
-
-
 def _launch_ranks(script, world, env=None, timeout=300):
-    import socket
-
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "tests", script)]
-    return _run(cmd, env, timeout)
+    """Launcher + ranks (tests/proc_util.py); normal run times here are 4-15 s.  If the job is not done after `timeout` seconds
+    the launcher and every rank are killed and the test FAILS with the ranks' last output: this file is the dress rehearsal
+    of the first 8-GPU run, and a deadlock of the eight-rank path must be red, not a skip `pytest -x` sails past.  (The one
+    benign cause of slowness - a ninth GPU process oversubscribing the hardware scheduler - is this pytest process itself,
+    and `_fresh_parent` has skipped before we get here if it holds a HIP context.)"""
+    return proc_util.launch_ranks(script, world, env=env, timeout=timeout)
 
 
 def test_p2p_allgather_8_processes():
@@ -114,8 +96,8 @@ def test_bench_eight_ranks_share_one_gpu_p2p(tmp_path):
     _fresh_parent()
     common = ["--frames", "512", "--layers", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline"]
     rep = os.path.join(str(tmp_path), "report.json")
-    r = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--transport", "p2p", "--report", rep] + common,
-             env={"RETAKE_BENCH_SHARE_GPU": "1"})
+    r = proc_util.run_job_or_fail([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--transport", "p2p",
+                                   "--report", rep] + common, env={"RETAKE_BENCH_SHARE_GPU": "1"}, timeout=300)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     last = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")][-1]
     assert len(last) < 4096, len(last)     # the short contract line; the report file holds the rest
@@ -140,7 +122,7 @@ def test_in_launch_id_shift_with_eight_competing_processes():
 
 
 def test_a_hung_rank_turns_the_rehearsal_red():
-    """The policy of `_run`: a job that does not finish FAILS (group killed, output tails in the message) - shown on a
+    """The policy of `_launch_ranks`: a job that does not finish FAILS (group killed, output tails in the message) - shown on a
     deliberately deadlocked rank (tests/mp_p2p_gpu.py's RETAKE_TEST_HANG_RANK hook: rank 5 never joins the group's set-up)."""
     _fresh_parent()
     with pytest.raises(pytest.fail.Exception, match="did not finish in 40 s"):

@@ -1,17 +1,15 @@
-"""World-size-2 gloo tests of the multi-GPU sharding's host logic (retake/sharded.py)."""
+"""World-size-2 gloo tests of the multi-GPU sharding's host logic (retake/_shard_transport.py, _chunk_gather.py, reached
+through retake/sharded.py), and the module layout of the sharded path: its surface, its one transport table, its imports."""
 import os
-import socket
+import subprocess
+import sys
 
 import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+import proc_util
 
 
 def _worker(rank, world, port, fn_name, ret):
@@ -31,7 +29,7 @@ def _spawn(fn_name, world=2):
     sys.path.insert(0, os.path.join(root, "video-retake_amd"))
     mgr = mp.Manager()
     ret = mgr.dict()
-    mp.spawn(_worker, args=(world, _free_port(), fn_name, ret), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, proc_util.free_port(), fn_name, ret), nprocs=world, join=True)
     return [ret[r] for r in range(world)]
 
 
@@ -294,6 +292,101 @@ def test_plain_rope_ids_and_an_empty_block_through_the_gather_helpers():
         assert kshapes == [(1, 2, 6, 4)] * 2 and kcol == [1, 2, 3, 4, 21, 22]
         assert vcol == [0.5, 1.5, 2.5, 3.5, 20.5, 21.5]
         assert pshapes == [(1, 6), (1, 6)] and pcol == [0, 1, 2, 3, 2000, 2001]
+
+
+def _ragged_helper(rank, world):
+    """The one ragged assembly (pad along the row dimension, gather, rank-major, padding dropped) through its callers, for
+    the counts (3, 0) - one rank holds nothing - and (2, 2) - the equal-count path: rows [n, 5] and ids [3, 1, n] / [1, n]
+    must equal `all_gather_cat` of the unpadded blocks.  `all_gather_cat` takes equal shapes only, so for (3, 0) every rank
+    builds the concatenation it stands for from the blocks themselves (they are functions of the rank)."""
+    from retake import sharded
+
+    layers = 2
+    ok = True
+    for counts in ((3, 0), (2, 2)):
+        def rows(r):
+            return torch.arange(counts[r] * 5, dtype=torch.float32).reshape(counts[r], 5) + 100 * r
+
+        def ids(r, pshape):
+            n = counts[r]   # (pshape[0] * n ids: the other dimension of [3, 1, n] is 1)
+            return [torch.arange(pshape[0] * n).reshape(pshape + (n,)) + 1000 * r + l for l in range(layers)]
+
+        equal = len(set(counts)) == 1
+        assert sharded.gather_counts(counts[rank], "cpu") == list(counts)
+        got = sharded.all_gather_rows_ragged(rows(rank))
+        ok &= bool(torch.equal(got, torch.cat([rows(r) for r in range(world)], 0))) and tuple(got.shape) == (sum(counts), 5)
+        if equal:
+            ok &= bool(torch.equal(got, sharded.all_gather_cat(rows(rank), 0)))
+        for pshape in ((3, 1), (1,)):
+            got = sharded.all_gather_ids(ids(rank, pshape))
+            for l in range(layers):
+                ok &= bool(torch.equal(got[l], torch.cat([ids(r, pshape)[l] for r in range(world)], -1)))
+                ok &= tuple(got[l].shape) == pshape + (sum(counts),)
+                if equal:
+                    ok &= bool(torch.equal(got[l], sharded.all_gather_cat(ids(rank, pshape)[l], -1)))
+    return ok
+
+
+def test_ragged_helper_equals_the_concatenation_of_the_unpadded_blocks():
+    assert all(_spawn("_ragged_helper"))
+
+
+# ---------------------------------------------------------------------------------------------------
+# the module layout of the sharded path
+# ---------------------------------------------------------------------------------------------------
+# what tests, tools and docs reach as `retake.sharded.X`
+SURFACE = ["ChunkGather", "ChunkGatherP2P", "PhaseTimer", "ShardedPivotKV", "_P2P", "all_gather_caches", "all_gather_cat",
+           "all_gather_ids", "all_gather_rows", "all_gather_rows_ragged", "bench_main", "disable_p2p", "dpselect_sharded",
+           "enable_p2p", "exchange_temporal_offsets", "gather_counts", "measure_sharded", "plan_frame_exchange", "shard_chunks",
+           "sharded_video_step", "verify_sharded_equals_sequential"]
+BENCH_NAMES = ["bench_main", "measure_sharded", "sharded_video_step", "verify_sharded_equals_sequential"]
+
+
+def test_sharded_module_surface_is_unchanged():
+    import types
+
+    from retake import sharded
+
+    assert sorted(sharded.__all__) == SURFACE
+    for name in SURFACE:
+        assert getattr(sharded, name) is not None, name
+    # nothing public is defined (or re-exported) beside the list: the bench names are forwarded, not bound
+    public = sorted(n for n, v in vars(sharded).items() if not n.startswith("_") and not isinstance(v, types.ModuleType)
+                    and getattr(v, "__module__", "") != "typing" and n != "annotations")
+    assert public == sorted(set(SURFACE) - {"_P2P"} - set(BENCH_NAMES)), public
+    with pytest.raises(AttributeError):
+        sharded.no_such_name
+
+
+def test_sharded_modules_share_one_transport_table():
+    import retake._shard_transport as tr
+    from retake import sharded, sharded_bench
+
+    assert sharded._P2P is tr._P2P and sharded_bench._P2P is tr._P2P
+    for name in BENCH_NAMES:
+        assert getattr(sharded, name) is getattr(sharded_bench, name)
+
+
+@pytest.mark.parametrize("code", ["import retake.sharded_bench",
+                                  "import retake.sharded; retake.sharded.bench_main",
+                                  "import retake.sharded_bench; import retake.sharded; retake.sharded.bench_main",
+                                  "import retake.sharded; retake.sharded.bench_main; import retake.sharded_bench"])
+def test_sharded_import_orders_in_a_fresh_interpreter(code):
+    env = {**os.environ, "PYTHONPATH": os.pathsep.join([proc_util.ROOT, os.path.join(proc_util.ROOT, "video-retake_amd")])}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=proc_util.ROOT, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+
+
+def test_only_sharded_bench_imports_the_bench_script():
+    pkg = os.path.join(proc_util.ROOT, "video-retake_amd", "retake")
+    seen = 0
+    for dp, _, fns in os.walk(pkg):
+        for fn in fns:
+            if fn.endswith(".py"):
+                seen += 1
+                txt = open(os.path.join(dp, fn), errors="replace").read()
+                assert ("import bench" in txt) == (fn == "sharded_bench.py"), f"{fn}: import bench"
+    assert seen > 10
 
 
 def test_phase_timer_sums_spans_between_marks_per_step():

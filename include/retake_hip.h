@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (89 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (95 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -69,6 +69,11 @@
  *   §T  "Question focus"                rtk_pivotkv_focus_gather_batched: the pinned rows, the video rows a question's queries
  *                                       choose and the question's rows of every layer gathered out of place into a small
  *                                       cache of their own (opt-in: PivotKVCache.watch_question / focus)
+ *   §U  "Page-sparse decode"            rtk_pivotkv_page_summary_batched, rtk_attention_page_bound, rtk_attention_decode_paged,
+ *                                       rtk_attention_decode_sparse (+ their _workspace_bytes): per-page key bounds beside the
+ *                                       rows, and a packed decode call that reads, per kv head and token, the pinned rows, the
+ *                                       pages with the highest bound and the rows behind the video (opt-in:
+ *                                       sparse_decode(cache) of retake/_sparse_decode.py)
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -1348,6 +1353,82 @@ typedef struct rtk_focus_unit {
 } rtk_focus_unit;
 #define RTK_FOCUS_MAX_UNITS 48   /* moving units per launch (the array travels as a kernel argument) */
 int rtk_pivotkv_focus_gather_batched(const rtk_focus_unit* units, int n_units, rtk_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * §U  Page-sparse decode (opt-in: sparse_decode(cache) / dense_decode(cache), retake/_sparse_decode.py; NOT in the reference, and a rule of this
+ * project's own: what it does to answer quality has not been evaluated).  The video rows stay where they lie; a small index
+ * of per-page key bounds sits beside them, and each decode call picks, per kv head, the pages whose upper bound on the
+ * logit is highest (after Quest, Tang et al. 2024) and attends over the pinned rows, those pages and the rows behind the video.
+ *
+ * Per layer: `first` pinned rows, `ve` rows up to the end of the video, n = ve - first region rows, pages = ceil(n / 32);
+ * page p is region rows [32 p, min(32 p + 32, n)) - RTK_PAGE_ROWS = 32 is the packed decode kernel's key tile T.
+ *
+ * rtk_pivotkv_page_summary_batched - one call for all layers of a device, one streaming launch (per RTK_PAGE_SUMMARY_MAX_UNITS
+ *   units) that reads K once: summ[g, p, 0, d] = max, summ[g, p, 1, d] = min over the rows r of page p of k[g, first + r, d],
+ *   in the dtype of k, exact (one of the inputs, bit for bit; of -0 and +0 the max is +0, the min -0; inputs are finite).
+ *   k is [Hkv, rows, D] with rows D elements apart and heads k_stride_h elements apart; summ is [Hkv, pages, 2, D] with heads
+ *   summ_stride_h elements apart.  The partial last page is taken over its existing rows; no row outside [first, first + n)
+ *   is read, no byte outside summ's pages * 2 * D elements per head written.  A unit with n == 0 is skipped.  One wave per
+ *   (kv head, page), each load instruction four whole 256-byte rows (pivotkv_pages.hip).  RTK_BF16 / RTK_F16 with D == 128
+ *   (RTK_EUNSUPPORTED otherwise).  `units` is a HOST array; n_units == 0 launches nothing and returns 0.  RTK_EINVAL, before
+ *   any launch, for NULL pointers, negative counts, pointers or strides that are not 16-byte aligned, a head stride below
+ *   the rows of a head.
+ * rtk_attention_page_bound - ub[g, p] = max over the packed rows r = (hh, i), hh < Hq / Hkv, i < Lq, of
+ *       sum_d max(q[g (Hq / Hkv) + hh, i, d] * summ[g, p, 0, d], q[..] * summ[g, p, 1, d])
+ *   into ub fp32 [Hkv, pages].  The products are exact in fp32 (both operands are 16-bit); the sum is fp32, a lane adding its
+ *   8 channels in order and the 16 lanes of a page folded 1, 2, 4, 8 apart, r in ascending order: a function of the shape
+ *   alone, so the bits depend on neither strides nor addresses.  No scale is applied.  Every raw logit of a packed row of the
+ *   group against a key of the page is <= ub[g, p], up to the rounding of that sum.  Errors as above.
+ * rtk_attention_decode_paged - rtk_attention_decode's arithmetic over the VIRTUAL key space of whole 32-key tiles
+ *       [ rows [0, first) of k / v, padded to a multiple of 32 | page list[g][0], list[g][1], .. | rows [ve, Lk) ]
+ *   with list a DEVICE int32 array [Hkv, keep_pages] of page numbers.  Rows a padded head tile or the partial last page would
+ *   name beyond its segment get logit -inf and contribute nothing, whatever the memory there holds.  Only the tail has a
+ *   diagonal (key row j of the tail is visible to query row i when j <= q_offset + i, in physical rows); q_offset >= ve - 1
+ *   is required, so that every query row sees the whole region.  The splits are rtk_attention_decode's plan over the virtual
+ *   key count K = 32 ceil(first / 32) + 32 keep_pages + Lk - ve; the partials have its layout
+ *   (rtk_attention_decode_paged_workspace_bytes = nsplit * Hq * Lq * (D + 2) * 4) and are folded by the same second launch.
+ *   Each list entry is read once per tile and clamped into [0, pages - 1] in the kernel: a bad list can only name a wrong
+ *   page, never a byte outside rows [first, ve).  With first % 32 == 0 and n % 32 == 0 the result equals, bit for bit,
+ *   rtk_attention_decode over the concatenation of those rows (q_offset moved accordingly); with keep_pages == pages and
+ *   the identity list as well, over the rows as they lie.  No atomics, no flags, no waiting between workgroups.
+ * rtk_attention_decode_sparse - the chain in one call: rtk_attention_page_bound, then
+ *   rtk_pivotkv_budget_select_batched as it is with one unit per kv head (score = ub + g * pages, n = pages,
+ *   keep = keep_pages: the last page always, of the others the keep_pages - 1 with the highest ub, ties to the lowest
+ *   index, ascending), then the paged kernel and the combine.  Its workspace is [ub fp32 [Hkv, pages] | lists int32
+ *   [Hkv, keep_pages] | partials], each part starting at a multiple of 16 bytes; ub and the lists of the last call stay
+ *   readable there.  The caller chooses keep_pages = min(ceil(keep_rows / 32), pages).
+ * Envelope of the two attention calls, as rtk_attention_decode: RTK_BF16 / RTK_F16, D == 128, (Hq / Hkv) * Lq <= 16 -
+ * RTK_EUNSUPPORTED otherwise, before any launch.  RTK_EINVAL, before any launch: NULL pointers, non-positive sizes,
+ * first < 0, first > ve, ve > Lk, keep_pages outside [1, pages], q_offset < ve - 1 or < Lk - Lq, pointers or strides that
+ * are not multiples of 16 bytes, a short or misaligned workspace.  The workspace queries return 0, with the message set,
+ * for a shape the call would refuse.
+ * ------------------------------------------------------------------------------------------- */
+#define RTK_PAGE_ROWS 32
+typedef struct rtk_page_summary_unit {
+    const void* k;            /* row 0 of kv head 0 of the layer's key buffer */
+    int64_t k_stride_h;       /* elements between kv heads */
+    int64_t first;            /* pinned rows: the region starts here */
+    int64_t n;                /* region rows */
+    void*   summ;             /* out: [Hkv, ceil(n / 32), 2, D] */
+    int64_t summ_stride_h;    /* elements between kv heads */
+} rtk_page_summary_unit;
+#define RTK_PAGE_SUMMARY_MAX_UNITS 64   /* units per launch (the array travels as a kernel argument) */
+int rtk_pivotkv_page_summary_batched(const rtk_page_summary_unit* units, int n_units, int Hkv, int D, int dtype,
+                                     rtk_stream_t stream);
+int rtk_attention_page_bound(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* summ, int64_t summ_stride_h,
+                             int Hq, int Hkv, int Lq, int pages, int D, int dtype, float* ub, rtk_stream_t stream);
+size_t rtk_attention_decode_paged_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages, int D,
+                                                  int dtype);
+int rtk_attention_decode_paged(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                               int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                               int D, int dtype, float scale, int first, int ve, const int32_t* list, int keep_pages,
+                               void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+size_t rtk_attention_decode_sparse_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages, int D,
+                                                   int dtype);
+int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                                int D, int dtype, float scale, int first, int ve, const void* summ, int64_t summ_stride_h,
+                                int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

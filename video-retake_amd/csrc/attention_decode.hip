@@ -24,7 +24,8 @@
 // (attention_decode_d128_body.inc) with another buffer's 16-bit rows between the archive and the kernel's own
 // (rtk_attention_decode_shared); attn_decode_group_d128_kernel (rtk_attention_decode_group, below) serves one token of
 // several branches; attn_decode_wide_d128_kernel (attention_decode_wide.cuh, rtk_attention_decode_wide*) serves
-// 16 < R <= 64 packed rows as two to four column groups.  The body, the group kernel and the wide kernel share
+// 16 < R <= 64 packed rows as two to four column groups; attn_decode_paged_d128_kernel (attention_decode_paged.cuh,
+// rtk_attention_decode_paged / _sparse) reads the middle of ONE buffer through a per-kv-head page list.  The body, the group kernel and the wide kernel share
 // dec_step_off, dec_v_frag and dec_softmax_step; their tile loads, dequantise-and-stage step and four-wave fold are
 // written in each (as shared functions they compile the existing kernels differently).  Host side: the entry
 // points of the narrow and the wide family are decode_call with their family and segments - its checks and fall-throughs,
@@ -35,6 +36,7 @@
 // call over the concatenation.  (The k-steps of S^T take channels 64 a + 16 g + 8 b + j, step 2 a + b, lane group g: 16
 // consecutive codes of a row dequantise into one lane's operands of two steps.)
 #include <algorithm>
+#include <vector>
 
 #include "attention_shared.cuh"
 
@@ -133,6 +135,7 @@ __global__ __launch_bounds__(256, 2) void attn_decode_d128_shared_kernel(
 }
 
 #include "attention_decode_wide.cuh"
+#include "attention_decode_paged.cuh"
 
 struct DecodePlan {
     int nsplit, keys_per_split;
@@ -567,6 +570,74 @@ int group_launch(const GroupPlan& gp, const GroupArgs& ga, const Archive8& a8, c
     return attn_combine<DT>(p, out, heads, 1, 128, nsplit, st);
 }
 
+// ---- page-sparse decode (rtk_attention_decode_paged / _sparse; the kernel: attention_decode_paged.cuh) ----
+// what both entry points take beside the common decode arguments, and what follows from it
+struct PagedGeom {
+    int first, ve, keep_pages;
+    int pages;             // ceil((ve - first) / 32)
+    long long keys;        // the virtual key count: head padded to whole tiles + keep_pages tiles + the tail
+};
+// the shape checks of the paged calls, before anything is launched; `g` is filled on success
+int paged_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int D, int dtype, int first, int ve, int keep_pages,
+                      PagedGeom& g) {
+    int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
+    if (rc != RTK_OK) return rc;
+    rc = decode_check_envelope(who, DEC_NARROW, Hq, Hkv, Lq, D, dtype);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG(first >= 0 && first <= ve, "%s: first %d is not in [0, ve = %d]", who, first, ve);
+    RTK_CHECK_ARG(ve <= Lk, "%s: ve %d exceeds Lk %d", who, ve, Lk);
+    const int pages = (int)(((long long)ve - first + DEC_T - 1) / DEC_T);
+    RTK_CHECK_ARG(keep_pages >= 1 && keep_pages <= pages, "%s: keep_pages %d is not in [1, pages = %d]", who, keep_pages, pages);
+    if (Lk > 0x3fffffff - 2 * DEC_T) {
+        set_error("%s: unsupported extent: %d keys", who, Lk);
+        return RTK_EUNSUPPORTED;
+    }
+    g = PagedGeom{first, ve, keep_pages, pages,
+                  ((long long)first + DEC_T - 1) / DEC_T * DEC_T + (long long)keep_pages * DEC_T + (Lk - ve)};
+    return RTK_OK;
+}
+// the operand checks: layout (RTK_EINVAL here, as retake_hip.h states for these calls), then what rtk_attention_decode checks
+int paged_check_operands(const char* who, const AttnArgs& a, const PagedGeom& g) {
+    RTK_CHECK_ARG(a.off >= g.ve - 1, "%s: q_offset %d < ve - 1 = %d (every query row sees the whole region)", who, a.off, g.ve - 1);
+    RTK_CHECK_ARG((((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out) & 15) == 0 && (a.q_sh * 2) % 16 == 0 &&
+                      (a.q_sl * 2) % 16 == 0 && (a.kv_sh * 2) % 16 == 0 && (a.kv_sl * 2) % 16 == 0,
+                  "%s: pointers and strides must be multiples of 16 bytes", who);
+    return attn_check_operands(who, a.q, a.q_sh, a.q_sl, a.k, a.v, a.kv_sh, a.kv_sl, nullptr, nullptr, nullptr, nullptr, 0, 0, a.out,
+                               a.Lq, a.Lk, a.off, a.D, a.dtype, a.scale, 0, DEC_T);
+}
+inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+// the workspace of rtk_attention_decode_sparse: [ub fp32 [Hkv, pages] | lists int32 [Hkv, keep_pages] | partials], each part
+// starting at a multiple of 16 bytes
+struct SparseLayout {
+    size_t lists_at, partials_at, bytes;
+};
+SparseLayout sparse_layout(int Hkv, const PagedGeom& g, const DecodePlan& pl) {
+    SparseLayout s;
+    s.lists_at = align16((size_t)Hkv * g.pages * sizeof(float));
+    s.partials_at = s.lists_at + align16((size_t)Hkv * g.keep_pages * sizeof(int32_t));
+    s.bytes = s.partials_at + pl.ws_bytes;
+    return s;
+}
+int paged_check_workspace(const char* who, const char* query, size_t need, const void* workspace, size_t workspace_bytes) {
+    RTK_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes; query %s)", who,
+                  workspace ? workspace_bytes : (size_t)0, need, query);
+    RTK_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    return RTK_OK;
+}
+// the paged kernel over `partials`, then the combine
+template <int DT> int paged_launch(const DecodePlan& pl, const AttnArgs& a, const PagedGeom& g, const int32_t* list, void* partials) {
+    const Partials p = split_partials(partials, pl.nsplit, a.Hq, a.Lq, 128);
+    hipLaunchKernelGGL((attn_decode_paged_d128_kernel<DT>), dim3((unsigned)pl.nsplit, (unsigned)a.Hkv), dim3(256), 0, a.st,
+                       (const char*)a.q, a.q_sh, a.q_sl, (const char*)a.k, (const char*)a.v, a.kv_sh, (uint32_t)(a.kv_sl * 2), p.acc,
+                       p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, base2_scale(a.scale), pl.keys_per_split, g.first, g.ve, list,
+                       g.keep_pages);
+    RTK_LAUNCH_CHECK("attn_decode_paged_d128_kernel");
+    return attn_combine<DT>(p, a.out, a.Hq, a.Lq, 128, pl.nsplit, a.st);
+}
+int paged_forward(const DecodePlan& pl, const AttnArgs& a, const PagedGeom& g, const int32_t* list, void* partials) {
+    return a.dtype == RTK_BF16 ? paged_launch<RTK_BF16>(pl, a, g, list, partials) : paged_launch<RTK_F16>(pl, a, g, list, partials);
+}
+
 }  // namespace
 }  // namespace rtk
 
@@ -723,4 +794,75 @@ extern "C" int rtk_attention_decode_group(const rtk_decode_branch* branches, int
     const float c2 = base2_scale(scale);
     if (dtype == RTK_BF16) return group_launch<RTK_BF16>(gp, ga, a8, s16, out, Hkv, c2, workspace, (hipStream_t)stream);
     return group_launch<RTK_F16>(gp, ga, a8, s16, out, Hkv, c2, workspace, (hipStream_t)stream);
+}
+
+// ---- page-sparse decode (retake_hip.h §U) ----
+extern "C" size_t rtk_attention_decode_paged_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages,
+                                                             int D, int dtype) {
+    PagedGeom g;
+    if (paged_check_shape("rtk_attention_decode_paged_workspace_bytes", Hq, Hkv, Lq, Lk, D, dtype, first, ve, keep_pages, g) != RTK_OK)
+        return 0;
+    return decode_plan(Hq, Hkv, Lq, g.keys).ws_bytes;
+}
+
+extern "C" int rtk_attention_decode_paged(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                          int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
+                                          int q_offset, int D, int dtype, float scale, int first, int ve, const int32_t* list,
+                                          int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream) {
+    const char* who = "rtk_attention_decode_paged";
+    RTK_CHECK_ARG(q && k && v && out && list, "%s: NULL q / k / v / out / list pointer", who);
+    const AttnArgs a{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                     scale, workspace, workspace_bytes, (hipStream_t)stream};
+    PagedGeom g;
+    int rc = paged_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype, first, ve, keep_pages, g);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG(((uintptr_t)list & 3) == 0, "%s: list must be 4-byte aligned", who);
+    rc = paged_check_operands(who, a, g);
+    if (rc != RTK_OK) return rc;
+    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, g.keys);
+    rc = paged_check_workspace(who, "rtk_attention_decode_paged_workspace_bytes", pl.ws_bytes, workspace, workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    return paged_forward(pl, a, g, list, workspace);
+}
+
+extern "C" size_t rtk_attention_decode_sparse_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages,
+                                                              int D, int dtype) {
+    PagedGeom g;
+    if (paged_check_shape("rtk_attention_decode_sparse_workspace_bytes", Hq, Hkv, Lq, Lk, D, dtype, first, ve, keep_pages, g) != RTK_OK)
+        return 0;
+    return sparse_layout(Hkv, g, decode_plan(Hq, Hkv, Lq, g.keys)).bytes;
+}
+
+extern "C" int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                           int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
+                                           int q_offset, int D, int dtype, float scale, int first, int ve, const void* summ,
+                                           int64_t summ_stride_h, int keep_pages, void* workspace, size_t workspace_bytes,
+                                           rtk_stream_t stream) {
+    const char* who = "rtk_attention_decode_sparse";
+    RTK_CHECK_ARG(q && k && v && out && summ, "%s: NULL q / k / v / out / summ pointer", who);
+    const AttnArgs a{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                     scale, workspace, workspace_bytes, (hipStream_t)stream};
+    PagedGeom g;
+    int rc = paged_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype, first, ve, keep_pages, g);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG(((uintptr_t)summ & 15) == 0 && (summ_stride_h * 2) % 16 == 0 && summ_stride_h >= (int64_t)g.pages * 2 * D,
+                  "%s: summ must be 16-byte aligned with a head stride of at least pages * 2 * D = %lld elements", who,
+                  (long long)g.pages * 2 * D);
+    rc = paged_check_operands(who, a, g);
+    if (rc != RTK_OK) return rc;
+    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, g.keys);
+    const SparseLayout sl = sparse_layout(Hkv, g, pl);
+    rc = paged_check_workspace(who, "rtk_attention_decode_sparse_workspace_bytes", sl.bytes, workspace, workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    float* ub = (float*)workspace;
+    int32_t* lists = (int32_t*)((char*)workspace + sl.lists_at);
+    // the bound, the selection (one unit per kv head: the existing launcher as it is), the paged kernel, the combine
+    rc = rtk_attention_page_bound(q, q_stride_h, q_stride_l, summ, summ_stride_h, Hq, Hkv, Lq, g.pages, D, dtype, ub, stream);
+    if (rc != RTK_OK) return rc;
+    std::vector<rtk_budget_select_unit> sel((size_t)Hkv);
+    for (int h = 0; h < Hkv; ++h)
+        sel[h] = rtk_budget_select_unit{ub + (size_t)h * g.pages, lists + (size_t)h * g.keep_pages, g.pages, g.keep_pages};
+    rc = rtk_pivotkv_budget_select_batched(sel.data(), Hkv, stream);
+    if (rc != RTK_OK) return rc;
+    return paged_forward(pl, a, g, lists, (char*)workspace + sl.partials_at);
 }

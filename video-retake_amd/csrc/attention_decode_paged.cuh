@@ -1,0 +1,209 @@
+// attention_decode_paged.cuh - the packed decode kernel with its MIDDLE segment read through a page list (retake_hip.h §U
+// "Page-sparse decode", rtk_attention_decode_paged / rtk_attention_decode_sparse).  Included by attention_decode.hip after
+// the narrow kernels, whose constants and helpers (DEC_*, mma32, wave_lds_sync, dec_step_off, dec_v_frag, dec_softmax_step)
+// it uses; the tile loads and the four-wave fold are written out here as in attention_decode_d128_body.inc, which stays
+// untouched (as shared functions they would compile the existing kernels differently - DESIGN.md).
+//
+// The keys of one kv head are ONE buffer k [Lk rows]; the kernel walks a VIRTUAL key space of whole 32-key tiles
+//     [ rows [0, first), padded to firstp = 32 ceil(first / 32) | page list[0], list[1], .. list[keep_pages - 1] | rows [ve, Lk) ]
+// where page p is rows first + [32 p, min(32 p + 32, n)), n = ve - first.  Everything that depends on a tile's place - the
+// split it belongs to, the wave that takes it, the order of the fold - is decided in the virtual space, exactly as the
+// packed kernel decides it in its physical one, so with first % 32 == 0 and n % 32 == 0 the call IS rtk_attention_decode
+// over the concatenation of those rows, bit for bit.
+//   * Each segment has a buffer descriptor of its own over exactly its rows - [0, first), [first, ve), [ve, Lk) - so the rows
+//     a padded head tile or the partial last page would name beyond its segment READ AS ZERO (K and V alike), whatever the
+//     memory there holds, and their logits are set to -inf as the packed kernel does for keys >= Lk.
+//   * A list entry is read once per tile as a wave-uniform number and clamped into [0, pages - 1]: a bad list names a wrong
+//     page, never a byte outside rows [first, ve).
+//   * Only the tail has a diagonal; the launcher admits q_offset >= ve - 1 only, so every packed row sees the head and
+//     the pages whole.
+// No atomics, no flags, no waiting between workgroups; plain vector stores.
+
+template <int DT>
+__global__ __launch_bounds__(256, 2) void attn_decode_paged_d128_kernel(
+    const char* __restrict__ q, int64_t q_sh, int64_t q_sl, const char* __restrict__ k, const char* __restrict__ v,
+    int64_t kv_sh, uint32_t kv_row_bytes, float* __restrict__ part_acc, float* __restrict__ part_ml, int Hq, int G, int Lq,
+    int Lk, int off, float c2, int keys_per_split, int first, int ve, const int32_t* __restrict__ list, int keep_pages) {
+    __shared__ __attribute__((aligned(16))) char lds[4 * DEC_WAVE_LDS];   // [wave]: V tile, then the wave's O
+    __shared__ float ml_s[4][DEC_R][2];
+    // the virtual key space: head tiles [0, firstp) | listed pages [firstp, tv) | tail rows [tv, Lkv)
+    const int n = ve - first, pages = (n + DEC_T - 1) / DEC_T;
+    const int firstp = (first + DEC_T - 1) / DEC_T * DEC_T, tv = firstp + keep_pages * DEC_T;
+    const int Lkv = tv + (Lk - ve), offv = off - ve + tv;
+    const int tid = threadIdx.x, lane = tid & 63, wave = uniform_int(tid >> 6);
+    const int c = lane & 15, g = lane >> 4;   // packed row (column) and lane group
+    const int split = blockIdx.x, hkv = blockIdx.y, R = G * Lq;
+    const int qi = c % Lq, qg = c / Lq;       // query position and head-in-group of packed row c
+    const int k_lo = split * keys_per_split;
+    const int k_hi = min(min(Lkv, offv + Lq), k_lo + keys_per_split);   // exclusive: first key no row of the range sees
+    const int vis_r = min(offv + qi, Lkv - 1);                          // last (virtual) key packed row c sees
+    const int32_t* __restrict__ my_list = list + (int64_t)hkv * keep_pages;
+
+    // a descriptor per segment over exactly its rows (built per tile from these wave-uniform numbers): a row past its
+    // segment's last reads as zero
+    const char* kh = k + (int64_t)hkv * kv_sh * 2;
+    const char* vh = v + (int64_t)hkv * kv_sh * 2;
+    const uint32_t head_bytes = first > 0 ? (uint32_t)(first - 1) * kv_row_bytes + 256u : 0u;
+    const uint32_t reg_bytes = n > 0 ? (uint32_t)(n - 1) * kv_row_bytes + 256u : 0u;
+    const uint32_t tail_bytes = Lk > ve ? (uint32_t)(Lk - ve - 1) * kv_row_bytes + 256u : 0u;
+    const int64_t reg_at = (int64_t)first * kv_row_bytes, tail_at = (int64_t)ve * kv_row_bytes;
+
+    // Q fragments (B operand): packed row c, zero for c >= R
+    u32x4 qf[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qf[s] = u32x4{0u, 0u, 0u, 0u};
+    if (c < R) {
+        const char* qr = q + ((int64_t)(hkv * G + qg) * q_sh + (int64_t)qi * q_sl) * 2;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) qf[s] = *(const u32x4*)(qr + dec_step_off(s, g));
+    }
+
+    // Where a virtual tile lies (all wave-uniform): its segment's byte offset in the head and byte extent, its first row
+    // within the segment, whether it is a tail tile, and - head and pages - the last key of the tile that exists.  `locate`
+    // describes the tile whose loads are issued next; `process` takes its copy before it locates the following one.
+    int64_t t_at = 0;
+    uint32_t t_bytes = 0;
+    int t_row0 = 0, t_last = 0;
+    bool t_tail = false;
+    auto locate = [&](int kb) {
+        if (kb < firstp) {
+            t_at = 0, t_bytes = head_bytes, t_row0 = kb, t_last = first - 1 - kb, t_tail = false;
+        } else if (kb < tv) {
+            const int e = uniform_int(my_list[(kb - firstp) / DEC_T]);
+            const int p = min(max(e, 0), pages - 1);   // inside the region whatever the list says
+            t_at = reg_at, t_bytes = reg_bytes, t_row0 = DEC_T * p, t_last = min(DEC_T, n - DEC_T * p) - 1, t_tail = false;
+        } else {
+            t_at = tail_at, t_bytes = tail_bytes, t_row0 = kb - tv, t_last = 0, t_tail = true;
+        }
+    };
+
+    // One tile's operands, in flight from the moment the previous tile's are consumed: kr[4 b + s] = the step-s chunk of key
+    // row 16 b + c; vr[u] = chunk c of V row 4 u + g
+    u32x4 kr[8], vr[8];
+    auto load_k = [&]() {
+        const __amdgpu_buffer_rsrc_t r = bounded_rsrc(kh + t_at, t_bytes);
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                kr[4 * b + s] = load16(r, (uint32_t)(t_row0 + 16 * b + c) * kv_row_bytes + (uint32_t)dec_step_off(s, g));
+    };
+    auto load_v = [&]() {
+        const __amdgpu_buffer_rsrc_t r = bounded_rsrc(vh + t_at, t_bytes);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) vr[u] = load16(r, (uint32_t)(t_row0 + 4 * u + g) * kv_row_bytes + 16u * c);
+    };
+
+    char* vt = lds + wave * DEC_WAVE_LDS;
+    // transposed V reads, as attention_decode_d128_body.inc lays them out
+    const int v_rd = DEC_VPITCH * (4 * g + (c >> 2)) + 8 * (c & 3);
+
+    f32x4 oacc[8];
+#pragma unroll
+    for (int db = 0; db < 8; ++db) oacc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+
+    // tile kb (located, its loads in flight); `next`: this wave has a tile at kb + DEC_STEP
+    auto process = [&](int kb, bool next) {
+        const bool tail = t_tail;
+        const int last = t_last;
+        u32x4 ka[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ka[e] = kr[e];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) *(u32x4*)(vt + DEC_VPITCH * (4 * u + g) + 16 * c) = vr[u];
+        if (next) {
+            locate(kb + DEC_STEP);
+            load_v();
+        }
+        wave_lds_sync();
+        // logits: s0[e] = key 4 g + e, s1[e] = key 16 + 4 g + e of the tile, packed row c
+        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            s0 = mma32<DT>(ka[s], qf[s], s0);
+            s1 = mma32<DT>(ka[4 + s], qf[s], s1);
+        }
+        if (next) load_k();
+        // the last key of the tile this row sees: its diagonal or the end of the keys in the tail, else the last row of
+        // the head / of the page, which every row sees
+        const int lim = tail ? vis_r - kb : last;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (4 * g + e > lim) s0[e] = -INFINITY;
+            if (16 + 4 * g + e > lim) s1[e] = -INFINITY;
+        }
+        const u32x4 pf = dec_softmax_step<DT>(s0, s1, c2, m, l, oacc);
+        if (!tail || kb + DEC_T - 1 <= offv) {   // every row sees every key of the tile that exists (the others read as zero)
+#pragma unroll
+            for (int db = 0; db < 8; ++db) oacc[db] = mma32<DT>(dec_v_frag(vt + v_rd, db), pf, oacc[db]);
+        } else {
+            // one pass per query position: V rows above its diagonal zeroed, the lanes of its packed rows keep the result
+            for (int i = 0; i < Lq; ++i) {
+                const int li = min(offv + i, Lkv - 1) - kb;
+                u32x4 keep;
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const int key = 16 * (w >> 1) + 4 * g + 2 * (w & 1);
+                    keep[w] = (key <= li ? 0xffffu : 0u) | (key + 1 <= li ? 0xffff0000u : 0u);
+                }
+#pragma unroll
+                for (int db = 0; db < 8; ++db) {
+                    const f32x4 t = mma32<DT>(dec_v_frag(vt + v_rd, db) & keep, pf, oacc[db]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) oacc[db][e] = qi == i ? t[e] : oacc[db][e];
+                }
+            }
+        }
+        wave_lds_sync();   // the reads above before the next tile's writes
+    };
+
+    // this wave's tiles: u = wave, wave + 4, ... of the range
+    const int kb0 = k_lo + DEC_T * wave;
+    if (kb0 < k_hi) {
+        locate(kb0);
+        load_k();
+        load_v();
+    }
+    for (int kb = kb0; kb < k_hi; kb += DEC_STEP) process(kb, kb + DEC_STEP < k_hi);
+
+    // fold the four waves in wave order; the workgroup leaves one partial per packed row
+    l += __shfl_xor(l, 16, WAVE);
+    l += __shfl_xor(l, 32, WAVE);
+    {
+        float* ow = (float*)vt;
+#pragma unroll
+        for (int db = 0; db < 8; ++db) *(f32x4*)(ow + c * DEC_OPITCH + 16 * db + 4 * g) = oacc[db];
+        if (g == 0) {
+            ml_s[wave][c][0] = m;
+            ml_s[wave][c][1] = l;
+        }
+    }
+    __syncthreads();
+    const int row = tid >> 4, ch = tid & 15;   // packed row, channels 8 ch .. 8 ch + 7
+    if (row >= R) return;
+    float mg = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) mg = fmaxf(mg, ml_s[w][row][0]);
+    f32x4 n0 = {0.f, 0.f, 0.f, 0.f}, n1 = {0.f, 0.f, 0.f, 0.f};
+    float den = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const float mw = ml_s[w][row][0];
+        if (mw == -INFINITY) continue;   // the wave had no key this row sees
+        const float wt = __builtin_amdgcn_exp2f(mw - mg);
+        const float* ow = (const float*)(lds + w * DEC_WAVE_LDS) + row * DEC_OPITCH + 8 * ch;
+        const f32x4 a = *(const f32x4*)ow, b = *(const f32x4*)(ow + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            n0[e] = __builtin_fmaf(wt, a[e], n0[e]);
+            n1[e] = __builtin_fmaf(wt, b[e], n1[e]);
+        }
+        den = __builtin_fmaf(wt, ml_s[w][row][1], den);
+    }
+    const size_t prow = ((size_t)split * Hq + (size_t)(hkv * G + row / Lq)) * Lq + row % Lq;
+    float* pa = part_acc + prow * 128 + 8 * ch;
+    *(f32x4*)pa = n0;
+    *(f32x4*)(pa + 4) = n1;
+    if (ch == 0) *(float2*)(part_ml + 2 * prow) = make_float2(mg, den);
+}

@@ -1,0 +1,211 @@
+// pivotkv_pages.hip - the page index of the page-sparse decode (retake_hip.h §U "Page-sparse decode"; NOT in the reference,
+// a rule of this project's own):
+//   page_summary_kernel   per arming: kmax / kmin [Hkv, pages, 2, D] of the stored keys of every layer of a device, one call
+//   page_bound_kernel     per decode call: ub[g, p], an upper bound on every raw logit of kv head g's packed rows against
+//                         every key of page p
+// A page is RTK_PAGE_ROWS = 32 region rows: one wave tile of the packed decode kernel.
+//
+// page_summary_kernel - streaming, reads K once.  One wave per (kv head, page); a row of D = 128 16-bit elements is 256
+// bytes = 16 lanes x 16 bytes, so a wave's load instruction takes FOUR whole rows (lane: chunk c = lane & 15 of row
+// 4 u + (lane >> 4), u = 0 .. 7) - every lane carries data and each row is one contiguous 256-byte run.  A lane folds its 8
+// rows element-wise, the four row groups are folded through the lanes 16 and 32 apart, and the lanes of group 0 / 1 store
+// the 256 bytes of kmax / kmin.  Max and min are taken on the order-preserving 16-bit key of the sign-magnitude encoding
+// (bf16 and fp16 alike: one kernel), so the result is one of the inputs, bit for bit; of -0 and +0 the max is +0 and the min
+// -0.  Rows >= n of the partial last page are not loaded.  No LDS, no atomics, no scratch.
+// Roofline: HBM, n x 256 bytes read + pages x 512 written per kv head.
+//
+// page_bound_kernel - a wave takes 4 pages, lane (page lane >> 4, chunk c): it holds 8 elements of kmax and of kmin in fp32
+// and, per packed row r = (hh, i), adds its 8 terms max(q kmax, q kmin) in channel order, folds the 16 chunks through the
+// lanes 1, 2, 4, 8 apart and keeps the running max over r in the order r = 0, 1, ...  Both operands are 16-bit, so each
+// product is exact in fp32; the order of the additions is a function of the shape alone, and so are the bits.
+#include <algorithm>
+
+#include "common.cuh"
+
+namespace rtk {
+namespace {
+
+constexpr int PG_ROWS = RTK_PAGE_ROWS;
+constexpr int PG_BLOCK = 256;
+constexpr int PG_WAVES = PG_BLOCK / WAVE;
+
+struct PageDev {
+    const char* k;        // row 0 of kv head 0
+    char* summ;           // [Hkv, pages, 2, 128] 16-bit
+    int64_t k_sh, s_sh;   // head strides, bytes
+    int32_t first, n;
+};
+struct PageUnits {
+    PageDev u[RTK_PAGE_SUMMARY_MAX_UNITS];
+};
+static_assert(sizeof(PageUnits) <= 4096, "the units travel as a kernel argument");
+
+// order-preserving key of a sign-magnitude 16-bit float and back
+__device__ __forceinline__ uint32_t ord16(uint32_t x) { return x ^ ((x & 0x8000u) ? 0xffffu : 0x8000u); }
+__device__ __forceinline__ uint32_t unord16(uint32_t y) { return y ^ ((y & 0x8000u) ? 0x8000u : 0xffffu); }
+
+__global__ __launch_bounds__(PG_BLOCK) void page_summary_kernel(PageUnits units) {
+    const PageDev& un = units.u[blockIdx.z];
+    const int lane = threadIdx.x & (WAVE - 1), wave = uniform_int(threadIdx.x / WAVE);
+    const int c = lane & 15, g = lane >> 4;
+    const int n = un.n, pages = (n + PG_ROWS - 1) / PG_ROWS;
+    const int p = blockIdx.x * PG_WAVES + wave, h = blockIdx.y;
+    if (p >= pages) return;   // (wave-uniform: the grid is sized for the launch's largest unit)
+    const char* kp = un.k + (int64_t)h * un.k_sh + ((int64_t)un.first + (int64_t)PG_ROWS * p) * 256 + 16 * c;
+    const int rows = min(PG_ROWS, n - PG_ROWS * p);   // of this page: >= 1
+    uint32_t hi[8], lo[8];   // keys of the lane's 8 elements: running max, running min
+#pragma unroll
+    for (int e = 0; e < 8; ++e) hi[e] = 0u, lo[e] = 0xffffu;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        const int r = 4 * u + g;
+        if (r < rows) {
+            const u32x4 t = __builtin_nontemporal_load((const u32x4*)(kp + (int64_t)r * 256));
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const uint32_t a = ord16(t[w] & 0xffffu), b = ord16(t[w] >> 16);
+                hi[2 * w] = max(hi[2 * w], a), lo[2 * w] = min(lo[2 * w], a);
+                hi[2 * w + 1] = max(hi[2 * w + 1], b), lo[2 * w + 1] = min(lo[2 * w + 1], b);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        hi[e] = max(hi[e], (uint32_t)__shfl_xor((int)hi[e], 16, WAVE));
+        hi[e] = max(hi[e], (uint32_t)__shfl_xor((int)hi[e], 32, WAVE));
+        lo[e] = min(lo[e], (uint32_t)__shfl_xor((int)lo[e], 16, WAVE));
+        lo[e] = min(lo[e], (uint32_t)__shfl_xor((int)lo[e], 32, WAVE));
+    }
+    if (g < 2) {   // group 0 stores kmax, group 1 kmin: 16 lanes x 16 bytes each
+        u32x4 o;
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            o[w] = g == 0 ? (unord16(hi[2 * w]) | (unord16(hi[2 * w + 1]) << 16)) : (unord16(lo[2 * w]) | (unord16(lo[2 * w + 1]) << 16));
+        *(u32x4*)(un.summ + (int64_t)h * un.s_sh + (int64_t)p * 512 + 256 * g + 16 * c) = o;
+    }
+}
+
+template <int DT> __device__ __forceinline__ void unpack8(const u32x4& t, float (&f)[8]) {
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        f[2 * w] = H16<DT>::lo(t[w]);
+        f[2 * w + 1] = H16<DT>::hi(t[w]);
+    }
+}
+
+template <int DT>
+__global__ __launch_bounds__(PG_BLOCK) void page_bound_kernel(const char* __restrict__ q, int64_t q_sh, int64_t q_sl,
+                                                              const char* __restrict__ summ, int64_t s_sh, int G, int Lq,
+                                                              int pages, float* __restrict__ ub) {
+    const int lane = threadIdx.x & (WAVE - 1), wave = uniform_int(threadIdx.x / WAVE);
+    const int c = lane & 15, j = lane >> 4;
+    const int hkv = blockIdx.y;
+    const int p = (blockIdx.x * PG_WAVES + wave) * 4 + j;
+    const int pc = min(p, pages - 1);   // a page past the end re-reads the last one and stores nothing
+    const char* sp = summ + ((int64_t)hkv * s_sh) * 2 + (int64_t)pc * 512 + 16 * c;
+    float kx[8], kn[8];
+    unpack8<DT>(*(const u32x4*)sp, kx);
+    unpack8<DT>(*(const u32x4*)(sp + 256), kn);
+    float best = -INFINITY;
+    for (int hh = 0; hh < G; ++hh)
+        for (int i = 0; i < Lq; ++i) {
+            float qv[8];
+            unpack8<DT>(*(const u32x4*)(q + ((int64_t)(hkv * G + hh) * q_sh + (int64_t)i * q_sl) * 2 + 16 * c), qv);
+            float acc = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) acc = acc + fmaxf(qv[e] * kx[e], qv[e] * kn[e]);
+            acc = acc + __shfl_xor(acc, 1, WAVE);
+            acc = acc + __shfl_xor(acc, 2, WAVE);
+            acc = acc + __shfl_xor(acc, 4, WAVE);
+            acc = acc + __shfl_xor(acc, 8, WAVE);
+            best = fmaxf(best, acc);
+        }
+    if (c == 0 && p < pages) ub[(int64_t)hkv * pages + p] = best;
+}
+
+int pages_check_envelope(const char* who, int D, int dtype) {
+    if (dtype != RTK_BF16 && dtype != RTK_F16) {
+        set_error("%s: unsupported dtype code %d (RTK_BF16 or RTK_F16)", who, dtype);
+        return RTK_EUNSUPPORTED;
+    }
+    if (D != 128) {
+        set_error("%s: unsupported head_dim %d (128)", who, D);
+        return RTK_EUNSUPPORTED;
+    }
+    return RTK_OK;
+}
+
+}  // namespace
+}  // namespace rtk
+
+using namespace rtk;
+
+extern "C" int rtk_pivotkv_page_summary_batched(const rtk_page_summary_unit* units, int n_units, int Hkv, int D, int dtype,
+                                                rtk_stream_t stream) {
+    const char* who = "rtk_pivotkv_page_summary_batched";
+    int rc = have_units(units, n_units, who);
+    if (rc <= 0) return rc;
+    RTK_CHECK_ARG(Hkv >= 1 && Hkv <= 65535, "%s: Hkv %d", who, Hkv);
+    rc = pages_check_envelope(who, D, dtype);
+    if (rc != RTK_OK) return rc;
+    for (int i = 0; i < n_units; ++i) {
+        const rtk_page_summary_unit& u = units[i];
+        RTK_CHECK_ARG(u.first >= 0 && u.n >= 0 && u.first + u.n <= 0x3fffffff, "%s: unit %d: first %lld / n %lld", who, i,
+                      (long long)u.first, (long long)u.n);
+        if (u.n == 0) continue;
+        RTK_CHECK_ARG(u.k && u.summ, "%s: unit %d: NULL k / summ", who, i);
+        const int64_t pages = (u.n + PG_ROWS - 1) / PG_ROWS;
+        RTK_CHECK_ARG((((uintptr_t)u.k | (uintptr_t)u.summ) & 15) == 0 && (u.k_stride_h * 2) % 16 == 0 && (u.summ_stride_h * 2) % 16 == 0,
+                      "%s: unit %d: k / summ / head strides not 16-byte aligned", who, i);
+        RTK_CHECK_ARG(u.k_stride_h >= 0 && (Hkv == 1 || u.k_stride_h >= (u.first + u.n) * D), "%s: unit %d: k_stride_h %lld is smaller than the rows of a head",
+                      who, i, (long long)u.k_stride_h);
+        RTK_CHECK_ARG(u.summ_stride_h >= 0 && (Hkv == 1 || u.summ_stride_h >= pages * 2 * D),
+                      "%s: unit %d: summ_stride_h %lld is smaller than pages * 2 * D = %lld", who, i, (long long)u.summ_stride_h,
+                      (long long)(pages * 2 * D));
+    }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned grid_x = 0;   // of the launch being filled: its largest unit's
+    return launch_units<PageUnits>(
+        n_units,
+        [&](int i, PageDev& dv) {
+            const rtk_page_summary_unit& u = units[i];
+            if (u.n == 0) return false;
+            dv = PageDev{(const char*)u.k, (char*)u.summ, u.k_stride_h * 2, u.summ_stride_h * 2, (int32_t)u.first, (int32_t)u.n};
+            const unsigned pages = (unsigned)((u.n + PG_ROWS - 1) / PG_ROWS);
+            grid_x = std::max(grid_x, (pages + PG_WAVES - 1) / PG_WAVES);
+            return true;
+        },
+        [&](const PageUnits& pu, int n) -> int {
+            hipLaunchKernelGGL(page_summary_kernel, dim3(grid_x, (unsigned)Hkv, (unsigned)n), dim3(PG_BLOCK), 0, st, pu);
+            RTK_LAUNCH_CHECK("page_summary_kernel");
+            grid_x = 0;
+            return RTK_OK;
+        });
+}
+
+extern "C" int rtk_attention_page_bound(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* summ,
+                                        int64_t summ_stride_h, int Hq, int Hkv, int Lq, int pages, int D, int dtype, float* ub,
+                                        rtk_stream_t stream) {
+    const char* who = "rtk_attention_page_bound";
+    RTK_CHECK_ARG(q && summ && ub, "%s: NULL q / summ / ub pointer", who);
+    RTK_CHECK_ARG(Hq >= 1 && Hkv >= 1 && Lq >= 1 && pages >= 1, "%s: Hq, Hkv, Lq and pages must be positive", who);
+    RTK_CHECK_ARG(Hq % Hkv == 0, "%s: Hq %d is not a multiple of Hkv %d", who, Hq, Hkv);
+    RTK_CHECK_ARG(Hkv <= 65535 && pages <= 0x3fffffff / 512, "%s: Hkv %d / pages %d too large", who, Hkv, pages);
+    const int rc = pages_check_envelope(who, D, dtype);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG((((uintptr_t)q | (uintptr_t)summ) & 15) == 0 && ((uintptr_t)ub & 3) == 0 && (q_stride_h * 2) % 16 == 0 &&
+                      (q_stride_l * 2) % 16 == 0 && (summ_stride_h * 2) % 16 == 0,
+                  "%s: q / summ and their strides must be multiples of 16 bytes, ub of 4", who);
+    RTK_CHECK_ARG(q_stride_h >= 0 && q_stride_l >= D && (Hkv == 1 || summ_stride_h >= (int64_t)pages * 2 * D),
+                  "%s: q_stride_l below head_dim, a negative stride, or summ_stride_h below pages * 2 * D", who);
+    const dim3 grid((unsigned)((pages + 4 * PG_WAVES - 1) / (4 * PG_WAVES)), (unsigned)Hkv);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == RTK_BF16)
+        hipLaunchKernelGGL((page_bound_kernel<RTK_BF16>), grid, dim3(PG_BLOCK), 0, st, (const char*)q, q_stride_h, q_stride_l,
+                           (const char*)summ, summ_stride_h, Hq / Hkv, Lq, pages, ub);
+    else
+        hipLaunchKernelGGL((page_bound_kernel<RTK_F16>), grid, dim3(PG_BLOCK), 0, st, (const char*)q, q_stride_h, q_stride_l,
+                           (const char*)summ, summ_stride_h, Hq / Hkv, Lq, pages, ub);
+    RTK_LAUNCH_CHECK("page_bound_kernel");
+    return RTK_OK;
+}

@@ -179,6 +179,15 @@ class FocusUnit(C.Structure):
                 ("head", _i64), ("first", _i64), ("n", _i64), ("keep", _i64), ("tail_src", _i64), ("tail", _i64), ("idx", _vp)]
 
 
+PAGE_ROWS = 32                 # RTK_PAGE_ROWS: region rows per page of the page-sparse decode (the decode kernel's key tile)
+PAGE_SUMMARY_MAX_UNITS = 64    # RTK_PAGE_SUMMARY_MAX_UNITS: units per kernel launch of rtk_pivotkv_page_summary_batched
+
+
+class PageSummaryUnit(C.Structure):
+    """rtk_page_summary_unit (include/retake_hip.h)."""
+    _fields_ = [("k", _vp), ("k_stride_h", _i64), ("first", _i64), ("n", _i64), ("summ", _vp), ("summ_stride_h", _i64)]
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -276,6 +285,14 @@ _SIGNATURES = {
     "rtk_pivotkv_rescore_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _vp, _sz, _vp]),
     "rtk_pivotkv_rescore_fp8k_batched": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _f, _i64, _i64, _vp, _sz, _vp]),
     "rtk_pivotkv_focus_gather_batched": (C.c_int, [_vp, _i, _vp]),
+    "rtk_pivotkv_page_summary_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp]),
+    "rtk_attention_page_bound": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "rtk_attention_decode_paged_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_paged": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i,
+                                         _vp, _i, _vp, _sz, _vp]),
+    "rtk_attention_decode_sparse_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_sparse": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i,
+                                          _vp, _i64, _i, _vp, _sz, _vp]),
     "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),

@@ -31,6 +31,8 @@ Where the rest lives (the names are re-exported here, and the other modules of t
     native_attention  chunk_attention, native_attention (causal offset from the HF mask), the fp8 row helpers
     _video_bound      the bounded video region: the sliding window and the video budget, planned and committed by one mechanism
     _focus            the question-focused decode cache: watch_question / focus, the rows a question's queries choose
+    _sparse_decode    the page-sparse decode route: sparse_decode(cache) / dense_decode(cache), per-page key bounds beside
+                      the rows (functions that take the cache; `attention` asks it while armed)
     _flush            the deferred eviction of a chunk: _flush, its one-call and stage-by-stage routes, what they call
     _update_stages    `update` stage by stage (_update_general): every shape the one-call hot path here does not serve
     _marks            restore points and branches: mark / rewind / crop / fork, never run during a prefill
@@ -44,7 +46,8 @@ from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
-from . import _flush as _fl, _focus, _marks, _native as nv, _update_stages as _us, _video_bound   # (`_flush` is the method)
+from . import (_flush as _fl, _focus, _marks, _native as nv, _sparse_decode, _update_stages as _us,   # (`_flush` is the method)
+               _video_bound)
 from ._cache_state import (CacheMark, _Batch, _CacheView, _LayerMark, _LayerStore, _Rotary, _Side, _Update,  # noqa: F401
                            _inv_stamp, _on_device, _version_of)
 from ._hf_cache import DynamicCache, _hf_dynamic_cache_is_legacy, _ListDynamicCache  # noqa: F401
@@ -90,7 +93,6 @@ class PivotKVCache(DynamicCache):
     # question focus (not in the reference; _focus)
     _watch = None                 # armed by watch_question: the capture's buffers (None: off, nothing is copied)
     focused_from = None           # a focused cache (PivotKVCache.focus): the parent's `video_end` it was focused at
-
     def __init__(self, config, reserve_tokens: Optional[int] = None, reserve_archive_tokens: Optional[int] = None) -> None:
         """reserve_tokens (not in the reference): tokens per layer this cache is expected to hold at most - compressed
         prompt + one uncompressed chunk + generation.  The first allocation of a layer takes that size, which saves the
@@ -271,6 +273,12 @@ class PivotKVCache(DynamicCache):
         self.window_dropped: List[int] = []   # per layer: rows the window has dropped so far (also counted as evicted)
         self.budget_dropped: List[int] = []   # ... and the budget
         self._attn_ws: Dict[Any, torch.Tensor] = {}
+        # page-sparse decode (not in the reference, a rule of this project's own - answer quality is not evaluated): the
+        # functions of retake/_sparse_decode.py take the cache - sparse_decode(cache, keep_rows) arms, dense_decode(cache)
+        # disarms.  They are NOT bound as methods: the class keeps exactly the names it had, and the state lives here
+        self._sparse = None               # the page index while armed (None: off, `attention` is exactly as without it)
+        self.sparse_attention_calls = 0   # attention calls that took rtk_attention_decode_sparse
+        self.page_summary_calls = 0       # rtk_pivotkv_page_summary_batched calls so far (one per device and arming)
 
     def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None, layer_idx=None):
         """The chunk's attention over the views `update` / `update_pre_rope` / `append_pre_rope` returned, in one HIP
@@ -278,6 +286,11 @@ class PivotKVCache(DynamicCache):
         kv_cache_dtype="fp8_e4m3": `layer_idx` names the layer whose archive precedes those views; query_offset counts
         over archive + views; a shape the library declines raises NotImplementedError (no other route reads the archive)."""
         archive = shared = None
+        if self._sparse is not None:   # _sparse_decode.sparse_decode armed: the page-sparse call where it serves, else the routes below
+            out = _sparse_decode.route(self, query_states, key_states, value_states, scaling, query_offset, layer_idx)
+            if out is not None:
+                self.attention_calls += 1
+                return out
         if self.kv_cache_dtype is not None:
             if layer_idx is None:
                 raise ValueError("PivotKVCache.attention needs layer_idx when kv_cache_dtype is set")
@@ -407,7 +420,10 @@ class PivotKVCache(DynamicCache):
           row_scores        the fp32 score buffers of the video regions - the key exists only with video_budget_rows on
           observe_queries   the layers' last rotated query rows - the key exists only with video_budget_rescore on (the
                             re-scoring's scratch counts as worker_scratch)
-          focus_queries     the layers' watched query rows - the key exists only while watch_question is armed."""
+          focus_queries     the layers' watched query rows - the key exists only while watch_question is armed
+          page_summaries    the per-page key bounds of the page-sparse decode, and
+          sparse_workspace  the per-layer workspaces of its calls (bounds, page lists, partials) - the keys exist only
+                            while sparse_decode is armed."""
         def nbytes(t):
             return 0 if t is None else t.numel() * t.element_size()
 
@@ -444,6 +460,8 @@ class PivotKVCache(DynamicCache):
             out["observe_queries"] = sum(nbytes(st.oq) for st in self._layers)
         if self._watch is not None:
             out["focus_queries"] = _focus.watched_bytes(self)
+        if self._sparse is not None:
+            out.update(_sparse_decode.sparse_bytes(self))
         out["worker_scratch"] = sum(nbytes(t) for t in self._ws.values()) + sum(nbytes(t) for sd in self._sides for t in sd.ws.values())
         out["attention_workspace"] = sum(nbytes(t) for t in self._attn_ws.values())
         out["total"] = sum(out.values())

@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (95 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (100 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -73,7 +73,9 @@
  *                                       rtk_attention_decode_sparse (+ their _workspace_bytes): per-page key bounds beside the
  *                                       rows, and a packed decode call that reads, per kv head and token, the pinned rows, the
  *                                       pages with the highest bound and the rows behind the video (opt-in:
- *                                       sparse_decode(cache) of retake/_sparse_decode.py)
+ *                                       sparse_decode(cache) of retake/_sparse_decode.py); rtk_pivotkv_page_summary_fp8k_batched,
+ *                                       rtk_attention_decode_paged_fp8kv, rtk_attention_decode_sparse_fp8kv: the same with the
+ *                                       pages in an fp8 archive (opt-in: sparse_decode(cache, archive=True))
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -1402,6 +1404,38 @@ int rtk_pivotkv_focus_gather_batched(const rtk_focus_unit* units, int n_units, r
  * first < 0, first > ve, ve > Lk, keep_pages outside [1, pages], q_offset < ve - 1 or < Lk - Lq, pointers or strides that
  * are not multiples of 16 bytes, a short or misaligned workspace.  The workspace queries return 0, with the message set,
  * for a shape the call would refuse.
+ *
+ * Over an fp8 archive (§K; opt-in: sparse_decode(cache, archive=True) on a cache with kv_cache_dtype) the region is the
+ * ARCHIVE: n = L8 rows, pages = ceil(L8 / 32), page p is archive rows [32 p, min(32 p + 32, L8)); the 16-bit buffer holds the
+ * pinned rows and everything behind the video and follows the archive, as in rtk_attention_decode_fp8kv.
+ * rtk_pivotkv_page_summary_fp8k_batched - rtk_pivotkv_page_summary_batched over e4m3 codes and scales: summ[g, p, 0 / 1, d] =
+ *   max / min over the existing rows j of page p of K[g, j, d] = dtype(float(code) * scale), rule 5 of §K (exact in the
+ *   model dtype), stored as above ([Hkv, pages, 2, D] of `dtype`, the same +-0 convention) - bit for bit
+ *   rtk_pivotkv_page_summary_batched over rtk_fp8kv_dequant of the same rows.  Row j of head g: codes at k8 + g * k8_stride_h
+ *   + j * D BYTES, scale at k_scale + g * scale_stride_h + j.  One wave per (kv head, page), each load instruction eight
+ *   whole 128-byte code rows, a row's scale loaded once per row; rows >= n are not read, neither codes nor scales.
+ *   RTK_BF16 / RTK_F16 with D == 128 (RTK_EUNSUPPORTED otherwise).  RTK_EINVAL, before any launch: NULL pointers, a negative
+ *   n, k8 / summ / their head strides not 16-byte aligned, k_scale not 4-byte aligned, a head stride below the rows of a
+ *   head, n * D at or above 2 GiB (the archive's limit per head).  A unit with n == 0 is skipped; 16 bytes of summaries per
+ *   (kv head, row) beside 132 bytes of K codes + scale.
+ * rtk_attention_decode_paged_fp8kv - rtk_attention_decode_fp8kv's arithmetic over the VIRTUAL key space of whole 32-key tiles
+ *       [ archive page list[g][0], list[g][1], .. list[g][keep_pages - 1] | 16-bit rows [0, Lk) ]
+ *   K = 32 keep_pages + Lk virtual keys; the splits are rtk_attention_decode's plan over K, the partials have its layout
+ *   (rtk_attention_decode_paged_fp8kv_workspace_bytes = nsplit * Hq * Lq * (D + 2) * 4) and the same second launch folds
+ *   them.  Archive rows a partial page names beyond L8 read as zero codes and zero scales (descriptors bounded at exactly
+ *   L8 * 128 and L8 * 4 bytes) and get logit -inf.  Only the 16-bit rows have a diagonal: q_offset counts 16-bit rows and
+ *   must be >= Lk - Lq; every archive row is visible to every query row.  Each list entry is read once per tile and clamped
+ *   into [0, pages - 1].  With the identity list the result equals rtk_attention_decode_fp8kv over the archive as it lies,
+ *   bit for bit; with a list that names the partial page last or not at all, that call over the gathered codes and scales.
+ * rtk_attention_decode_sparse_fp8kv - the chain in one call, as rtk_attention_decode_sparse: rtk_attention_page_bound on
+ *   summ, rtk_pivotkv_budget_select_batched, the fp8 paged kernel, the combine; the workspace is [ub | lists | partials] with
+ *   the same layout.  The summaries are 16-bit values of the keys the attention really uses, so the bound holds against the
+ *   dequantised keys.
+ * Envelope and errors of the two attention calls: those of rtk_attention_decode_fp8kv's shape (RTK_BF16 / RTK_F16, D == 128,
+ * (Hq / Hkv) * Lq <= 16 - RTK_EUNSUPPORTED otherwise), and RTK_EINVAL, before any launch, for NULL pointers, non-positive
+ * sizes, L8 < 1, keep_pages outside [1, pages], q_offset < Lk - Lq, pointers or strides that are not multiples of 16 bytes
+ * (scales: 4), a short or misaligned workspace.  The workspace queries return 0, with the message set, for a shape the call
+ * would refuse.  No atomics, no flags, no waiting between workgroups.
  * ------------------------------------------------------------------------------------------- */
 #define RTK_PAGE_ROWS 32
 typedef struct rtk_page_summary_unit {
@@ -1429,6 +1463,32 @@ int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, int64_t q_str
                                 int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
                                 int D, int dtype, float scale, int first, int ve, const void* summ, int64_t summ_stride_h,
                                 int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+
+typedef struct rtk_page_summary_fp8k_unit {
+    const void*  k8;             /* codes of archive row 0 of kv head 0 */
+    int64_t      k8_stride_h;    /* BYTES between kv heads, >= n*D */
+    const float* k_scale;        /* scale of row j of head g at k_scale + g*scale_stride_h + j */
+    int64_t      scale_stride_h; /* floats, >= n */
+    int64_t      n;              /* archive rows */
+    void*        summ;           /* out: [Hkv, ceil(n / 32), 2, D] of `dtype` */
+    int64_t      summ_stride_h;  /* elements between kv heads */
+} rtk_page_summary_fp8k_unit;
+int rtk_pivotkv_page_summary_fp8k_batched(const rtk_page_summary_fp8k_unit* units, int n_units, int Hkv, int D, int dtype,
+                                          rtk_stream_t stream);
+size_t rtk_attention_decode_paged_fp8kv_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int L8, int keep_pages, int D, int dtype);
+int rtk_attention_decode_paged_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                     int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                                     const float* k_scale, const float* v_scale, int L8, int64_t stride8_h, int64_t scale_stride_h,
+                                     void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D, int dtype, float scale,
+                                     const int32_t* list, int keep_pages, void* workspace, size_t workspace_bytes,
+                                     rtk_stream_t stream);
+size_t rtk_attention_decode_sparse_fp8kv_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int L8, int keep_pages, int D, int dtype);
+int rtk_attention_decode_sparse_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                      int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                                      const float* k_scale, const float* v_scale, int L8, int64_t stride8_h, int64_t scale_stride_h,
+                                      void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D, int dtype, float scale,
+                                      const void* summ, int64_t summ_stride_h, int keep_pages, void* workspace,
+                                      size_t workspace_bytes, rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

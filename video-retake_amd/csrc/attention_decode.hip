@@ -25,7 +25,8 @@
 // (rtk_attention_decode_shared); attn_decode_group_d128_kernel (rtk_attention_decode_group, below) serves one token of
 // several branches; attn_decode_wide_d128_kernel (attention_decode_wide.cuh, rtk_attention_decode_wide*) serves
 // 16 < R <= 64 packed rows as two to four column groups; attn_decode_paged_d128_kernel (attention_decode_paged.cuh,
-// rtk_attention_decode_paged / _sparse) reads the middle of ONE buffer through a per-kv-head page list.  The body, the group kernel and the wide kernel share
+// rtk_attention_decode_paged / _sparse) reads the middle of ONE buffer through a per-kv-head page list, and
+// attn_decode_paged_fp8kv_d128_kernel (the same file, rtk_attention_decode_paged_fp8kv / _sparse_fp8kv) the e4m3 archive.  The body, the group kernel and the wide kernel share
 // dec_step_off, dec_v_frag and dec_softmax_step; their tile loads, dequantise-and-stage step and four-wave fold are
 // written in each (as shared functions they compile the existing kernels differently).  Host side: the entry
 // points of the narrow and the wide family are decode_call with their family and segments - its checks and fall-throughs,
@@ -638,6 +639,46 @@ int paged_forward(const DecodePlan& pl, const AttnArgs& a, const PagedGeom& g, c
     return a.dtype == RTK_BF16 ? paged_launch<RTK_BF16>(pl, a, g, list, partials) : paged_launch<RTK_F16>(pl, a, g, list, partials);
 }
 
+// ---- page-sparse decode over an fp8 archive (rtk_attention_decode_paged_fp8kv / _sparse_fp8kv): the pages are the archive's ----
+// the shape checks of both calls, before anything is launched: those of rtk_attention_decode_fp8kv, then the pages;
+// `g` is filled on success (first = 0, ve = L8: the region is the archive)
+int paged8_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype, int keep_pages, PagedGeom& g) {
+    const int rc = decode_check_shape(who, DEC_NARROW, 1, Hq, Hkv, Lq, Lk, L8, 0, D, dtype);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG(L8 >= 1, "%s: L8 %d: the call needs an archive (rtk_attention_decode serves a cache without one)", who, L8);
+    const int pages = (L8 + DEC_T - 1) / DEC_T;
+    RTK_CHECK_ARG(keep_pages >= 1 && keep_pages <= pages, "%s: keep_pages %d is not in [1, pages = %d]", who, keep_pages, pages);
+    g = PagedGeom{0, L8, keep_pages, pages, (long long)keep_pages * DEC_T + Lk};
+    return RTK_OK;
+}
+// the operand checks: layout (RTK_EINVAL here, as for the 16-bit paged calls), then what rtk_attention_decode_fp8kv checks
+int paged8_check_operands(const char* who, const AttnArgs& a, const DecodeSegs& sg, Archive8& a8) {
+    const int rc = make_archive8(who, sg.k8, sg.v8, sg.k_scale, sg.v_scale, sg.L8, sg.sh8, sg.shs, a8);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG((((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out | (uintptr_t)sg.k8 | (uintptr_t)sg.v8) & 15) == 0 &&
+                      (a.q_sh * 2) % 16 == 0 && (a.q_sl * 2) % 16 == 0 && (a.kv_sh * 2) % 16 == 0 && (a.kv_sl * 2) % 16 == 0 &&
+                      sg.sh8 % 16 == 0,
+                  "%s: pointers and strides must be multiples of 16 bytes", who);
+    RTK_CHECK_ARG((((uintptr_t)sg.k_scale | (uintptr_t)sg.v_scale) & 3) == 0, "%s: the scales must be 4-byte aligned", who);
+    return attn_check_operands(who, a.q, a.q_sh, a.q_sl, a.k, a.v, a.kv_sh, a.kv_sl, a8.k8, a8.v8, a8.ks, a8.vs, a8.sh8, a8.shs, a.out,
+                               a.Lq, a.Lk, a.off, a.D, a.dtype, a.scale, 0, DEC_T);
+}
+// the fp8 paged kernel over `partials`, then the combine
+template <int DT>
+int paged8_launch(const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const PagedGeom& g, const int32_t* list, void* partials) {
+    const Partials p = split_partials(partials, pl.nsplit, a.Hq, a.Lq, 128);
+    hipLaunchKernelGGL((attn_decode_paged_fp8kv_d128_kernel<DT>), dim3((unsigned)pl.nsplit, (unsigned)a.Hkv), dim3(256), 0, a.st,
+                       (const char*)a.q, a.q_sh, a.q_sl, (const char*)a.k, (const char*)a.v, a.kv_sh, (uint32_t)(a.kv_sl * 2),
+                       rows_extent(a.Lk, a.kv_sl, 128, 2), p.acc, p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, base2_scale(a.scale),
+                       pl.keys_per_split, a8, list, g.keep_pages);
+    RTK_LAUNCH_CHECK("attn_decode_paged_fp8kv_d128_kernel");
+    return attn_combine<DT>(p, a.out, a.Hq, a.Lq, 128, pl.nsplit, a.st);
+}
+int paged8_forward(const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const PagedGeom& g, const int32_t* list, void* partials) {
+    return a.dtype == RTK_BF16 ? paged8_launch<RTK_BF16>(pl, a, a8, g, list, partials)
+                               : paged8_launch<RTK_F16>(pl, a, a8, g, list, partials);
+}
+
 }  // namespace
 }  // namespace rtk
 
@@ -865,4 +906,82 @@ extern "C" int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, in
     rc = rtk_pivotkv_budget_select_batched(sel.data(), Hkv, stream);
     if (rc != RTK_OK) return rc;
     return paged_forward(pl, a, g, lists, (char*)workspace + sl.partials_at);
+}
+
+// ---- page-sparse decode over an fp8 archive (retake_hip.h §U) ----
+extern "C" size_t rtk_attention_decode_paged_fp8kv_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int L8, int keep_pages, int D,
+                                                                   int dtype) {
+    PagedGeom g;
+    if (paged8_check_shape("rtk_attention_decode_paged_fp8kv_workspace_bytes", Hq, Hkv, Lq, Lk, L8, D, dtype, keep_pages, g) != RTK_OK)
+        return 0;
+    return decode_plan(Hq, Hkv, Lq, g.keys).ws_bytes;
+}
+
+extern "C" int rtk_attention_decode_paged_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                                int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                                                const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                                int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                                                int D, int dtype, float scale, const int32_t* list, int keep_pages, void* workspace,
+                                                size_t workspace_bytes, rtk_stream_t stream) {
+    const char* who = "rtk_attention_decode_paged_fp8kv";
+    RTK_CHECK_ARG(q && k && v && out && list, "%s: NULL q / k / v / out / list pointer", who);
+    const AttnArgs a{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                     scale, workspace, workspace_bytes, (hipStream_t)stream};
+    const DecodeSegs sg{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h};
+    PagedGeom g;
+    int rc = paged8_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype, keep_pages, g);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG(((uintptr_t)list & 3) == 0, "%s: list must be 4-byte aligned", who);
+    Archive8 a8;
+    rc = paged8_check_operands(who, a, sg, a8);
+    if (rc != RTK_OK) return rc;
+    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, g.keys);
+    rc = paged_check_workspace(who, "rtk_attention_decode_paged_fp8kv_workspace_bytes", pl.ws_bytes, workspace, workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    return paged8_forward(pl, a, a8, g, list, workspace);
+}
+
+extern "C" size_t rtk_attention_decode_sparse_fp8kv_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int L8, int keep_pages, int D,
+                                                                    int dtype) {
+    PagedGeom g;
+    if (paged8_check_shape("rtk_attention_decode_sparse_fp8kv_workspace_bytes", Hq, Hkv, Lq, Lk, L8, D, dtype, keep_pages, g) != RTK_OK)
+        return 0;
+    return sparse_layout(Hkv, g, decode_plan(Hq, Hkv, Lq, g.keys)).bytes;
+}
+
+extern "C" int rtk_attention_decode_sparse_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                                 int64_t kv_stride_h, int64_t kv_stride_l, const void* k8, const void* v8,
+                                                 const float* k_scale, const float* v_scale, int L8, int64_t stride8_h,
+                                                 int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
+                                                 int D, int dtype, float scale, const void* summ, int64_t summ_stride_h,
+                                                 int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream) {
+    const char* who = "rtk_attention_decode_sparse_fp8kv";
+    RTK_CHECK_ARG(q && k && v && out && summ, "%s: NULL q / k / v / out / summ pointer", who);
+    const AttnArgs a{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                     scale, workspace, workspace_bytes, (hipStream_t)stream};
+    const DecodeSegs sg{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h};
+    PagedGeom g;
+    int rc = paged8_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype, keep_pages, g);
+    if (rc != RTK_OK) return rc;
+    RTK_CHECK_ARG(((uintptr_t)summ & 15) == 0 && (summ_stride_h * 2) % 16 == 0 && summ_stride_h >= (int64_t)g.pages * 2 * D,
+                  "%s: summ must be 16-byte aligned with a head stride of at least pages * 2 * D = %lld elements", who,
+                  (long long)g.pages * 2 * D);
+    Archive8 a8;
+    rc = paged8_check_operands(who, a, sg, a8);
+    if (rc != RTK_OK) return rc;
+    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, g.keys);
+    const SparseLayout sl = sparse_layout(Hkv, g, pl);
+    rc = paged_check_workspace(who, "rtk_attention_decode_sparse_fp8kv_workspace_bytes", sl.bytes, workspace, workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    float* ub = (float*)workspace;
+    int32_t* lists = (int32_t*)((char*)workspace + sl.lists_at);
+    // the bound, the selection (one unit per kv head: the existing launchers as they are), the fp8 paged kernel, the combine
+    rc = rtk_attention_page_bound(q, q_stride_h, q_stride_l, summ, summ_stride_h, Hq, Hkv, Lq, g.pages, D, dtype, ub, stream);
+    if (rc != RTK_OK) return rc;
+    std::vector<rtk_budget_select_unit> sel((size_t)Hkv);
+    for (int h = 0; h < Hkv; ++h)
+        sel[h] = rtk_budget_select_unit{ub + (size_t)h * g.pages, lists + (size_t)h * g.keep_pages, g.pages, g.keep_pages};
+    rc = rtk_pivotkv_budget_select_batched(sel.data(), Hkv, stream);
+    if (rc != RTK_OK) return rc;
+    return paged8_forward(pl, a, a8, g, lists, (char*)workspace + sl.partials_at);
 }

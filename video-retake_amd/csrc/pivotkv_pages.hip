@@ -1,6 +1,7 @@
 // pivotkv_pages.hip - the page index of the page-sparse decode (retake_hip.h §U "Page-sparse decode"; NOT in the reference,
 // a rule of this project's own):
 //   page_summary_kernel   per arming: kmax / kmin [Hkv, pages, 2, D] of the stored keys of every layer of a device, one call
+//   page_summary_fp8k_kernel   the same over the e4m3 key rows of an fp8 archive (codes + scales), see at the kernel
 //   page_bound_kernel     per decode call: ub[g, p], an upper bound on every raw logit of kv head g's packed rows against
 //                         every key of page p
 // A page is RTK_PAGE_ROWS = 32 region rows: one wave tile of the packed decode kernel.
@@ -20,7 +21,7 @@
 // product is exact in fp32; the order of the additions is a function of the shape alone, and so are the bits.
 #include <algorithm>
 
-#include "common.cuh"
+#include "fp8kv.cuh"
 
 namespace rtk {
 namespace {
@@ -82,6 +83,77 @@ __global__ __launch_bounds__(PG_BLOCK) void page_summary_kernel(PageUnits units)
         for (int w = 0; w < 4; ++w)
             o[w] = g == 0 ? (unord16(hi[2 * w]) | (unord16(hi[2 * w + 1]) << 16)) : (unord16(lo[2 * w]) | (unord16(lo[2 * w + 1]) << 16));
         *(u32x4*)(un.summ + (int64_t)h * un.s_sh + (int64_t)p * 512 + 256 * g + 16 * c) = o;
+    }
+}
+
+// page_summary_fp8k_kernel - the same summaries over the e4m3 key rows of an fp8 archive: K[g, j, d] =
+// dtype(float(code) * scale), fp8kv.cuh's one dequantisation, so the summaries are 16-bit values of the keys the attention
+// really uses.  One wave per (kv head, page); a code row is 128 bytes = 8 lanes x 16 bytes, so a wave's load instruction
+// takes EIGHT whole rows (lane: codes 16 c .. 16 c + 15, c = lane & 7, of row 8 u + (lane >> 3), u = 0 .. 3) and the row's
+// scale is loaded once per row.  A lane folds its 4 rows element-wise on the ordered 16-bit keys, the eight row groups are
+// folded through the lanes 8, 16 and 32 apart, and the lanes of row group 0 / 1 store the 256 bytes of kmax / kmin, 32 each.
+// Rows >= n are not loaded, neither codes nor scales.  No LDS, no atomics, no scratch.
+// Roofline: HBM, n x 132 bytes read + pages x 512 written per kv head.
+struct PageDev8 {
+    const char* k8;        // codes of row 0 of kv head 0
+    const float* ks;       // scales of row 0 of kv head 0
+    char* summ;            // [Hkv, pages, 2, 128] 16-bit
+    int64_t k8_sh, s_sh;   // head strides, bytes
+    int64_t ks_sh;         // head stride, floats
+    int32_t n, pad;
+};
+struct PageUnits8 {
+    PageDev8 u[RTK_PAGE_SUMMARY_MAX_UNITS];
+};
+static_assert(sizeof(PageUnits8) <= 4096, "the units travel as a kernel argument");
+
+template <int DT> __global__ __launch_bounds__(PG_BLOCK) void page_summary_fp8k_kernel(PageUnits8 units) {
+    const PageDev8& un = units.u[blockIdx.z];
+    const int lane = threadIdx.x & (WAVE - 1), wave = uniform_int(threadIdx.x / WAVE);
+    const int c = lane & 7, g = lane >> 3;
+    const int n = un.n, pages = (n + PG_ROWS - 1) / PG_ROWS;
+    const int p = blockIdx.x * PG_WAVES + wave, h = blockIdx.y;
+    if (p >= pages) return;   // (wave-uniform: the grid is sized for the launch's largest unit)
+    const char* kp = un.k8 + (int64_t)h * un.k8_sh + (int64_t)PG_ROWS * p * 128 + 16 * c;
+    const float* sp = un.ks + (int64_t)h * un.ks_sh + (int64_t)PG_ROWS * p;
+    const int rows = min(PG_ROWS, n - PG_ROWS * p);   // of this page: >= 1
+    uint32_t hi[16], lo[16];   // keys of the lane's 16 elements: running max, running min
+#pragma unroll
+    for (int e = 0; e < 16; ++e) hi[e] = 0u, lo[e] = 0xffffu;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int r = 8 * u + g;
+        if (r < rows) {
+            const u32x4 codes = __builtin_nontemporal_load((const u32x4*)(kp + (int64_t)r * 128));
+            const float scale = __builtin_nontemporal_load(sp + r);
+            u32x4 t[2];
+            fp8_dequant16<DT>(codes, scale, t[0], t[1]);
+#pragma unroll
+            for (int w = 0; w < 8; ++w) {
+                const uint32_t x = t[w >> 2][w & 3];
+                const uint32_t a = ord16(x & 0xffffu), b = ord16(x >> 16);
+                hi[2 * w] = max(hi[2 * w], a), lo[2 * w] = min(lo[2 * w], a);
+                hi[2 * w + 1] = max(hi[2 * w + 1], b), lo[2 * w + 1] = min(lo[2 * w + 1], b);
+            }
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+#pragma unroll
+        for (int d = 8; d < WAVE; d *= 2) {
+            hi[e] = max(hi[e], (uint32_t)__shfl_xor((int)hi[e], d, WAVE));
+            lo[e] = min(lo[e], (uint32_t)__shfl_xor((int)lo[e], d, WAVE));
+        }
+    }
+    if (g < 2) {   // row group 0 stores kmax, group 1 kmin: 8 lanes x 32 bytes each
+        u32x4 o[2];
+#pragma unroll
+        for (int w = 0; w < 8; ++w)
+            o[w >> 2][w & 3] = g == 0 ? (unord16(hi[2 * w]) | (unord16(hi[2 * w + 1]) << 16))
+                                      : (unord16(lo[2 * w]) | (unord16(lo[2 * w + 1]) << 16));
+        char* out = un.summ + (int64_t)h * un.s_sh + (int64_t)p * 512 + 256 * g + 32 * c;
+        *(u32x4*)out = o[0];
+        *(u32x4*)(out + 16) = o[1];
     }
 }
 
@@ -178,6 +250,58 @@ extern "C" int rtk_pivotkv_page_summary_batched(const rtk_page_summary_unit* uni
         [&](const PageUnits& pu, int n) -> int {
             hipLaunchKernelGGL(page_summary_kernel, dim3(grid_x, (unsigned)Hkv, (unsigned)n), dim3(PG_BLOCK), 0, st, pu);
             RTK_LAUNCH_CHECK("page_summary_kernel");
+            grid_x = 0;
+            return RTK_OK;
+        });
+}
+
+extern "C" int rtk_pivotkv_page_summary_fp8k_batched(const rtk_page_summary_fp8k_unit* units, int n_units, int Hkv, int D,
+                                                     int dtype, rtk_stream_t stream) {
+    const char* who = "rtk_pivotkv_page_summary_fp8k_batched";
+    int rc = have_units(units, n_units, who);
+    if (rc <= 0) return rc;
+    RTK_CHECK_ARG(Hkv >= 1 && Hkv <= 65535, "%s: Hkv %d", who, Hkv);
+    rc = pages_check_envelope(who, D, dtype);
+    if (rc != RTK_OK) return rc;
+    for (int i = 0; i < n_units; ++i) {
+        const rtk_page_summary_fp8k_unit& u = units[i];
+        RTK_CHECK_ARG(u.n >= 0 && u.n <= 0x3fffffff, "%s: unit %d: n %lld", who, i, (long long)u.n);
+        if (u.n == 0) continue;
+        RTK_CHECK_ARG(u.k8 && u.k_scale && u.summ, "%s: unit %d: NULL k8 / k_scale / summ", who, i);
+        // the archive's limit (rtk_attention_decode_fp8kv): the codes of one head stay below 2 GiB
+        RTK_CHECK_ARG(u.n * D < (1ll << 31) - PG_ROWS * D, "%s: unit %d: n %lld: the codes of one head span 2 GiB or more", who, i,
+                      (long long)u.n);
+        const int64_t pages = (u.n + PG_ROWS - 1) / PG_ROWS;
+        RTK_CHECK_ARG((((uintptr_t)u.k8 | (uintptr_t)u.summ) & 15) == 0 && u.k8_stride_h % 16 == 0 && (u.summ_stride_h * 2) % 16 == 0 &&
+                          ((uintptr_t)u.k_scale & 3) == 0,
+                      "%s: unit %d: k8 / summ / head strides not 16-byte aligned, or k_scale not 4-byte aligned", who, i);
+        RTK_CHECK_ARG(u.k8_stride_h >= 0 && (Hkv == 1 || u.k8_stride_h >= u.n * D),
+                      "%s: unit %d: k8_stride_h %lld is smaller than the rows of a head", who, i, (long long)u.k8_stride_h);
+        RTK_CHECK_ARG(u.scale_stride_h >= 0 && (Hkv == 1 || u.scale_stride_h >= u.n),
+                      "%s: unit %d: scale_stride_h %lld is smaller than the rows of a head", who, i, (long long)u.scale_stride_h);
+        RTK_CHECK_ARG(u.summ_stride_h >= 0 && (Hkv == 1 || u.summ_stride_h >= pages * 2 * D),
+                      "%s: unit %d: summ_stride_h %lld is smaller than pages * 2 * D = %lld", who, i, (long long)u.summ_stride_h,
+                      (long long)(pages * 2 * D));
+    }
+    hipStream_t st = (hipStream_t)stream;
+    unsigned grid_x = 0;   // of the launch being filled: its largest unit's
+    return launch_units<PageUnits8>(
+        n_units,
+        [&](int i, PageDev8& dv) {
+            const rtk_page_summary_fp8k_unit& u = units[i];
+            if (u.n == 0) return false;
+            dv = PageDev8{(const char*)u.k8, u.k_scale, (char*)u.summ, u.k8_stride_h, u.summ_stride_h * 2, u.scale_stride_h, (int32_t)u.n, 0};
+            const unsigned pages = (unsigned)((u.n + PG_ROWS - 1) / PG_ROWS);
+            grid_x = std::max(grid_x, (pages + PG_WAVES - 1) / PG_WAVES);
+            return true;
+        },
+        [&](const PageUnits8& pu, int n) -> int {
+            const dim3 grid(grid_x, (unsigned)Hkv, (unsigned)n);
+            if (dtype == RTK_BF16)
+                hipLaunchKernelGGL((page_summary_fp8k_kernel<RTK_BF16>), grid, dim3(PG_BLOCK), 0, st, pu);
+            else
+                hipLaunchKernelGGL((page_summary_fp8k_kernel<RTK_F16>), grid, dim3(PG_BLOCK), 0, st, pu);
+            RTK_LAUNCH_CHECK("page_summary_fp8k_kernel");
             grid_x = 0;
             return RTK_OK;
         });

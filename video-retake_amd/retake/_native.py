@@ -188,6 +188,12 @@ class PageSummaryUnit(C.Structure):
     _fields_ = [("k", _vp), ("k_stride_h", _i64), ("first", _i64), ("n", _i64), ("summ", _vp), ("summ_stride_h", _i64)]
 
 
+class PageSummaryFp8kUnit(C.Structure):
+    """rtk_page_summary_fp8k_unit (include/retake_hip.h): the unit over the e4m3 key rows of an fp8 archive."""
+    _fields_ = [("k8", _vp), ("k8_stride_h", _i64), ("k_scale", _vp), ("scale_stride_h", _i64), ("n", _i64), ("summ", _vp),
+                ("summ_stride_h", _i64)]
+
+
 class UpdateIO(C.Structure):
     """rtk_update_io (include/retake_hip.h)."""
     _fields_ = [("q", _vp), ("q_stride_h", _i64), ("q_stride_l", _i64), ("k", _vp), ("k_stride_h", _i64),
@@ -293,6 +299,13 @@ _SIGNATURES = {
     "rtk_attention_decode_sparse_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
     "rtk_attention_decode_sparse": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _i,
                                           _vp, _i64, _i, _vp, _sz, _vp]),
+    "rtk_pivotkv_page_summary_fp8k_batched": (C.c_int, [_vp, _i, _i, _i, _i, _vp]),
+    "rtk_attention_decode_paged_fp8kv_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_paged_fp8kv": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp,
+                                               _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _sz, _vp]),
+    "rtk_attention_decode_sparse_fp8kv_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_sparse_fp8kv": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp,
+                                                _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64, _i, _vp, _sz, _vp]),
     "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),

@@ -1,6 +1,6 @@
 """The page-sparse decode rule (include/retake_hip.h "Page-sparse decode"; retake/_sparse_decode.py) in numpy / float64
 torch: summaries and selection exact, bound and attention in float64.  Tensors come in as they lie on any device; everything
-is computed on the CPU."""
+is computed on the CPU.  Below the rule: what the GPU tests of the paged calls and of the armed cache share."""
 import numpy as np
 import torch
 
@@ -77,3 +77,53 @@ def gather(K, V, first, ve, Lk, lists):
     assert len({len(i) for i in idx}) == 1
     pick = lambda T: torch.stack([T[0, g, idx[g]] for g in range(T.shape[1])])[None].contiguous()   # noqa: E731
     return pick(K), pick(V)
+
+
+# ---- shared by tests/test_attention_paged*_gpu.py and tests/test_sparse_decode*_gpu.py ----
+def dev():
+    return torch.device("cuda:0")
+
+
+def code(t):
+    import retake._native as nv
+
+    return nv.dtype_code(t)
+
+
+def with_slack(rows, slack, fill=0):
+    """[1, Hkv, L, ...] -> a buffer [1, Hkv, L + slack, ...] holding `rows`, `fill` behind them."""
+    buf = torch.full((1, rows.shape[1], rows.shape[2] + slack) + tuple(rows.shape[3:]), fill, dtype=rows.dtype, device=rows.device)
+    buf[:, :, :rows.shape[2]] = rows
+    return buf
+
+
+def call_painted(name, need, call):
+    """A native call, call(workspace pointer) -> rc, over a workspace of exactly `need` bytes with 64 painted bytes behind it,
+    which must stay as they were."""
+    import retake._native as nv
+
+    assert need, nv.lib.rtk_last_error()
+    ws = torch.empty(need + 64, dtype=torch.uint8, device=dev())
+    ws[need:] = 0x5a
+    nv.check(call(nv.ptr(ws)), name)
+    torch.cuda.synchronize()
+    assert (ws[need:] == 0x5a).all(), "the call wrote behind its workspace"
+
+
+def dequant(codes, scales, dtype):
+    from retake.native_attention import fp8_dequantize_rows
+
+    return fp8_dequantize_rows(codes.contiguous(), scales.contiguous(), dtype)
+
+
+def gather_archive(archive, n, lists):
+    """(k8, v8, k_scale, v_scale) [1, Hkv, >= n, ..] -> the same four over the existing rows of the pages each kv head's list
+    names, in list order (any ints: clamped into [0, pages - 1] as the kernel does); every head must name as many rows."""
+    idx = [gathered_rows(0, n, n, lst).to(archive[0].device) for lst in lists]
+    assert len({len(i) for i in idx}) == 1
+    return tuple(torch.stack([t[0, g].index_select(0, i) for g, i in enumerate(idx)])[None].contiguous() for t in archive)
+
+
+def token(d, route, seed, **kw):
+    """One decode token of test_focus_gpu's driver through the route -> [(rotated q, K view, V view)] per layer."""
+    return d.feed(d.cache, seed, d.text_ids(1), route, **kw)

@@ -11,6 +11,8 @@ import pytest
 import torch
 
 import attention_ref as ar
+import sparse_decode_ref as sr
+from sparse_decode_ref import code as _code, dequant as _dequant, dev
 from test_attention_decode_gpu import _against_fp64, _bits, _plan
 from test_sparse_decode_fp8_cpu import refusals_of_the_fp8_paged_calls
 
@@ -22,16 +24,6 @@ DTYPES = [torch.bfloat16, torch.float16]
 IDS = ["bf16", "fp16"]
 
 
-def dev():
-    return torch.device("cuda:0")
-
-
-def _code(t):
-    import retake._native as nv
-
-    return nv.dtype_code(t)
-
-
 class _Case:
     """q [1, Hq, Lq, D]; an archive of L8 rows and 16-bit buffers of Lk rows, each with SLACK rows of capacity behind."""
 
@@ -40,38 +32,18 @@ class _Case:
 
         q, k, v = ar.make_inputs(kind, seed, Hq, Hkv, Lq, L8 + Lk, D, dtype, dev())
         self.q, self.L8, self.Lk, self.Hkv, self.dtype = q, L8, Lk, Hkv, dtype
-        self.k8, self.v8 = (torch.zeros((1, Hkv, L8 + SLACK, D), dtype=torch.uint8, device=dev()) for _ in range(2))
-        self.ks, self.vs = (torch.ones((1, Hkv, L8 + SLACK), dtype=torch.float32, device=dev()) for _ in range(2))
-        for src, codes, scales in ((k, self.k8, self.ks), (v, self.v8, self.vs)):
-            c, s = fp8_quantize_rows(src[:, :, :L8].contiguous())
-            codes[:, :, :L8], scales[:, :, :L8] = c, s
-        self.k, self.v = (torch.zeros((1, Hkv, Lk + SLACK, D), dtype=dtype, device=dev()) for _ in range(2))
-        self.k[:, :, :Lk], self.v[:, :, :Lk] = k[:, :, L8:], v[:, :, L8:]
+        (k8, ks), (v8, vs) = (fp8_quantize_rows(src[:, :, :L8].contiguous()) for src in (k, v))
+        self.k8, self.v8 = sr.with_slack(k8, SLACK), sr.with_slack(v8, SLACK)
+        self.ks, self.vs = sr.with_slack(ks, SLACK, 1), sr.with_slack(vs, SLACK, 1)
+        self.k, self.v = sr.with_slack(k[:, :, L8:], SLACK), sr.with_slack(v[:, :, L8:], SLACK)
 
     def archive(self):
         n = self.L8
         return self.k8[:, :, :n], self.v8[:, :, :n], self.ks[:, :, :n], self.vs[:, :, :n]
 
-    def rows_of(self, lst):
-        """Archive rows of one kv head's list, clamped as the kernel clamps."""
-        pages, rows = -(-self.L8 // PAGE), []
-        for p in lst:
-            p = min(max(int(p), 0), pages - 1)
-            rows += range(PAGE * p, min(PAGE * p + PAGE, self.L8))
-        return torch.tensor(rows, dtype=torch.long, device=dev())
-
     def gathered(self, lists):
         """(k8, v8, k_scale, v_scale) of the listed pages' existing rows, [1, Hkv, L', D] / [1, Hkv, L']."""
-        idx = [self.rows_of(lists[g]) for g in range(self.Hkv)]
-        assert len({len(i) for i in idx}) == 1
-        pick = lambda T: torch.stack([T[0, g].index_select(0, idx[g]) for g in range(self.Hkv)])[None].contiguous()   # noqa: E731
-        return pick(self.k8), pick(self.v8), pick(self.ks), pick(self.vs)
-
-
-def _dequant(codes, scales, dtype):
-    from retake.native_attention import fp8_dequantize_rows
-
-    return fp8_dequantize_rows(codes.contiguous(), scales.contiguous(), dtype)
+        return sr.gather_archive((self.k8, self.v8, self.ks, self.vs), self.L8, lists)
 
 
 def _fp8kv(c, archive, off=None):
@@ -102,18 +74,12 @@ def _paged8(c, lists, off=None):
     lst = torch.as_tensor(lists).to(torch.int32).to(dev()).contiguous()
     keep = lst.shape[1]
     need = nv.lib.rtk_attention_decode_paged_fp8kv_workspace_bytes(Hq, Hkv, Lq, Lk, L8, keep, D, _code(q))
-    assert need, nv.lib.rtk_last_error()
-    assert need == _plan(Hkv, PAGE * keep + Lk)[0] * Hq * Lq * (D + 2) * 4
-    ws = torch.empty(need + 64, dtype=torch.uint8, device=dev())
-    ws[need:] = 0x5a
+    assert need == _plan(Hkv, PAGE * keep + Lk)[0] * Hq * Lq * (D + 2) * 4, nv.lib.rtk_last_error()
     out = torch.empty((1, Lq, Hq, D), dtype=q.dtype, device=dev())
-    nv.check(nv.lib.rtk_attention_decode_paged_fp8kv(nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(c.k), nv.ptr(c.v), c.k.stride(1),
-                                                     c.k.stride(2), nv.ptr(c.k8), nv.ptr(c.v8), nv.ptr(c.ks), nv.ptr(c.vs), L8,
-                                                     c.k8.stride(1), c.ks.stride(1), nv.ptr(out), Hq, Hkv, Lq, Lk,
-                                                     Lk - Lq if off is None else off, D, _code(q), D ** -0.5, nv.ptr(lst), keep,
-                                                     nv.ptr(ws), need, nv.stream()), "rtk_attention_decode_paged_fp8kv")
-    torch.cuda.synchronize()
-    assert (ws[need:] == 0x5a).all(), "the call wrote behind its workspace"
+    sr.call_painted("rtk_attention_decode_paged_fp8kv", need, lambda ws: nv.lib.rtk_attention_decode_paged_fp8kv(
+        nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(c.k), nv.ptr(c.v), c.k.stride(1), c.k.stride(2), nv.ptr(c.k8), nv.ptr(c.v8),
+        nv.ptr(c.ks), nv.ptr(c.vs), L8, c.k8.stride(1), c.ks.stride(1), nv.ptr(out), Hq, Hkv, Lq, Lk, Lk - Lq if off is None else off, D,
+        _code(q), D ** -0.5, nv.ptr(lst), keep, ws, need, nv.stream()))
     return out, need
 
 

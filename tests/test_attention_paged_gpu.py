@@ -8,22 +8,13 @@ import pytest
 import torch
 
 import sparse_decode_ref as sr
+from sparse_decode_ref import code as _code, dev
 from test_attention_decode_gpu import _against_fp64, _bits, _plan
 from test_sparse_decode_cpu import refusals_of_the_paged_calls
 
 pytestmark = pytest.mark.gpu
 D, PAGE = 128, 32
 SLACK = 37   # rows of the buffers behind Lk
-
-
-def dev():
-    return torch.device("cuda:0")
-
-
-def _code(t):
-    import retake._native as nv
-
-    return nv.dtype_code(t)
 
 
 def _make(seed, Hq, Hkv, Lq, Lk, dtype, q_gain=1.0):
@@ -58,16 +49,10 @@ def _paged(q, k, v, Lk, first, ve, lists, off=None):
     Hkv, keep = k.shape[1], lists.shape[1]
     lst = lists.to(torch.int32).to(dev()).contiguous()
     need = nv.lib.rtk_attention_decode_paged_workspace_bytes(Hq, Hkv, Lq, Lk, first, ve, keep, D, _code(q))
-    assert need, nv.lib.rtk_last_error()
-    ws = torch.empty(need + 64, dtype=torch.uint8, device=dev())
-    ws[need:] = 0x5a
     out = torch.empty((1, Lq, Hq, D), dtype=q.dtype, device=dev())
-    nv.check(nv.lib.rtk_attention_decode_paged(nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2),
-                                               nv.ptr(out), Hq, Hkv, Lq, Lk, Lk - Lq if off is None else off, D, _code(q),
-                                               D ** -0.5, first, ve, nv.ptr(lst), keep, nv.ptr(ws), need, nv.stream()),
-             "rtk_attention_decode_paged")
-    torch.cuda.synchronize()
-    assert (ws[need:] == 0x5a).all(), "the call wrote behind its workspace"
+    sr.call_painted("rtk_attention_decode_paged", need, lambda ws: nv.lib.rtk_attention_decode_paged(
+        nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2), nv.ptr(out), Hq, Hkv, Lq, Lk,
+        Lk - Lq if off is None else off, D, _code(q), D ** -0.5, first, ve, nv.ptr(lst), keep, ws, need, nv.stream()))
     return out
 
 

@@ -12,6 +12,7 @@ import torch
 
 import retake._sparse_decode as sd
 import sparse_decode_ref as sr
+from sparse_decode_ref import dequant as _dequant, token as _token
 from test_attention_decode_gpu import _against_fp64
 from test_focus_gpu import D, LAYERS, QUESTION, TEXT, _Drv, _qkv
 from test_rewind_gpu import _bits, _same, _same_state, _state, dev
@@ -79,17 +80,6 @@ def _parent(*key):
     return d.fresh()
 
 
-def _token(d, route, seed, **kw):
-    """One decode token through the route -> [(rotated q, K view, V view)] per layer."""
-    return d.feed(d.cache, seed, d.text_ids(1), route, **kw)
-
-
-def _dequant(codes, scales, dtype):
-    from retake.native_attention import fp8_dequantize_rows
-
-    return fp8_dequantize_rows(codes.contiguous(), scales.contiguous(), dtype)
-
-
 def _dequant_keys(cache, l, dtype):
     """The layer's archived keys as the attention uses them, [Hkv, n, D]."""
     a = cache.archive(l)
@@ -98,10 +88,7 @@ def _dequant_keys(cache, l, dtype):
 
 def _gathered(cache, l, lists):
     """(k8, v8, k_scale, v_scale) of the pages each kv head's list names: their existing rows, in list order."""
-    n = cache.archive_len(l)
-    idx = [torch.cat([torch.arange(PAGE * p, min(PAGE * p + PAGE, n)) for p in lists[g].tolist()]).to(dev()) for g in range(Hkv)]
-    assert len({len(i) for i in idx}) == 1
-    return tuple(torch.stack([t[0, g].index_select(0, idx[g]) for g in range(Hkv)])[None].contiguous() for t in cache.archive(l))
+    return sr.gather_archive(cache.archive(l), cache.archive_len(l), lists)
 
 
 @pytest.mark.parametrize("dtype", DTYPES, ids=IDS)

@@ -9,6 +9,7 @@ import torch
 
 import retake._sparse_decode as sd
 import sparse_decode_ref as sr
+from sparse_decode_ref import token as _token
 from test_attention_decode_gpu import _against_fp64
 from test_focus_gpu import D, L, LAYERS, QUESTION, TEXT, _Drv, _build, _geometry, _parent
 from test_rewind_gpu import _bits, _same_state, _state, dev
@@ -18,11 +19,6 @@ DTYPES = [torch.bfloat16, torch.float16]
 IDS = ["bf16", "fp16"]
 Hq, Hkv, CHUNKS, PAGE = 4, 2, 5, 32
 KEEP_ROWS = 96   # 3 of the 10 pages
-
-
-def _token(d, route, seed, **kw):
-    """One decode token through the route -> [(rotated q, K view, V view)] per layer."""
-    return d.feed(d.cache, seed, d.text_ids(1), route, **kw)
 
 
 def _fresh(d):

@@ -30,7 +30,9 @@
 // dec_step_off, dec_v_frag and dec_softmax_step; their tile loads, dequantise-and-stage step and four-wave fold are
 // written in each (as shared functions they compile the existing kernels differently).  Host side: the entry
 // points of the narrow and the wide family are decode_call with their family and segments - its checks and fall-throughs,
-// then decode_forward (operands, plan, workspace, dtype) -> decode_launch -> decode_launch_d128, the one launcher.
+// then decode_forward (operands, plan, workspace, dtype) -> decode_launch -> decode_launch_d128, the one launcher; the
+// four page-sparse entry points are paged_call with their names, their kind (16-bit rows / fp8 archive) and a page list
+// or summaries - one shape check, one operand check, one bound -> select -> paged chain, one launcher.
 // FP8 = true: the keys are [e4m3 archive | 16-bit rows], counted in a key space where the archive is padded to whole
 // 32-key tiles (a tile is of one kind).  Archive tiles are dequantised (fp8_dequant16) into the registers / the LDS image
 // a 16-bit tile of the dequantised rows would have left, so with L8 % 32 == 0 every fp32 sum is grouped as in the 16-bit
@@ -571,90 +573,46 @@ int group_launch(const GroupPlan& gp, const GroupArgs& ga, const Archive8& a8, c
     return attn_combine<DT>(p, out, heads, 1, 128, nsplit, st);
 }
 
-// ---- page-sparse decode (rtk_attention_decode_paged / _sparse; the kernel: attention_decode_paged.cuh) ----
-// what both entry points take beside the common decode arguments, and what follows from it
+// ---- page-sparse decode (rtk_attention_decode_{paged,sparse}{,_fp8kv}; the kernels: attention_decode_paged.cuh) ----
+// The four calls are paged_call (below) with their names and what they take: `arch8` - the pages are the e4m3 archive's
+// (first = 0, ve = L8: the region is the archive), else rows [first, ve) of k / v - and a page list or, `sparse`, summaries.
 struct PagedGeom {
     int first, ve, keep_pages;
     int pages;             // ceil((ve - first) / 32)
-    long long keys;        // the virtual key count: head padded to whole tiles + keep_pages tiles + the tail
+    long long keys;        // the virtual key count: head padded to whole tiles + keep_pages tiles + the rows after the pages
 };
-// the shape checks of the paged calls, before anything is launched; `g` is filled on success
-int paged_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int D, int dtype, int first, int ve, int keep_pages,
-                      PagedGeom& g) {
-    int rc = attn_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype);
+// the shape checks of the paged calls, before anything is launched: those of rtk_attention_decode / _fp8kv, then the
+// pages; `g` is filled on success
+int paged_check_shape(const char* who, bool arch8, int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype, int first, int ve,
+                      int keep_pages, PagedGeom& g) {
+    const int rc = decode_check_shape(who, DEC_NARROW, arch8, Hq, Hkv, Lq, Lk, L8, 0, D, dtype);
     if (rc != RTK_OK) return rc;
-    rc = decode_check_envelope(who, DEC_NARROW, Hq, Hkv, Lq, D, dtype);
-    if (rc != RTK_OK) return rc;
-    RTK_CHECK_ARG(first >= 0 && first <= ve, "%s: first %d is not in [0, ve = %d]", who, first, ve);
-    RTK_CHECK_ARG(ve <= Lk, "%s: ve %d exceeds Lk %d", who, ve, Lk);
+    if (arch8) {
+        RTK_CHECK_ARG(L8 >= 1, "%s: L8 %d: the call needs an archive (rtk_attention_decode serves a cache without one)", who, L8);
+        first = 0, ve = L8;
+    } else {
+        RTK_CHECK_ARG(first >= 0 && first <= ve, "%s: first %d is not in [0, ve = %d]", who, first, ve);
+        RTK_CHECK_ARG(ve <= Lk, "%s: ve %d exceeds Lk %d", who, ve, Lk);
+    }
     const int pages = (int)(((long long)ve - first + DEC_T - 1) / DEC_T);
     RTK_CHECK_ARG(keep_pages >= 1 && keep_pages <= pages, "%s: keep_pages %d is not in [1, pages = %d]", who, keep_pages, pages);
-    if (Lk > 0x3fffffff - 2 * DEC_T) {
+    if (!arch8 && Lk > 0x3fffffff - 2 * DEC_T) {
         set_error("%s: unsupported extent: %d keys", who, Lk);
         return RTK_EUNSUPPORTED;
     }
     g = PagedGeom{first, ve, keep_pages, pages,
-                  ((long long)first + DEC_T - 1) / DEC_T * DEC_T + (long long)keep_pages * DEC_T + (Lk - ve)};
+                  ((long long)first + DEC_T - 1) / DEC_T * DEC_T + (long long)keep_pages * DEC_T + (arch8 ? Lk : Lk - ve)};
     return RTK_OK;
 }
-// the operand checks: layout (RTK_EINVAL here, as retake_hip.h states for these calls), then what rtk_attention_decode checks
-int paged_check_operands(const char* who, const AttnArgs& a, const PagedGeom& g) {
-    RTK_CHECK_ARG(a.off >= g.ve - 1, "%s: q_offset %d < ve - 1 = %d (every query row sees the whole region)", who, a.off, g.ve - 1);
-    RTK_CHECK_ARG((((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out) & 15) == 0 && (a.q_sh * 2) % 16 == 0 &&
-                      (a.q_sl * 2) % 16 == 0 && (a.kv_sh * 2) % 16 == 0 && (a.kv_sl * 2) % 16 == 0,
-                  "%s: pointers and strides must be multiples of 16 bytes", who);
-    return attn_check_operands(who, a.q, a.q_sh, a.q_sl, a.k, a.v, a.kv_sh, a.kv_sl, nullptr, nullptr, nullptr, nullptr, 0, 0, a.out,
-                               a.Lq, a.Lk, a.off, a.D, a.dtype, a.scale, 0, DEC_T);
-}
-inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
-// the workspace of rtk_attention_decode_sparse: [ub fp32 [Hkv, pages] | lists int32 [Hkv, keep_pages] | partials], each part
-// starting at a multiple of 16 bytes
-struct SparseLayout {
-    size_t lists_at, partials_at, bytes;
-};
-SparseLayout sparse_layout(int Hkv, const PagedGeom& g, const DecodePlan& pl) {
-    SparseLayout s;
-    s.lists_at = align16((size_t)Hkv * g.pages * sizeof(float));
-    s.partials_at = s.lists_at + align16((size_t)Hkv * g.keep_pages * sizeof(int32_t));
-    s.bytes = s.partials_at + pl.ws_bytes;
-    return s;
-}
-int paged_check_workspace(const char* who, const char* query, size_t need, const void* workspace, size_t workspace_bytes) {
-    RTK_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes; query %s)", who,
-                  workspace ? workspace_bytes : (size_t)0, need, query);
-    RTK_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
-    return RTK_OK;
-}
-// the paged kernel over `partials`, then the combine
-template <int DT> int paged_launch(const DecodePlan& pl, const AttnArgs& a, const PagedGeom& g, const int32_t* list, void* partials) {
-    const Partials p = split_partials(partials, pl.nsplit, a.Hq, a.Lq, 128);
-    hipLaunchKernelGGL((attn_decode_paged_d128_kernel<DT>), dim3((unsigned)pl.nsplit, (unsigned)a.Hkv), dim3(256), 0, a.st,
-                       (const char*)a.q, a.q_sh, a.q_sl, (const char*)a.k, (const char*)a.v, a.kv_sh, (uint32_t)(a.kv_sl * 2), p.acc,
-                       p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, base2_scale(a.scale), pl.keys_per_split, g.first, g.ve, list,
-                       g.keep_pages);
-    RTK_LAUNCH_CHECK("attn_decode_paged_d128_kernel");
-    return attn_combine<DT>(p, a.out, a.Hq, a.Lq, 128, pl.nsplit, a.st);
-}
-int paged_forward(const DecodePlan& pl, const AttnArgs& a, const PagedGeom& g, const int32_t* list, void* partials) {
-    return a.dtype == RTK_BF16 ? paged_launch<RTK_BF16>(pl, a, g, list, partials) : paged_launch<RTK_F16>(pl, a, g, list, partials);
-}
-
-// ---- page-sparse decode over an fp8 archive (rtk_attention_decode_paged_fp8kv / _sparse_fp8kv): the pages are the archive's ----
-// the shape checks of both calls, before anything is launched: those of rtk_attention_decode_fp8kv, then the pages;
-// `g` is filled on success (first = 0, ve = L8: the region is the archive)
-int paged8_check_shape(const char* who, int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype, int keep_pages, PagedGeom& g) {
-    const int rc = decode_check_shape(who, DEC_NARROW, 1, Hq, Hkv, Lq, Lk, L8, 0, D, dtype);
-    if (rc != RTK_OK) return rc;
-    RTK_CHECK_ARG(L8 >= 1, "%s: L8 %d: the call needs an archive (rtk_attention_decode serves a cache without one)", who, L8);
-    const int pages = (L8 + DEC_T - 1) / DEC_T;
-    RTK_CHECK_ARG(keep_pages >= 1 && keep_pages <= pages, "%s: keep_pages %d is not in [1, pages = %d]", who, keep_pages, pages);
-    g = PagedGeom{0, L8, keep_pages, pages, (long long)keep_pages * DEC_T + Lk};
-    return RTK_OK;
-}
-// the operand checks: layout (RTK_EINVAL here, as for the 16-bit paged calls), then what rtk_attention_decode_fp8kv checks
-int paged8_check_operands(const char* who, const AttnArgs& a, const DecodeSegs& sg, Archive8& a8) {
-    const int rc = make_archive8(who, sg.k8, sg.v8, sg.k_scale, sg.v_scale, sg.L8, sg.sh8, sg.shs, a8);
-    if (rc != RTK_OK) return rc;
+// the operand checks: the archive (`a8` stays empty without), layout (RTK_EINVAL here, as retake_hip.h states for these
+// calls), then what rtk_attention_decode / _fp8kv checks
+int paged_check_operands(const char* who, bool arch8, const AttnArgs& a, const DecodeSegs& sg, const PagedGeom& g, Archive8& a8) {
+    if (arch8) {
+        const int rc = make_archive8(who, sg.k8, sg.v8, sg.k_scale, sg.v_scale, sg.L8, sg.sh8, sg.shs, a8);
+        if (rc != RTK_OK) return rc;
+    } else {
+        RTK_CHECK_ARG(a.off >= g.ve - 1, "%s: q_offset %d < ve - 1 = %d (every query row sees the whole region)", who, a.off, g.ve - 1);
+    }
     RTK_CHECK_ARG((((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v | (uintptr_t)a.out | (uintptr_t)sg.k8 | (uintptr_t)sg.v8) & 15) == 0 &&
                       (a.q_sh * 2) % 16 == 0 && (a.q_sl * 2) % 16 == 0 && (a.kv_sh * 2) % 16 == 0 && (a.kv_sl * 2) % 16 == 0 &&
                       sg.sh8 % 16 == 0,
@@ -663,20 +621,96 @@ int paged8_check_operands(const char* who, const AttnArgs& a, const DecodeSegs& 
     return attn_check_operands(who, a.q, a.q_sh, a.q_sl, a.k, a.v, a.kv_sh, a.kv_sl, a8.k8, a8.v8, a8.ks, a8.vs, a8.sh8, a8.shs, a.out,
                                a.Lq, a.Lk, a.off, a.D, a.dtype, a.scale, 0, DEC_T);
 }
-// the fp8 paged kernel over `partials`, then the combine
+inline size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+// the workspace of a sparse call: [ub fp32 [Hkv, pages] | lists int32 [Hkv, keep_pages] | partials], each part starting at
+// a multiple of 16 bytes; a paged call's is the partials alone
+struct SparseLayout {
+    size_t lists_at, partials_at, bytes;
+};
+SparseLayout sparse_layout(bool sparse, int Hkv, const PagedGeom& g, const DecodePlan& pl) {
+    SparseLayout s{0, 0, pl.ws_bytes};
+    if (sparse) {
+        s.lists_at = align16((size_t)Hkv * g.pages * sizeof(float));
+        s.partials_at = s.lists_at + align16((size_t)Hkv * g.keep_pages * sizeof(int32_t));
+        s.bytes = s.partials_at + pl.ws_bytes;
+    }
+    return s;
+}
+int paged_check_workspace(const char* who, const char* query, size_t need, const void* workspace, size_t workspace_bytes) {
+    RTK_CHECK_ARG(workspace && workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes; query %s)", who,
+                  workspace ? workspace_bytes : (size_t)0, need, query);
+    RTK_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", who);
+    return RTK_OK;
+}
+// One launch of the paged kernel of the call's kind over `partials`, then the combine.  (The two kernels' parameter lists
+// differ in their middle - kv_bytes - so the launch is written per kind, not as decode_launch_d128's trailing pack.)
 template <int DT>
-int paged8_launch(const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const PagedGeom& g, const int32_t* list, void* partials) {
+int paged_launch(bool arch8, const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const PagedGeom& g, const int32_t* list,
+                 void* partials) {
     const Partials p = split_partials(partials, pl.nsplit, a.Hq, a.Lq, 128);
-    hipLaunchKernelGGL((attn_decode_paged_fp8kv_d128_kernel<DT>), dim3((unsigned)pl.nsplit, (unsigned)a.Hkv), dim3(256), 0, a.st,
-                       (const char*)a.q, a.q_sh, a.q_sl, (const char*)a.k, (const char*)a.v, a.kv_sh, (uint32_t)(a.kv_sl * 2),
-                       rows_extent(a.Lk, a.kv_sl, 128, 2), p.acc, p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, base2_scale(a.scale),
-                       pl.keys_per_split, a8, list, g.keep_pages);
-    RTK_LAUNCH_CHECK("attn_decode_paged_fp8kv_d128_kernel");
+    const dim3 grid((unsigned)pl.nsplit, (unsigned)a.Hkv);
+    const char *q = (const char*)a.q, *k = (const char*)a.k, *v = (const char*)a.v;
+    const uint32_t row_bytes = (uint32_t)(a.kv_sl * 2);
+    const float c2 = base2_scale(a.scale);
+    if (arch8)
+        hipLaunchKernelGGL((attn_decode_paged_fp8kv_d128_kernel<DT>), grid, dim3(256), 0, a.st, q, a.q_sh, a.q_sl, k, v, a.kv_sh,
+                           row_bytes, rows_extent(a.Lk, a.kv_sl, 128, 2), p.acc, p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, c2,
+                           pl.keys_per_split, a8, list, g.keep_pages);
+    else
+        hipLaunchKernelGGL((attn_decode_paged_d128_kernel<DT>), grid, dim3(256), 0, a.st, q, a.q_sh, a.q_sl, k, v, a.kv_sh, row_bytes,
+                           p.acc, p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, c2, pl.keys_per_split, g.first, g.ve, list,
+                           g.keep_pages);
+    RTK_LAUNCH_CHECK(arch8 ? "attn_decode_paged_fp8kv_d128_kernel" : "attn_decode_paged_d128_kernel");
     return attn_combine<DT>(p, a.out, a.Hq, a.Lq, 128, pl.nsplit, a.st);
 }
-int paged8_forward(const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const PagedGeom& g, const int32_t* list, void* partials) {
-    return a.dtype == RTK_BF16 ? paged8_launch<RTK_BF16>(pl, a, a8, g, list, partials)
-                               : paged8_launch<RTK_F16>(pl, a, a8, g, list, partials);
+
+// A workspace query of the four: 0 with the error set for a shape the call does not take
+size_t paged_query(const char* query, bool arch8, bool sparse, int Hq, int Hkv, int Lq, int Lk, int L8, int first, int ve,
+                   int keep_pages, int D, int dtype) {
+    PagedGeom g;
+    if (paged_check_shape(query, arch8, Hq, Hkv, Lq, Lk, L8, D, dtype, first, ve, keep_pages, g) != RTK_OK) return 0;
+    return sparse_layout(sparse, Hkv, g, decode_plan(Hq, Hkv, Lq, g.keys)).bytes;
+}
+
+// An entry point of the four (`query`: the one that sizes its workspace; `sg`: its archive, empty for the 16-bit kind;
+// `pick`: its page list [Hkv, keep_pages] or, `sparse`, its summaries with head stride summ_sh): the checks in the order
+// retake_hip.h states, then the paged kernel and the combine - after, `sparse`, the bound and the selection (one unit per
+// kv head: the existing launchers as they are) have written the lists into the workspace.
+int paged_call(const char* who, const char* query, bool arch8, bool sparse, const AttnArgs& a, const DecodeSegs& sg, int first, int ve,
+               int keep_pages, const void* pick, int64_t summ_sh) {
+    RTK_CHECK_ARG(a.q && a.k && a.v && a.out && pick, "%s: NULL q / k / v / out / %s pointer", who, sparse ? "summ" : "list");
+    PagedGeom g;
+    int rc = paged_check_shape(who, arch8, a.Hq, a.Hkv, a.Lq, a.Lk, sg.L8, a.D, a.dtype, first, ve, keep_pages, g);
+    if (rc != RTK_OK) return rc;
+    if (sparse)
+        RTK_CHECK_ARG(((uintptr_t)pick & 15) == 0 && (summ_sh * 2) % 16 == 0 && summ_sh >= (int64_t)g.pages * 2 * a.D,
+                      "%s: summ must be 16-byte aligned with a head stride of at least pages * 2 * D = %lld elements", who,
+                      (long long)g.pages * 2 * a.D);
+    else
+        RTK_CHECK_ARG(((uintptr_t)pick & 3) == 0, "%s: list must be 4-byte aligned", who);
+    Archive8 a8{};
+    rc = paged_check_operands(who, arch8, a, sg, g, a8);
+    if (rc != RTK_OK) return rc;
+    const DecodePlan pl = decode_plan(a.Hq, a.Hkv, a.Lq, g.keys);
+    const SparseLayout sl = sparse_layout(sparse, a.Hkv, g, pl);
+    rc = paged_check_workspace(who, query, sl.bytes, a.workspace, a.workspace_bytes);
+    if (rc != RTK_OK) return rc;
+    const int32_t* list = (const int32_t*)pick;
+    if (sparse) {
+        float* ub = (float*)a.workspace;
+        int32_t* lists = (int32_t*)((char*)a.workspace + sl.lists_at);
+        rc = rtk_attention_page_bound(a.q, a.q_sh, a.q_sl, pick, summ_sh, a.Hq, a.Hkv, a.Lq, g.pages, a.D, a.dtype, ub, (rtk_stream_t)a.st);
+        if (rc != RTK_OK) return rc;
+        std::vector<rtk_budget_select_unit> sel((size_t)a.Hkv);
+        for (int h = 0; h < a.Hkv; ++h)
+            sel[h] = rtk_budget_select_unit{ub + (size_t)h * g.pages, lists + (size_t)h * g.keep_pages, g.pages, g.keep_pages};
+        rc = rtk_pivotkv_budget_select_batched(sel.data(), a.Hkv, (rtk_stream_t)a.st);
+        if (rc != RTK_OK) return rc;
+        list = lists;
+    }
+    void* partials = (char*)a.workspace + sl.partials_at;
+    return a.dtype == RTK_BF16 ? paged_launch<RTK_BF16>(arch8, pl, a, a8, g, list, partials)
+                               : paged_launch<RTK_F16>(arch8, pl, a, a8, g, list, partials);
 }
 
 }  // namespace
@@ -837,41 +871,25 @@ extern "C" int rtk_attention_decode_group(const rtk_decode_branch* branches, int
     return group_launch<RTK_F16>(gp, ga, a8, s16, out, Hkv, c2, workspace, (hipStream_t)stream);
 }
 
-// ---- page-sparse decode (retake_hip.h §U) ----
+// ---- page-sparse decode (retake_hip.h §U): paged_call with the call's names, kind and operands ----
 extern "C" size_t rtk_attention_decode_paged_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages,
                                                              int D, int dtype) {
-    PagedGeom g;
-    if (paged_check_shape("rtk_attention_decode_paged_workspace_bytes", Hq, Hkv, Lq, Lk, D, dtype, first, ve, keep_pages, g) != RTK_OK)
-        return 0;
-    return decode_plan(Hq, Hkv, Lq, g.keys).ws_bytes;
+    return paged_query("rtk_attention_decode_paged_workspace_bytes", false, false, Hq, Hkv, Lq, Lk, 0, first, ve, keep_pages, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_paged(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
                                           int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
                                           int q_offset, int D, int dtype, float scale, int first, int ve, const int32_t* list,
                                           int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream) {
-    const char* who = "rtk_attention_decode_paged";
-    RTK_CHECK_ARG(q && k && v && out && list, "%s: NULL q / k / v / out / list pointer", who);
-    const AttnArgs a{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
-                     scale, workspace, workspace_bytes, (hipStream_t)stream};
-    PagedGeom g;
-    int rc = paged_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype, first, ve, keep_pages, g);
-    if (rc != RTK_OK) return rc;
-    RTK_CHECK_ARG(((uintptr_t)list & 3) == 0, "%s: list must be 4-byte aligned", who);
-    rc = paged_check_operands(who, a, g);
-    if (rc != RTK_OK) return rc;
-    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, g.keys);
-    rc = paged_check_workspace(who, "rtk_attention_decode_paged_workspace_bytes", pl.ws_bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    return paged_forward(pl, a, g, list, workspace);
+    return paged_call("rtk_attention_decode_paged", "rtk_attention_decode_paged_workspace_bytes", false, false,
+                      AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                               scale, workspace, workspace_bytes, (hipStream_t)stream},
+                      DecodeSegs{}, first, ve, keep_pages, list, 0);
 }
 
 extern "C" size_t rtk_attention_decode_sparse_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages,
                                                               int D, int dtype) {
-    PagedGeom g;
-    if (paged_check_shape("rtk_attention_decode_sparse_workspace_bytes", Hq, Hkv, Lq, Lk, D, dtype, first, ve, keep_pages, g) != RTK_OK)
-        return 0;
-    return sparse_layout(Hkv, g, decode_plan(Hq, Hkv, Lq, g.keys)).bytes;
+    return paged_query("rtk_attention_decode_sparse_workspace_bytes", false, true, Hq, Hkv, Lq, Lk, 0, first, ve, keep_pages, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -879,42 +897,15 @@ extern "C" int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, in
                                            int q_offset, int D, int dtype, float scale, int first, int ve, const void* summ,
                                            int64_t summ_stride_h, int keep_pages, void* workspace, size_t workspace_bytes,
                                            rtk_stream_t stream) {
-    const char* who = "rtk_attention_decode_sparse";
-    RTK_CHECK_ARG(q && k && v && out && summ, "%s: NULL q / k / v / out / summ pointer", who);
-    const AttnArgs a{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
-                     scale, workspace, workspace_bytes, (hipStream_t)stream};
-    PagedGeom g;
-    int rc = paged_check_shape(who, Hq, Hkv, Lq, Lk, D, dtype, first, ve, keep_pages, g);
-    if (rc != RTK_OK) return rc;
-    RTK_CHECK_ARG(((uintptr_t)summ & 15) == 0 && (summ_stride_h * 2) % 16 == 0 && summ_stride_h >= (int64_t)g.pages * 2 * D,
-                  "%s: summ must be 16-byte aligned with a head stride of at least pages * 2 * D = %lld elements", who,
-                  (long long)g.pages * 2 * D);
-    rc = paged_check_operands(who, a, g);
-    if (rc != RTK_OK) return rc;
-    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, g.keys);
-    const SparseLayout sl = sparse_layout(Hkv, g, pl);
-    rc = paged_check_workspace(who, "rtk_attention_decode_sparse_workspace_bytes", sl.bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    float* ub = (float*)workspace;
-    int32_t* lists = (int32_t*)((char*)workspace + sl.lists_at);
-    // the bound, the selection (one unit per kv head: the existing launcher as it is), the paged kernel, the combine
-    rc = rtk_attention_page_bound(q, q_stride_h, q_stride_l, summ, summ_stride_h, Hq, Hkv, Lq, g.pages, D, dtype, ub, stream);
-    if (rc != RTK_OK) return rc;
-    std::vector<rtk_budget_select_unit> sel((size_t)Hkv);
-    for (int h = 0; h < Hkv; ++h)
-        sel[h] = rtk_budget_select_unit{ub + (size_t)h * g.pages, lists + (size_t)h * g.keep_pages, g.pages, g.keep_pages};
-    rc = rtk_pivotkv_budget_select_batched(sel.data(), Hkv, stream);
-    if (rc != RTK_OK) return rc;
-    return paged_forward(pl, a, g, lists, (char*)workspace + sl.partials_at);
+    return paged_call("rtk_attention_decode_sparse", "rtk_attention_decode_sparse_workspace_bytes", false, true,
+                      AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                               scale, workspace, workspace_bytes, (hipStream_t)stream},
+                      DecodeSegs{}, first, ve, keep_pages, summ, summ_stride_h);
 }
 
-// ---- page-sparse decode over an fp8 archive (retake_hip.h §U) ----
 extern "C" size_t rtk_attention_decode_paged_fp8kv_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int L8, int keep_pages, int D,
                                                                    int dtype) {
-    PagedGeom g;
-    if (paged8_check_shape("rtk_attention_decode_paged_fp8kv_workspace_bytes", Hq, Hkv, Lq, Lk, L8, D, dtype, keep_pages, g) != RTK_OK)
-        return 0;
-    return decode_plan(Hq, Hkv, Lq, g.keys).ws_bytes;
+    return paged_query("rtk_attention_decode_paged_fp8kv_workspace_bytes", true, false, Hq, Hkv, Lq, Lk, L8, 0, 0, keep_pages, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_paged_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -923,30 +914,16 @@ extern "C" int rtk_attention_decode_paged_fp8kv(const void* q, int64_t q_stride_
                                                 int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
                                                 int D, int dtype, float scale, const int32_t* list, int keep_pages, void* workspace,
                                                 size_t workspace_bytes, rtk_stream_t stream) {
-    const char* who = "rtk_attention_decode_paged_fp8kv";
-    RTK_CHECK_ARG(q && k && v && out && list, "%s: NULL q / k / v / out / list pointer", who);
-    const AttnArgs a{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
-                     scale, workspace, workspace_bytes, (hipStream_t)stream};
-    const DecodeSegs sg{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h};
-    PagedGeom g;
-    int rc = paged8_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype, keep_pages, g);
-    if (rc != RTK_OK) return rc;
-    RTK_CHECK_ARG(((uintptr_t)list & 3) == 0, "%s: list must be 4-byte aligned", who);
-    Archive8 a8;
-    rc = paged8_check_operands(who, a, sg, a8);
-    if (rc != RTK_OK) return rc;
-    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, g.keys);
-    rc = paged_check_workspace(who, "rtk_attention_decode_paged_fp8kv_workspace_bytes", pl.ws_bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    return paged8_forward(pl, a, a8, g, list, workspace);
+    return paged_call("rtk_attention_decode_paged_fp8kv", "rtk_attention_decode_paged_fp8kv_workspace_bytes", true, false,
+                      AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                               scale, workspace, workspace_bytes, (hipStream_t)stream},
+                      DecodeSegs{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h}, 0, 0,
+                      keep_pages, list, 0);
 }
 
 extern "C" size_t rtk_attention_decode_sparse_fp8kv_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int L8, int keep_pages, int D,
                                                                     int dtype) {
-    PagedGeom g;
-    if (paged8_check_shape("rtk_attention_decode_sparse_fp8kv_workspace_bytes", Hq, Hkv, Lq, Lk, L8, D, dtype, keep_pages, g) != RTK_OK)
-        return 0;
-    return sparse_layout(Hkv, g, decode_plan(Hq, Hkv, Lq, g.keys)).bytes;
+    return paged_query("rtk_attention_decode_sparse_fp8kv_workspace_bytes", true, true, Hq, Hkv, Lq, Lk, L8, 0, 0, keep_pages, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_sparse_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -955,33 +932,9 @@ extern "C" int rtk_attention_decode_sparse_fp8kv(const void* q, int64_t q_stride
                                                  int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
                                                  int D, int dtype, float scale, const void* summ, int64_t summ_stride_h,
                                                  int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream) {
-    const char* who = "rtk_attention_decode_sparse_fp8kv";
-    RTK_CHECK_ARG(q && k && v && out && summ, "%s: NULL q / k / v / out / summ pointer", who);
-    const AttnArgs a{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
-                     scale, workspace, workspace_bytes, (hipStream_t)stream};
-    const DecodeSegs sg{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h};
-    PagedGeom g;
-    int rc = paged8_check_shape(who, Hq, Hkv, Lq, Lk, L8, D, dtype, keep_pages, g);
-    if (rc != RTK_OK) return rc;
-    RTK_CHECK_ARG(((uintptr_t)summ & 15) == 0 && (summ_stride_h * 2) % 16 == 0 && summ_stride_h >= (int64_t)g.pages * 2 * D,
-                  "%s: summ must be 16-byte aligned with a head stride of at least pages * 2 * D = %lld elements", who,
-                  (long long)g.pages * 2 * D);
-    Archive8 a8;
-    rc = paged8_check_operands(who, a, sg, a8);
-    if (rc != RTK_OK) return rc;
-    const DecodePlan pl = decode_plan(Hq, Hkv, Lq, g.keys);
-    const SparseLayout sl = sparse_layout(Hkv, g, pl);
-    rc = paged_check_workspace(who, "rtk_attention_decode_sparse_fp8kv_workspace_bytes", sl.bytes, workspace, workspace_bytes);
-    if (rc != RTK_OK) return rc;
-    float* ub = (float*)workspace;
-    int32_t* lists = (int32_t*)((char*)workspace + sl.lists_at);
-    // the bound, the selection (one unit per kv head: the existing launchers as they are), the fp8 paged kernel, the combine
-    rc = rtk_attention_page_bound(q, q_stride_h, q_stride_l, summ, summ_stride_h, Hq, Hkv, Lq, g.pages, D, dtype, ub, stream);
-    if (rc != RTK_OK) return rc;
-    std::vector<rtk_budget_select_unit> sel((size_t)Hkv);
-    for (int h = 0; h < Hkv; ++h)
-        sel[h] = rtk_budget_select_unit{ub + (size_t)h * g.pages, lists + (size_t)h * g.keep_pages, g.pages, g.keep_pages};
-    rc = rtk_pivotkv_budget_select_batched(sel.data(), Hkv, stream);
-    if (rc != RTK_OK) return rc;
-    return paged8_forward(pl, a, a8, g, lists, (char*)workspace + sl.partials_at);
+    return paged_call("rtk_attention_decode_sparse_fp8kv", "rtk_attention_decode_sparse_fp8kv_workspace_bytes", true, true,
+                      AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                               scale, workspace, workspace_bytes, (hipStream_t)stream},
+                      DecodeSegs{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h}, 0, 0,
+                      keep_pages, summ, summ_stride_h);
 }

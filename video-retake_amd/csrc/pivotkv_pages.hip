@@ -4,7 +4,8 @@
 //   page_summary_fp8k_kernel   the same over the e4m3 key rows of an fp8 archive (codes + scales), see at the kernel
 //   page_bound_kernel     per decode call: ub[g, p], an upper bound on every raw logit of kv head g's packed rows against
 //                         every key of page p
-// A page is RTK_PAGE_ROWS = 32 region rows: one wave tile of the packed decode kernel.
+// A page is RTK_PAGE_ROWS = 32 region rows: one wave tile of the packed decode kernel.  Host side: the two summary entry
+// points are summary_call with their units, kernel, the checks on their own K operand and their device unit's fill.
 //
 // page_summary_kernel - streaming, reads K once.  One wave per (kv head, page); a row of D = 128 16-bit elements is 256
 // bytes = 16 lanes x 16 bytes, so a wave's load instruction takes FOUR whole rows (lane: chunk c = lane & 15 of row
@@ -207,6 +208,49 @@ int pages_check_envelope(const char* who, int D, int dtype) {
     return RTK_OK;
 }
 
+// What the two summary calls share (`Units` / `kern`: the kind's device units and kernel): the call's checks; per unit
+// `check_k` - the checks on its own K operand, the first of them on its row counts - and, with rows, the checks on summ;
+// then launch_units with `fill`, every launch's grid sized for its largest unit.
+template <class Units, class Unit, class CheckK, class Fill>
+int summary_call(const char* who, void (*kern)(Units), const char* kern_name, const Unit* units, int n_units, int Hkv, int D, int dtype,
+                 rtk_stream_t stream, CheckK&& check_k, Fill&& fill) {
+    int rc = have_units(units, n_units, who);
+    if (rc <= 0) return rc;
+    RTK_CHECK_ARG(Hkv >= 1 && Hkv <= 65535, "%s: Hkv %d", who, Hkv);
+    rc = pages_check_envelope(who, D, dtype);
+    if (rc != RTK_OK) return rc;
+    for (int i = 0; i < n_units; ++i) {
+        const Unit& u = units[i];
+        rc = check_k(u, i);
+        if (rc != RTK_OK) return rc;
+        if (u.n == 0) continue;
+        const int64_t pages = (u.n + PG_ROWS - 1) / PG_ROWS;
+        RTK_CHECK_ARG(u.summ, "%s: unit %d: NULL summ", who, i);
+        RTK_CHECK_ARG(((uintptr_t)u.summ & 15) == 0 && (u.summ_stride_h * 2) % 16 == 0,
+                      "%s: unit %d: summ / summ_stride_h not 16-byte aligned", who, i);
+        RTK_CHECK_ARG(u.summ_stride_h >= 0 && (Hkv == 1 || u.summ_stride_h >= pages * 2 * D),
+                      "%s: unit %d: summ_stride_h %lld is smaller than pages * 2 * D = %lld", who, i, (long long)u.summ_stride_h,
+                      (long long)(pages * 2 * D));
+    }
+    unsigned grid_x = 0;   // of the launch being filled: its largest unit's
+    return launch_units<Units>(
+        n_units,
+        [&](int i, auto& dv) {
+            const Unit& u = units[i];
+            if (u.n == 0) return false;
+            dv = fill(u);
+            const unsigned pages = (unsigned)((u.n + PG_ROWS - 1) / PG_ROWS);
+            grid_x = std::max(grid_x, (pages + PG_WAVES - 1) / PG_WAVES);
+            return true;
+        },
+        [&](const Units& pu, int n) -> int {
+            hipLaunchKernelGGL(kern, dim3(grid_x, (unsigned)Hkv, (unsigned)n), dim3(PG_BLOCK), 0, (hipStream_t)stream, pu);
+            RTK_LAUNCH_CHECK(kern_name);
+            grid_x = 0;
+            return RTK_OK;
+        });
+}
+
 }  // namespace
 }  // namespace rtk
 
@@ -215,95 +259,47 @@ using namespace rtk;
 extern "C" int rtk_pivotkv_page_summary_batched(const rtk_page_summary_unit* units, int n_units, int Hkv, int D, int dtype,
                                                 rtk_stream_t stream) {
     const char* who = "rtk_pivotkv_page_summary_batched";
-    int rc = have_units(units, n_units, who);
-    if (rc <= 0) return rc;
-    RTK_CHECK_ARG(Hkv >= 1 && Hkv <= 65535, "%s: Hkv %d", who, Hkv);
-    rc = pages_check_envelope(who, D, dtype);
-    if (rc != RTK_OK) return rc;
-    for (int i = 0; i < n_units; ++i) {
-        const rtk_page_summary_unit& u = units[i];
-        RTK_CHECK_ARG(u.first >= 0 && u.n >= 0 && u.first + u.n <= 0x3fffffff, "%s: unit %d: first %lld / n %lld", who, i,
-                      (long long)u.first, (long long)u.n);
-        if (u.n == 0) continue;
-        RTK_CHECK_ARG(u.k && u.summ, "%s: unit %d: NULL k / summ", who, i);
-        const int64_t pages = (u.n + PG_ROWS - 1) / PG_ROWS;
-        RTK_CHECK_ARG((((uintptr_t)u.k | (uintptr_t)u.summ) & 15) == 0 && (u.k_stride_h * 2) % 16 == 0 && (u.summ_stride_h * 2) % 16 == 0,
-                      "%s: unit %d: k / summ / head strides not 16-byte aligned", who, i);
-        RTK_CHECK_ARG(u.k_stride_h >= 0 && (Hkv == 1 || u.k_stride_h >= (u.first + u.n) * D), "%s: unit %d: k_stride_h %lld is smaller than the rows of a head",
-                      who, i, (long long)u.k_stride_h);
-        RTK_CHECK_ARG(u.summ_stride_h >= 0 && (Hkv == 1 || u.summ_stride_h >= pages * 2 * D),
-                      "%s: unit %d: summ_stride_h %lld is smaller than pages * 2 * D = %lld", who, i, (long long)u.summ_stride_h,
-                      (long long)(pages * 2 * D));
-    }
-    hipStream_t st = (hipStream_t)stream;
-    unsigned grid_x = 0;   // of the launch being filled: its largest unit's
-    return launch_units<PageUnits>(
-        n_units,
-        [&](int i, PageDev& dv) {
-            const rtk_page_summary_unit& u = units[i];
-            if (u.n == 0) return false;
-            dv = PageDev{(const char*)u.k, (char*)u.summ, u.k_stride_h * 2, u.summ_stride_h * 2, (int32_t)u.first, (int32_t)u.n};
-            const unsigned pages = (unsigned)((u.n + PG_ROWS - 1) / PG_ROWS);
-            grid_x = std::max(grid_x, (pages + PG_WAVES - 1) / PG_WAVES);
-            return true;
-        },
-        [&](const PageUnits& pu, int n) -> int {
-            hipLaunchKernelGGL(page_summary_kernel, dim3(grid_x, (unsigned)Hkv, (unsigned)n), dim3(PG_BLOCK), 0, st, pu);
-            RTK_LAUNCH_CHECK("page_summary_kernel");
-            grid_x = 0;
+    return summary_call<PageUnits>(
+        who, page_summary_kernel, "page_summary_kernel", units, n_units, Hkv, D, dtype, stream,
+        [&](const rtk_page_summary_unit& u, int i) -> int {
+            RTK_CHECK_ARG(u.first >= 0 && u.n >= 0 && u.first + u.n <= 0x3fffffff, "%s: unit %d: first %lld / n %lld", who, i,
+                          (long long)u.first, (long long)u.n);
+            if (u.n == 0) return RTK_OK;
+            RTK_CHECK_ARG(u.k, "%s: unit %d: NULL k", who, i);
+            RTK_CHECK_ARG(((uintptr_t)u.k & 15) == 0 && (u.k_stride_h * 2) % 16 == 0, "%s: unit %d: k / k_stride_h not 16-byte aligned",
+                          who, i);
+            RTK_CHECK_ARG(u.k_stride_h >= 0 && (Hkv == 1 || u.k_stride_h >= (u.first + u.n) * D),
+                          "%s: unit %d: k_stride_h %lld is smaller than the rows of a head", who, i, (long long)u.k_stride_h);
             return RTK_OK;
+        },
+        [](const rtk_page_summary_unit& u) {
+            return PageDev{(const char*)u.k, (char*)u.summ, u.k_stride_h * 2, u.summ_stride_h * 2, (int32_t)u.first, (int32_t)u.n};
         });
 }
 
 extern "C" int rtk_pivotkv_page_summary_fp8k_batched(const rtk_page_summary_fp8k_unit* units, int n_units, int Hkv, int D,
                                                      int dtype, rtk_stream_t stream) {
     const char* who = "rtk_pivotkv_page_summary_fp8k_batched";
-    int rc = have_units(units, n_units, who);
-    if (rc <= 0) return rc;
-    RTK_CHECK_ARG(Hkv >= 1 && Hkv <= 65535, "%s: Hkv %d", who, Hkv);
-    rc = pages_check_envelope(who, D, dtype);
-    if (rc != RTK_OK) return rc;
-    for (int i = 0; i < n_units; ++i) {
-        const rtk_page_summary_fp8k_unit& u = units[i];
-        RTK_CHECK_ARG(u.n >= 0 && u.n <= 0x3fffffff, "%s: unit %d: n %lld", who, i, (long long)u.n);
-        if (u.n == 0) continue;
-        RTK_CHECK_ARG(u.k8 && u.k_scale && u.summ, "%s: unit %d: NULL k8 / k_scale / summ", who, i);
-        // the archive's limit (rtk_attention_decode_fp8kv): the codes of one head stay below 2 GiB
-        RTK_CHECK_ARG(u.n * D < (1ll << 31) - PG_ROWS * D, "%s: unit %d: n %lld: the codes of one head span 2 GiB or more", who, i,
-                      (long long)u.n);
-        const int64_t pages = (u.n + PG_ROWS - 1) / PG_ROWS;
-        RTK_CHECK_ARG((((uintptr_t)u.k8 | (uintptr_t)u.summ) & 15) == 0 && u.k8_stride_h % 16 == 0 && (u.summ_stride_h * 2) % 16 == 0 &&
-                          ((uintptr_t)u.k_scale & 3) == 0,
-                      "%s: unit %d: k8 / summ / head strides not 16-byte aligned, or k_scale not 4-byte aligned", who, i);
-        RTK_CHECK_ARG(u.k8_stride_h >= 0 && (Hkv == 1 || u.k8_stride_h >= u.n * D),
-                      "%s: unit %d: k8_stride_h %lld is smaller than the rows of a head", who, i, (long long)u.k8_stride_h);
-        RTK_CHECK_ARG(u.scale_stride_h >= 0 && (Hkv == 1 || u.scale_stride_h >= u.n),
-                      "%s: unit %d: scale_stride_h %lld is smaller than the rows of a head", who, i, (long long)u.scale_stride_h);
-        RTK_CHECK_ARG(u.summ_stride_h >= 0 && (Hkv == 1 || u.summ_stride_h >= pages * 2 * D),
-                      "%s: unit %d: summ_stride_h %lld is smaller than pages * 2 * D = %lld", who, i, (long long)u.summ_stride_h,
-                      (long long)(pages * 2 * D));
-    }
-    hipStream_t st = (hipStream_t)stream;
-    unsigned grid_x = 0;   // of the launch being filled: its largest unit's
-    return launch_units<PageUnits8>(
-        n_units,
-        [&](int i, PageDev8& dv) {
-            const rtk_page_summary_fp8k_unit& u = units[i];
-            if (u.n == 0) return false;
-            dv = PageDev8{(const char*)u.k8, u.k_scale, (char*)u.summ, u.k8_stride_h, u.summ_stride_h * 2, u.scale_stride_h, (int32_t)u.n, 0};
-            const unsigned pages = (unsigned)((u.n + PG_ROWS - 1) / PG_ROWS);
-            grid_x = std::max(grid_x, (pages + PG_WAVES - 1) / PG_WAVES);
-            return true;
-        },
-        [&](const PageUnits8& pu, int n) -> int {
-            const dim3 grid(grid_x, (unsigned)Hkv, (unsigned)n);
-            if (dtype == RTK_BF16)
-                hipLaunchKernelGGL((page_summary_fp8k_kernel<RTK_BF16>), grid, dim3(PG_BLOCK), 0, st, pu);
-            else
-                hipLaunchKernelGGL((page_summary_fp8k_kernel<RTK_F16>), grid, dim3(PG_BLOCK), 0, st, pu);
-            RTK_LAUNCH_CHECK("page_summary_fp8k_kernel");
-            grid_x = 0;
+    return summary_call<PageUnits8>(
+        who, dtype == RTK_BF16 ? page_summary_fp8k_kernel<RTK_BF16> : page_summary_fp8k_kernel<RTK_F16>, "page_summary_fp8k_kernel", units,
+        n_units, Hkv, D, dtype, stream,
+        [&](const rtk_page_summary_fp8k_unit& u, int i) -> int {
+            RTK_CHECK_ARG(u.n >= 0 && u.n <= 0x3fffffff, "%s: unit %d: n %lld", who, i, (long long)u.n);
+            if (u.n == 0) return RTK_OK;
+            RTK_CHECK_ARG(u.k8 && u.k_scale, "%s: unit %d: NULL k8 / k_scale", who, i);
+            // the archive's limit (rtk_attention_decode_fp8kv): the codes of one head stay below 2 GiB
+            RTK_CHECK_ARG(u.n * D < (1ll << 31) - PG_ROWS * D, "%s: unit %d: n %lld: the codes of one head span 2 GiB or more", who, i,
+                          (long long)u.n);
+            RTK_CHECK_ARG(((uintptr_t)u.k8 & 15) == 0 && u.k8_stride_h % 16 == 0 && ((uintptr_t)u.k_scale & 3) == 0,
+                          "%s: unit %d: k8 / k8_stride_h not 16-byte aligned, or k_scale not 4-byte aligned", who, i);
+            RTK_CHECK_ARG(u.k8_stride_h >= 0 && (Hkv == 1 || u.k8_stride_h >= u.n * D),
+                          "%s: unit %d: k8_stride_h %lld is smaller than the rows of a head", who, i, (long long)u.k8_stride_h);
+            RTK_CHECK_ARG(u.scale_stride_h >= 0 && (Hkv == 1 || u.scale_stride_h >= u.n),
+                          "%s: unit %d: scale_stride_h %lld is smaller than the rows of a head", who, i, (long long)u.scale_stride_h);
             return RTK_OK;
+        },
+        [](const rtk_page_summary_fp8k_unit& u) {
+            return PageDev8{(const char*)u.k8, u.k_scale, (char*)u.summ, u.k8_stride_h, u.summ_stride_h * 2, u.scale_stride_h, (int32_t)u.n, 0};
         });
 }
 

@@ -62,6 +62,64 @@ class _Sparse:
         self.archive = archive
 
 
+class _Rows16:
+    """The kind archive=False: the region is rows [pinned, length at `video_end`) of the layer's 16-bit buffers."""
+    Unit, summary = nv.PageSummaryUnit, "rtk_pivotkv_page_summary_batched"
+    query, call = "rtk_attention_decode_sparse_workspace_bytes", "rtk_attention_decode_sparse"
+    none = "no layer holds video rows behind its pinned rows"
+
+    @staticmethod
+    def region(st, m):
+        """(region rows, geometry without the pages) at arming; None: a layer without video rows"""
+        first, n = st.pinned, m.length - st.pinned
+        return None if first < 0 or n < 1 else (n, (first, m.length))
+
+    own = staticmethod(lambda st: True)   # the layout of the buffers only this kind reads
+
+    @staticmethod
+    def fill(u, st, geom, n):
+        u.k, u.k_stride_h, u.first, u.n = st._k.data_ptr(), st._k.stride(1), geom[0], n
+
+    rows16 = staticmethod(lambda geom: geom[1])          # the 16-bit rows at `video_end`
+    views = staticmethod(lambda st, geom: True)          # what a routed call's layer must still hold
+    before = staticmethod(lambda geom: 0)                # the rows query_offset counts before k's
+    least = staticmethod(lambda geom: geom[1] - 1)       # the q_offset from which every query row sees the region whole
+    region_args = staticmethod(lambda geom: geom[:2])    # of the workspace query, behind Lk
+    archive_args = staticmethod(lambda st, geom: ())     # of the call, behind the kv strides
+    tail_args = region_args                              # of the call, behind scale
+
+
+class _Archive8:
+    """The kind archive=True: the region is the fp8 archive as recorded at `video_end`, from archive row 0."""
+    Unit, summary = nv.PageSummaryFp8kUnit, "rtk_pivotkv_page_summary_fp8k_batched"
+    query, call = "rtk_attention_decode_sparse_fp8kv_workspace_bytes", "rtk_attention_decode_sparse_fp8kv"
+    none = "no layer holds archived video rows"
+
+    @staticmethod
+    def region(st, m):
+        return None if st.k8 is None or m.len8 < 1 or st.len8 < m.len8 else (m.len8, (m.length, m.len8))
+
+    @staticmethod
+    def own(st):
+        k, k8, ks8 = st._k, st.k8, st.ks8
+        return k8.stride(3) == 1 and k8.stride(2) == k8.shape[3] and ks8.stride(2) == 1 and k8.shape[1] == k.shape[1] \
+            and k8.shape[3] == k.shape[3]
+
+    @staticmethod
+    def fill(u, st, geom, n):
+        u.k8, u.k8_stride_h, u.k_scale, u.scale_stride_h = st.k8.data_ptr(), st.k8.stride(1), st.ks8.data_ptr(), st.ks8.stride(1)
+        u.n = n
+
+    rows16 = staticmethod(lambda geom: geom[0])
+    views = staticmethod(lambda st, geom: st.len8 == geom[1])
+    before = staticmethod(lambda geom: geom[1])          # query_offset counts over archive + views; q_offset in 16-bit rows
+    least = staticmethod(lambda geom: 0)                 # every archive row is visible to every query row
+    region_args = staticmethod(lambda geom: geom[1:2])
+    archive_args = staticmethod(lambda st, geom: (nv.ptr(st.k8), nv.ptr(st.v8), nv.ptr(st.ks8), nv.ptr(st.vs8), geom[1],
+                                                  st.k8.stride(1), st.ks8.stride(1)))
+    tail_args = staticmethod(lambda geom: ())
+
+
 def _is_int(x, least):
     return isinstance(x, int) and not isinstance(x, bool) and x >= least
 
@@ -72,12 +130,17 @@ def _mark_moved(cache, mark) -> bool:
         or cache._flushes != ve.flushes or cache._compressed_in_forward or len(cache._layers) != ve.n_layers
 
 
+def _check_mark(cache, mark, who, then):
+    if _mark_moved(cache, mark):
+        raise ValueError(f"{who}: {then}")
+
+
 def sparse_decode(cache, keep_rows: int = 8192, archive: bool = False) -> None:
     """Arm the page-sparse decode route (see the module docstring).  ValueError, before any launch: keep_rows not an int
     >= 1 (a bool is not an int), archive not a bool, a cache without `video_end`, attention_kernel other than "hip",
     kv_cache_dtype set without archive=True (the pages of an fp8 cache are its archive's: an opt-in of its own), archive=True
     on a cache without kv_cache_dtype.  NotImplementedError: a branch, a focused cache, defer_rerotation, an fp32 model or
-    head_dim other than 128.  Arming again rebuilds the index."""
+    head_dim other than 128.  Arming again rebuilds the index: ONE summary call of the kind per device."""
     who = "sparse_decode"
     if not _is_int(keep_rows, 1):
         raise ValueError(f"{who}: keep_rows must be an int >= 1, got {keep_rows!r}")
@@ -107,89 +170,41 @@ def sparse_decode(cache, keep_rows: int = 8192, archive: bool = False) -> None:
                          "rows to index")
     cache._flush()
     cache._shift_latch_check()
-    if _mark_moved(cache, ve):
-        raise ValueError(f"{who}: `video_end` does not describe the cache's rows any more (a chunk, a slide, an eviction or a "
-                         "rewind below it since) - finish the prefill first")
-    if archive:
-        cache._sparse = _arm_archive(cache, keep_rows, ve, who)
-        return
-    plan = []
+    _check_mark(cache, ve, who, "`video_end` does not describe the cache's rows any more (a chunk, a slide, an eviction or a "
+                "rewind below it since) - finish the prefill first")
+    kind = _Archive8 if archive else _Rows16
+    by_device = {}
     for l, (st, m) in enumerate(zip(cache._layers, ve.layers)):
         k = st._k
-        if k is None or not m.has_kv:
-            continue
-        first, n = st.pinned, m.length - st.pinned
-        if first < 0 or n < 1:
-            continue   # a layer without video rows: its calls take the existing routes
+        region = None if k is None or not m.has_kv else kind.region(st, m)
+        if region is None:
+            continue   # a layer without rows to index: its calls take the existing routes
         if k.dtype not in (torch.bfloat16, torch.float16):
             raise NotImplementedError(f"{who} needs a bfloat16 or float16 model, got {k.dtype} in layer {l}")
         if k.shape[3] != 128:
             raise NotImplementedError(f"{who} needs head_dim 128, got {k.shape[3]} in layer {l}")
-        if st.c.cap == 0 or k.stride(3) != 1 or k.stride(2) != k.shape[3]:
+        if st.c.cap == 0 or k.stride(3) != 1 or k.stride(2) != k.shape[3] or not kind.own(st):
             raise ValueError(f"{who}: layer {l}'s buffers are not the cache's own dense blocks")
-        plan.append((l, st, first, m.length, n))
-    if not plan:
-        raise ValueError(f"{who}: no layer holds video rows behind its pinned rows")
-    sp = _Sparse(keep_rows, ve)
-    by_device = {}
-    for p in plan:
-        by_device.setdefault(p[1]._k.get_device(), []).append(p)
+        by_device.setdefault(k.get_device(), []).append((l, st) + region)
+    if not by_device:
+        raise ValueError(f"{who}: {kind.none}")
+    sp = _Sparse(keep_rows, ve, archive)
     for dev, ps in by_device.items():
-        units = (nv.PageSummaryUnit * len(ps))()
+        units = (kind.Unit * len(ps))()
         k0 = ps[0][1]._k
-        for u, (l, st, first, length, n) in zip(units, ps):
+        for u, (l, st, n, geom) in zip(units, ps):
             k = st._k
             if k.shape[1] != k0.shape[1] or k.dtype != k0.dtype:
                 raise ValueError(f"{who}: layer {l} differs from layer {ps[0][0]} in kv heads or dtype")
             pages = (n + PAGE - 1) // PAGE
             s = sp.summ[l] = torch.empty((k.shape[1], pages, 2, k.shape[3]), dtype=k.dtype, device=k.device)
-            sp.geom[l] = (first, length, pages)
-            u.k, u.k_stride_h, u.first, u.n, u.summ, u.summ_stride_h = k.data_ptr(), k.stride(1), first, n, s.data_ptr(), s.stride(0)
-        nv.check(_on_device(dev, nv.lib.rtk_pivotkv_page_summary_batched, units, len(ps), k0.shape[1], k0.shape[3],
-                            nv.dtype_code(k0), nv.raw_stream(dev)), "rtk_pivotkv_page_summary_batched")
+            sp.geom[l] = geom + (pages,)
+            kind.fill(u, st, geom, n)
+            u.summ, u.summ_stride_h = s.data_ptr(), s.stride(0)
+        nv.check(_on_device(dev, getattr(nv.lib, kind.summary), units, len(ps), k0.shape[1], k0.shape[3], nv.dtype_code(k0),
+                            nv.raw_stream(dev)), kind.summary)
         cache.page_summary_calls += 1
     cache._sparse = sp
-
-
-def _arm_archive(cache, keep_rows, ve, who):
-    """The index over the fp8 archive of every layer: ONE rtk_pivotkv_page_summary_fp8k_batched call per device over the K
-    codes and scales from archive row 0."""
-    plan = []
-    for l, (st, m) in enumerate(zip(cache._layers, ve.layers)):
-        k = st._k
-        if k is None or not m.has_kv or st.k8 is None or m.len8 < 1 or st.len8 < m.len8:
-            continue   # a layer without archived rows: its calls take the existing routes
-        if k.dtype not in (torch.bfloat16, torch.float16):
-            raise NotImplementedError(f"{who} needs a bfloat16 or float16 model, got {k.dtype} in layer {l}")
-        if k.shape[3] != 128:
-            raise NotImplementedError(f"{who} needs head_dim 128, got {k.shape[3]} in layer {l}")
-        k8, ks8 = st.k8, st.ks8
-        if st.c.cap == 0 or k.stride(3) != 1 or k.stride(2) != k.shape[3] or k8.stride(3) != 1 or k8.stride(2) != k8.shape[3] \
-                or ks8.stride(2) != 1 or k8.shape[1] != k.shape[1] or k8.shape[3] != k.shape[3]:
-            raise ValueError(f"{who}: layer {l}'s buffers are not the cache's own dense blocks")
-        plan.append((l, st, m.length, m.len8))
-    if not plan:
-        raise ValueError(f"{who}: no layer holds archived video rows")
-    sp = _Sparse(keep_rows, ve, archive=True)
-    by_device = {}
-    for p in plan:
-        by_device.setdefault(p[1]._k.get_device(), []).append(p)
-    for dev, ps in by_device.items():
-        units = (nv.PageSummaryFp8kUnit * len(ps))()
-        k0 = ps[0][1]._k
-        for u, (l, st, length, n) in zip(units, ps):
-            k = st._k
-            if k.shape[1] != k0.shape[1] or k.dtype != k0.dtype:
-                raise ValueError(f"{who}: layer {l} differs from layer {ps[0][0]} in kv heads or dtype")
-            pages = (n + PAGE - 1) // PAGE
-            s = sp.summ[l] = torch.empty((k.shape[1], pages, 2, k.shape[3]), dtype=k.dtype, device=k.device)
-            sp.geom[l] = (length, n, pages)
-            u.k8, u.k8_stride_h, u.k_scale, u.scale_stride_h = st.k8.data_ptr(), st.k8.stride(1), st.ks8.data_ptr(), st.ks8.stride(1)
-            u.n, u.summ, u.summ_stride_h = n, s.data_ptr(), s.stride(0)
-        nv.check(_on_device(dev, nv.lib.rtk_pivotkv_page_summary_fp8k_batched, units, len(ps), k0.shape[1], k0.shape[3],
-                            nv.dtype_code(k0), nv.raw_stream(dev)), "rtk_pivotkv_page_summary_fp8k_batched")
-        cache.page_summary_calls += 1
-    return sp
 
 
 def dense_decode(cache) -> None:
@@ -205,7 +220,9 @@ def sparse_bytes(cache) -> dict:
 
 def route(cache, q, k, v, scaling, query_offset, layer_idx):
     """What PivotKVCache.attention asks first while armed: the sparse call's output [1, Lq, Hq, D], or None - take the
-    existing routes.  ValueError for a call without layer_idx and for a `video_end` that is no longer the recorded one."""
+    existing routes.  ValueError for a call without layer_idx and for a `video_end` that is no longer the recorded one.
+    On an fp8 cache k / v are the layer's 16-bit views and the archive precedes them; query_offset counts over archive +
+    views, as PivotKVCache.attention states."""
     sp = cache._sparse
     who = "PivotKVCache.attention (sparse_decode armed)"
     if layer_idx is None:
@@ -213,70 +230,26 @@ def route(cache, q, k, v, scaling, query_offset, layer_idx):
     geom = sp.geom.get(layer_idx)
     if geom is None or q.dim() != 4 or k.dim() != 4 or q.shape[0] != 1:
         return None
-    if sp.archive:
-        return _route_archive(cache, sp, who, geom, q, k, v, scaling, query_offset, layer_idx)
-    first, ve, pages = geom
+    kind = _Archive8 if sp.archive else _Rows16
+    pages = geom[2]
     _, Hq, Lq, D = q.shape
     _, Hkv, Lk, _ = k.shape
-    if Lk <= ve:
+    if Lk <= kind.rows16(geom):   # no row behind `video_end`
         return None
-    if _mark_moved(cache, sp.mark):
-        raise ValueError(f"{who}: `video_end` is no longer the mark recorded by sparse_decode - a chunk, a slide, an eviction "
-                         "or a rewind below it happened since, and the page index no longer describes the rows.  Call "
-                         "sparse_decode again (or dense_decode)")
+    _check_mark(cache, sp.mark, who, "`video_end` is no longer the mark recorded by sparse_decode - a chunk, a slide, an "
+                "eviction or a rewind below it happened since, and the page index no longer describes the rows.  Call "
+                "sparse_decode again (or dense_decode)")
     st, summ = cache._layers[layer_idx], sp.summ[layer_idx]
-    if k.data_ptr() != st._k.data_ptr() or v.data_ptr() != st._v.data_ptr() or k.stride() != v.stride() or k.stride(3) != 1 \
-            or q.stride(3) != 1 or not (q.dtype == k.dtype == v.dtype == summ.dtype) or Hkv != summ.shape[0] or D != summ.shape[3] \
-            or Hq % Hkv:
-        return None
-    q_off = Lk - Lq if query_offset is None else int(query_offset)
-    if q_off < ve - 1 or q_off < Lk - Lq:
-        return None
-    keep_pages = min((sp.keep_rows + PAGE - 1) // PAGE, pages)
-    code = nv.dtype_code(q)
-    need = nv.lib.rtk_attention_decode_sparse_workspace_bytes(Hq, Hkv, Lq, Lk, first, ve, keep_pages, D, code)
-    if not need:
-        return None   # outside the packed envelope: the existing routes
-    ws = sp.ws.get(layer_idx)
-    if ws is None or ws.numel() < need:
-        ws = sp.ws[layer_idx] = torch.empty(need, dtype=torch.uint8, device=q.device)
-    out = torch.empty((1, Lq, Hq, D), dtype=q.dtype, device=q.device)
-    scale = float(D) ** -0.5 if scaling is None else float(scaling)
-    rc = nv.lib.rtk_attention_decode_sparse(nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2),
-                                            nv.ptr(out), Hq, Hkv, Lq, Lk, q_off, D, code, scale, first, ve, nv.ptr(summ),
-                                            summ.stride(0), keep_pages, nv.ptr(ws), ws.numel(),
-                                            nv.raw_stream(q.device.index))
-    if rc == nv.RTK_EUNSUPPORTED:
-        return None
-    nv.check(rc, "rtk_attention_decode_sparse")
-    sp.last[layer_idx] = (Hkv, pages, keep_pages)
-    cache.sparse_attention_calls += 1
-    return out
-
-
-def _route_archive(cache, sp, who, geom, q, k, v, scaling, query_offset, layer_idx):
-    """`route` on an fp8 cache: k / v are the layer's 16-bit views, the archive precedes them; query_offset counts over
-    archive + views, as PivotKVCache.attention states."""
-    ve16, n8, pages = geom
-    _, Hq, Lq, D = q.shape
-    _, Hkv, Lk, _ = k.shape
-    if Lk <= ve16:
-        return None
-    if _mark_moved(cache, sp.mark):
-        raise ValueError(f"{who}: `video_end` is no longer the mark recorded by sparse_decode - a chunk, a slide, an eviction "
-                         "or a rewind below it happened since, and the page index no longer describes the rows.  Call "
-                         "sparse_decode again (or dense_decode)")
-    st, summ = cache._layers[layer_idx], sp.summ[layer_idx]
-    if st.len8 != n8 or k.data_ptr() != st._k.data_ptr() or v.data_ptr() != st._v.data_ptr() or k.stride() != v.stride() \
+    if not kind.views(st, geom) or k.data_ptr() != st._k.data_ptr() or v.data_ptr() != st._v.data_ptr() or k.stride() != v.stride() \
             or k.stride(3) != 1 or q.stride(3) != 1 or not (q.dtype == k.dtype == v.dtype == summ.dtype) or Hkv != summ.shape[0] \
             or D != summ.shape[3] or Hq % Hkv:
         return None
-    q_off = Lk - Lq if query_offset is None else int(query_offset) - n8   # in 16-bit rows
-    if q_off < Lk - Lq:
+    q_off = Lk - Lq if query_offset is None else int(query_offset) - kind.before(geom)
+    if q_off < kind.least(geom) or q_off < Lk - Lq:
         return None
     keep_pages = min((sp.keep_rows + PAGE - 1) // PAGE, pages)
     code = nv.dtype_code(q)
-    need = nv.lib.rtk_attention_decode_sparse_fp8kv_workspace_bytes(Hq, Hkv, Lq, Lk, n8, keep_pages, D, code)
+    need = getattr(nv.lib, kind.query)(Hq, Hkv, Lq, Lk, *kind.region_args(geom), keep_pages, D, code)
     if not need:
         return None   # outside the packed envelope: the existing routes
     ws = sp.ws.get(layer_idx)
@@ -284,14 +257,13 @@ def _route_archive(cache, sp, who, geom, q, k, v, scaling, query_offset, layer_i
         ws = sp.ws[layer_idx] = torch.empty(need, dtype=torch.uint8, device=q.device)
     out = torch.empty((1, Lq, Hq, D), dtype=q.dtype, device=q.device)
     scale = float(D) ** -0.5 if scaling is None else float(scaling)
-    rc = nv.lib.rtk_attention_decode_sparse_fp8kv(nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2),
-                                                  nv.ptr(st.k8), nv.ptr(st.v8), nv.ptr(st.ks8), nv.ptr(st.vs8), n8, st.k8.stride(1),
-                                                  st.ks8.stride(1), nv.ptr(out), Hq, Hkv, Lq, Lk, q_off, D, code, scale,
-                                                  nv.ptr(summ), summ.stride(0), keep_pages, nv.ptr(ws), ws.numel(),
-                                                  nv.raw_stream(q.device.index))
+    rc = getattr(nv.lib, kind.call)(nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2),
+                                    *kind.archive_args(st, geom), nv.ptr(out), Hq, Hkv, Lq, Lk, q_off, D, code, scale,
+                                    *kind.tail_args(geom), nv.ptr(summ), summ.stride(0), keep_pages, nv.ptr(ws), ws.numel(),
+                                    nv.raw_stream(q.device.index))
     if rc == nv.RTK_EUNSUPPORTED:
         return None
-    nv.check(rc, "rtk_attention_decode_sparse_fp8kv")
+    nv.check(rc, kind.call)
     sp.last[layer_idx] = (Hkv, pages, keep_pages)
     cache.sparse_attention_calls += 1
     return out

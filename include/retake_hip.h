@@ -24,7 +24,7 @@
  *     tables are always fp32; indices are int64 and masks are 1 byte per element (torch.bool layout);
  *   - strides are in ELEMENTS; the innermost (channel / head_dim) axis is always contiguous.
  *
- * Contents (100 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
+ * Contents (104 entry points; search for the section title).  A binding of the hot path needs §A, §B, §E and the four
  * calls of §G; §D / §F are the stage-by-stage forms the same kernels are also reachable through.
  *   §A  version / errors                rtk_version, rtk_last_error, rtk_arch
  *   §B  "DPSelect"                      rtk_dpselect_dis, rtk_dpselect_select, rtk_gather_frames
@@ -75,7 +75,10 @@
  *                                       pages with the highest bound and the rows behind the video (opt-in:
  *                                       sparse_decode(cache) of retake/_sparse_decode.py); rtk_pivotkv_page_summary_fp8k_batched,
  *                                       rtk_attention_decode_paged_fp8kv, rtk_attention_decode_sparse_fp8kv: the same with the
- *                                       pages in an fp8 archive (opt-in: sparse_decode(cache, archive=True))
+ *                                       pages in an fp8 archive (opt-in: sparse_decode(cache, archive=True));
+ *                                       rtk_attention_decode_paged_wide, rtk_attention_decode_sparse_wide (+ their
+ *                                       _workspace_bytes): the 16-bit calls for up to 64 packed rows, one list per kv head for
+ *                                       all their rows (opt-in: sparse_decode(cache, wide=True))
  */
 #ifndef RETAKE_HIP_H
 #define RETAKE_HIP_H
@@ -1436,6 +1439,24 @@ int rtk_pivotkv_focus_gather_batched(const rtk_focus_unit* units, int n_units, r
  * sizes, L8 < 1, keep_pages outside [1, pages], q_offset < Lk - Lq, pointers or strides that are not multiples of 16 bytes
  * (scales: 4), a short or misaligned workspace.  The workspace queries return 0, with the message set, for a shape the call
  * would refuse.  No atomics, no flags, no waiting between workgroups.
+ *
+ * Several new tokens (opt-in: sparse_decode(cache, wide=True)): the wide family of the two 16-bit attention calls, for the
+ * verification call of assisted generation and short turns.
+ * rtk_attention_decode_paged_wide - rtk_attention_decode_paged with rtk_attention_decode_wide's arithmetic (§P: packed row
+ *   r = i * G + g, two to four column groups, a tile on the diagonal judged per group) for 16 < (Hq / Hkv) * Lq <= 64 packed
+ *   rows, over the same virtual key space: ALL Lq rows of the call share the kv head's one list.  Segments, descriptors,
+ *   the clamp of a list entry, the diagonal (only the tail has one), q_offset >= ve - 1, the plan over the virtual key
+ *   count, the partials and the second launch are those of rtk_attention_decode_paged.  With first % 32 == 0 and
+ *   n % 32 == 0 the result equals, bit for bit, rtk_attention_decode_wide over the concatenation of those rows; with the
+ *   identity list as well, over the rows as they lie.
+ * rtk_attention_decode_sparse_wide - the chain of rtk_attention_decode_sparse around it: rtk_attention_page_bound (its max
+ *   runs over the packed rows of EVERY position: a page that any one row needs is ranked by that row),
+ *   rtk_pivotkv_budget_select_batched with one unit per kv head, the wide paged kernel, the combine; the workspace is
+ *   [ub | lists | partials] with the same layout.  The output is not what Lq one-token sparse calls would give.
+ * Envelope: RTK_BF16 / RTK_F16, D == 128, (Hq / Hkv) * Lq <= 64 - RTK_EUNSUPPORTED otherwise, before any launch.  With
+ * (Hq / Hkv) * Lq <= 16 the call IS rtk_attention_decode_paged / rtk_attention_decode_sparse (and its workspace query
+ * theirs), as rtk_attention_decode_wide is rtk_attention_decode.  Checks, their order and RTK_EINVAL as for the narrow
+ * calls.  No atomics, no flags, no waiting between workgroups.  rtk_version() is unchanged: additions only.
  * ------------------------------------------------------------------------------------------- */
 #define RTK_PAGE_ROWS 32
 typedef struct rtk_page_summary_unit {
@@ -1489,6 +1510,19 @@ int rtk_attention_decode_sparse_fp8kv(const void* q, int64_t q_stride_h, int64_t
                                       void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset, int D, int dtype, float scale,
                                       const void* summ, int64_t summ_stride_h, int keep_pages, void* workspace,
                                       size_t workspace_bytes, rtk_stream_t stream);
+size_t rtk_attention_decode_paged_wide_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages, int D,
+                                                       int dtype);
+int rtk_attention_decode_paged_wide(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                    int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
+                                    int q_offset, int D, int dtype, float scale, int first, int ve, const int32_t* list,
+                                    int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream);
+size_t rtk_attention_decode_sparse_wide_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages, int D,
+                                                        int dtype);
+int rtk_attention_decode_sparse_wide(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                     int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
+                                     int q_offset, int D, int dtype, float scale, int first, int ve, const void* summ,
+                                     int64_t summ_stride_h, int keep_pages, void* workspace, size_t workspace_bytes,
+                                     rtk_stream_t stream);
 
 #ifdef __cplusplus
 }

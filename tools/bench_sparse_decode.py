@@ -32,7 +32,20 @@ which only the summary build reads: random finite codes):
   gathered8_K        (b) rtk_attention_decode_fp8kv over a gathered archive of K rows: what a focused fp8 cache pays per token;
   sparse16_K         (c) the 16-bit chain, rtk_attention_decode_sparse, on the dequantised rows;
   summary_build8     rtk_pivotkv_page_summary_fp8k_batched over the 28 layers: what arming costs;
-  copy_k_code_bytes  rtk_profile_copy of the K codes' bytes."""
+  copy_k_code_bytes  rtk_profile_copy of the K codes' bytes.
+
+    python tools/bench_sparse_decode.py --wide [--out profiles/sparse_decode_wide_bench.json] [--parent-lib PATH]
+
+Several new tokens (sparse_decode(cache, wide=True), rtk_attention_decode_sparse_wide): one layer of the same geometry, its
+buffers filled directly, Lq 3 / 6 / 9 query rows (21 / 42 / 63 packed rows) x keep_rows 4 096 / 8 192 / 16 384; then one row
+each at Hq 8 / Hkv 4 (Lq 9) and Hq 8 / Hkv 8 (Lq 17) with keep_rows 8 192, their names prefixed g2_ / g1_:
+  wide_full_L        (a) rtk_attention_decode_wide over ALL rows (from --parent-lib when given): what multi_token_attention pays;
+  chunk_L            (b) the chunk kernel over all rows (chunk_attention as it is): what a cache without that key pays;
+  sparse_wide_L_K    (c) the whole chain, rtk_attention_decode_sparse_wide: bound, selection, wide paged attention, combine;
+  bound_L, select_K, paged_wide_L_K   its launches alone, on the chain's own operands;
+  sparse_1_K         (d) the narrow chain, rtk_attention_decode_sparse, one query row on the same buffers.
+A gain over (a) is claimed (`beats_wide_full`) only where the difference of medians exceeds the sum of the two interquartile
+ranges."""
 from __future__ import annotations
 
 import argparse
@@ -64,7 +77,7 @@ of = lambda chain, row: [(r, fn) for r, fn in chain.items() if r.split("@")[0] =
 def libraries(args):
     """[(tag, library)]: this build's under "", then every --parent-lib under "@parent1", "@parent2", .. with `names` bound."""
     names = ["rtk_attention_decode", "rtk_attention_decode_workspace_bytes", "rtk_attention_decode_fp8kv",
-             "rtk_attention_decode_workspace_bytes_fp8kv"]
+             "rtk_attention_decode_workspace_bytes_fp8kv", "rtk_attention_decode_wide", "rtk_attention_decode_wide_workspace_bytes"]
     names += [f"rtk_attention_decode_{c}{k}{w}" for c in ("paged", "sparse") for k in ("", "_fp8kv") for w in ("", "_workspace_bytes")]
     libs = [("", nv.lib)]
     for i, path in enumerate(args.parent_lib):
@@ -118,7 +131,7 @@ def select_lists(q1, summ, stream):
     return bound, select, lists
 
 
-def measure_and_report(args, work, report, method, derive):
+def measure_and_report(args, work, report, method, derive, what="one layer's call, one query row per head"):
     """Every row of `work` [(name, fn)] INTERLEAVED, HIP events, the libraries of a row taking turns at going first; `report`
     gains each row's statistics, what `derive` adds (it returns the mode's lines for stdout) and, with --parent-lib, the
     samples of the contested rows and `versus_parent`."""
@@ -134,7 +147,7 @@ def measure_and_report(args, work, report, method, derive):
             if rep >= args.warmup:
                 samples[name].append(e0.elapsed_time(e1) * 1e3)
     report["method"] = (f"one process, HIP events, interleaved, median and quartiles of {args.reps} after {args.warmup} warm-up "
-                        "rounds; one layer's call, one query row per head" + method)
+                        f"rounds; {what}" + method)
     for name in samples:
         report[name] = stat(samples[name])
     lines = derive(report)
@@ -255,10 +268,112 @@ def main_fp8(args, libs, full_lib):
     measure_and_report(args, work, report, "", derive)
 
 
+def main_wide(args, full_lib):
+    dev, stream = torch.device("cuda:0"), nv.stream()
+    g = torch.Generator(device=dev).manual_seed(7)
+    bf, scale = torch.bfloat16, D ** -0.5
+    ve, Lk = PINNED + N, PINNED + N + QUESTION
+    rnd = lambda *shape: (1.7 * torch.randn(shape, generator=g, device=dev)).to(bf)   # noqa: E731
+    work, routes, hold = [], {}, []
+
+    def geometry(prefix, hq, hkv, Lqs, keeps, narrow):
+        """The rows of one head geometry over a layer of its own: [(name, fn)] appended to `work`."""
+        k, v = rnd(1, hkv, Lk, D), rnd(1, hkv, Lk, D)
+        summ = torch.empty((hkv, PAGES, 2, D), dtype=bf, device=dev)
+        u = (nv.PageSummaryUnit * 1)()
+        u[0].k, u[0].k_stride_h, u[0].first, u[0].n, u[0].summ, u[0].summ_stride_h = k.data_ptr(), k.stride(1), PINNED, N, summ.data_ptr(), summ.stride(0)
+        call(nv.lib, "rtk_pivotkv_page_summary_batched", u, 1, hkv, D, BF, stream)()
+        ub = torch.empty((hkv, PAGES), dtype=torch.float32, device=dev)
+        hold.extend([k, v, summ, ub, u])
+        selects = {}
+        for Lq in Lqs:
+            q = rnd(1, hq, Lq, D)
+            out = torch.empty((1, Lq, hq, D), dtype=bf, device=dev)
+            hold.extend([q, out])
+            a = (nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2), nv.ptr(out), hq, hkv, Lq, Lk,
+                 Lk - Lq, D, BF, scale)
+            assert (hq // hkv) * Lq > 16
+            work.append((f"{prefix}wide_full_{Lq}", call(full_lib, "rtk_attention_decode_wide", *a, *sized(
+                full_lib, "rtk_attention_decode_wide_workspace_bytes", hq, hkv, Lq, Lk, D, BF), stream)))
+            fws, route = {}, []
+            run_chunk = lambda q=q, fws=fws, route=route: chunk_attention(q, k, v, workspace=fws, route=route)   # noqa: E731
+            assert run_chunk() is not None
+            routes[f"{prefix}chunk_{Lq}"] = route[0]
+            work.append((f"{prefix}chunk_{Lq}", run_chunk))
+            bound = call(nv.lib, "rtk_attention_page_bound", nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(summ), summ.stride(0), hq,
+                         hkv, Lq, PAGES, D, BF, nv.ptr(ub), stream)
+            bound()
+            work.append((f"{prefix}bound_{Lq}", bound))
+            for K in keeps:
+                kp = KEEP_PAGES[K]
+                chain = "rtk_attention_decode_sparse_wide"
+                work.append((f"{prefix}sparse_wide_{Lq}_{K}", call(nv.lib, chain, *a, PINNED, ve, nv.ptr(summ), summ.stride(0), kp, *sized(
+                    nv.lib, chain + "_workspace_bytes", hq, hkv, Lq, Lk, PINNED, ve, kp, D, BF), stream)))
+                lists = torch.empty((hkv, kp), dtype=torch.int32, device=dev)
+                units = (nv.BudgetSelectUnit * hkv)(*[nv.BudgetSelectUnit(ub[h].data_ptr(), lists[h].data_ptr(), PAGES, kp)
+                                                      for h in range(hkv)])
+                select = call(nv.lib, "rtk_pivotkv_budget_select_batched", units, hkv, stream)
+                select()   # (the lists of the last Lq's bounds: the paged launch alone reads them)
+                hold.extend([lists, units])
+                if K not in selects:
+                    selects[K] = select
+                    work.append((f"{prefix}select_{K}", select))
+                work.append((f"{prefix}paged_wide_{Lq}_{K}", call(nv.lib, "rtk_attention_decode_paged_wide", *a, PINNED, ve, nv.ptr(lists),
+                                                                   kp, *sized(nv.lib, "rtk_attention_decode_paged_wide_workspace_bytes", hq,
+                                                                              hkv, Lq, Lk, PINNED, ve, kp, D, BF), stream)))
+        if narrow:   # (d) one query row on the same buffers
+            narrow_rows(prefix, hq, hkv, k, v, summ, keeps)
+
+    def narrow_rows(prefix, hq, hkv, k, v, summ, keeps):
+        Lq = 1
+        q = rnd(1, hq, Lq, D)
+        out = torch.empty((1, Lq, hq, D), dtype=bf, device=dev)
+        hold.extend([q, out])
+        a = (nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2), nv.ptr(out), hq, hkv, Lq, Lk, Lk - Lq,
+             D, BF, scale)
+        for K in keeps:
+            work.append((f"{prefix}sparse_1_{K}", call(nv.lib, "rtk_attention_decode_sparse", *a, PINNED, ve, nv.ptr(summ), summ.stride(0),
+                                                       KEEP_PAGES[K], *sized(nv.lib, "rtk_attention_decode_sparse_workspace_bytes", hq, hkv,
+                                                                             Lq, Lk, PINNED, ve, KEEP_PAGES[K], D, BF), stream)))
+
+    LQS = (3, 6, 9)
+    geometry("", Hq, Hkv, LQS, KEEPS, True)
+    geometry("g2_", 8, 4, (9,), (8192,), False)
+    geometry("g1_", 8, 8, (17,), (8192,), False)
+
+    report = {"device": torch.cuda.get_device_name(0),
+              "geometry": {"layers": LAYERS, "Hq": Hq, "Hkv": Hkv, "D": D, "dtype": "bf16", "n": N, "pages": PAGES, "pinned": PINNED,
+                           "tail": QUESTION, "keep_rows": list(KEEPS), "Lq": list(LQS),
+                           "g2_": {"Hq": 8, "Hkv": 4, "Lq": 9, "keep_rows": 8192}, "g1_": {"Hq": 8, "Hkv": 8, "Lq": 17, "keep_rows": 8192}},
+              "wide_full_from": "parent commit's library" if args.parent_lib else "this build (same kernel code as the parent's)",
+              "chunk_routes": routes}
+
+    def derive(report):
+        iqr = lambda r: r["q3_us"] - r["q1_us"]   # noqa: E731
+        lines = []
+        for prefix, Lqs, keeps in (("", LQS, KEEPS), ("g2_", (9,), (8192,)), ("g1_", (17,), (8192,))):
+            for Lq in Lqs:
+                full, chunk = report[f"{prefix}wide_full_{Lq}"], report[f"{prefix}chunk_{Lq}"]
+                for K in keeps:
+                    r = report[f"{prefix}sparse_wide_{Lq}_{K}"]
+                    r.update(wide_full_over_chain=round(full["median_us"] / r["median_us"], 2),
+                             chunk_over_chain=round(chunk["median_us"] / r["median_us"], 2),
+                             beats_wide_full=bool(full["median_us"] - r["median_us"] > iqr(full) + iqr(r)))
+                    lines.append(f"{prefix}Lq {Lq} keep_rows {K}: the chain {r['median_us']:.0f} us; the wide call over all rows "
+                                 f"{r['wide_full_over_chain']:.2f} x, the chunk kernel {r['chunk_over_chain']:.2f} x; gain over the wide "
+                                 f"call beyond both IQRs: {r['beats_wide_full']}")
+        return lines
+
+    measure_and_report(args, work, report, "; the launches alone run on the chain's own operands", derive,
+                       "one layer's call, Lq query rows per head")
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default=None, help="default: profiles/sparse_decode_bench.json (--fp8: sparse_decode_fp8_bench.json)")
+    ap.add_argument("--out", default=None, help="default: profiles/sparse_decode_bench.json (--fp8: sparse_decode_fp8_bench.json, "
+                    "--wide: sparse_decode_wide_bench.json)")
     ap.add_argument("--fp8", action="store_true", help="the chain over an fp8 archive (rtk_attention_decode_sparse_fp8kv)")
+    ap.add_argument("--wide", action="store_true", help="several new tokens (rtk_attention_decode_sparse_wide)")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--parent-lib", action="append", default=[], metavar="PATH",
@@ -267,11 +382,14 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("bench_sparse_decode.py measures on the GPU; none is visible (Time: not measured)")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "sparse_decode_fp8_bench.json" if args.fp8 else "sparse_decode_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "sparse_decode_fp8_bench.json" if args.fp8 else
+                                "sparse_decode_wide_bench.json" if args.wide else "sparse_decode_bench.json")
     libs = libraries(args)
     full_lib = libs[1 if args.parent_lib else 0][1]
     if args.fp8:
         return main_fp8(args, libs, full_lib)
+    if args.wide:
+        return main_wide(args, full_lib)
     dev, stream = torch.device("cuda:0"), nv.stream()
     g = torch.Generator(device=dev).manual_seed(7)
     cache = parent(dev, g)

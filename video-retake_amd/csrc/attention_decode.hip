@@ -26,13 +26,15 @@
 // several branches; attn_decode_wide_d128_kernel (attention_decode_wide.cuh, rtk_attention_decode_wide*) serves
 // 16 < R <= 64 packed rows as two to four column groups; attn_decode_paged_d128_kernel (attention_decode_paged.cuh,
 // rtk_attention_decode_paged / _sparse) reads the middle of ONE buffer through a per-kv-head page list, and
-// attn_decode_paged_fp8kv_d128_kernel (the same file, rtk_attention_decode_paged_fp8kv / _sparse_fp8kv) the e4m3 archive.  The body, the group kernel and the wide kernel share
+// attn_decode_paged_fp8kv_d128_kernel (the same file, rtk_attention_decode_paged_fp8kv / _sparse_fp8kv) the e4m3 archive;
+// attn_decode_paged_wide_d128_kernel (the same file, rtk_attention_decode_paged_wide / _sparse_wide) is the wide kernel's
+// body over the 16-bit page walk.  The body, the group kernel and the wide kernel share
 // dec_step_off, dec_v_frag and dec_softmax_step; their tile loads, dequantise-and-stage step and four-wave fold are
 // written in each (as shared functions they compile the existing kernels differently).  Host side: the entry
 // points of the narrow and the wide family are decode_call with their family and segments - its checks and fall-throughs,
 // then decode_forward (operands, plan, workspace, dtype) -> decode_launch -> decode_launch_d128, the one launcher; the
-// four page-sparse entry points are paged_call with their names, their kind (16-bit rows / fp8 archive) and a page list
-// or summaries - one shape check, one operand check, one bound -> select -> paged chain, one launcher.
+// six page-sparse entry points are paged_call with their family, their names, their kind (16-bit rows / fp8 archive) and
+// a page list or summaries - one shape check, one operand check, one bound -> select -> paged chain, one launcher.
 // FP8 = true: the keys are [e4m3 archive | 16-bit rows], counted in a key space where the archive is padded to whole
 // 32-key tiles (a tile is of one kind).  Archive tiles are dequantised (fp8_dequant16) into the registers / the LDS image
 // a 16-bit tile of the dequantised rows would have left, so with L8 % 32 == 0 every fp32 sum is grouped as in the 16-bit
@@ -573,9 +575,11 @@ int group_launch(const GroupPlan& gp, const GroupArgs& ga, const Archive8& a8, c
     return attn_combine<DT>(p, out, heads, 1, 128, nsplit, st);
 }
 
-// ---- page-sparse decode (rtk_attention_decode_{paged,sparse}{,_fp8kv}; the kernels: attention_decode_paged.cuh) ----
-// The four calls are paged_call (below) with their names and what they take: `arch8` - the pages are the e4m3 archive's
-// (first = 0, ve = L8: the region is the archive), else rows [first, ve) of k / v - and a page list or, `sparse`, summaries.
+// ---- page-sparse decode (rtk_attention_decode_{paged,sparse}{,_fp8kv,_wide}; the kernels: attention_decode_paged.cuh) ----
+// The six calls are paged_call (below) with their family, their names and what they take: `arch8` - the pages are the e4m3
+// archive's (first = 0, ve = L8: the region is the archive), else rows [first, ve) of k / v - and a page list or, `sparse`,
+// summaries.  The family is that of the packed entry points: DEC_WIDE (16-bit rows only) admits up to 64 packed rows and
+// at R <= DEC_R IS the narrow call.
 struct PagedGeom {
     int first, ve, keep_pages;
     int pages;             // ceil((ve - first) / 32)
@@ -583,9 +587,9 @@ struct PagedGeom {
 };
 // the shape checks of the paged calls, before anything is launched: those of rtk_attention_decode / _fp8kv, then the
 // pages; `g` is filled on success
-int paged_check_shape(const char* who, bool arch8, int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype, int first, int ve,
+int paged_check_shape(const char* who, const DecodeFamily& f, bool arch8, int Hq, int Hkv, int Lq, int Lk, int L8, int D, int dtype, int first, int ve,
                       int keep_pages, PagedGeom& g) {
-    const int rc = decode_check_shape(who, DEC_NARROW, arch8, Hq, Hkv, Lq, Lk, L8, 0, D, dtype);
+    const int rc = decode_check_shape(who, f, arch8, Hq, Hkv, Lq, Lk, L8, 0, D, dtype);
     if (rc != RTK_OK) return rc;
     if (arch8) {
         RTK_CHECK_ARG(L8 >= 1, "%s: L8 %d: the call needs an archive (rtk_attention_decode serves a cache without one)", who, L8);
@@ -643,7 +647,9 @@ int paged_check_workspace(const char* who, const char* query, size_t need, const
     return RTK_OK;
 }
 // One launch of the paged kernel of the call's kind over `partials`, then the combine.  (The two kernels' parameter lists
-// differ in their middle - kv_bytes - so the launch is written per kind, not as decode_launch_d128's trailing pack.)
+// differ in their middle - kv_bytes - so the launch is written per kind, not as decode_launch_d128's trailing pack.)  More
+// than DEC_R packed rows (the wide family's 16-bit calls; the checks admit no other) take the wide kernel of their column
+// groups, whose parameter list is the 16-bit kind's.
 template <int DT>
 int paged_launch(bool arch8, const DecodePlan& pl, const AttnArgs& a, const Archive8& a8, const PagedGeom& g, const int32_t* list,
                  void* partials) {
@@ -652,6 +658,16 @@ int paged_launch(bool arch8, const DecodePlan& pl, const AttnArgs& a, const Arch
     const char *q = (const char*)a.q, *k = (const char*)a.k, *v = (const char*)a.v;
     const uint32_t row_bytes = (uint32_t)(a.kv_sl * 2);
     const float c2 = base2_scale(a.scale);
+    const int ncg = ((a.Hq / a.Hkv) * a.Lq + DEC_R - 1) / DEC_R;
+    if (ncg > 1) {
+        const auto kern = ncg == 2   ? attn_decode_paged_wide_d128_kernel<DT, 2>
+                          : ncg == 3 ? attn_decode_paged_wide_d128_kernel<DT, 3>
+                                     : attn_decode_paged_wide_d128_kernel<DT, 4>;
+        hipLaunchKernelGGL(kern, grid, dim3(256), 0, a.st, q, a.q_sh, a.q_sl, k, v, a.kv_sh, row_bytes, p.acc, p.ml, a.Hq,
+                           a.Hq / a.Hkv, a.Lq, a.Lk, a.off, c2, pl.keys_per_split, g.first, g.ve, list, g.keep_pages);
+        RTK_LAUNCH_CHECK("attn_decode_paged_wide_d128_kernel");
+        return attn_combine<DT>(p, a.out, a.Hq, a.Lq, 128, pl.nsplit, a.st);
+    }
     if (arch8)
         hipLaunchKernelGGL((attn_decode_paged_fp8kv_d128_kernel<DT>), grid, dim3(256), 0, a.st, q, a.q_sh, a.q_sl, k, v, a.kv_sh,
                            row_bytes, rows_extent(a.Lk, a.kv_sl, 128, 2), p.acc, p.ml, a.Hq, a.Hq / a.Hkv, a.Lq, a.Lk, a.off, c2,
@@ -664,24 +680,29 @@ int paged_launch(bool arch8, const DecodePlan& pl, const AttnArgs& a, const Arch
     return attn_combine<DT>(p, a.out, a.Hq, a.Lq, 128, pl.nsplit, a.st);
 }
 
-// A workspace query of the four: 0 with the error set for a shape the call does not take
-size_t paged_query(const char* query, bool arch8, bool sparse, int Hq, int Hkv, int Lq, int Lk, int L8, int first, int ve,
+// A workspace query of the six: 0 with the error set for a shape the call's family does not take
+size_t paged_query(const DecodeFamily& f, const char* query, bool arch8, bool sparse, int Hq, int Hkv, int Lq, int Lk, int L8, int first, int ve,
                    int keep_pages, int D, int dtype) {
     PagedGeom g;
-    if (paged_check_shape(query, arch8, Hq, Hkv, Lq, Lk, L8, D, dtype, first, ve, keep_pages, g) != RTK_OK) return 0;
+    if (paged_check_shape(query, f, arch8, Hq, Hkv, Lq, Lk, L8, D, dtype, first, ve, keep_pages, g) != RTK_OK) return 0;
     return sparse_layout(sparse, Hkv, g, decode_plan(Hq, Hkv, Lq, g.keys)).bytes;
 }
 
-// An entry point of the four (`query`: the one that sizes its workspace; `sg`: its archive, empty for the 16-bit kind;
+// An entry point of the six (`f`: its family; `query`: the one that sizes its workspace; `sg`: its archive, empty for the 16-bit kind;
 // `pick`: its page list [Hkv, keep_pages] or, `sparse`, its summaries with head stride summ_sh): the checks in the order
 // retake_hip.h states, then the paged kernel and the combine - after, `sparse`, the bound and the selection (one unit per
-// kv head: the existing launchers as they are) have written the lists into the workspace.
-int paged_call(const char* who, const char* query, bool arch8, bool sparse, const AttnArgs& a, const DecodeSegs& sg, int first, int ve,
+// kv head: the existing launchers as they are) have written the lists into the workspace.  As among the packed entry
+// points, a call of the wide family with at most DEC_R packed rows is the narrow call of the same kind.
+int paged_call(const DecodeFamily& f, const char* who, const char* query, bool arch8, bool sparse, const AttnArgs& a, const DecodeSegs& sg, int first, int ve,
                int keep_pages, const void* pick, int64_t summ_sh) {
     RTK_CHECK_ARG(a.q && a.k && a.v && a.out && pick, "%s: NULL q / k / v / out / %s pointer", who, sparse ? "summ" : "list");
     PagedGeom g;
-    int rc = paged_check_shape(who, arch8, a.Hq, a.Hkv, a.Lq, a.Lk, sg.L8, a.D, a.dtype, first, ve, keep_pages, g);
+    int rc = paged_check_shape(who, f, arch8, a.Hq, a.Hkv, a.Lq, a.Lk, sg.L8, a.D, a.dtype, first, ve, keep_pages, g);
     if (rc != RTK_OK) return rc;
+    if (f.max_rows > DEC_R && (a.Hq / a.Hkv) * a.Lq <= DEC_R)
+        return paged_call(DEC_NARROW, sparse ? "rtk_attention_decode_sparse" : "rtk_attention_decode_paged",
+                          sparse ? "rtk_attention_decode_sparse_workspace_bytes" : "rtk_attention_decode_paged_workspace_bytes", arch8,
+                          sparse, a, sg, first, ve, keep_pages, pick, summ_sh);
     if (sparse)
         RTK_CHECK_ARG(((uintptr_t)pick & 15) == 0 && (summ_sh * 2) % 16 == 0 && summ_sh >= (int64_t)g.pages * 2 * a.D,
                       "%s: summ must be 16-byte aligned with a head stride of at least pages * 2 * D = %lld elements", who,
@@ -874,14 +895,14 @@ extern "C" int rtk_attention_decode_group(const rtk_decode_branch* branches, int
 // ---- page-sparse decode (retake_hip.h §U): paged_call with the call's names, kind and operands ----
 extern "C" size_t rtk_attention_decode_paged_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages,
                                                              int D, int dtype) {
-    return paged_query("rtk_attention_decode_paged_workspace_bytes", false, false, Hq, Hkv, Lq, Lk, 0, first, ve, keep_pages, D, dtype);
+    return paged_query(DEC_NARROW, "rtk_attention_decode_paged_workspace_bytes", false, false, Hq, Hkv, Lq, Lk, 0, first, ve, keep_pages, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_paged(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
                                           int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
                                           int q_offset, int D, int dtype, float scale, int first, int ve, const int32_t* list,
                                           int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream) {
-    return paged_call("rtk_attention_decode_paged", "rtk_attention_decode_paged_workspace_bytes", false, false,
+    return paged_call(DEC_NARROW, "rtk_attention_decode_paged", "rtk_attention_decode_paged_workspace_bytes", false, false,
                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
                                scale, workspace, workspace_bytes, (hipStream_t)stream},
                       DecodeSegs{}, first, ve, keep_pages, list, 0);
@@ -889,7 +910,7 @@ extern "C" int rtk_attention_decode_paged(const void* q, int64_t q_stride_h, int
 
 extern "C" size_t rtk_attention_decode_sparse_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages,
                                                               int D, int dtype) {
-    return paged_query("rtk_attention_decode_sparse_workspace_bytes", false, true, Hq, Hkv, Lq, Lk, 0, first, ve, keep_pages, D, dtype);
+    return paged_query(DEC_NARROW, "rtk_attention_decode_sparse_workspace_bytes", false, true, Hq, Hkv, Lq, Lk, 0, first, ve, keep_pages, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -897,7 +918,7 @@ extern "C" int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, in
                                            int q_offset, int D, int dtype, float scale, int first, int ve, const void* summ,
                                            int64_t summ_stride_h, int keep_pages, void* workspace, size_t workspace_bytes,
                                            rtk_stream_t stream) {
-    return paged_call("rtk_attention_decode_sparse", "rtk_attention_decode_sparse_workspace_bytes", false, true,
+    return paged_call(DEC_NARROW, "rtk_attention_decode_sparse", "rtk_attention_decode_sparse_workspace_bytes", false, true,
                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
                                scale, workspace, workspace_bytes, (hipStream_t)stream},
                       DecodeSegs{}, first, ve, keep_pages, summ, summ_stride_h);
@@ -905,7 +926,7 @@ extern "C" int rtk_attention_decode_sparse(const void* q, int64_t q_stride_h, in
 
 extern "C" size_t rtk_attention_decode_paged_fp8kv_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int L8, int keep_pages, int D,
                                                                    int dtype) {
-    return paged_query("rtk_attention_decode_paged_fp8kv_workspace_bytes", true, false, Hq, Hkv, Lq, Lk, L8, 0, 0, keep_pages, D, dtype);
+    return paged_query(DEC_NARROW, "rtk_attention_decode_paged_fp8kv_workspace_bytes", true, false, Hq, Hkv, Lq, Lk, L8, 0, 0, keep_pages, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_paged_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -914,7 +935,7 @@ extern "C" int rtk_attention_decode_paged_fp8kv(const void* q, int64_t q_stride_
                                                 int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
                                                 int D, int dtype, float scale, const int32_t* list, int keep_pages, void* workspace,
                                                 size_t workspace_bytes, rtk_stream_t stream) {
-    return paged_call("rtk_attention_decode_paged_fp8kv", "rtk_attention_decode_paged_fp8kv_workspace_bytes", true, false,
+    return paged_call(DEC_NARROW, "rtk_attention_decode_paged_fp8kv", "rtk_attention_decode_paged_fp8kv_workspace_bytes", true, false,
                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
                                scale, workspace, workspace_bytes, (hipStream_t)stream},
                       DecodeSegs{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h}, 0, 0,
@@ -923,7 +944,7 @@ extern "C" int rtk_attention_decode_paged_fp8kv(const void* q, int64_t q_stride_
 
 extern "C" size_t rtk_attention_decode_sparse_fp8kv_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int L8, int keep_pages, int D,
                                                                     int dtype) {
-    return paged_query("rtk_attention_decode_sparse_fp8kv_workspace_bytes", true, true, Hq, Hkv, Lq, Lk, L8, 0, 0, keep_pages, D, dtype);
+    return paged_query(DEC_NARROW, "rtk_attention_decode_sparse_fp8kv_workspace_bytes", true, true, Hq, Hkv, Lq, Lk, L8, 0, 0, keep_pages, D, dtype);
 }
 
 extern "C" int rtk_attention_decode_sparse_fp8kv(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
@@ -932,9 +953,43 @@ extern "C" int rtk_attention_decode_sparse_fp8kv(const void* q, int64_t q_stride
                                                  int64_t scale_stride_h, void* out, int Hq, int Hkv, int Lq, int Lk, int q_offset,
                                                  int D, int dtype, float scale, const void* summ, int64_t summ_stride_h,
                                                  int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream) {
-    return paged_call("rtk_attention_decode_sparse_fp8kv", "rtk_attention_decode_sparse_fp8kv_workspace_bytes", true, true,
+    return paged_call(DEC_NARROW, "rtk_attention_decode_sparse_fp8kv", "rtk_attention_decode_sparse_fp8kv_workspace_bytes", true, true,
                       AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
                                scale, workspace, workspace_bytes, (hipStream_t)stream},
                       DecodeSegs{nullptr, nullptr, 0, 0, 0, k8, v8, k_scale, v_scale, L8, stride8_h, scale_stride_h}, 0, 0,
                       keep_pages, summ, summ_stride_h);
+}
+
+// ---- the wide family of the 16-bit page-sparse calls (16 < (Hq / Hkv) * Lq <= 64; at most 16 rows: the call above) ----
+extern "C" size_t rtk_attention_decode_paged_wide_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages,
+                                                                  int D, int dtype) {
+    return paged_query(DEC_WIDE, "rtk_attention_decode_paged_wide_workspace_bytes", false, false, Hq, Hkv, Lq, Lk, 0, first, ve,
+                       keep_pages, D, dtype);
+}
+
+extern "C" int rtk_attention_decode_paged_wide(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                               int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
+                                               int q_offset, int D, int dtype, float scale, int first, int ve, const int32_t* list,
+                                               int keep_pages, void* workspace, size_t workspace_bytes, rtk_stream_t stream) {
+    return paged_call(DEC_WIDE, "rtk_attention_decode_paged_wide", "rtk_attention_decode_paged_wide_workspace_bytes", false, false,
+                      AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                               scale, workspace, workspace_bytes, (hipStream_t)stream},
+                      DecodeSegs{}, first, ve, keep_pages, list, 0);
+}
+
+extern "C" size_t rtk_attention_decode_sparse_wide_workspace_bytes(int Hq, int Hkv, int Lq, int Lk, int first, int ve, int keep_pages,
+                                                                   int D, int dtype) {
+    return paged_query(DEC_WIDE, "rtk_attention_decode_sparse_wide_workspace_bytes", false, true, Hq, Hkv, Lq, Lk, 0, first, ve,
+                       keep_pages, D, dtype);
+}
+
+extern "C" int rtk_attention_decode_sparse_wide(const void* q, int64_t q_stride_h, int64_t q_stride_l, const void* k, const void* v,
+                                                int64_t kv_stride_h, int64_t kv_stride_l, void* out, int Hq, int Hkv, int Lq, int Lk,
+                                                int q_offset, int D, int dtype, float scale, int first, int ve, const void* summ,
+                                                int64_t summ_stride_h, int keep_pages, void* workspace, size_t workspace_bytes,
+                                                rtk_stream_t stream) {
+    return paged_call(DEC_WIDE, "rtk_attention_decode_sparse_wide", "rtk_attention_decode_sparse_wide_workspace_bytes", false, true,
+                      AttnArgs{q, q_stride_h, q_stride_l, k, v, kv_stride_h, kv_stride_l, out, Hq, Hkv, Lq, Lk, q_offset, D, dtype,
+                               scale, workspace, workspace_bytes, (hipStream_t)stream},
+                      DecodeSegs{}, first, ve, keep_pages, summ, summ_stride_h);
 }

@@ -306,6 +306,12 @@ _SIGNATURES = {
     "rtk_attention_decode_sparse_fp8kv_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "rtk_attention_decode_sparse_fp8kv": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i, _i64, _i64, _vp,
                                                 _i, _i, _i, _i, _i, _i, _i, _f, _vp, _i64, _i, _vp, _sz, _vp]),
+    "rtk_attention_decode_paged_wide_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_paged_wide": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i,
+                                              _i, _vp, _i, _vp, _sz, _vp]),
+    "rtk_attention_decode_sparse_wide_workspace_bytes": (C.c_size_t, [_i, _i, _i, _i, _i, _i, _i, _i, _i]),
+    "rtk_attention_decode_sparse_wide": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i, _i, _i, _i, _i, _i, _i, _f, _i,
+                                               _i, _vp, _i64, _i, _vp, _sz, _vp]),
     "rtk_dpselect_ingest": (C.c_int, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "rtk_dpselect_select_ring": (C.c_int, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "rtk_p2p_alloc": (C.c_int, [_sz, _i, C.POINTER(_vp)]),

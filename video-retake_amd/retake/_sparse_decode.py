@@ -26,6 +26,17 @@ the layer's own buffers - is ONE rtk_attention_decode_sparse call (bound, select
 in `sparse_attention_calls`; every other call takes the existing routes, bit for bit.  The index survives
 `rewind(video_end)`: the next question pays nothing.  `dense_decode(cache)` disarms and frees.
 
+Several new tokens: `sparse_decode(cache, keep_rows, wide=True)` also routes a call with 16 < (Hq / Hkv) * Lq <= 64 packed
+rows - the verification call of assisted generation (num_assistant_tokens + 1 rows), a few-token continuation, a short
+follow-up after `rewind(video_end)` - as ONE rtk_attention_decode_sparse_wide call, under the narrow route's other
+conditions; it counts in `sparse_attention_calls` and in `sparse_wide_calls(cache)`.  The key is its own opt-in (it does
+not need `multi_token_attention`; without it every call goes exactly where it went, bit for bit) and serves every G the
+library serves.  The rule: ALL Lq rows of the call share ONE list per kv head.  ub[g, p] above is the max over the packed
+rows of EVERY position, so a page that any one draft row needs is ranked by that row - and a verification call's output is
+not what Lq one-token sparse calls, each with a list of its own, would give.  What that does to answer quality and to
+draft acceptance has not been evaluated (there are no weights here).  `crop()` of rows behind `video_end` (a rejected
+draft) and `rewind(video_end)` leave the index armed and valid: no new summary call.
+
 kv_cache_dtype="fp8_e4m3": `sparse_decode(cache, keep_rows, archive=True)` arms the route over the fp8 ARCHIVE.  The region
 is the archive as recorded at `video_end` - n = len8 rows, page p is archive rows [32 p, min(32 p + 32, n)) - and the 16-bit
 buffer holds the pinned rows and everything behind the video; as in rtk_attention_decode_fp8kv every archive row is visible
@@ -40,7 +51,7 @@ and scales (16 bytes of summaries per (kv head, row) beside 132 of K codes + sca
 K + V); a served call is ONE rtk_attention_decode_sparse_fp8kv call.  The key is independent of `archive_rescore`.
 
 Not served (refused at arming, before any launch): kv_cache_dtype without archive=True (and archive=True without
-kv_cache_dtype), a branch, a focused cache, defer_rerotation, an fp32 model, head_dim != 128.  Not built: the wide kernel, the sharded path, incremental index updates
+kv_cache_dtype), a branch, a focused cache, defer_rerotation, an fp32 model, head_dim != 128, archive=True together with wide=True.  Not built: the wide kernel over the fp8 archive, branches, the sharded path, incremental index updates
 while the video grows (a chunk after arming makes the next routed call raise: arm again)."""
 import torch
 
@@ -48,24 +59,27 @@ from . import _native as nv
 from ._cache_state import _on_device
 
 PAGE = nv.PAGE_ROWS
+NARROW_ROWS = 16   # packed rows of the narrow kernel (DEC_R): a call with more takes the wide entry points
 
 
 class _Sparse:
     """An armed route: keep_rows, the `video_end` recorded at arming, and per layer the summaries [Hkv, pages, 2, D], the
     geometry (first, ve, pages) and the workspace of the layer's last routed call (ub | lists | partials).  `archive`: the
-    pages are the fp8 archive's; the geometry is then (16-bit rows at `video_end`, len8 at `video_end`, pages)."""
+    pages are the fp8 archive's; the geometry is then (16-bit rows at `video_end`, len8 at `video_end`, pages).  `wide`: calls
+    of 17 to 64 packed rows are routed too; `wide_calls` counts them."""
 
-    __slots__ = ("keep_rows", "mark", "summ", "geom", "ws", "last", "archive")
+    __slots__ = ("keep_rows", "mark", "summ", "geom", "ws", "last", "archive", "wide", "wide_calls")
 
-    def __init__(self, keep_rows, mark, archive=False):
+    def __init__(self, keep_rows, mark, archive=False, wide=False):
         self.keep_rows, self.mark, self.summ, self.geom, self.ws, self.last = keep_rows, mark, {}, {}, {}, {}
-        self.archive = archive
+        self.archive, self.wide, self.wide_calls = archive, wide, 0
 
 
 class _Rows16:
     """The kind archive=False: the region is rows [pinned, length at `video_end`) of the layer's 16-bit buffers."""
     Unit, summary = nv.PageSummaryUnit, "rtk_pivotkv_page_summary_batched"
     query, call = "rtk_attention_decode_sparse_workspace_bytes", "rtk_attention_decode_sparse"
+    wide_query, wide_call = "rtk_attention_decode_sparse_wide_workspace_bytes", "rtk_attention_decode_sparse_wide"
     none = "no layer holds video rows behind its pinned rows"
 
     @staticmethod
@@ -135,9 +149,10 @@ def _check_mark(cache, mark, who, then):
         raise ValueError(f"{who}: {then}")
 
 
-def sparse_decode(cache, keep_rows: int = 8192, archive: bool = False) -> None:
+def sparse_decode(cache, keep_rows: int = 8192, archive: bool = False, wide: bool = False) -> None:
     """Arm the page-sparse decode route (see the module docstring).  ValueError, before any launch: keep_rows not an int
-    >= 1 (a bool is not an int), archive not a bool, a cache without `video_end`, attention_kernel other than "hip",
+    >= 1 (a bool is not an int), archive or wide not a bool, archive=True together with wide=True (the wide paged kernel
+    over the fp8 archive is not built), a cache without `video_end`, attention_kernel other than "hip",
     kv_cache_dtype set without archive=True (the pages of an fp8 cache are its archive's: an opt-in of its own), archive=True
     on a cache without kv_cache_dtype.  NotImplementedError: a branch, a focused cache, defer_rerotation, an fp32 model or
     head_dim other than 128.  Arming again rebuilds the index: ONE summary call of the kind per device."""
@@ -146,6 +161,11 @@ def sparse_decode(cache, keep_rows: int = 8192, archive: bool = False) -> None:
         raise ValueError(f"{who}: keep_rows must be an int >= 1, got {keep_rows!r}")
     if not isinstance(archive, bool):
         raise ValueError(f"{who}: archive must be a bool, got {archive!r}")
+    if not isinstance(wide, bool):
+        raise ValueError(f"{who}: wide must be a bool, got {wide!r}")
+    if archive and wide:
+        raise ValueError(f"{who}: archive=True together with wide=True is not served - the wide paged kernel over the fp8 "
+                         "archive is not built")
     if cache.focused_from is not None:
         raise NotImplementedError(f"{who}: this cache is a focused cache (PivotKVCache.focus) - it already holds the rows one "
                                   "question reads")
@@ -188,7 +208,7 @@ def sparse_decode(cache, keep_rows: int = 8192, archive: bool = False) -> None:
         by_device.setdefault(k.get_device(), []).append((l, st) + region)
     if not by_device:
         raise ValueError(f"{who}: {kind.none}")
-    sp = _Sparse(keep_rows, ve, archive)
+    sp = _Sparse(keep_rows, ve, archive, wide)
     for dev, ps in by_device.items():
         units = (kind.Unit * len(ps))()
         k0 = ps[0][1]._k
@@ -210,6 +230,12 @@ def sparse_decode(cache, keep_rows: int = 8192, archive: bool = False) -> None:
 def dense_decode(cache) -> None:
     """Disarm the route and free the index and its workspaces; every call takes the existing routes again."""
     cache._sparse = None
+
+
+def sparse_wide_calls(cache) -> int:
+    """The routed calls of more than 16 packed rows since arming (each also counts in `sparse_attention_calls`);
+    ValueError while not armed."""
+    return _armed(cache, "sparse_wide_calls").wide_calls
 
 
 def sparse_bytes(cache) -> dict:
@@ -249,7 +275,9 @@ def route(cache, q, k, v, scaling, query_offset, layer_idx):
         return None
     keep_pages = min((sp.keep_rows + PAGE - 1) // PAGE, pages)
     code = nv.dtype_code(q)
-    need = getattr(nv.lib, kind.query)(Hq, Hkv, Lq, Lk, *kind.region_args(geom), keep_pages, D, code)
+    wide = sp.wide and (Hq // Hkv) * Lq > NARROW_ROWS
+    query, call = (kind.wide_query, kind.wide_call) if wide else (kind.query, kind.call)
+    need = getattr(nv.lib, query)(Hq, Hkv, Lq, Lk, *kind.region_args(geom), keep_pages, D, code)
     if not need:
         return None   # outside the packed envelope: the existing routes
     ws = sp.ws.get(layer_idx)
@@ -257,15 +285,16 @@ def route(cache, q, k, v, scaling, query_offset, layer_idx):
         ws = sp.ws[layer_idx] = torch.empty(need, dtype=torch.uint8, device=q.device)
     out = torch.empty((1, Lq, Hq, D), dtype=q.dtype, device=q.device)
     scale = float(D) ** -0.5 if scaling is None else float(scaling)
-    rc = getattr(nv.lib, kind.call)(nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2),
+    rc = getattr(nv.lib, call)(nv.ptr(q), q.stride(1), q.stride(2), nv.ptr(k), nv.ptr(v), k.stride(1), k.stride(2),
                                     *kind.archive_args(st, geom), nv.ptr(out), Hq, Hkv, Lq, Lk, q_off, D, code, scale,
                                     *kind.tail_args(geom), nv.ptr(summ), summ.stride(0), keep_pages, nv.ptr(ws), ws.numel(),
                                     nv.raw_stream(q.device.index))
     if rc == nv.RTK_EUNSUPPORTED:
         return None
-    nv.check(rc, kind.call)
+    nv.check(rc, call)
     sp.last[layer_idx] = (Hkv, pages, keep_pages)
     cache.sparse_attention_calls += 1
+    sp.wide_calls += wide
     return out
 
 

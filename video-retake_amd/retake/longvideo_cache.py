@@ -277,7 +277,7 @@ class PivotKVCache(DynamicCache):
         # functions of retake/_sparse_decode.py take the cache - sparse_decode(cache, keep_rows) arms, dense_decode(cache)
         # disarms.  They are NOT bound as methods: the class keeps exactly the names it had, and the state lives here
         self._sparse = None               # the page index while armed (None: off, `attention` is exactly as without it)
-        self.sparse_attention_calls = 0   # attention calls that took rtk_attention_decode_sparse (an fp8 cache: _sparse_fp8kv)
+        self.sparse_attention_calls = 0   # attention calls that took rtk_attention_decode_sparse (an fp8 cache: _sparse_fp8kv; wide=True: _sparse_wide)
         self.page_summary_calls = 0       # rtk_pivotkv_page_summary_batched (_fp8k_batched) calls so far (one per device and arming)
 
     def attention(self, query_states, key_states, value_states, *, scaling=None, query_offset=None, layer_idx=None):
